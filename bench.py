@@ -10,14 +10,25 @@ Langevin) per GPU, one independent replica per GPU (BASELINE.json metric / confi
 A "step" is one fused force + BAOAB kernel over the whole system (mythos_amd/csrc/langevin_core.inc).
 The timed region is one ``mythos_langevin_advance`` call of exactly K steps with the state resident in HBM
 (loaded into the integrator before the clock starts), bracketed by barrier + synchronize, MAX over ranks.
-It is measured ``--repeats`` times back to back (the trajectory continues from sample to sample; default 5, or 21
-when K < 500).  **value = N_gpus * repeats * K / the SUM of the samples**: every scheduled list rebuild that falls into
-the repeats is paid for in it (round 3 reported the median sample, which for K = 20 never contains a rebuild: ADVICE r3);
-the median rate is ``steps_per_s_median``, all samples are in ``config.samples_ms`` and the scheduled rebuilds inside
-each in ``config.scheduled_rebuilds_per_sample``.  A GPU that sat idle until the clock starts runs its first
-milliseconds at clocks still coming up; the untimed warm-up is therefore at least W steps AND at least
-``--min-warmup-ms`` of stepping (``config.warmup_steps_done``).  Nothing else is inside a sample: the per-dispatch HIP
-events behind ``roofline.kernel_ms`` are taken in a second, untimed pass.  For N > 1 every rank steps its own replica
+``--repeats R`` measures it R times back to back (the trajectory continues from sample to sample; default 1, so that
+K is the number of timed steps).  **value = N_gpus * R * K / the SUM of the samples**: every scheduled list rebuild that
+falls into the timed steps is paid for in it; ``ms_per_step`` is the mean time of one timed step, the median rate is
+``steps_per_s_median``, all samples are in ``config.samples_ms`` and the scheduled rebuilds inside each in
+``config.scheduled_rebuilds_per_sample``.  The trajectory starts at the ideal helix with W untimed warm-up steps, and
+the list is built at the first of them and rebuilt every ``--rebuild-every`` steps after.  That rebuild phase is fixed:
+a short run whose W + K stays under ``--rebuild-every`` (e.g. K = 20, W = 5) contains no rebuild and pays for none
+(``config.timed_region`` says how many it held); only runs long against the schedule pay their share.
+A GPU that sat idle until the clock starts runs its first milliseconds at clocks still coming up; before the warm-up a
+system and integrator of their own therefore step for at least ``--min-warmup-ms`` and are discarded (the W + K steps
+are the same trajectory from run to run whatever this ramp took; ``config.warmup_steps_done`` counts both).  Earlier
+versions let the ramp continue the measured trajectory, so the timed steps started after ~10 k steps of thermalisation
+instead of W.  ``--dump-outputs DIR`` writes, after the timed steps, the state a caller of
+the timed path receives (positions, quaternions, linear and angular momenta; with ``--save-every`` also the last saved
+frame and energy row) as ``DIR/<name>.npy`` in the run's precision.
+
+A plain run does only that: set up, warm up, time, dump, print.  ``--full`` adds every other measurement below (each
+outside the timed region): the per-dispatch HIP events behind ``roofline.kernel_ms`` in a second, untimed pass, the
+other precision, ``config.save_every_1``, the secondary configs and the CPU baselines.  For N > 1 every rank steps its own replica
 (weak scaling; the MD data path has no collective): barrier + synchronize, the rank's clock around its K steps,
 synchronize + barrier, MAX over ranks.  ``--save-every S`` stores positions + quaternions every S steps inside the
 timed region (the reference's run stores every step, jaxmd.py:84-99); with ``--trace-energy`` also the energies, and
@@ -25,7 +36,7 @@ for N > 1 those are all-gathered over RCCL (one collective).  The headline preci
 at 1e-3); the same measurement in the reference's fp64 is ``f64_steps_per_s`` / ``f64_frac`` / ``f64_kernel_ms`` and
 ``config.f64``.
 
-Rank 0 prints ONE JSON line with the fields of the driver contract plus
+Rank 0 prints ONE JSON line with the fields of the driver contract plus, under ``--full``,
   roofline      HBM roofline of the step kernel: algorithmic bytes per launch (2 x 14 state
                 words + 13 B topology + 4 B per neighbour entry, per nucleotide) / the kernel's mean duration,
                 measured with HIP events on the launch stream.  ``traffic`` is the PMC-measured HBM-side byte count per
@@ -93,20 +104,26 @@ def parse_args():
                     help="least length of the untimed, event-instrumented pass behind the timed region (dev: short runs of wrong-physics bounds)")
     ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (exactly --steps steps) is run this many times back to back, each bracketed by barrier + "
-                         "synchronize; value = steps / the MEDIAN sample, every sample is in config.samples_ms "
-                         "(default 5; 21 for timed regions under 500 steps)")
+                         "synchronize; value = all steps / their total time, every sample is in config.samples_ms "
+                         "(default 1; MARTINI workload: 5, or 21 for timed regions under 500 steps)")
     ap.add_argument("--min-warmup-ms", type=float, default=150.0,
-                    help="the untimed warm-up lasts at least --warmup steps and at least this long (GPU clocks ramp for the "
-                         "first milliseconds after idling)")
+                    help="before the warm-up, a system and integrator of their own step for at least this long and are discarded "
+                         "(GPU clocks ramp for the first milliseconds after idling); the --warmup steps that follow start the "
+                         "measured trajectory from the initial state (0: no ramp)")
     ap.add_argument("--debug-set", action="append", default=[], metavar="KEY=VALUE",
                     help="dev A/B: mythos_debug_set switches (mythos_amd._lib.DEBUG_KEYS), e.g. mm_subcells=1")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configs (cfg1 / cfg2 / cfg4) and save_every_1")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="development aid: all ranks share cuda:0 and meet over gloo (a 1-GPU box cannot run RCCL "
                          "between ranks); the printed line is then marked as a rehearsal, not a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="headline workload: also the roofline pass, the other precision, save_every_1, the secondary configs and "
+                         "the CPU baselines (--no-second-dtype, --no-secondary and --cpu-steps select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline workload: write the state the timed path produced in its last step as DIR/<name>.npy")
     args = ap.parse_args()
-    if args.repeats is None:
-        args.repeats = 5 if args.steps >= 500 else 21
+    if args.dump_outputs is not None and args.workload != "oxdna2-12kbp":
+        ap.error("--dump-outputs is implemented for the headline workload (oxdna2-12kbp)")
     return args
 
 
@@ -271,7 +288,8 @@ def martini_main(args):
     # collapse under them).  0.5 / 12 for its margin.
     skin, every = (0.5 if args.skin is None else args.skin), (12 if args.rebuild_every is None else args.rebuild_every)
     inner = None if args.inner_list is None else tuple(float(v) for v in args.inner_list.split(","))
-    m = measure_martini(dev, args.dtype, args.steps, args.warmup, skin, every, repeats=max(1, args.repeats if args.repeats else 3), inner=inner)
+    repeats = args.repeats if args.repeats else (5 if args.steps >= 500 else 21)
+    m = measure_martini(dev, args.dtype, args.steps, args.warmup, skin, every, repeats=max(1, repeats), inner=inner)
     kms = m["timing"]["kernel_ms"]
     fr = _frac(m["alg"], kms)
     cpu = None if args.cpu_steps == 0 else martini_cpu_baseline(m["port_args"], m["xt"], m["bt"], m["kT"], 0.3, 10)
@@ -307,53 +325,74 @@ def spawn_ranks(args) -> int:
     return subprocess.run(cmd, env=env, check=False).returncode
 
 
-def measure(args, dtype_name: str, top, c0, q0, sim, flat, dev, seed: int, dist=None, md=None, positions_too: bool = False) -> dict:
+def measure(args, dtype_name: str, top, c0, q0, sim, flat, dev, seed: int, dist=None, md=None, positions_too: bool = False,
+            instrument: bool = False, want_outputs: bool = False) -> dict:
     """Warm up, time ``args.steps`` steps of the resident state (barrier + synchronize on both sides, MAX over
-    ranks) ``args.repeats`` times, then - outside the timed region - the same number of steps with 16 dispatches
-    bracketed by HIP events on the launch stream (a bracketed dispatch costs ~8 us of queue time, so it is not part of
-    the timed run).  ``positions_too``: afterwards the same samples once more with every step's positions + quaternions
-    stored (config.save_every_1)."""
+    ranks) ``args.repeats`` times and copy the state out.  ``want_outputs``: that state (and with --save-every the last
+    saved frame) as host arrays under "outputs".  ``instrument``: then - outside the timed region - the same number of
+    steps with 16 dispatches bracketed by HIP events on the launch stream (a bracketed dispatch costs ~8 us of queue time,
+    so it is not part of the timed run).  ``positions_too``: afterwards the same samples once more with every step's
+    positions + quaternions stored (config.save_every_1)."""
     dtype = torch.float32 if dtype_name == "f32" else torch.float64
     kT = sim["kT"]
-    system = OxdnaSystem(2, top.seq, top.is_end, top.bonded_neighbors, box=None, dtype=dtype, device=dev)
-    system.set_params(flat)
-    integ = LangevinIntegrator(
-        system, dt=sim["dt"], kT=kT, gamma_t=kT / sim["diff_coef"], gamma_r=kT / sim["rot_diff_coef"],
-        mass=sim["nucleotide_mass"], inertia=sim["moment_of_inertia"], seed=seed,
-    )
-    integ.set_neighbor_policy(R_CUT, args.skin, args.rebuild_every)
+
+    def create():
+        system = OxdnaSystem(2, top.seq, top.is_end, top.bonded_neighbors, box=None, dtype=dtype, device=dev)
+        system.set_params(flat)
+        integ = LangevinIntegrator(
+            system, dt=sim["dt"], kT=kT, gamma_t=kT / sim["diff_coef"], gamma_r=kT / sim["rot_diff_coef"],
+            mass=sim["nucleotide_mass"], inertia=sim["moment_of_inertia"], seed=seed,
+        )
+        integ.set_neighbor_policy(R_CUT, args.skin, args.rebuild_every)
+        return system, integ
+
     c = torch.as_tensor(c0, dtype=dtype, device=dev).contiguous()
     q = torch.as_tensor(q0, dtype=dtype, device=dev).contiguous()
+
+    # ---- clock ramp (untimed, discarded): --min-warmup-ms of stepping on a system and integrator of its own.  Its length
+    #      follows the wall clock; the trajectory below starts from objects that never saw it (step counter, rebuild
+    #      schedule and count, list sizing), so that it is the same in every run with the same arguments
+    ramp = 0
+    if args.min_warmup_ms > 0:
+        r_system, r_integ = create()
+        r_integ.load(c, q, *r_integ.init_momenta())
+        t_w = time.perf_counter()
+        while (time.perf_counter() - t_w) * 1e3 < args.min_warmup_ms:
+            r_integ.advance(max(args.warmup, 100))
+            torch.cuda.synchronize(dev)
+            ramp += max(args.warmup, 100)
+        r_integ.close()
+        r_system.close()
+
+    system, integ = create()
     p, L = integ.init_momenta()
     integ.load(c, q, p, L)  # inputs resident in HBM, in the integrator's layout, before the clock starts
-
-    # ---- warm-up (untimed): W steps, and on until --min-warmup-ms of stepping have passed (clock ramp); it also
-    #      thermalises the ideal helix
-    t_w = time.perf_counter()
+    # ---- warm-up (untimed): W steps from the ideal helix.  The list is built at its first step and rebuilt every
+    #      --rebuild-every steps after: the rebuild phase is fixed, and the timed steps hold the scheduled rebuilds whose
+    #      turn falls among them (none when W + K < --rebuild-every)
     integ.advance(args.warmup)
     torch.cuda.synchronize(dev)
-    warm_done = args.warmup
-    while (time.perf_counter() - t_w) * 1e3 < args.min_warmup_ms:
-        integ.advance(max(args.warmup, 100))
-        torch.cuda.synchronize(dev)
-        warm_done += max(args.warmup, 100)
+    warm_done = ramp + args.warmup
 
     world = 1 if dist is None else dist.get_world_size()
+    repeats = max(1, args.repeats or 1)
 
     def timed(save_every: int, want_energy: bool):
-        """args.repeats samples of exactly args.steps steps -> (samples [s], scheduled rebuilds per sample, recoveries)"""
+        """``repeats`` samples of exactly args.steps steps -> (samples [s], scheduled rebuilds per sample, recoveries,
+        what the last sample's advance returned)"""
         samples, rebuilds, recoveries = [], [], 0
         # rows of saved states go into tensors allocated once, outside the clock (what is timed is the integrator's path;
         # a caller that wants fresh tensors per call pays torch's allocator, ~20 us per call, on top)
         n_save = args.steps // save_every if save_every > 0 else 0
         rows = ((torch.empty((n_save, top.n_nucleotides, 3), dtype=dtype, device=dev), torch.empty((n_save, top.n_nucleotides, 4), dtype=dtype, device=dev))
                 if n_save else None)
-        for _ in range(max(1, args.repeats)):
+        for _ in range(repeats):
             if dist is not None:
                 dist.barrier()
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
-            _, _, et = integ.advance(args.steps, save_every=save_every, want_energy=want_energy, out=rows)
+            last = integ.advance(args.steps, save_every=save_every, want_energy=want_energy, out=rows)
+            et = last[2]
             if dist is not None and et is not None:
                 # a run that saves energies (--save-every + --trace-energy) gathers them inside the timed region: per-replica
                 # trace, replica id = rank, ONE all-gather over RCCL / xGMI and no host read-back.  Otherwise a replica
@@ -371,44 +410,81 @@ def measure(args, dtype_name: str, top, c0, q0, sim, flat, dev, seed: int, dist=
             samples.append(elapsed)
             rebuilds.append(integ.last_rebuilds())
             recoveries += integ.last_recoveries()
-        return samples, rebuilds, recoveries
+        return samples, rebuilds, recoveries, last
 
     # ---- timed region
-    samples, rebuilds, recoveries = timed(args.save_every, args.trace_energy)
+    samples, rebuilds, recoveries, last = timed(args.save_every, args.trace_energy)
     total = sum(samples)
     order = sorted(range(len(samples)), key=lambda k: samples[k])
     mid = order[len(order) // 2]  # the median sample (the upper one of an even count)
 
+    # ---- what a caller of the timed path receives: the state after its last step (store closes that step's half kick)
+    integ.store(c, q, p, L)
+    torch.cuda.synchronize(dev)
+    assert torch.isfinite(c).all() and torch.isfinite(q).all(), "state diverged"
+    outputs = None
+    if want_outputs:
+        outputs = {"center": c, "quaternion": q, "momentum": p, "angular_momentum": L}
+        tc, tq, et = last
+        if tc is not None:
+            outputs.update(trajectory_center_last=tc[-1], trajectory_quaternion_last=tq[-1])
+        if et is not None:
+            outputs["energy_trace_last"] = et[-1]
+        outputs = {k: v.cpu().numpy() for k, v in outputs.items()}
+
     out_pos = None
     if positions_too and world == 1:
-        ps, _, _ = timed(1, False)
+        ps, _, _, _ = timed(1, False)
         word = 4 if dtype_name == "f32" else 8
         out_pos = {"steps_per_s": len(ps) * args.steps / sum(ps), "vs_no_output": (len(ps) * args.steps / sum(ps)) / (len(samples) * args.steps / total),
                    "bytes_written_per_step": 7 * word * top.n_nucleotides, "samples_ms": [1e3 * t for t in ps]}
 
-    # ---- instrumented pass (untimed): duration of the step kernel from HIP events attached to sampled dispatches on
-    #      the launch stream (rocprofv3's kernel trace of the same command, profiles/, is the cross-check)
-    integ.set_timing(16)
-    integ.advance(max(args.steps, args.instrument_steps))  # sampled dispatches far apart: a bracketed one disturbs the few behind it
-    timing = integ.last_kernel_ms()
-    integ.set_timing(0)
-    integ.store(c, q, p, L)
-    torch.cuda.synchronize(dev)
-    assert torch.isfinite(c).all() and torch.isfinite(q).all(), "state diverged"
+    timing = {"kernel_ms": None, "loop_ms_per_launch": None}
+    if instrument:
+        # ---- instrumented pass (untimed): duration of the step kernel from HIP events attached to sampled dispatches on
+        #      the launch stream (rocprofv3's kernel trace of the same command, profiles/, is the cross-check)
+        integ.set_timing(16)
+        integ.advance(max(args.steps, args.instrument_steps))  # sampled dispatches far apart: a bracketed one disturbs the few behind it
+        timing = integ.last_kernel_ms()
+        integ.set_timing(0)
+        integ.store(c, q, p, L)
+        torch.cuda.synchronize(dev)
+        assert torch.isfinite(c).all() and torch.isfinite(q).all(), "state diverged"
     mx, nbar = system.neighbor_stats()
     n = top.n_nucleotides
     alg = algorithmic_bytes_per_step(n, nbar, 4 if dtype_name == "f32" else 8)
     if args.save_every > 0:
         alg += 7 * (4 if dtype_name == "f32" else 8) * n / args.save_every  # trajectory output adds 7 s N / save_every
     kms = timing["kernel_ms"]
-    achieved = alg / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
+    achieved = None if kms is None else alg / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
     if out_pos is not None:
         out_pos["algorithmic_bytes_per_step"] = algorithmic_bytes_per_step(n, nbar, 4 if dtype_name == "f32" else 8) + out_pos["bytes_written_per_step"]
     return {"elapsed_mean": total / len(samples), "elapsed_median": samples[mid],
             "steps_per_s": world * len(samples) * args.steps / total, "steps_per_s_median": world * args.steps / samples[mid],
             "kernel_ms": kms, "loop_ms_per_launch": timing["loop_ms_per_launch"], "alg": alg, "achieved": achieved,
             "mean_row": nbar, "max_row": mx, "recoveries": recoveries, "samples_ms": [1e3 * t for t in samples],
-            "rebuilds": rebuilds, "rebuilds_total": sum(rebuilds), "warmup_steps_done": warm_done, "save_every_1": out_pos}
+            "rebuilds": rebuilds, "rebuilds_total": sum(rebuilds), "warmup_steps_done": warm_done, "save_every_1": out_pos,
+            "outputs": outputs}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, outputs: dict) -> None:
+    """``outputs`` as ``directory/<name>.npy``.  Over DUMP_LIMIT_BYTES in all, the per-nucleotide arrays are cut to a
+    fixed, seeded sample of nucleotides (the same rows of each; their indices in sample_index.npy)."""
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = outputs["center"].shape[0]
+        per_row = sum(a.nbytes for a in outputs.values() if a.ndim == 2 and a.shape[0] == n) / n
+        keep = int(0.9 * DUMP_LIMIT_BYTES / (per_row + 8))
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        outputs = {k: (a[idx] if a.ndim == 2 and a.shape[0] == n else a) for k, a in outputs.items()}
+        outputs["sample_index"] = idx.astype(np.float64)
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def _timed_region(args, m, m2) -> str:
@@ -750,12 +826,15 @@ def main():
     n = top.n_nucleotides
     flat = fp.pack_flat(fp.derive_flat(2, cfg, kt=kT, salt_conc=sim["salt_conc"], half_charged_ends=True), _lib.param_names())
 
-    extras = world == 1 and not args.no_secondary
-    m = measure(args, args.dtype, top, c0, q0, sim, flat, dev, rank, dist, md, positions_too=extras and args.save_every == 0)
+    extras = args.full and world == 1 and not args.no_secondary
+    m = measure(args, args.dtype, top, c0, q0, sim, flat, dev, rank, dist, md, positions_too=extras and args.save_every == 0,
+                instrument=args.full, want_outputs=args.dump_outputs is not None and rank == 0)
+    if m["outputs"] is not None:
+        dump_outputs(args.dump_outputs, m["outputs"])
     # the reference computes in fp64 (jax_enable_x64): the same measurement at that precision goes into the same line
     other = "f64" if args.dtype == "f32" else "f32"
-    m2 = (measure(args, other, top, c0, q0, sim, flat, dev, rank, dist, md, positions_too=extras and args.save_every == 0)
-          if not args.no_second_dtype else None)
+    m2 = (measure(args, other, top, c0, q0, sim, flat, dev, rank, dist, md, positions_too=extras and args.save_every == 0, instrument=True)
+          if args.full and not args.no_second_dtype else None)
 
     if rank == 0:
         out = {
@@ -787,13 +866,15 @@ def main():
                 "scheduled_rebuilds_per_sample": m["rebuilds"],
                 "warmup_steps_done": m["warmup_steps_done"],
                 "ms_per_step_median": 1e3 * m["elapsed_median"] / args.steps,
-                "precision": f"headline {args.dtype} (north_star: fp32 at 1e-3); the reference's fp64 is config.{other} and f64_steps_per_s",
+                "precision": (f"headline {args.dtype} (north_star: fp32 at 1e-3); the reference's fp64 is config.{other} and f64_steps_per_s"
+                              if m2 is not None else f"headline {args.dtype} (north_star: fp32 at 1e-3); the other precision: --full"),
+                "full": args.full,
             },
             # value = steps_per_s_mean: all repeats over their total time, list rebuilds included; the median sample beside it
             "steps_per_s_mean": m["steps_per_s"],
             "steps_per_s_median": m["steps_per_s_median"],
             "nproc": os.cpu_count(),
-            "roofline": {
+            "roofline": None if m["kernel_ms"] is None else {
                 "bound": "hbm",
                 "achieved": m["achieved"],
                 "peak": HBM_PEAK_GBS,
@@ -836,7 +917,7 @@ def main():
         cpu_steps = args.cpu_steps
         if cpu_steps < 0:
             cpu_steps = 60 if n > 8000 else 400  # capped at about 20 s of host work
-        if cpu_steps > 0 and world == 1:
+        if args.full and cpu_steps > 0 and world == 1:
             from mythos_amd.simulators.neighbors import verlet_pairs_numpy
 
             # two CPU numbers: the C++/OpenMP port (the value: the faster, fairer baseline) and, as in round 1, the

@@ -22,14 +22,14 @@ one() {  # name, "alg-bytes args", command...
   rm -rf $out/${name}_trace $out/${name}_pmc   # (gpurun_out/ travels back only while it is small)
   echo "[profiles] $name done"
 }
-short="--steps 500 --warmup 100 --cpu-steps 0 --no-second-dtype --no-secondary --repeats 1 --min-warmup-ms 0"
+short="--full --steps 500 --warmup 100 --cpu-steps 0 --no-second-dtype --no-secondary --repeats 1 --min-warmup-ms 0"
 # algorithmic bytes per launch: n (2 * 14 * s + 13 + 4 * nbar), nbar = 24.61 at skin 0.9 (bench.py prints it)
 if [ "$part" != rest ]; then
 one md_12kbp_f32 "--alg-bytes md_step_kernel<float=5362560" python bench.py $short
 one md_12kbp_f64 "--alg-bytes md_step_kernel<double=8050560" python bench.py $short --dtype f64
 # the reference's run: every step's positions + quaternions stored by the plain instantiation (+ 7 s N bytes per launch)
 one md_12kbp_f32_traj "--alg-bytes md_step_kernel<float=6034560" python bench.py $short --save-every 1
-one md_100kbp_f32 "" python bench.py --bp 100000 --steps 150 --warmup 30 --cpu-steps 0 --no-second-dtype --no-secondary --repeats 1 --min-warmup-ms 0
+one md_100kbp_f32 "" python bench.py --full --bp 100000 --steps 150 --warmup 30 --cpu-steps 0 --no-second-dtype --no-secondary --repeats 1 --min-warmup-ms 0
 one md_rna2 "" python scripts/bench_rna2.py 500
 one md_na1 "" python scripts/bench_na1.py
 fi
@@ -40,8 +40,8 @@ one martini_md "" python bench.py --workload martini-bilayer --steps 500 --warmu
 one energy_difftre "" python scripts/bench_energy.py --difftre
 one energy_difftre_obs "" python scripts/bench_energy.py --obs
 one observables "" python scripts/bench_observables.py
-# the headline kernel: trace of the DEFAULT bench command (what the driver's number comes from) + HBM traffic passes
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --cpu-steps 0 --no-secondary > $out/bench_profiled.log 2>&1
+# the headline kernel: trace of the bench command with every measurement of its line (--full) + HBM traffic passes
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --full --cpu-steps 0 --no-secondary > $out/bench_profiled.log 2>&1
 cp "$(find $out/stats -name '*kernel_stats.csv' | head -n 1)" $out/profiles/${tag}_bench_kernel_stats.csv
 grep '^{' $out/bench_profiled.log | tail -n 1 > $out/profiles/${tag}_bench_profiled_line.json || true
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python bench.py $short > $out/pmc_fetch.log 2>&1

@@ -8,7 +8,7 @@ for lib in $1 $2 $1 $2; do
   echo "== $lib" >> $out
   for bp in 12000 100000; do
     steps=2000; [ $bp = 100000 ] && steps=300
-    MYTHOS_HIP_LIB=$lib python bench.py --bp $bp --steps $steps --warmup 100 --cpu-steps 0 --no-second-dtype --repeats 3 2>/dev/null | tail -n 1 | python -c "
+    MYTHOS_HIP_LIB=$lib python bench.py --full --bp $bp --steps $steps --warmup 100 --cpu-steps 0 --no-second-dtype --repeats 3 2>/dev/null | tail -n 1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$bp f32 steps/s', round(d['value']), 'kernel_us', round(d['roofline']['kernel_ms']*1e3,2), 'recoveries', d['config'].get('neighbor_list',{}).get('out_of_turn_rebuilds'))" >> $out 2>&1
   done
 done

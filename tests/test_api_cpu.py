@@ -312,6 +312,40 @@ def test_bench_strings_fit_the_drivers_parsed_record():
         assert f"= {launches} launches" in txt and f"+ {n * (steps // 50)} list rebuilds" in txt
 
 
+def test_bench_dump_outputs_keeps_under_its_limit(tmp_path):
+    """bench.py --dump-outputs: arrays as <name>.npy, unchanged while they fit; past the limit the same seeded sample of
+    nucleotides from every per-nucleotide array, its indices beside them, and arrays of other shapes whole."""
+    import importlib.util
+    from pathlib import Path
+
+    spec = importlib.util.spec_from_file_location("bench_module", Path(__file__).resolve().parent.parent / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    small = {"center": rng.standard_normal((50, 3)).astype(np.float32), "energy_trace_last": rng.standard_normal(10)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for k, a in small.items():
+        b = np.load(tmp_path / "small" / f"{k}.npy")
+        assert b.dtype == a.dtype and np.array_equal(a, b)
+    assert not (tmp_path / "small" / "sample_index.npy").exists()
+
+    n = 1_000_000
+    big = {"center": np.arange(3 * n, dtype=np.float64).reshape(n, 3), "quaternion": np.arange(4 * n, dtype=np.float64).reshape(n, 4),
+           "momentum": np.ones((n, 3)), "angular_momentum": np.ones((n, 3)), "energy_trace_last": np.arange(10.0)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= bench.DUMP_LIMIT_BYTES
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and idx[-1] < n
+    rows = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "center.npy"), big["center"][rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "quaternion.npy"), big["quaternion"][rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "energy_trace_last.npy"), big["energy_trace_last"])
+    for f in files:  # the same sample from run to run
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+
+
 def test_units_as_the_reference_defines_them():
     """mythos_amd.utils.units mirrors mythos/utils/units.py:5-38; the defaults of the package are at its 296.15 K."""
     from mythos_amd.input import defaults

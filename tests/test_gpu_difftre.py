@@ -171,7 +171,7 @@ def test_bench_with_two_ranks_prints_one_line_of_the_contract():
 
     root = Path(__file__).resolve().parent.parent
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--bp", "300", "--steps", "20",
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--gpus", "2", "--rehearse-on-one-gpu", "--bp", "300", "--steps", "20",
                         "--warmup", "5", "--cpu-steps", "0", "--repeats", "3"], capture_output=True, text=True, env=env, timeout=900,
                        cwd=root, check=False)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -190,6 +190,69 @@ def test_bench_with_two_ranks_prints_one_line_of_the_contract():
     assert "rehearsal" in d["config"] and d["f64_steps_per_s"] > 0 and "f64" in d["config"]["timed_region"]
     for text in (d["config"]["workload"], d["config"]["timed_region"], d["metric"]):
         assert len(text) <= 120, text
+
+
+def test_plain_bench_times_its_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    """`python bench.py` without --full: one sample of exactly --steps steps, no measurement beside the headline, and
+    --dump-outputs writes the state after the last timed step: bitwise what one LangevinIntegrator.run of W + K steps
+    from the same duplex, seed and list policy hands back (advance(a); advance(b) is advance(a + b), store closes the
+    frame), from two processes whose clock ramps before the warm-up differ in length."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    from mythos_amd import _lib
+    from mythos_amd.energy import flat_params as fp
+    from mythos_amd.hip_system import LangevinIntegrator, OxdnaSystem
+    from mythos_amd.input import defaults
+    from mythos_amd.utils import generators
+
+    root = Path(__file__).resolve().parent.parent
+    lines = []
+    for d, ramp_ms in (("a", "30"), ("b", "400")):
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--bp", "300", "--steps", "60", "--warmup", "10",
+                            "--min-warmup-ms", ramp_ms, "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=600, cwd=root, check=False)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines.append([json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")])
+    for ln in lines:
+        assert len(ln) == 1
+        d = ln[0]
+        assert d["steps"] == 60 and d["warmup"] == 10 and d["dtype"] == "f32" and d["unit"] == "steps/s" and d["higher_is_better"] is True
+        assert len(d["config"]["samples_ms"]) == 1 and d["config"]["full"] is False
+        assert d["ms_per_step"] == pytest.approx(d["config"]["samples_ms"][0] / 60) and d["value"] == pytest.approx(1e3 / d["ms_per_step"])
+        assert d["roofline"] is None and d["cpu_baseline"] is None and "secondary" not in d and "f64_steps_per_s" not in d
+        assert "save_every_1" not in d["config"] and "f64" not in d["config"]
+    assert lines[0][0]["config"]["warmup_steps_done"] < lines[1][0]["config"]["warmup_steps_done"]  # the ramps differ
+
+    # the reference: the same system stepped W + K = 70 steps in one run (bench.py's defaults: dt 0.005, seed = rank 0,
+    # skin 0.9, rebuild every 50, oxDNA2 with salt 0.5 and half-charged ends)
+    sim, cfg = defaults.default_configs_for("dna2")
+    kT = sim["kT"]
+    top, c0, q0 = generators.ideal_duplex(300, model=2, seed=1234)
+    flat = fp.pack_flat(fp.derive_flat(2, cfg, kt=kT, salt_conc=sim["salt_conc"], half_charged_ends=True), _lib.param_names())
+    s = OxdnaSystem(2, top.seq, top.is_end, top.bonded_neighbors, box=None, dtype=torch.float32, device="cuda:0")
+    s.set_params(flat)
+    integ = LangevinIntegrator(s, dt=0.005, kT=kT, gamma_t=kT / sim["diff_coef"], gamma_r=kT / sim["rot_diff_coef"],
+                               mass=sim["nucleotide_mass"], inertia=sim["moment_of_inertia"], seed=0)
+    integ.set_neighbor_policy(3.25, 0.9, 50)
+    c = torch.as_tensor(c0, dtype=torch.float32, device="cuda:0").contiguous()
+    q = torch.as_tensor(q0, dtype=torch.float32, device="cuda:0").contiguous()
+    p, ang = integ.init_momenta()
+    integ.run(c, q, p, ang, 70)
+    ref = {"center": c, "quaternion": q, "momentum": p, "angular_momentum": ang}
+    assert not np.array_equal(c.cpu().numpy(), c0.astype(np.float32))
+
+    assert {f.stem for f in (tmp_path / "a").glob("*.npy")} == set(ref)
+    for name, want in ref.items():
+        want = want.cpu().numpy()
+        for d in ("a", "b"):
+            got = np.load(tmp_path / d / f"{name}.npy")
+            assert got.dtype == np.float32 and got.shape == want.shape and np.isfinite(got).all()
+            np.testing.assert_array_equal(got, want, err_msg=f"{d}/{name}")
+    integ.close()
+    s.close()
 
 
 def test_the_collectives_run_through_rccl_on_this_gpu():
