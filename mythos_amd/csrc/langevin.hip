@@ -26,20 +26,12 @@ mythos_sim_t* mythos_langevin_create(mythos_system_t* sys, double dt, double kT,
   for (int k = 0; k < 3; ++k) s->inertia[k] = inertia ? inertia[k] : 1.0;
   s->seed = seed;
   const size_t v4 = (sys->dtype == MYTHOS_F32 ? sizeof(float4) : sizeof(double4)) * (size_t)sys->n;
-  s->epart_blocks = (sys->n + kMdPPB - 1) / kMdPPB;
-  bool ok = true;
+  bool ok = md_run_create(*s);
   for (int k = 0; k < 2; ++k)
     for (int a = 0; a < mythos_sim::kFrameArrays; ++a) ok = ok && hipMalloc(&s->frame[k][a], v4) == hipSuccess;
   ok = ok && hipMalloc(&s->keep_hi, v4) == hipSuccess && hipMalloc(&s->keep_lo, v4) == hipSuccess;
-  ok = ok && hipMalloc((void**)&s->d_flags, mythos_sim::kCtlWords * sizeof(int)) == hipSuccess &&
-       hipMalloc((void**)&s->d_epart, (size_t)s->epart_blocks * 64 * sizeof(double)) == hipSuccess &&
-       hipEventCreate(&s->ev0) == hipSuccess && hipEventCreate(&s->ev1) == hipSuccess &&
-       hipHostMalloc((void**)&s->h_ctl, 8 * sizeof(int), hipHostMallocDefault) == hipSuccess &&
-       hipHostGetDevicePointer((void**)&s->d_ctl, s->h_ctl, 0) == hipSuccess &&
-       hipMemset(s->d_flags, 0, mythos_sim::kCtlWords * sizeof(int)) == hipSuccess;
-  if (ok) std::fill(s->h_ctl, s->h_ctl + 8, 0);
-  for (int k = 0; ok && k < mythos_sim::kMaxSamples; ++k)
-    ok = hipEventCreate(&s->sa[k]) == hipSuccess && hipEventCreate(&s->sb[k]) == hipSuccess;
+  // (one row of partials per workgroup of the narrowest launch: 16 lanes per nucleotide)
+  ok = ok && hipMalloc((void**)&s->d_epart, (size_t)((sys->n + 15) / 16) * kTraceWidth * sizeof(double)) == hipSuccess;
   if (ok && !sys->d_ref_pos) ok = hipMalloc(&sys->d_ref_pos, v4) == hipSuccess;
   if (ok && !sys->d_ref_off) ok = hipMalloc(&sys->d_ref_off, v4) == hipSuccess;
   if (ok && !sys->d_ref_a1) ok = hipMalloc(&sys->d_ref_a1, v4) == hipSuccess;
@@ -60,17 +52,10 @@ void mythos_langevin_destroy(mythos_sim_t* s) {
     if (u) (void)hipFree(u);
   if (s->keep_hi) (void)hipFree(s->keep_hi);
   if (s->keep_lo) (void)hipFree(s->keep_lo);
-  if (s->d_flags) (void)hipFree(s->d_flags);
   if (s->d_chunk_order) (void)hipFree(s->d_chunk_order);
   if (s->d_chunk_keys) (void)hipFree(s->d_chunk_keys);
-  if (s->h_ctl) (void)hipHostFree(s->h_ctl);
   if (s->d_epart) (void)hipFree(s->d_epart);
-  if (s->ev0) (void)hipEventDestroy(s->ev0);
-  if (s->ev1) (void)hipEventDestroy(s->ev1);
-  for (int k = 0; k < mythos_sim::kMaxSamples; ++k) {
-    if (s->sa[k]) (void)hipEventDestroy(s->sa[k]);
-    if (s->sb[k]) (void)hipEventDestroy(s->sb[k]);
-  }
+  md_run_destroy(*s);
   delete s;
 }
 
@@ -216,7 +201,7 @@ int mythos_langevin_store(mythos_sim_t* s, void* center, void* quat, void* p_lin
   return md_store(s, center, quat, p_lin, p_ang, (hipStream_t)stream);
 }
 
-int64_t mythos_langevin_get_step(const mythos_sim_t* s) { return s ? s->step : -1; }
+int64_t mythos_langevin_get_step(const mythos_sim_t* s) { return md_get_step(s); }
 
 int mythos_langevin_set_step(mythos_sim_t* s, int64_t step) {
   if (!s || step < 0) {
@@ -238,33 +223,15 @@ int mythos_langevin_set_seed(mythos_sim_t* s, uint64_t seed) {
 
 int mythos_langevin_last_kernel_ms(const mythos_sim_t* s, double* kernel_ms, double* loop_ms_per_launch,
                                    int* launches, int* samples) {
-  if (!s) {
-    set_error("mythos_langevin_last_kernel_ms: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  if (kernel_ms) *kernel_ms = s->last_kernel_ms;
-  if (loop_ms_per_launch) *loop_ms_per_launch = s->last_avg_ms;
-  if (launches) *launches = s->last_launches;
-  if (samples) *samples = s->last_samples;
-  return MYTHOS_OK;
+  return md_last_kernel_ms(s, kernel_ms, loop_ms_per_launch, launches, samples, "mythos_langevin_last_kernel_ms");
 }
 
 int mythos_langevin_last_recoveries(const mythos_sim_t* s, int* recoveries) {
-  if (!s || !recoveries) {
-    set_error("mythos_langevin_last_recoveries: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  *recoveries = s->last_recoveries;
-  return MYTHOS_OK;
+  return md_last_count(s, &MdRun::last_recoveries, recoveries, "mythos_langevin_last_recoveries");
 }
 
 int mythos_langevin_last_rebuilds(const mythos_sim_t* s, int* scheduled) {
-  if (!s || !scheduled) {
-    set_error("mythos_langevin_last_rebuilds: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  *scheduled = s->last_rebuilds;
-  return MYTHOS_OK;
+  return md_last_count(s, &MdRun::last_rebuilds, scheduled, "mythos_langevin_last_rebuilds");
 }
 
 int mythos_langevin_set_option(mythos_sim_t* s, int option, int64_t value) {
@@ -280,13 +247,6 @@ int mythos_langevin_set_option(mythos_sim_t* s, int option, int64_t value) {
   return MYTHOS_OK;
 }
 
-int mythos_langevin_set_timing(mythos_sim_t* s, int samples) {
-  if (!s || samples < 0) {
-    set_error("mythos_langevin_set_timing: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  s->timing_samples = std::min(samples, (int)mythos_sim::kMaxSamples);
-  return MYTHOS_OK;
-}
+int mythos_langevin_set_timing(mythos_sim_t* s, int samples) { return md_set_timing(s, samples, "mythos_langevin_set_timing"); }
 
 }  // extern "C"

@@ -27,8 +27,6 @@
 // L2 / Infinity-Cache resident, the kernel is bound by VALU issue and latency, not by bytes.
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include <hip/hip_ext.h>
@@ -43,6 +41,7 @@
 #endif
 
 #include "chunk_order.h"
+#include "md_driver.h"
 #include "oxdna_gather.h"
 #include "philox.h"
 
@@ -123,11 +122,10 @@ __device__ __forceinline__ void free_rotor(R* q, R* L, R h, const R* inv_I) {
 }
 
 template <typename R>
-__device__ __forceinline__ void drift(R* x, R* q, const R* p, R* L, R h, const LangevinConst<R>& K, bool rotate = true) {
+__device__ __forceinline__ void drift(R* x, R* q, const R* p, R* L, R h, const LangevinConst<R>& K) {
   x[0] += h * p[0] * K.inv_mass;
   x[1] += h * p[1] * K.inv_mass;
   x[2] += h * p[2] * K.inv_mass;
-  if (!rotate) return;
   free_rotor<2>(q, L, R(0.5) * h, K.inv_inertia);
   free_rotor<1>(q, L, R(0.5) * h, K.inv_inertia);
   free_rotor<0>(q, L, h, K.inv_inertia);
@@ -241,43 +239,11 @@ __device__ __forceinline__ R f3_radial(R eps, R tw, const F3P<R>& fp, V3<R> d, R
   return v.f;
 }
 
-// Diagnostics are compiled in only with -DMYTHOS_MD_DIAG (make DIAG=1): in the product build no stamp executes and
-// the ablation word is a compile-time zero.
-#ifdef MYTHOS_MD_DIAG
-// Diagnostic stamps (ablate bit 7): lane 0 of every wavefront records s_memtime (bit 8: the 100 MHz
-// s_memrealtime instead) at the phase boundaries
-// into the (otherwise unused) energy scratch; no output value depends on them.
-// (bit 9: slots 5 and 6 carry, instead of time stamps, the length of the wavefront's angular work list and where it ran -
-// XCC_ID << 32 | HW_ID, i.e. XCD, shader engine, CU, SIMD - for scripts/stamps_where.py)
-#define MD_STAMP_SLOT(k) \
-  reinterpret_cast<unsigned long long*>(e_part)[(((step & 1) * n_blocks + (size_t)bid) * 4 + (threadIdx.x >> 6)) * 8 + (k)]
-#define MD_STAMP(k)                                                                                   \
-  do {                                                                                                \
-    if ((ablate & 128) && (threadIdx.x & 63) == 0 && !((ablate & 512) && ((k) == 5 || (k) == 6)))      \
-      MD_STAMP_SLOT(k) = (ablate & 256) ? __builtin_amdgcn_s_memrealtime() : __builtin_readcyclecounter(); \
-  } while (0)
-#define MD_STAMP_VAL(k, v)                                                          \
-  do {                                                                              \
-    if ((ablate & 128) && (ablate & 512) && (threadIdx.x & 63) == 0) MD_STAMP_SLOT(k) = (unsigned long long)(v); \
-  } while (0)
-__device__ __forceinline__ unsigned long long md_where() {
-  unsigned int hw, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  return ((unsigned long long)xcc << 32) | hw;
-}
-#define MD_ABLATE(x) (x)
-#else
-#define MD_STAMP(k) do { } while (0)
-#define MD_STAMP_VAL(k, v) do { } while (0)
-#define MD_ABLATE(x) 0
-#endif
-
 // Wave priority by phase: the further a wavefront is from the end of the kernel, the higher its s_setprio level.
 // The SIMD's arbiter serves the older wavefront first, so of the three workgroups that share a CU the first to arrive
 // ran ahead (done after 9.2 us) and the last one finished alone, with one wavefront per SIMD and nothing to hide its
-// latencies behind (11.7 us; scripts/stamps_where.py).  With the priority tied to progress the workgroup that lags
-// wins the arbitration, the three advance together and the CU is busy to the end: 12 kbp 65.8 k -> 69.3 k steps/s,
+// latencies behind (11.7 us; cycle stamps of a diagnostic build, since removed).  With the priority tied to progress the
+// workgroup that lags wins the arbitration, the three advance together and the CU is busy to the end: 12 kbp 65.8 k -> 69.3 k steps/s,
 // 256 replicas 68.0 k -> 72.1 k, 100 kbp 12.8 k -> 13.0 k.  Five decimal digits = the level of the phases radial-close,
 // radial-far, angular, fold, integrate; 33210 against its neighbours on one box: 32210 69.1 k (100 kbp 12.7 k),
 // 33200 / 32100 / 33100 / 33211 67.3 - 67.5 k, the reverse order 65.8 k (= none); the wavefront with the short angular
@@ -435,9 +401,10 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     const typename Vec4T<R>::type* __restrict__ ref_off, const typename Vec4T<R>::type* __restrict__ ref_a1,
     int* __restrict__ flags,
     R* __restrict__ traj_c, R* __restrict__ traj_q, double* __restrict__ e_part, const int* __restrict__ chunk_order,
-    const int* __restrict__ list_overflow, int k_index, int ablate_arg, int prio_on, const PseqView<R> pseq) {
+    const int* __restrict__ list_overflow, int k_index, int /* unused */, int prio_on, const PseqView<R> pseq) {
+  // (the unused word keeps the kernel-argument layout the register allocation of these kernels was measured with:
+  // without it prio_on and pseq move up and the fp32 12 kbp kernel spills its scalars differently, 1 % slower)
   using V4 = typename Vec4T<R>::type;
-  const int ablate = MD_ABLATE(ablate_arg);
   constexpr int G = GL, PPB = kMdBlock / GL;
   static_assert(GL == 8 || GL == 16, "lanes per nucleotide");
   static_assert(!DENSE || GL == kMdG, "DENSE serves large grids");
@@ -536,7 +503,7 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     }
   }
   const int* __restrict__ row = rows + (size_t)ii * row_stride;
-  const int len = (valid && !(ablate & 1)) ? row_len[ii] : 0;
+  const int len = valid ? row_len[ii] : 0;
   const int close_end = min(len, row_close[ii]);  // [2, close_end): any term may act; [close_end, len): backbone only
 
   R e[T_COUNT];
@@ -544,7 +511,6 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   for (int k = 0; k < T_COUNT; ++k) e[k] = R(0);
   V3<R> gbk{R(0), R(0), R(0)}, gba{R(0), R(0), R(0)};  // sum of dV/dd acting on self's backbone / base site
 
-  MD_STAMP(0);
   MD_PRIO(0);
   // ---- phase 1: radial pass over the unbonded slots
   const RadSet<R> rs0 = (MODEL == 4) ? radset_from<R, 2>(P, cut_from<R>(P, cut.rcom2)) : radset_from<R, MODEL>(P, cut);
@@ -762,9 +728,7 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     for (int t = 0; t < 2; ++t) item_cnt[t][grp] = valid ? n_items[t] : 0;
   }
   if (threadIdx.x == 0) s_halt = halt_word;
-  MD_STAMP(1);
   __syncthreads();  // self_lds, rad_lds and item_cnt are visible
-  MD_STAMP(2);
   MD_PRIO(2);
   if (s_halt != 0) return;  // halted: nothing has been written to global memory yet
   if (vb == 0 && threadIdx.x == 0) flags[2] = k_index + 1;
@@ -812,8 +776,6 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     const bool pool_over = kPooled && row_base[kPooled ? pw : 0][PPB] > kPool;
     if (pool_over && threadIdx.x == 0) atomicMax(flags + 3, k_index + 1);
     const int n_list = pool_over ? 0 : item_pre[pw][PPB];
-    MD_STAMP_VAL(5, n_list);
-    MD_STAMP_VAL(6, md_where());
     const int half = (n_list + 1) >> 1;
     const int q_lo = wave == 2 ? half : 0;                      // this wavefront's slice [q_lo, q_hi) of the list
     const int q_hi = wave == 1 ? half : n_list;
@@ -821,8 +783,8 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     const int n_sweeps = (n_total + 63) / 64;
     // bonded wave: one sweep over slots 0 / 1 of the 32 nucleotides, and a second over slots 2 / 3 only in
     // systems with circular strands (a ring's two ends carry a second bond in one role)
-    const int my_sweeps = bonded_wave ? (((ablate & 16) || pool_over) ? 0 : (extra_bonds ? 2 : 1)) : ((ablate & 8) ? 0 : n_sweeps);
-    for (int sweep = 0; sweep < ((ablate & 2) ? 0 : my_sweeps); ++sweep) {
+    const int my_sweeps = bonded_wave ? (pool_over ? 0 : (extra_bonds ? 2 : 1)) : n_sweeps;
+    for (int sweep = 0; sweep < my_sweeps; ++sweep) {
       int p, idx, sl;
       bool active;
       if (bonded_wave) {
@@ -914,16 +876,14 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   if (integrates) {
     pm = in.mom[i_int], lm = in.ang[i_int], qv = in.q[i_int];
     if (do_step && K.skin_half_sq > R(0)) r0 = ref_pos[i_int], f0 = ref_off[i_int], a0 = ref_a1[i_int];
-    if (do_step && !MD_ABLATE(ablate & (4 | 32))) normals6(seed, (uint32_t)i_int, step, 0u, z);
+    if (do_step) normals6(seed, (uint32_t)i_int, step, 0u, z);
 #pragma unroll
     for (int k = 0; k < 6; ++k) md_pin(z[k]);
     md_pin(pm.x), md_pin(pm.y), md_pin(pm.z);
     md_pin(lm.x), md_pin(lm.y), md_pin(lm.z);
     md_pin(qv.x), md_pin(qv.y), md_pin(qv.z), md_pin(qv.w);
   }
-  MD_STAMP(3);
   __syncthreads();
-  MD_STAMP(4);
   MD_PRIO(3);
 
   // ---- fold: each group gathers its owner's result rows (one per lane), adds the radial-pass
@@ -992,9 +952,7 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     fr[0] = -sg.dc.x, fr[1] = -sg.dc.y, fr[2] = -sg.dc.z;
     fr[3] = dot(own.a1, tl), fr[4] = dot(own.a2, tl), fr[5] = dot(own.a3, tl);
   }
-  MD_STAMP(5);
   __syncthreads();
-  MD_STAMP(6);
   MD_PRIO(4);
   double ke_t = 0.0, ke_r = 0.0;
   if (integrates) {
@@ -1048,21 +1006,21 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     // kept both in scratch memory in the oxNA instantiations)
     const bool bk3 = MODEL == 3 || int_rna;
     V3<R> nbk{bk3 ? n3.x : n2.x, bk3 ? n3.y : n2.y, bk3 ? n3.z : n2.z};
-    if (do_step && !(ablate & 4)) {
+    if (do_step) {
       p[0] += K.half_dt * F.x;
       p[1] += K.half_dt * F.y;
       p[2] += K.half_dt * F.z;
       L[0] += K.half_dt * tb[0];
       L[1] += K.half_dt * tb[1];
       L[2] += K.half_dt * tb[2];
-      drift(xd, qs, p, L, K.half_dt, K, !(ablate & 64));
+      drift(xd, qs, p, L, K.half_dt, K);
       p[0] = K.c1_t * p[0] + K.c2_t * z[0];
       p[1] = K.c1_t * p[1] + K.c2_t * z[1];
       p[2] = K.c1_t * p[2] + K.c2_t * z[2];
       L[0] = K.c1_r * L[0] + K.c2_r[0] * z[3];
       L[1] = K.c1_r * L[1] + K.c2_r[1] * z[4];
       L[2] = K.c1_r * L[2] + K.c2_r[2] * z[5];
-      drift(xd, qs, p, L, K.half_dt, K, !(ablate & 64));
+      drift(xd, qs, p, L, K.half_dt, K);
       if constexpr (kHiLo<R>) {
         // centre += displacement in (hi, lo) form: the displacement goes to the low part, then one fast two-sum
         // re-normalises (|hi| >= |lo + d| always holds here)
@@ -1120,7 +1078,6 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     out.mom[i] = V4{p[0], p[1], p[2], R(0)};
     out.ang[i] = V4{L[0], L[1], L[2], R(0)};
   }
-  MD_STAMP(7);
   if constexpr (SAVE) {
     if (lane == 0) {
 #pragma unroll
@@ -1136,24 +1093,6 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
       for (int g = 0; g < PPB; ++g) s += e_lds[g][threadIdx.x];
       e_part[(size_t)bid * kTraceWidth + threadIdx.x] = s;
     }
-  }
-}
-
-// 256 threads = 16 columns (10 used) x 16 groups of workgroup partials, the group sums added in a fixed order (one thread
-// per column was a chain of n_blocks dependent loads: 110 us per saved step at 12 kbp)
-static __global__ __launch_bounds__(256) void reduce_trace_kernel(const double* __restrict__ part, int n_blocks, double* __restrict__ out) {
-  __shared__ double acc[16][17];
-  const int k = threadIdx.x & 15, g = threadIdx.x >> 4;
-  double s = 0.0;
-  if (k < kTraceWidth)
-    for (int b = g; b < n_blocks; b += 16) s += part[(size_t)b * kTraceWidth + k];
-  acc[g][k] = s;
-  __syncthreads();
-  if (g == 0 && k < kTraceWidth && out) {
-    double t = 0.0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) t += acc[j][k];
-    out[k] = t;
   }
 }
 
@@ -1266,72 +1205,35 @@ __global__ void init_momenta_kernel(int n, R sd_t, R sd_r0, R sd_r1, R sd_r2, ui
 
 using namespace mythos;
 
-struct mythos_sim {
+struct mythos_sim : mythos::MdRun {
   mythos_system* sys = nullptr;
   double dt = 0, kT = 0, gamma_t = 0, gamma_r = 0, mass = 1, inertia[3] = {1, 1, 1};
-  uint64_t seed = 0;
-  int64_t step = 0;
-  // neighbour policy
+  // neighbour policy (MdRun::rebuild_every: 0 = the system's static rows)
   double r_cut = 0, skin = 0;
-  int rebuild_every = 0;
   // device state: two ping-pong frames of 8 vec4 arrays each (p0, p1, p2, p3, q, pl, mom, ang)
   static constexpr int kFrameArrays = 8;
   void* frame[2][kFrameArrays] = {};
-  int cur = 0;             // the frame that holds the current state
-  bool resident = false;   // the frames hold a state (mythos_langevin_load, or the last run)
-  bool list_valid = false; // the rows were built from this state's history and the rebuild schedule continues
-  bool open = false;       // the frame holds x_n and momenta short of the closing half kick of step n (advance_typed)
-  int since_build = 0;     // steps taken since the rows were built
   int builds = 0;          // scheduled rebuilds so far (the chunk order is refreshed every 64th)
   int list_epoch = 0;      // sys->list_epoch the rows in use belong to
   // centres as the last run handed them out (hi) and the low parts that went with them (fp32 systems)
   void *keep_hi = nullptr, *keep_lo = nullptr;
   bool keep_valid = false;
-  static constexpr int kCtlWords = 4;  // [0] error bits (2 NaN), [1] halt, [2] progress, [3] aborted launch + 1
   bool items_big = false;              // the ITEMS = 32 instantiation is in use (a launch of this load found 16 too few)
   bool want_unfused = false;           // mythos_langevin_set_option(MYTHOS_LANGEVIN_UNFUSED): takes effect at the next load
   bool unfused = false;                // the resident state lives in the unfused path's buffers (decided by load)
   int param_epoch = 0;                 // sys->param_epoch the packed site offsets of the resident frames were derived from
-  int* d_flags = nullptr;
-  // control words as the device published them at the end of a segment: [0..3] d_flags, [4..6] the list builder's
-  // overflow words.  Pinned host memory the publishing kernel writes directly: one stream synchronisation per
-  // segment and no copy commands.
-  int* h_ctl = nullptr;
-  int* d_ctl = nullptr;          // device address of h_ctl
-  int last_recoveries = 0;       // halts of the last run that were rebuilt and resumed
-  int last_rebuilds = 0;         // scheduled list rebuilds inside the last advance (the first build of a list not counted)
-  bool list_fitted = false;      // a synchronising, growing build has sized rows and buckets for this integrator
   int lanes = kMdG;              // lanes per nucleotide of the step launches of this load (8, or 16 for small systems: md_lanes_for)
   int chunk_cap = 0;             // chunks d_chunk_order / d_chunk_keys have room for
   int* d_chunk_order = nullptr;  // [blocks] spatial order of the workgroups' chunks of nucleotides (null: index order)
   unsigned long long* d_chunk_keys = nullptr;
-  double* d_epart = nullptr;
-  int epart_blocks = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // sampled per-launch timing: every kSampleStride-th step launch is bracketed by its own event pair
-  static constexpr int kMaxSamples = 16;
-  int timing_samples = 0;  // dispatches per run timed with their own event pair (set_timing; ~8 us each)
-  hipEvent_t sa[kMaxSamples] = {}, sb[kMaxSamples] = {};
+  double* d_epart = nullptr;     // [blocks][kTraceWidth] energy-trace partials of a saving launch
   // oxNA (model 4), unfused path: packed state + gradients of the energy kernel + list reference (see unfused_*)
   void *u_c = nullptr, *u_q = nullptr, *u_p = nullptr, *u_l = nullptr, *u_gc = nullptr, *u_gq = nullptr, *u_ref = nullptr;
   double* u_e = nullptr;  // [8] term energies of the last force evaluation + [2] kinetic energies
   bool u_forces_valid = false;
-  double last_avg_ms = 0;     // (ev1 - ev0) / launches: includes rebuilds and inter-kernel gaps
-  double last_kernel_ms = 0;  // mean over the sampled single-launch intervals
-  int last_launches = 0;
-  int last_samples = 0;
 };
 
 namespace mythos {
-
-// End of a segment: hand the control words to the host (pinned memory) and clear the ones a later segment starts
-// from, so that neither a copy command nor a memset sits between two runs.
-static __global__ void publish_ctl_kernel(int* __restrict__ flags, int* __restrict__ overflow, int* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  out[0] = flags[0], out[1] = flags[1], out[2] = flags[2], out[3] = flags[3];
-  out[4] = overflow ? overflow[0] : 0, out[5] = overflow ? overflow[1] : 0, out[6] = overflow ? overflow[2] : 0;
-  flags[0] = 0, flags[2] = 0;  // the halt word stays until the host has recovered (later launches must see it)
-}
 
 template <typename R>
 static LangevinConst<R> make_const(const mythos_sim* s) {
@@ -1452,17 +1354,13 @@ static int unpack_typed(mythos_sim* sim, R* center, R* quat, R* p_lin, R* p_ang,
   return 0;
 }
 
-// n_steps on the resident state and ONE stream synchronisation per segment of kSegment launches - the host has to see
-// the halt word before it can say the steps were taken.  Nothing else is between two calls: the list and its rebuild
-// schedule carry over, the control words are published and cleared by a one-thread kernel, events are recorded only
-// when timing was asked for.
-// Launch k evaluates the forces at x_k, closes step k - 1 with them (the second half kick) and takes step k up to its
-// first half kick and drift.  close = true: n_steps + 1 launches, the last one only closes (momenta p_n in the frame).
-// close = false (mythos_langevin_advance): n_steps launches; the frame is left OPEN - x_n with momenta short of their
-// closing half kick, sim->open - and whoever comes next supplies it with the force evaluation it needs anyway: the next
-// advance in its first launch (which is then the same launch as launch n of one longer call: advance(a); advance(b) is
-// advance(a + b) launch for launch), mythos_langevin_store through a zero-step closing call.  A call whose last step
-// saves a trace row evaluates at x_n for that row and closes while it is there.
+// n_steps on the resident state: md_drive (md_driver.h) runs the launches, the list's rebuild schedule and the recovery
+// from a halt; what is oxDNA's is here - the frame's site offsets after a parameter change, the choice of instantiation
+// per launch, the chunk order, and the wider work lists after an aborted launch.
+// Rows with energies (e_trace != NULL) come from the energy-trace instantiation: launch k evaluates at x_k, writes row
+// k / save_every - 1 (positions, term and kinetic energies) and a reduction launch follows.  Rows WITHOUT energies - the
+// reference's own semantics of run - cost two stores in the plain instantiation: launch k, which produces x_{k+1}, writes
+// it to its row as well; such a call needs no closing launch for its last row and leaves the frame open like any other.
 template <typename R, int MODEL>
 static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool close, R* traj_center, R* traj_quat, double* e_trace,
                          hipStream_t st) {
@@ -1478,272 +1376,119 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
   const long long dbg_dense = debug_value(MYTHOS_DEBUG_MD_DENSE);  // (tests: 1 forces the DENSE instantiation, 2 forbids it)
   const bool dense_grid = !lanes16 && (dbg_dense == 1 || (dbg_dense != 2 && grid > 4 * sim_cus));
   const int prio_on = (sizeof(R) == 8 && grid > 3 * sim_cus) ? 0 : 1;  // (see MYTHOS_MD_PRIO_MAP)
-  // Rows with energies (e_trace != NULL) come from the energy-trace instantiation: launch k evaluates at x_k, writes row
-  // k / save_every - 1 (positions, term and kinetic energies) and a reduction launch follows.  Rows WITHOUT energies - the
-  // reference's own semantics of run - cost two stores in the plain instantiation: launch k, which produces x_{k+1}, writes
-  // it to its row as well; such a call needs no closing launch for its last row and leaves the frame open like any other.
-  const bool energy_rows = save_every > 0 && e_trace != nullptr;
-  const bool plain_rows = save_every > 0 && e_trace == nullptr && (traj_center != nullptr || traj_quat != nullptr);
-  const bool closes = close || (energy_rows && n_steps > 0 && n_steps % save_every == 0);
-  const int n_launch = closes ? n_steps + 1 : n_steps;
-  if (n_launch == 0) return MYTHOS_OK;  // (advance(0) on an open or a closed frame: nothing to do)
-  const bool was_open = sim->open;
   const R* Pdev = device_params_of<R>(sys);
   const BoxT<R> box = make_box<R>(sys);
   const LangevinConst<R> K = make_const<R>(sim);
   const MdCut<R> cut = make_cut<R>(sys);
   const Frame<R> fr[2] = {frame_of<R>(sim, 0), frame_of<R>(sim, 1)};
-  int cur = sim->cur;
   if (sim->param_epoch != sys->param_epoch) {  // mythos_oxdna_set_params / set_nucleotide_types since the load
     const OxParams<R>& Ph = params_of<R>(sys);
     const double* Prna = oxdna_param_set(sys, sys->param_sets() == 1 ? 0 : 1);
     hipLaunchKernelGGL((rederive_frame_kernel<R, (MODEL == 4 ? 0 : back_axis<MODEL>())>), dim3((n + 255) / 256), dim3(256), 0, st, n,
                        Ph[GEO_BACK_A1], (MODEL >= 2) ? Ph[GEO_BACK_A2] : R(0), R(Prna[GEO_BACK_A1]), R(Prna[GEO_BACK_A2]),
-                       (const int*)sys->d_meta, fr[cur]);
+                       (const int*)sys->d_meta, fr[sim->cur]);
     MYTHOS_HIP_TRY(hipGetLastError());
     sim->param_epoch = sys->param_epoch;
   }
-#ifdef MYTHOS_MD_DIAG
-  const char* abl = getenv("MYTHOS_MD_ABLATE");  // profiling aid: bit 0/1/2 skip radial / angular / integrate
-  const int ablate = abl ? atoi(abl) : 0;
-#else
-  const int ablate = 0;
-#endif
   const bool dynamic_list = sim->rebuild_every > 0;
-  const bool timing = sim->timing_samples > 0;
   // a probabilistic sequence (mythos_oxdna_set_pseq): the PSEQ instantiations - since round 4 with the short work lists
   // too (ITEMS = 16, abort -> wide fallback as the plain path), so such a run steps at the plain rate's occupancy
   PseqView<R> pseq;
   const bool use_pseq = sys->pseq_terms != 0;
   if (debug_value(MYTHOS_DEBUG_MD_ITEMS_BIG) == 1) sim->items_big = true;  // (tests: the wide instantiations without a crowded system)
   if (use_pseq) pseq.marg = (const R*)sys->d_ps_marg, pseq.unit = sys->d_ps_unit, pseq.bp = (const R*)sys->d_ps_bp, pseq.terms = sys->pseq_terms;
+  int* halt_words = dynamic_list ? sys->d_overflow : nullptr;
+  auto launch_step = [&](int k, const LaunchRow& row) {
+    const int cur = row.cur;
+    const bool save = row.save;
+    const R kick_close = R(row.kick_close);
+    R* tc = ((save || row.save_next) && traj_center) ? traj_center + (size_t)row.sidx * n * 3 : nullptr;
+    R* tq = ((save || row.save_next) && traj_quat) ? traj_quat + (size_t)row.sidx * n * 4 : nullptr;
+    const V4* ref = (const V4*)sys->d_ref_pos;
+    const V4* ref_off = (const V4*)sys->d_ref_off;
+    const V4* ref_a1 = (const V4*)sys->d_ref_a1;
+    auto launch_pseq = [&](auto save_tag, auto items_tag, hipEvent_t ea, hipEvent_t eb) {
+      constexpr bool SV = decltype(save_tag)::value;
+      constexpr int IT = decltype(items_tag)::value;
+      auto go = [&](auto lanes_tag) {
+        hipExtLaunchKernelGGL((md_step_kernel<R, MODEL, SV, IT, true, false, decltype(lanes_tag)::value>), dim3(grid), dim3(kMdBlock), 0, st, ea, eb, 0,
+                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->d_rows, sys->d_row_len, row_close_of(sys),
+                              sys->row_stride, sys->extra_bonds ? 1 : 0, kick_close, row.do_step, sim->seed, (uint64_t)(sim->step + k), ref,
+                              ref_off, ref_a1, sim->d_flags, tc, tq, sim->d_epart, sim->d_chunk_order, halt_words, k, 0, prio_on, pseq);
+      };
+      if (lanes16) go(std::integral_constant<int, 16>{}); else go(std::integral_constant<int, 8>{});
+    };
+    auto launch = [&](auto save_tag, auto items_tag, hipEvent_t ea, hipEvent_t eb) {
+      constexpr bool SV = decltype(save_tag)::value;
+      constexpr int IT = decltype(items_tag)::value;
+      // with events: the pair receives the begin / end time stamps of THIS dispatch (the same stamps a profiler's
+      // kernel trace reports), not the time between two markers in the queue
+      auto go = [&](auto dense_tag, auto lanes_tag) {
+        hipExtLaunchKernelGGL((md_step_kernel<R, MODEL, SV, IT, false, decltype(dense_tag)::value, decltype(lanes_tag)::value>), dim3(grid), dim3(kMdBlock), 0, st, ea, eb, 0,
+                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->d_rows, sys->d_row_len, row_close_of(sys),
+                              sys->row_stride, sys->extra_bonds ? 1 : 0, kick_close, row.do_step, sim->seed, (uint64_t)(sim->step + k), ref,
+                              ref_off, ref_a1, sim->d_flags, tc, tq, sim->d_epart, sim->d_chunk_order, halt_words, k, 0, prio_on, PseqView<R>{});
+      };
+      using L8 = std::integral_constant<int, 8>;
+      using L16 = std::integral_constant<int, 16>;
+      if (lanes16) {
+        go(std::false_type{}, L16{});
+      } else if constexpr (sizeof(R) == 4 && !SV && IT == kMdItems && MODEL <= 2) {
+        if (dense_grid) go(std::true_type{}, L8{}); else go(std::false_type{}, L8{});
+      } else {
+        go(std::false_type{}, L8{});
+      }
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    using Small = std::integral_constant<int, kMdItems>;
+    using BigS = std::integral_constant<int, md_items_big<R, true>()>;
+    using BigN = std::integral_constant<int, md_items_big<R, false>()>;
+    const hipEvent_t ea = row.ea, eb = row.eb;
+    if (use_pseq) {
+      if (save) {
+        if (sim->items_big) launch_pseq(T{}, BigS{}, ea, eb); else launch_pseq(T{}, Small{}, ea, eb);
+      } else {
+        if (sim->items_big) launch_pseq(F{}, BigN{}, ea, eb); else launch_pseq(F{}, Small{}, ea, eb);
+      }
+    } else if (save) {
+      if (sim->items_big) launch(T{}, BigS{}, ea, eb); else launch(T{}, Small{}, ea, eb);
+    } else {
+      if (sim->items_big) launch(F{}, BigN{}, ea, eb); else launch(F{}, Small{}, ea, eb);
+    }
+    if (save)
+      hipLaunchKernelGGL(reduce_trace_kernel<kTraceWidth>, dim3(1), dim3(256), 0, st, sim->d_epart, blocks,
+                         e_trace + (size_t)row.sidx * kTraceWidth);
+  };
   auto rebuild = [&](int buf) -> int {
     if ((++sim->builds & 63) == 0)
       if (int rc = update_chunk_order<R>(sim, fr[buf].p0, blocks, st)) return rc;
     return rows_build_device(sys, fr[buf].p0, true, sim->r_cut, sim->skin, fr[buf].p3, fr[buf].p1, true, st);
   };
-  // k index at which the rows in use were built (negative: so many steps before this call)
-  int built_at = 0;
-  if (dynamic_list) {
-    if (!sim->list_fitted) {
-      // the first build of this integrator sizes rows (a quarter of headroom) and cell buckets (none more than half
-      // full) with a synchronising build; later ones just rebuild - should that overflow, the next step kernel
-      // halts and the recovery below grows what is needed
-      if (int rc = rows_build_until_fit(sys, fr[cur].p0, true, sim->r_cut, sim->skin, fr[cur].p3, fr[cur].p1, true, true, st))
-        return rc;
-      sim->list_fitted = true;
-    } else if (!sim->list_valid) {
-      if (int rc = rebuild(cur)) return rc;
-    } else {
-      built_at = -sim->since_build;
-    }
-    sim->list_valid = true;
-  }
-  if (timing) MYTHOS_HIP_TRY(hipEventRecord(sim->ev0, st));
-  int launches = 0, samples = 0, recoveries = 0, scheduled_rebuilds = 0;
-  const int max_samples = std::min(sim->timing_samples, (int)mythos_sim::kMaxSamples);  // 0: no dispatch is bracketed
-  const int sample_stride = std::max(1, n_launch / std::max(1, max_samples));
-  int* halt_words = dynamic_list ? sys->d_overflow : nullptr;
-  // The kernels of a run are queued in segments of kSegment; after each the host looks at the halt word.  A step that
-  // moves a site out of its skin, or a rebuild that overflows its rows or spill list, halts the launches behind it
-  // (they return at once); the host then rebuilds at the last valid state - growing what overflowed - and resumes
-  // there.  A run never integrates on a stale or truncated list, and neither condition is an error any more; what
-  // it costs is the empty launches behind the halt (at most a segment) and a synchronisation.
-  constexpr int kMaxRecoveries = 64;
-  const long long dbg_seg = debug_value(MYTHOS_DEBUG_MD_SEGMENT);
-  const int kSegment = dbg_seg > 0 ? (int)std::min<long long>(dbg_seg, 1 << 20) : 8192;
-  int k = 0, seg_len = kSegment;  // a run that has halted once looks more often: less queued behind the next halt
-  int err_bits = 0, ovw[kOverflowWords] = {0, 0, 0};
-  while (k < n_launch) {
-    const int seg_end = std::min(n_launch - 1, k + seg_len - 1);
-    // The device's progress word (flags[2], cleared by publish_ctl_kernel after every segment) says nothing when the
-    // FIRST launch of a segment halts before writing it (a scheduled rebuild in front of it overflowed): the launches
-    // of the earlier segments count all the same.
-    const int seg_start = k;
-    for (; k <= seg_end; ++k) {
-      const bool last = (k == n_steps);  // (reached only by a call that closes)
-      const bool save = energy_rows && k > 0 && (k % save_every == 0);
-      const bool save_next = plain_rows && !last && ((k + 1) % save_every == 0);  // this launch's OUTPUT is a saved state
-      const int sidx = save ? (k / save_every - 1) : (save_next ? ((k + 1) / save_every - 1) : 0);
-      // (a closing-only launch rebuilds too when the schedule says so: the launch a longer call would issue at this index
-      // does, and the forces that close step n must come off the same rows either way - sums over rows built at different
-      // states differ in their last bits)
-      if (dynamic_list && k - built_at >= sim->rebuild_every) {
-        if (int rc = rebuild(cur)) return rc;
-        built_at = k;
-        ++scheduled_rebuilds;
-        if (debug_value(MYTHOS_DEBUG_MD_OVERFLOW_AT) == k + 1) {  // test hook: this build claims a row did not fit
-          debug_clear(MYTHOS_DEBUG_MD_OVERFLOW_AT);
-          MYTHOS_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)sys->d_overflow, sys->row_stride + 1, 1, st));
-        }
-      }
-      const R kick_close = (k == 0 && !was_open) ? R(0) : R(0.5);
-      const int do_step = last ? 0 : 1;
-      R* tc = ((save || save_next) && traj_center) ? traj_center + (size_t)sidx * n * 3 : nullptr;
-      R* tq = ((save || save_next) && traj_quat) ? traj_quat + (size_t)sidx * n * 4 : nullptr;
-      const V4* ref = (const V4*)sys->d_ref_pos;
-      const V4* ref_off = (const V4*)sys->d_ref_off;
-      const V4* ref_a1 = (const V4*)sys->d_ref_a1;
-      const bool sampled = !save && (k % sample_stride == sample_stride / 2) && samples < max_samples;
-      auto launch_pseq = [&](auto save_tag, auto items_tag, hipEvent_t ea, hipEvent_t eb) {
-        constexpr bool SV = decltype(save_tag)::value;
-        constexpr int IT = decltype(items_tag)::value;
-        auto go = [&](auto lanes_tag) {
-          hipExtLaunchKernelGGL((md_step_kernel<R, MODEL, SV, IT, true, false, decltype(lanes_tag)::value>), dim3(grid), dim3(kMdBlock), 0, st, ea, eb, 0,
-                                Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->d_rows, sys->d_row_len, row_close_of(sys),
-                                sys->row_stride, sys->extra_bonds ? 1 : 0, kick_close, do_step, sim->seed, (uint64_t)(sim->step + k), ref,
-                                ref_off, ref_a1, sim->d_flags, tc, tq, sim->d_epart, sim->d_chunk_order, halt_words, k, ablate, prio_on, pseq);
-        };
-        if (lanes16) go(std::integral_constant<int, 16>{}); else go(std::integral_constant<int, 8>{});
-      };
-      auto launch = [&](auto save_tag, auto items_tag, hipEvent_t ea, hipEvent_t eb) {
-        constexpr bool SV = decltype(save_tag)::value;
-        constexpr int IT = decltype(items_tag)::value;
-        // with events: the pair receives the begin / end time stamps of THIS dispatch (the same stamps a profiler's
-        // kernel trace reports), not the time between two markers in the queue
-        auto go = [&](auto dense_tag, auto lanes_tag) {
-          hipExtLaunchKernelGGL((md_step_kernel<R, MODEL, SV, IT, false, decltype(dense_tag)::value, decltype(lanes_tag)::value>), dim3(grid), dim3(kMdBlock), 0, st, ea, eb, 0,
-                                Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->d_rows, sys->d_row_len, row_close_of(sys),
-                                sys->row_stride, sys->extra_bonds ? 1 : 0, kick_close, do_step, sim->seed, (uint64_t)(sim->step + k), ref,
-                                ref_off, ref_a1, sim->d_flags, tc, tq, sim->d_epart, sim->d_chunk_order, halt_words, k, ablate, prio_on, PseqView<R>{});
-        };
-        using L8 = std::integral_constant<int, 8>;
-        using L16 = std::integral_constant<int, 16>;
-        if (lanes16) {
-          go(std::false_type{}, L16{});
-        } else if constexpr (sizeof(R) == 4 && !SV && IT == kMdItems && MODEL <= 2) {
-          if (dense_grid) go(std::true_type{}, L8{}); else go(std::false_type{}, L8{});
-        } else {
-          go(std::false_type{}, L8{});
-        }
-      };
-      using T = std::true_type;
-      using F = std::false_type;
-      using Small = std::integral_constant<int, kMdItems>;
-      using BigS = std::integral_constant<int, md_items_big<R, true>()>;
-      using BigN = std::integral_constant<int, md_items_big<R, false>()>;
-      hipEvent_t ea = nullptr, eb = nullptr;
-      if (sampled) ea = sim->sa[samples], eb = sim->sb[samples], ++samples;
-      if (use_pseq) {
-        if (save) {
-          if (sim->items_big) launch_pseq(T{}, BigS{}, ea, eb); else launch_pseq(T{}, Small{}, ea, eb);
-        } else {
-          if (sim->items_big) launch_pseq(F{}, BigN{}, ea, eb); else launch_pseq(F{}, Small{}, ea, eb);
-        }
-        if (save)
-          hipLaunchKernelGGL(reduce_trace_kernel, dim3(1), dim3(256), 0, st, sim->d_epart, blocks,
-                             e_trace ? e_trace + (size_t)sidx * kTraceWidth : nullptr);
-      } else if (save) {
-        if (sim->items_big) launch(T{}, BigS{}, ea, eb); else launch(T{}, Small{}, ea, eb);
-        hipLaunchKernelGGL(reduce_trace_kernel, dim3(1), dim3(256), 0, st, sim->d_epart, blocks,
-                           e_trace ? e_trace + (size_t)sidx * kTraceWidth : nullptr);
-      } else {
-        if (sim->items_big) launch(F{}, BigN{}, ea, eb); else launch(F{}, Small{}, ea, eb);
-      }
-      ++launches;
-      cur ^= 1;
-    }
-    if (timing && k >= n_launch) MYTHOS_HIP_TRY(hipEventRecord(sim->ev1, st));
-    hipLaunchKernelGGL(publish_ctl_kernel, dim3(1), dim3(1), 0, st, sim->d_flags, halt_words, sim->d_ctl);
-    MYTHOS_HIP_TRY(hipGetLastError());
-    MYTHOS_HIP_TRY(hipStreamSynchronize(st));
-    const int* ctl = sim->h_ctl;
-    err_bits |= ctl[0];
-    for (int w = 0; w < kOverflowWords; ++w) ovw[w] = ctl[4 + w];
-    if ((err_bits & 2) != 0) break;                              // NaN: reported below
-    const int aborted = ctl[3];  // launch index + 1 whose angular work lists were too short (its output does not count)
-    if (ctl[1] == 0 && ovw[0] == 0 && ovw[1] == 0 && aborted == 0) continue;  // nothing halted
-    if (aborted != 0) {
-      if (sim->items_big) {
-        // what is handed back: the positions after the last step that counted, momenta short of its closing half kick
-        sim->cur ^= ((aborted - 1) & 1);
-        sim->step += aborted - 1;
-        sim->open = was_open || aborted > 1;
-        (void)hipMemsetAsync(sim->d_flags + 1, 0, 3 * sizeof(int), st);  // the next call starts with clean halt / abort words
-        set_error("mythos_langevin_run: more than " + std::to_string(md_items_big<R, false>()) + " (" + std::to_string(md_items_big<R, true>()) +
-                  " on steps that save energies)"
-                  " neighbours of one nucleotide are inside the range of an angular term (overlapping bases?)");
-        return MYTHOS_ERR_OVERFLOW;
-      }
+  auto rebuild_until_fit = [&](int buf) -> int {
+    return rows_build_until_fit(sys, fr[buf].p0, true, sim->r_cut, sim->skin, fr[buf].p3, fr[buf].p1, true, true, st);
+  };
+  auto on_abort = [&]() -> int {
+    if (!sim->items_big) {
       sim->items_big = true;  // run that step again, and the rest of the run, with the wider instantiation
-    } else if (!dynamic_list) {
-      break;  // (a static list cannot halt; defensive)
+      return 0;
     }
-    // kernels 0 .. ran-1 count; the state they left is in the frame kernel `ran` reads (an aborted launch and
-    // everything behind it do not count: their inputs are untouched)
-    const int progressed = std::max(ctl[2], seg_start);
-    const int ran = aborted != 0 ? std::min(progressed, aborted - 1) : progressed;
-    if (++recoveries > kMaxRecoveries) {
-      sim->cur ^= (ran & 1);  // positions after the last step that counted, momenta short of its closing half kick
-      sim->step += ran;
-      sim->open = was_open || ran > 0;
-      (void)hipMemsetAsync(sim->d_flags + 1, 0, 3 * sizeof(int), st);
-      set_error("mythos_langevin_run: the neighbour list had to be rebuilt out of turn more than " + std::to_string(kMaxRecoveries) +
-                " times in one run: the skin (" + std::to_string(sim->skin) + ") is too small for a rebuild every " +
-                std::to_string(sim->rebuild_every) + " steps");
-      return MYTHOS_ERR_OVERFLOW;
-    }
-    cur = sim->cur ^ (ran & 1);
-    k = ran;
-    seg_len = std::max(std::min(256, kSegment), seg_len / 4);
-    MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_flags + 1, 0, 3 * sizeof(int), st));
-    if (dynamic_list) {
-      if (int rc = rows_build_until_fit(sys, fr[cur].p0, true, sim->r_cut, sim->skin, fr[cur].p3, fr[cur].p1, true, true, st))
-        return rc;
-      built_at = k;
-    }
-    ovw[0] = ovw[1] = 0;
-  }
-  sim->last_recoveries = recoveries;
-  sim->last_rebuilds = scheduled_rebuilds;
-  sim->cur = cur;
-  sim->open = !closes;
-  sim->since_build = n_steps - built_at;
-  if (timing) {
-    float ms = 0;
-    MYTHOS_HIP_TRY(hipEventElapsedTime(&ms, sim->ev0, sim->ev1));
-    sim->last_avg_ms = launches ? double(ms) / launches : 0.0;
-    double acc = 0;
-    for (int s = 0; s < samples; ++s) {
-      float t = 0;
-      MYTHOS_HIP_TRY(hipEventElapsedTime(&t, sim->sa[s], sim->sb[s]));
-      acc += t;
-    }
-    sim->last_kernel_ms = samples ? acc / samples : 0.0;
-  } else {
-    sim->last_avg_ms = sim->last_kernel_ms = 0.0;
-  }
-  sim->last_launches = launches;
-  sim->last_samples = samples;
-#ifdef MYTHOS_MD_DIAG
-  if (ablate & 128) {  // diagnostic build (make DIAG=1): dump the cycle stamps of the last launch
-    if (const char* path = getenv("MYTHOS_MD_STAMPS")) {
-      std::vector<unsigned long long> h((size_t)blocks * 64);  // two launches: even step | odd step
-      MYTHOS_HIP_TRY(hipMemcpy(h.data(), sim->d_epart, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      if (FILE* f = fopen(path, "wb")) {
-        fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
-        fclose(f);
-      }
-    }
-  }
-#endif
-  sim->step += n_steps;
-  if (err_bits & 2) {
-    sim->resident = false;
-    set_error("mythos_langevin_run: NaN in the state (time step too large or overlapping start configuration)");
-    return MYTHOS_ERR_NUMERIC;
-  }
-  if (dynamic_list && ovw[0] != 0) {
-    set_error("mythos_langevin_run: neighbour row capacity exceeded (" + std::to_string(ovw[0]) + " > " +
-              std::to_string(sys->row_stride) + "); rebuild with mythos_oxdna_build_neighbors first");
+    set_error("mythos_langevin_run: more than " + std::to_string(md_items_big<R, false>()) + " (" + std::to_string(md_items_big<R, true>()) +
+              " on steps that save energies)"
+              " neighbours of one nucleotide are inside the range of an angular term (overlapping bases?)");
     return MYTHOS_ERR_OVERFLOW;
-  }
-  if (dynamic_list && ovw[1] != 0) {
-    set_error("mythos_langevin_run: too many nucleotides (" + std::to_string(ovw[1]) +
-              ") did not fit the buckets of their cells during a neighbour rebuild");
-    return MYTHOS_ERR_OVERFLOW;
-  }
-  return MYTHOS_OK;
+  };
+  MdDrive d;
+  d.who = "mythos_langevin_run";
+  d.n_steps = n_steps, d.save_every = save_every, d.close = close;
+  d.energy_rows = save_every > 0 && e_trace != nullptr;
+  d.plain_rows = save_every > 0 && e_trace == nullptr && (traj_center != nullptr || traj_quat != nullptr);
+  d.dynamic_list = dynamic_list;
+  d.halt_words = halt_words;
+  d.row_stride = &sys->row_stride;
+  d.skin = sim->skin;
+  d.st = st;
+  return md_drive(*sim, d, launch_step, rebuild, rebuild_until_fit, on_abort);
 }
 
 // ------------------------------------------------------------------------------------------------

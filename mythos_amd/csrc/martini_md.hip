@@ -23,6 +23,7 @@
 
 #include "cell_list.h"
 #include "martini_internal.h"
+#include "md_driver.h"
 #include "philox.h"
 #include "wave_ops.h"
 
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
   const int i = bid * PPB + grp;
   const bool valid = i < n;
   const int ii = valid ? i : n - 1;
-  // Halt word (see mythos_langevin_run in langevin_core.inc): set by the step that moved a bead out of its skin, or by a
+  // Halt word (see md_drive, md_driver.h): set by the step that moved a bead out of its skin, or by a
   // rebuild that overflowed.  One lane requests it here; everybody looks at it behind the barrier in front of the
   // integration, before which nothing is written to global memory.
   __shared__ int s_halt;
@@ -368,24 +369,6 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
       for (int g = 0; g < PPB; ++g) s += s_e[g][threadIdx.x];
       e_part[(size_t)bid * kMmTrace + threadIdx.x] = s;
     }
-  }
-}
-
-// 256 threads = 16 columns x 16 groups of workgroup partials, the group sums added in a fixed order (as langevin_core.inc's)
-__global__ __launch_bounds__(256) void mm_reduce_trace_kernel(const double* __restrict__ part, int n_blocks, double* __restrict__ out) {
-  static_assert(kMmTrace <= 16, "one column per trace entry");
-  __shared__ double acc[16][17];
-  const int k = threadIdx.x & 15, g = threadIdx.x >> 4;
-  double s = 0.0;
-  if (k < kMmTrace)
-    for (int b = g; b < n_blocks; b += 16) s += part[(size_t)b * kMmTrace + k];
-  acc[g][k] = s;
-  __syncthreads();
-  if (g == 0 && k < kMmTrace && out) {
-    double t = 0.0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) t += acc[j][k];
-    out[k] = t;
   }
 }
 
@@ -624,13 +607,10 @@ __global__ __launch_bounds__(256) void mm_build_rows_allpairs_kernel(
 
 using namespace mythos;
 
-struct mythos_martini_sim {
+struct mythos_martini_sim : mythos::MdRun {
   mythos_martini* sys = nullptr;
   double dt = 0.02, kT = 2.27, gamma = 1.0;
-  uint64_t seed = 0;
-  long long step = 0;
-  double skin = 0.2;
-  int rebuild_every = 10;
+  double skin = 0.2;  // (MdRun::rebuild_every: 10 until set_neighbor_policy)
   void* frame[2] = {nullptr, nullptr};
   void *vel = nullptr, *ref_pos = nullptr, *d_inv_mass = nullptr;
   // Type tables of the step kernel: only the types that occur, renumbered 0 .. n_ctypes - 1 (the DMPC bilayer uses 4 of
@@ -643,7 +623,7 @@ struct mythos_martini_sim {
   int* d_bb_partner = nullptr;
   int2* d_ba_partner = nullptr;
   void* d_angle_ref = nullptr;  // per angle: cos(theta0) for the G96 form (once, instead of a cosine per lane and step), theta0 for the harmonic one
-  int *d_rows = nullptr, *d_row_len = nullptr, *d_cell = nullptr, *d_flags = nullptr, *d_overflow = nullptr;
+  int *d_rows = nullptr, *d_row_len = nullptr, *d_cell = nullptr, *d_overflow = nullptr;
   size_t cell_cap = 0;       // ints allocated at d_cell (cell_list.h CellBins: counters [2][H], buckets [H][cap])
   int cell_H = 0, cell_alloc_bucket_cap = 0, cell_bucket_cap = 64, cell_phase = 0;
   int row_stride = 256;
@@ -654,23 +634,7 @@ struct mythos_martini_sim {
   double inner_margin = 0.0;  // off until mythos_martini_langevin_set_inner_list asks for them
   int inner_every = 4;
   double* d_epart = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  static constexpr int kMaxSamples = 16;
-  int timing_samples = 0;  // dispatches per run timed with their own event pair (set_timing; ~8 us each)
-  hipEvent_t sa[kMaxSamples] = {}, sb[kMaxSamples] = {};
-  double last_kernel_ms = 0, last_avg_ms = 0;
-  int last_launches = 0, last_samples = 0, last_max_row = 0, last_recoveries = 0;
-  bool list_fitted = false;  // a synchronising, growing build has sized rows and buckets for this integrator
-  // resident state (mythos_martini_langevin_load / advance / store): the frames hold a state between calls
-  double box[3] = {0, 0, 0};
-  bool resident = false;    // frame[cur] + vel hold a state
-  bool list_valid = false;  // the rows were built from this state's history and the rebuild schedule continues
-  bool open = false;        // x_n with velocities short of the closing half kick of step n (advance)
-  int cur = 0;
-  int since_build = 0;      // steps taken since the rows were built
-  int last_rebuilds = 0;    // scheduled rebuilds inside the last advance
-  int* h_ctl = nullptr;     // pinned: [0..3] d_flags, [4..6] d_overflow as the device published them
-  int* d_ctl = nullptr;     // device address of h_ctl
+  double box[3] = {0, 0, 0};  // of the resident state (mythos_martini_langevin_load / advance / store)
 };
 
 namespace mythos {
@@ -732,13 +696,6 @@ hipLaunchKernelGGL((mm_build_rows_cells_kernel<R, kMmRowG>), dim3((n + 256 / kMm
   return 0;
 }
 
-// End of a segment: hand the control words to the host (pinned memory), as the oxDNA integrator does (langevin_core.inc).
-static __global__ void mm_publish_ctl_kernel(const int* __restrict__ flags, const int* __restrict__ overflow, int* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  out[0] = flags[0], out[1] = flags[1], out[2] = flags[2], out[3] = flags[3];
-  out[4] = overflow[0], out[5] = overflow[1], out[6] = overflow[2];
-}
-
 // pruned rows make sense inside the skin and when at least one launch walks them between two prunings
 static bool mm_inner_on(const mythos_martini_sim* sim) {
   return sim->inner_margin > 0 && sim->inner_margin < sim->skin && sim->inner_every >= 2;
@@ -780,13 +737,10 @@ static int mm_load_typed(mythos_martini_sim* sim, const R* pos, const R* v, cons
   return MYTHOS_OK;
 }
 
-// n_steps on the resident state (the protocol of advance_typed in langevin_core.inc).  Launch k evaluates the forces at
-// x_k, closes step k - 1 with them (second half kick) and takes step k up to its drift.  close = true: n_steps + 1
-// launches, the last one only closes.  close = false (mythos_martini_langevin_advance): n_steps launches, the frame is
-// left OPEN and whoever comes next supplies the closing half kick with the force evaluation it needs anyway - the next
-// advance in its first launch (advance(a); advance(b) is advance(a + b) launch for launch), store through a zero-step
-// closing call.  Rows with energies (e_trace != NULL) come from the energy-trace instantiation at x_k plus a reduction
-// launch; rows without are written by the launch that produces the saved state.
+// n_steps on the resident state: md_drive (md_driver.h) runs the launches, the list's rebuild schedule and the recovery
+// from a halt, as for oxDNA.  What is MARTINI's is here: the list builds and the pruned rows.  Rows with energies
+// (e_trace != NULL) come from the energy-trace instantiation at x_k plus a reduction launch; rows without are written by
+// the launch that produces the saved state.
 template <typename R>
 static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every, bool close, R* traj_pos, double* e_trace,
                             hipStream_t st) {
@@ -798,18 +752,9 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
   const double* box = sim->box;
   V4* fr[2] = {(V4*)sim->frame[0], (V4*)sim->frame[1]};
   V4* vel = (V4*)sim->vel;
-  const bool energy_rows = save_every > 0 && e_trace != nullptr;
-  const bool plain_rows = save_every > 0 && e_trace == nullptr && traj_pos != nullptr;
-  const bool closes = close || (energy_rows && n_steps > 0 && n_steps % save_every == 0);
-  const int n_launch = closes ? n_steps + 1 : n_steps;
-  if (n_launch == 0) return MYTHOS_OK;
-  const bool was_open = sim->open;
-  const int cur0 = sim->cur;
-  int cur = cur0;
-  MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_flags, 0, 4 * sizeof(int), st));
   // A build that may grow: rows until the longest fits with a quarter of headroom, buckets until none is more than
   // half full (fuller ones work, through the spill list, but slowly).  Used for the first build of an integrator and to
-  // recover from a halt (see below); the scheduled builds inside a call cannot stop to grow.
+  // recover from a halt; the scheduled builds inside a call cannot stop to grow.
   auto build_until_fit = [&](int buf) -> int {
     for (int attempt = 0;; ++attempt) {
       MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_overflow, 0, 3 * sizeof(int), st));
@@ -841,18 +786,6 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
       if (demand > 0) sim->cell_bucket_cap = ((2 * demand + 15) / 16) * 16;
     }
   };
-  // k index at which the rows in use were built (negative: so many steps before this call)
-  int built_at = 0;
-  if (!sim->list_fitted) {
-    if (int rc = build_until_fit(cur)) return rc;
-    sim->list_fitted = true;
-  } else if (!sim->list_valid) {
-    MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_overflow, 0, 3 * sizeof(int), st));
-    if (int rc = mm_rebuild<R>(sim, fr[cur], K, box, st)) return rc;
-  } else {
-    built_at = -sim->since_build;
-  }
-  sim->list_valid = true;
   const bool inner_on = mm_inner_on(sim);
   // the pruned rows share the Verlet rows' stride (a pruned row is a subset of its row: it cannot overflow)
   auto ensure_inner = [&]() -> int {
@@ -868,141 +801,61 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
   };
   if (int rc = ensure_inner()) return rc;
   const size_t lds = (size_t)2 * sim->n_ctypes * sim->n_ctypes * sizeof(R);
-  const bool timing = sim->timing_samples > 0;
-  if (timing) MYTHOS_HIP_TRY(hipEventRecord(sim->ev0, st));
-  int launches = 0, samples = 0, recoveries = 0, scheduled = 0;
-  const int max_samples = std::min(sim->timing_samples, (int)mythos_martini_sim::kMaxSamples);  // 0: no dispatch is bracketed
-  const int sample_stride = std::max(1, n_launch / std::max(1, max_samples));
-  // Segments of kSegment launches; a halted segment (a bead left its skin before the scheduled rebuild, or a rebuild
-  // overflowed: the launches behind it return at once) is followed by a growing rebuild at the last valid state and
-  // a resume there - the protocol of mythos_langevin_run (langevin_core.inc).
-  constexpr int kMaxRecoveries = 64;
-  const long long dbg_seg = debug_value(MYTHOS_DEBUG_MD_SEGMENT);
-  const int kSegment = dbg_seg > 0 ? (int)std::min<long long>(dbg_seg, 1 << 20) : 8192;
-  int k = 0, seg_len = kSegment;  // a call that has halted once looks more often: less queued behind the next halt
-  int err_bits = 0, ovw[3] = {0, 0, 0};
-  while (k < n_launch) {
-    const int seg_end = std::min(n_launch - 1, k + seg_len - 1);
-    for (; k <= seg_end; ++k) {
-      const bool last = (k == n_steps);  // (reached only by a call that closes)
-      const bool save = energy_rows && k > 0 && (k % save_every == 0);
-      const bool save_next = plain_rows && !last && ((k + 1) % save_every == 0);  // this launch's OUTPUT is a saved state
-      const int sidx = save ? (k / save_every - 1) : (save_next ? ((k + 1) / save_every - 1) : 0);
-      // (a closing-only launch rebuilds too when the schedule says so - as advance_typed in langevin_core.inc)
-      if (k - built_at >= sim->rebuild_every) {
-        if (int rc = mm_rebuild<R>(sim, fr[cur], K, box, st)) return rc;
-        built_at = k;
-        ++scheduled;
-      }
-      const R kick_close = (k == 0 && !was_open) ? R(0) : R(0.5);
-      const int do_step = last ? 0 : 1;
-      R* tp = ((save || save_next) && traj_pos) ? traj_pos + (size_t)sidx * n * 3 : nullptr;
-      const bool sampled = !save && (k % sample_stride == sample_stride / 2) && samples < max_samples;
-      // pruned rows: the launch d steps after the Verlet rows were built prunes when d is a multiple of inner_every (so
-      // the first launch on new rows does) and walks the pruned rows otherwise
-      const bool emit = inner_on && ((k - built_at) % sim->inner_every == 0);
-      const int* walk_rows = (inner_on && !emit) ? sim->d_rows_in : sim->d_rows;
-      const int* walk_len = (inner_on && !emit) ? sim->d_row_len_in : sim->d_row_len;
-      int* emit_rows = emit ? sim->d_rows_in : nullptr;
-      int* emit_len = emit ? sim->d_row_len_in : nullptr;
+  auto launch_step = [&](int k, const LaunchRow& row) {
+    const int cur = row.cur;
+    const R kick_close = R(row.kick_close);
+    const int do_step = row.do_step;
+    R* tp = ((row.save || row.save_next) && traj_pos) ? traj_pos + (size_t)row.sidx * n * 3 : nullptr;
+    // pruned rows: the launch d steps after the Verlet rows were built prunes when d is a multiple of inner_every (so
+    // the first launch on new rows does) and walks the pruned rows otherwise
+    const bool emit = inner_on && ((k - row.built_at) % sim->inner_every == 0);
+    const int* walk_rows = (inner_on && !emit) ? sim->d_rows_in : sim->d_rows;
+    const int* walk_len = (inner_on && !emit) ? sim->d_row_len_in : sim->d_row_len;
+    int* emit_rows = emit ? sim->d_rows_in : nullptr;
+    int* emit_len = emit ? sim->d_row_len_in : nullptr;
 #define MM_ARGS                                                                                                    \
   n, K, (const V4*)fr[cur], fr[cur ^ 1], vel, walk_rows, walk_len, sim->row_stride, (const R*)sim->d_csig2,          \
       (const R*)sim->d_ceps, m->d_bead_bonds, m->d_bead_angles, m->d_bonds, (const R*)m->d_bond_k,                      \
       (const R*)m->d_bond_r0, m->d_angles, (const R*)m->d_angle_k, (const R*)sim->d_angle_ref, kick_close, do_step,  \
       sim->seed, (uint64_t)(sim->step + k), (const V4*)sim->ref_pos, sim->d_flags, tp, sim->d_epart, sim->d_overflow, k, \
       emit_rows, emit_len, sim->d_bb_partner, sim->d_ba_partner
-      auto go = [&](auto save_tag, auto emit_tag) {
-        constexpr bool SV = decltype(save_tag)::value, EM = decltype(emit_tag)::value;
-        if (sampled) {
-          hipExtLaunchKernelGGL((martini_md_step_kernel<R, SV, EM>), dim3(grid), dim3(kMmBlock), lds, st, sim->sa[samples],
-                                sim->sb[samples], 0, MM_ARGS);
-        } else {
-          hipLaunchKernelGGL((martini_md_step_kernel<R, SV, EM>), dim3(grid), dim3(kMmBlock), lds, st, MM_ARGS);
-        }
-      };
-      if (save) {
-        if (emit) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{});
-        hipLaunchKernelGGL(mm_reduce_trace_kernel, dim3(1), dim3(256), 0, st, sim->d_epart, blocks,
-                           e_trace + (size_t)sidx * kMmTrace);
+    auto go = [&](auto save_tag, auto emit_tag) {
+      constexpr bool SV = decltype(save_tag)::value, EM = decltype(emit_tag)::value;
+      if (row.ea) {
+        hipExtLaunchKernelGGL((martini_md_step_kernel<R, SV, EM>), dim3(grid), dim3(kMmBlock), lds, st, row.ea, row.eb, 0, MM_ARGS);
       } else {
-        if (emit) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{});
-        if (sampled) ++samples;
+        hipLaunchKernelGGL((martini_md_step_kernel<R, SV, EM>), dim3(grid), dim3(kMmBlock), lds, st, MM_ARGS);
       }
+    };
 #undef MM_ARGS
-      ++launches;
-      cur ^= 1;
+    if (row.save) {
+      if (emit) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{});
+      hipLaunchKernelGGL(reduce_trace_kernel<kMmTrace>, dim3(1), dim3(256), 0, st, sim->d_epart, blocks,
+                         e_trace + (size_t)row.sidx * kMmTrace);
+    } else {
+      if (emit) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{});
     }
-    if (timing && k >= n_launch) MYTHOS_HIP_TRY(hipEventRecord(sim->ev1, st));
-    hipLaunchKernelGGL(mm_publish_ctl_kernel, dim3(1), dim3(1), 0, st, (const int*)sim->d_flags, (const int*)sim->d_overflow, sim->d_ctl);
-    MYTHOS_HIP_TRY(hipGetLastError());
-    MYTHOS_HIP_TRY(hipStreamSynchronize(st));
-    const int* ctl = sim->h_ctl;
-    err_bits |= ctl[0];
-    for (int w = 0; w < 3; ++w) ovw[w] = ctl[4 + w];
-    if ((err_bits & 2) != 0) break;                               // NaN: reported below
-    if (ctl[1] == 0 && ovw[0] == 0 && ovw[1] == 0) continue;      // nothing halted
-    const int ran = ctl[2];  // kernels 0 .. ran-1 ran; the state they left is in the frame kernel `ran` reads
-    if (++recoveries > kMaxRecoveries) {
-      sim->cur = cur0 ^ (ran & 1);
-      sim->step += ran;
-      sim->open = was_open || ran > 0;
-      sim->list_valid = false;
-      (void)hipMemsetAsync(sim->d_flags, 0, 4 * sizeof(int), st);
-      set_error("mythos_martini_langevin_run: the neighbour list had to be rebuilt out of turn more than " +
-                std::to_string(kMaxRecoveries) + " times in one run: the skin (" + std::to_string(sim->skin) +
-                ") is too small for a rebuild every " + std::to_string(sim->rebuild_every) + " steps" +
-                (mm_inner_on(sim) ? ", or the margin of the pruned rows (" + std::to_string(sim->inner_margin) +
-                                        ") for one pruning in " + std::to_string(sim->inner_every) + " steps"
-                                  : std::string()));
-      return MYTHOS_ERR_OVERFLOW;
-    }
-    k = ran;
-    cur = cur0 ^ (k & 1);
-    seg_len = std::max(std::min(256, kSegment), seg_len / 4);
-    MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_flags + 1, 0, sizeof(int), st));
-    if (int rc = build_until_fit(cur)) return rc;
-    if (int rc = ensure_inner()) return rc;  // (the rows may have grown)
-    built_at = k;
-    ovw[0] = ovw[1] = 0;
-  }
-  sim->last_recoveries = recoveries;
-  sim->last_rebuilds = scheduled;
-  sim->cur = cur;
-  sim->open = !closes;
-  sim->since_build = n_steps - built_at;
-  if (timing) {
-    float ms = 0;
-    MYTHOS_HIP_TRY(hipEventElapsedTime(&ms, sim->ev0, sim->ev1));
-    sim->last_avg_ms = launches ? double(ms) / launches : 0.0;
-    double acc = 0;
-    for (int q = 0; q < samples; ++q) {
-      float t = 0;
-      MYTHOS_HIP_TRY(hipEventElapsedTime(&t, sim->sa[q], sim->sb[q]));
-      acc += t;
-    }
-    sim->last_kernel_ms = samples ? acc / samples : 0.0;
-  } else {
-    sim->last_avg_ms = sim->last_kernel_ms = 0.0;
-  }
-  sim->last_launches = launches;
-  sim->last_samples = samples;
-  sim->step += n_steps;
-  if (err_bits & 2) {
-    sim->resident = false;
-    set_error("mythos_martini_langevin_run: NaN in the state (time step too large or overlapping start configuration)");
-    return MYTHOS_ERR_NUMERIC;
-  }
-  if (ovw[0] != 0) {
-    set_error("mythos_martini_langevin_run: neighbour row capacity exceeded (" + std::to_string(ovw[0]) + " > " +
-              std::to_string(sim->row_stride) + ")");
-    return MYTHOS_ERR_OVERFLOW;
-  }
-  if (ovw[1] != 0) {
-    set_error("mythos_martini_langevin_run: more than " + std::to_string(kCellSpill) +
-              " beads did not fit the buckets of their cells during a neighbour rebuild");
-    return MYTHOS_ERR_OVERFLOW;
-  }
-  return MYTHOS_OK;
+  };
+  MdDrive d;
+  d.who = "mythos_martini_langevin_run";
+  d.n_steps = n_steps, d.save_every = save_every, d.close = close;
+  d.energy_rows = save_every > 0 && e_trace != nullptr;
+  d.plain_rows = save_every > 0 && e_trace == nullptr && traj_pos != nullptr;
+  d.dynamic_list = true;
+  d.halt_words = sim->d_overflow;
+  d.row_stride = &sim->row_stride;
+  d.skin = sim->skin;
+  if (inner_on)
+    d.give_up_hint = ", or the margin of the pruned rows (" + std::to_string(sim->inner_margin) + ") for one pruning in " +
+                     std::to_string(sim->inner_every) + " steps";
+  d.st = st;
+  return md_drive(
+      *sim, d, launch_step, [&](int buf) { return mm_rebuild<R>(sim, fr[buf], K, box, st); },
+      [&](int buf) -> int {
+        if (int rc = build_until_fit(buf)) return rc;
+        return ensure_inner();  // (the rows may have grown)
+      },
+      [] { return 0; });  // (no MARTINI launch aborts)
 }
 
 // the resident frame -> caller's arrays (asynchronous on st); an open frame gets its closing half kick first
@@ -1024,16 +877,10 @@ void mythos_martini_langevin_destroy(mythos_martini_sim_t* s) {
   if (!s) return;
   (void)hipSetDevice(s->sys->device);
   void* ptrs[] = {s->frame[0], s->frame[1], s->vel, s->ref_pos, s->d_inv_mass, s->d_rows, s->d_row_len,
-                  s->d_cell,   s->d_flags,  s->d_overflow, s->d_epart, s->d_rows_in, s->d_row_len_in, s->d_angle_ref, s->d_ctypes, s->d_csig2, s->d_ceps, s->d_bb_partner, s->d_ba_partner};
+                  s->d_cell,   s->d_overflow, s->d_epart, s->d_rows_in, s->d_row_len_in, s->d_angle_ref, s->d_ctypes, s->d_csig2, s->d_ceps, s->d_bb_partner, s->d_ba_partner};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
-  if (s->h_ctl) (void)hipHostFree(s->h_ctl);
-  if (s->ev0) (void)hipEventDestroy(s->ev0);
-  if (s->ev1) (void)hipEventDestroy(s->ev1);
-  for (int k = 0; k < mythos_martini_sim::kMaxSamples; ++k) {
-    if (s->sa[k]) (void)hipEventDestroy(s->sa[k]);
-    if (s->sb[k]) (void)hipEventDestroy(s->sb[k]);
-  }
+  md_run_destroy(*s);
   delete s;
 }
 
@@ -1049,6 +896,7 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
   }
   auto* s = new mythos_martini_sim();
   s->sys = sys, s->dt = dt, s->kT = kT, s->gamma = gamma, s->seed = seed;
+  s->rebuild_every = 10;
   const int n = sys->n;
   const size_t w = sys->dtype == MYTHOS_F32 ? sizeof(float) : sizeof(double);
   std::vector<double> im(n);
@@ -1062,11 +910,10 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
     im[i] = 1.0 / mi;
   }
   const int blocks = (n + kMmPPB - 1) / kMmPPB;
-  bool ok = hipMalloc(&s->frame[0], (size_t)n * 4 * w) == hipSuccess && hipMalloc(&s->frame[1], (size_t)n * 4 * w) == hipSuccess &&
+  bool ok = md_run_create(*s) && hipMalloc(&s->frame[0], (size_t)n * 4 * w) == hipSuccess && hipMalloc(&s->frame[1], (size_t)n * 4 * w) == hipSuccess &&
             hipMalloc(&s->vel, (size_t)n * 4 * w) == hipSuccess && hipMalloc(&s->ref_pos, (size_t)n * 4 * w) == hipSuccess &&
             hipMalloc((void**)&s->d_rows, (size_t)n * s->row_stride * sizeof(int)) == hipSuccess &&
             hipMalloc((void**)&s->d_row_len, (size_t)n * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&s->d_flags, 4 * sizeof(int)) == hipSuccess &&
             hipMalloc((void**)&s->d_overflow, 3 * sizeof(int)) == hipSuccess &&
             hipMalloc((void**)&s->d_epart, (size_t)blocks * kMmTrace * sizeof(double)) == hipSuccess;
   ok = ok && (sys->dtype == MYTHOS_F32 ? upload_real_vec<float>(&s->d_inv_mass, im) : upload_real_vec<double>(&s->d_inv_mass, im));
@@ -1143,12 +990,7 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
     }
     ok = ok && (sys->dtype == MYTHOS_F32 ? upload_real_vec<float>(&s->d_angle_ref, ref) : upload_real_vec<double>(&s->d_angle_ref, ref));
   }
-  ok = ok && hipEventCreate(&s->ev0) == hipSuccess && hipEventCreate(&s->ev1) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&s->h_ctl, 8 * sizeof(int), hipHostMallocDefault) == hipSuccess &&
-       hipHostGetDevicePointer((void**)&s->d_ctl, s->h_ctl, 0) == hipSuccess && hipMemset(s->d_overflow, 0, 3 * sizeof(int)) == hipSuccess;
-  if (ok) std::fill(s->h_ctl, s->h_ctl + 8, 0);
-  for (int k = 0; ok && k < mythos_martini_sim::kMaxSamples; ++k)
-    ok = hipEventCreate(&s->sa[k]) == hipSuccess && hipEventCreate(&s->sb[k]) == hipSuccess;
+  ok = ok && hipMemset(s->d_overflow, 0, 3 * sizeof(int)) == hipSuccess;
   if (!ok) {
     set_error("mythos_martini_langevin_create: device allocation failed");
     mythos_martini_langevin_destroy(s);
@@ -1282,28 +1124,15 @@ int mythos_martini_langevin_store(mythos_martini_sim_t* s, void* pos, void* vel,
   return mm_store(s, pos, vel, (hipStream_t)stream);
 }
 
-int64_t mythos_martini_langevin_get_step(const mythos_martini_sim_t* s) { return s ? (int64_t)s->step : -1; }
+int64_t mythos_martini_langevin_get_step(const mythos_martini_sim_t* s) { return md_get_step(s); }
 
 int mythos_martini_langevin_last_rebuilds(const mythos_martini_sim_t* s, int* scheduled) {
-  if (!s || !scheduled) {
-    set_error("mythos_martini_langevin_last_rebuilds: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  *scheduled = s->last_rebuilds;
-  return MYTHOS_OK;
+  return md_last_count(s, &MdRun::last_rebuilds, scheduled, "mythos_martini_langevin_last_rebuilds");
 }
 
 int mythos_martini_langevin_last_kernel_ms(const mythos_martini_sim_t* s, double* kernel_ms, double* loop_ms_per_launch,
                                            int* launches, int* samples) {
-  if (!s) {
-    set_error("mythos_martini_langevin_last_kernel_ms: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  if (kernel_ms) *kernel_ms = s->last_kernel_ms;
-  if (loop_ms_per_launch) *loop_ms_per_launch = s->last_avg_ms;
-  if (launches) *launches = s->last_launches;
-  if (samples) *samples = s->last_samples;
-  return MYTHOS_OK;
+  return md_last_kernel_ms(s, kernel_ms, loop_ms_per_launch, launches, samples, "mythos_martini_langevin_last_kernel_ms");
 }
 
 int mythos_martini_langevin_neighbor_stats(const mythos_martini_sim_t* s, int* max_row, double* mean_row) {
@@ -1344,21 +1173,11 @@ int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* s, int which, i
 }
 
 int mythos_martini_langevin_last_recoveries(const mythos_martini_sim_t* s, int* recoveries) {
-  if (!s || !recoveries) {
-    set_error("mythos_martini_langevin_last_recoveries: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  *recoveries = s->last_recoveries;
-  return MYTHOS_OK;
+  return md_last_count(s, &MdRun::last_recoveries, recoveries, "mythos_martini_langevin_last_recoveries");
 }
 
 int mythos_martini_langevin_set_timing(mythos_martini_sim_t* s, int samples) {
-  if (!s || samples < 0) {
-    set_error("mythos_martini_langevin_set_timing: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  s->timing_samples = std::min(samples, (int)mythos_martini_sim::kMaxSamples);
-  return MYTHOS_OK;
+  return md_set_timing(s, samples, "mythos_martini_langevin_set_timing");
 }
 
 }  // extern "C"

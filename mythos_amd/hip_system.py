@@ -229,8 +229,58 @@ def _touched(*tensors) -> None:
             torch.autograd.graph.increment_version(t)
 
 
-class LangevinIntegrator:
+class _MdIntegrator:
+    """What the two Langevin integrators share: a handle of the C ABI whose entry points are named ``<_prefix>_*``
+    (mythos_langevin_* / mythos_martini_langevin_*) - its destruction, the step counter and the figures of the last run."""
+
+    _prefix = ""
+
+    def _fn(self, name):
+        return getattr(self._lib, f"{self._prefix}_{name}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    @property
+    def step(self) -> int:
+        return int(self._fn("get_step")(self._h))
+
+    def set_timing(self, samples: int) -> None:
+        """Bracket ``samples`` dispatches per run with HIP event pairs (0 = off, the default; see last_kernel_ms)."""
+        _lib.check(self._fn("set_timing")(self._h, int(samples)), "set_timing")
+
+    def _count(self, name: str) -> int:
+        r = C.c_int(0)
+        _lib.check(self._fn(name)(self._h, C.byref(r)), name)
+        return int(r.value)
+
+    def last_recoveries(self) -> int:
+        """Out-of-turn list rebuilds of the last run (a particle left its skin early, or rows / buckets had to grow)."""
+        return self._count("last_recoveries")
+
+    def last_rebuilds(self) -> int:
+        """Scheduled list rebuilds inside the last run / advance."""
+        return self._count("last_rebuilds")
+
+    def last_kernel_ms(self) -> dict:
+        """HIP-event timings of the last run (see include/mythos_hip.h)."""
+        k, loop, n, ns = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0)
+        _lib.check(self._fn("last_kernel_ms")(self._h, C.byref(k), C.byref(loop), C.byref(n), C.byref(ns)), "last_kernel_ms")
+        return {"kernel_ms": k.value, "loop_ms_per_launch": loop.value, "launches": n.value, "samples": ns.value}
+
+
+class LangevinIntegrator(_MdIntegrator):
     """BAOAB rigid-body Langevin dynamics bound to an :class:`OxdnaSystem`."""
+
+    _prefix = "mythos_langevin"
 
     def __init__(self, system: OxdnaSystem, dt, kT, gamma_t, gamma_r, mass=1.0, inertia=(1.0, 1.0, 1.0), seed=0):
         self.system = system
@@ -243,17 +293,6 @@ class LangevinIntegrator:
         if not self._h:
             raise _lib.MythosHipError(f"mythos_langevin_create: {_lib.last_error()}")
         self.dt, self.kT = float(dt), float(kT)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mythos_langevin_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     def set_neighbor_policy(self, r_cut: float, skin: float, every: int) -> None:
         _lib.check(
@@ -332,42 +371,13 @@ class LangevinIntegrator:
         _touched(center, quat, p_lin, p_ang)  # (the arrays are written even when closing an open frame failed)
         _lib.check(rc, "langevin_store")
 
-    @property
-    def step(self) -> int:
-        return int(self._lib.mythos_langevin_get_step(self._h))
-
-    @step.setter
+    @_MdIntegrator.step.setter
     def step(self, value: int) -> None:
         _lib.check(self._lib.mythos_langevin_set_step(self._h, int(value)), "set_step")
 
     def set_seed(self, seed: int) -> None:
         """Key of the noise from the next launch / init_momenta on (mythos_langevin_set_seed)."""
         _lib.check(self._lib.mythos_langevin_set_seed(self._h, C.c_uint64(int(seed) & (2**64 - 1))), "set_seed")
-
-    def set_timing(self, samples: int) -> None:
-        """Bracket ``samples`` dispatches per run with HIP event pairs (0 = off, the default; see last_kernel_ms)."""
-        _lib.check(self._lib.mythos_langevin_set_timing(self._h, int(samples)), "set_timing")
-
-    def last_recoveries(self) -> int:
-        """Out-of-turn list rebuilds of the last run (a site left its skin early, or rows / buckets had to grow)."""
-        r = C.c_int(0)
-        _lib.check(self._lib.mythos_langevin_last_recoveries(self._h, C.byref(r)), "last_recoveries")
-        return int(r.value)
-
-    def last_rebuilds(self) -> int:
-        """Scheduled list rebuilds inside the last run / advance."""
-        r = C.c_int(0)
-        _lib.check(self._lib.mythos_langevin_last_rebuilds(self._h, C.byref(r)), "last_rebuilds")
-        return int(r.value)
-
-    def last_kernel_ms(self) -> dict:
-        """HIP-event timings of the last run (see include/mythos_hip.h)."""
-        k, loop, n, ns = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0)
-        _lib.check(
-            self._lib.mythos_langevin_last_kernel_ms(self._h, C.byref(k), C.byref(loop), C.byref(n), C.byref(ns)),
-            "last_kernel_ms",
-        )
-        return {"kernel_ms": k.value, "loop_ms_per_launch": loop.value, "launches": n.value, "samples": ns.value}
 
 
 class MartiniSystem:
@@ -465,11 +475,12 @@ class MartiniSystem:
         return out
 
 
-class MartiniLangevinIntegrator:
+class MartiniLangevinIntegrator(_MdIntegrator):
     """BAOAB Langevin dynamics of a :class:`MartiniSystem` (mythos_martini_sim_t): LJ over a device-built Verlet
     list, bonds, angles; units nm, ps, amu, kJ/mol.  ``gamma`` is the friction rate in 1/ps."""
 
     KB = 0.0083144626  # kJ/mol/K
+    _prefix = "mythos_martini_langevin"
 
     def __init__(self, system: MartiniSystem, dt, kT, gamma, mass=None, seed=0):
         self.system = system
@@ -483,17 +494,6 @@ class MartiniLangevinIntegrator:
         self._h = self._lib.mythos_martini_langevin_create(system._h, float(dt), float(kT), float(gamma), mptr, int(seed))
         if not self._h:
             raise _lib.MythosHipError(f"mythos_martini_langevin_create: {_lib.last_error()}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mythos_martini_langevin_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
 
     def set_neighbor_policy(self, skin: float, every: int) -> None:
         _lib.check(self._lib.mythos_martini_langevin_set_neighbor_policy(self._h, float(skin), int(every)), "set_neighbor_policy")
@@ -554,31 +554,6 @@ class MartiniLangevinIntegrator:
         rc = self._lib.mythos_martini_langevin_store(self._h, _lib.ptr(pos), _lib.ptr(vel), _stream(self.system.device))
         _touched(pos, vel)
         _lib.check(rc, "martini_langevin_store")
-
-    @property
-    def step(self) -> int:
-        return int(self._lib.mythos_martini_langevin_get_step(self._h))
-
-    def last_rebuilds(self) -> int:
-        r = C.c_int(0)
-        _lib.check(self._lib.mythos_martini_langevin_last_rebuilds(self._h, C.byref(r)), "last_rebuilds")
-        return int(r.value)
-
-    def set_timing(self, samples: int) -> None:
-        """Bracket ``samples`` dispatches per run with HIP event pairs (0 = off, the default; see last_kernel_ms)."""
-        _lib.check(self._lib.mythos_martini_langevin_set_timing(self._h, int(samples)), "set_timing")
-
-    def last_recoveries(self) -> int:
-        """Out-of-turn list rebuilds of the last run (a bead left its skin early, or rows / buckets had to grow)."""
-        r = C.c_int(0)
-        _lib.check(self._lib.mythos_martini_langevin_last_recoveries(self._h, C.byref(r)), "last_recoveries")
-        return int(r.value)
-
-    def last_kernel_ms(self) -> dict:
-        k, loop, n, ns = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0)
-        _lib.check(self._lib.mythos_martini_langevin_last_kernel_ms(self._h, C.byref(k), C.byref(loop), C.byref(n), C.byref(ns)),
-                   "last_kernel_ms")
-        return {"kernel_ms": k.value, "loop_ms_per_launch": loop.value, "launches": n.value, "samples": ns.value}
 
     def rows(self, pruned: bool = False):
         """(rows (n, stride) int32, lengths (n,) int32) of the Verlet rows, or of the pruned rows, as numpy arrays

@@ -166,6 +166,30 @@ def test_a_bead_leaving_its_skin_halts_rebuilds_and_resumes_exactly():
         torch.testing.assert_close(x, y, rtol=1e-9, atol=1e-9)
 
 
+def test_a_nan_in_an_early_segment_is_reported_with_timing_on_and_drops_the_state():
+    """A NaN found behind the first of several segments, with timing on: the call ends there, before the event that
+    closes the run's interval is recorded - it reports the NaN (not a failed timing read-out) and the state is gone."""
+    from mythos_amd import _lib
+    from mythos_amd.hip_system import MartiniLangevinIntegrator
+
+    sysm, *_rest, x0, b0 = _make(torch.float32)
+    integ = MartiniLangevinIntegrator(sysm, dt=0.02, kT=KB * T, gamma=1.0, seed=4)
+    integ.set_neighbor_policy(0.3, 5)
+    integ.set_timing(4)
+    pos = torch.as_tensor(x0, dtype=torch.float32, device=sysm.device).contiguous()
+    vel = integ.init_velocities()
+    vel[0, 0] = float("nan")  # the first launch's output is not finite
+    integ.load(pos, vel, b0)
+    _lib.debug_set("md_segment", 4)
+    try:
+        with pytest.raises(FloatingPointError, match="NaN"):  # (MYTHOS_ERR_NUMERIC)
+            integ.advance(200)
+    finally:
+        _lib.debug_set("md_segment", 0)
+    with pytest.raises(_lib.MythosHipError, match="no resident state"):
+        integ.advance(1)
+
+
 def test_cfg3_bilayer_20480_beads():
     """BASELINE configs[2]: the shipped bilayer tiled 4 x 4; the tiled system must evolve like 16 copies at step 0
     (same energies per tile) and stay at temperature."""
