@@ -3,7 +3,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "mythos_internal.h"
+#include "cell_list.h"
 #include "observables.h"
 
 namespace mythos {
@@ -133,11 +133,11 @@ mythos_system_t* mythos_oxdna_create(int model, int n, const int32_t* seq, const
   }
   bool ok = hipMalloc((void**)&s->d_meta, n * sizeof(int)) == hipSuccess &&
             hipMalloc((void**)&s->d_row_len, (size_t)(2 + ROW_BONDED_SLOTS) * n * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&s->d_overflow, kOverflowWords * sizeof(int)) == hipSuccess &&
+            hipMalloc((void**)&s->list.d_overflow, kOverflowWords * sizeof(int)) == hipSuccess &&
             hipMemcpy(s->d_meta, meta.data(), n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(s->d_row_len + n, s->h_partners.data(), (size_t)ROW_BONDED_SLOTS * n * sizeof(int), hipMemcpyHostToDevice) ==
                 hipSuccess &&
-            hipMemset(s->d_overflow, 0, kOverflowWords * sizeof(int)) == hipSuccess;
+            hipMemset(s->list.d_overflow, 0, kOverflowWords * sizeof(int)) == hipSuccess;
   if (!ok) {
     set_error("mythos_oxdna_create: device allocation failed");
     mythos_oxdna_destroy(s);
@@ -150,10 +150,10 @@ void mythos_oxdna_destroy(mythos_system_t* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
   if (s->d_meta) (void)hipFree(s->d_meta);
-  if (s->d_rows) (void)hipFree(s->d_rows);
+  if (s->list.d_rows) (void)hipFree(s->list.d_rows);
   if (s->d_row_len) (void)hipFree(s->d_row_len);
-  if (s->d_overflow) (void)hipFree(s->d_overflow);
-  if (s->d_cell) (void)hipFree(s->d_cell);
+  if (s->list.d_overflow) (void)hipFree(s->list.d_overflow);
+  if (s->list.d_cell) (void)hipFree(s->list.d_cell);
   if (s->d_ref_pos) (void)hipFree(s->d_ref_pos);
   if (s->d_ref_off) (void)hipFree(s->d_ref_off);
   if (s->d_ref_a1) (void)hipFree(s->d_ref_a1);
@@ -342,17 +342,7 @@ int mythos_oxdna_neighbor_stats(mythos_system_t* s, int* max_row, double* mean_r
     return MYTHOS_ERR_NOT_READY;
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
-  std::vector<int> len(s->n);
-  MYTHOS_HIP_TRY(hipMemcpy(len.data(), s->d_row_len, s->n * sizeof(int), hipMemcpyDeviceToHost));
-  long long tot = 0;
-  int mx = 0;
-  for (int v : len) {
-    tot += v - ROW_BONDED_SLOTS;
-    mx = std::max(mx, v - ROW_BONDED_SLOTS);
-  }
-  if (max_row) *max_row = mx;
-  if (mean_row) *mean_row = double(tot) / s->n;
-  return MYTHOS_OK;
+  return row_stats(s->d_row_len, s->n, ROW_BONDED_SLOTS, max_row, mean_row);
 }
 
 int mythos_oxdna_energy(mythos_system_t* s, const void* center, const void* quat, int n_frames, double* e_terms,

@@ -1,12 +1,18 @@
 // Cell list shared by the neighbour-row builders (oxDNA: neighbors.hip, MARTINI: martini_md.hip): a hashed (free
-// space) or direct-mapped (periodic) table of fixed-capacity buckets filled by one kernel.  Kernels are file-local
-// (static) because this header is compiled into more than one translation unit.
+// space) or direct-mapped (periodic) table of fixed-capacity buckets filled by one kernel, the candidate table at the top
+// of both cell-row kernels, and the host side of a VerletRows store (mythos_internal.h): rows, cell grid and table, the
+// build that grows until it fits, row statistics.  Kernels are file-local (static) because this header is compiled into
+// more than one translation unit.
 #ifndef MYTHOS_CELL_LIST_H
 #define MYTHOS_CELL_LIST_H
 
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "mythos_internal.h"
 
 namespace mythos {
 
@@ -90,6 +96,7 @@ struct CellBins {
   }
   // view on one allocation of ints(H, cap, sizeof(R)) ints whose counter halves were zeroed when it was made (see
   // zero_offset / zero_ints); phase flips per build
+  CellBins() = default;
   CellBins(int* base, int H_, int cap_, size_t real_bytes, int phase, bool sites_ = false)
       : place(base), H(H_), cap(cap_), sites(sites_) {
     int* c = base + place_ints(H_, cap_, real_bytes, sites_);
@@ -237,10 +244,9 @@ static __global__ __launch_bounds__(256) void cell_sort_bins_kernel(int H, const
 }
 
 // mythos_debug_set(MYTHOS_DEBUG_CELL_BUCKET_CAP, places): fixes the bucket capacity (no growth), e.g. to a handful of
-// places to exercise the spill path in tests.  0: managed by the callers.
-long long debug_value(int key);
+// places to exercise the spill path in tests.  0: managed by cell_table / list_build_until_fit.
 static inline int cell_cap_override() {
-  const long long v = debug_value(0 /* MYTHOS_DEBUG_CELL_BUCKET_CAP */);
+  const long long v = debug_value(MYTHOS_DEBUG_CELL_BUCKET_CAP);
   return v > 0 ? (int)v : 0;
 }
 
@@ -250,7 +256,7 @@ static inline int next_pow2(int v) {
   return p;
 }
 
-// bins n particles at pos (stride 3 or 4 reals) into b; overflow: int[3] of the caller ([0] rows, [1] spill list over
+// bins n particles at pos (stride 3 or 4 reals) into b; overflow: the kOverflowWords of the caller ([0] rows, [1] spill list over
 // capacity, [2] fullest bucket if over half its capacity), not cleared here.  sort_buckets: order every bucket by particle index afterwards (one more launch).
 // off, a1 (with b.sites; real4 per particle): copied into the two site streams; the bucket sort moves the first stream only
 template <typename R, bool VEC4>
@@ -266,6 +272,141 @@ static inline void cell_bins_build(int n, const R* pos, CellGrid<R>& g, const Ce
   if (sort_buckets)
     hipLaunchKernelGGL((cell_sort_bins_kernel<R, VEC4>), dim3((b.H + 1 + 3) / 4), dim3(256), 0, st, b.H, b.cnt_cur, b.bucket, b.cap,
                        b.spill, pos, (typename CellPlace<R>::type*)b.place);
+}
+
+// The candidates of one row, at the top of both cell-row kernels: the 27 cells around (x, y, z) - edges wrap where the grid
+// is periodic - and the spill list (k = 27: particles whose bucket was full, candidates for every row), G at a time by the
+// G lanes of a group (l: the lane's index in it).  Fills the group's rows of the kernel's LDS tables: pre[k] .. pre[k + 1]
+// are the candidate numbers of cell k (pre[28] the total, returned), st[k] where its places start in the table, c[k] its
+// coordinates (a hashed table holds candidates of other cells too).  The running sum is an inclusive scan over the group's
+// lanes through the cross-lane network (one lane adding up 28 LDS words was 1.5 us of every row's chain).
+template <typename R, int G>
+__device__ __forceinline__ int cell_candidates(const CellGrid<R>& g, R x, R y, R z, const int* __restrict__ cell_cnt,
+                                               int cell_cap, int cell_H, int* pre, int* st, int (*c)[3], int l) {
+  int cx, cy, cz;
+  cell_of(g, x, y, z, cx, cy, cz);
+  int carry = 0;
+  if (l == 0) pre[0] = 0;
+  for (int k0 = 0; k0 < 28; k0 += G) {
+    const int k = k0 + l;
+    int cnt = 0;
+    if (k < 27) {
+      int ck[3] = {cx + k % 3 - 1, cy + (k / 3) % 3 - 1, cz + k / 9 - 1};
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        if (g.nc[a] > 0) ck[a] = (ck[a] + g.nc[a]) % g.nc[a];
+      const int h = cell_slot(g, ck[0], ck[1], ck[2]);
+      cnt = min(cell_cnt[h], cell_cap);
+      st[k] = h * cell_cap;
+      c[k][0] = ck[0], c[k][1] = ck[1], c[k][2] = ck[2];
+    } else if (k == 27) {
+      cnt = min(cell_cnt[cell_H], kCellSpill);
+    }
+    int run = cnt;
+#pragma unroll
+    for (int d = 1; d < G; d <<= 1) {
+      const int o = __shfl_up(run, d, G);
+      if (l >= d) run += o;
+    }
+    if (k < 28) pre[k + 1] = carry + run;
+    carry += __shfl(run, G - 1, G);
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  return pre[28];
+}
+
+// ---- host side of a VerletRows store
+
+// rows of n particles at the given stride; the allocation only grows
+static inline int rows_reserve(VerletRows& L, int n, int stride) {
+  if (int rc = grow_buffer(L.d_rows, L.rows_cap, (size_t)n * stride)) return rc;
+  L.stride = stride;
+  return 0;
+}
+
+// The cell grid of list range rl: cells of edge >= rl over a periodic box, or over free space (box == null; the table
+// hashes them).  false: the all-pairs kernel builds the rows instead - fewer than 512 particles, or a periodic edge
+// shorter than three cells.
+template <typename R>
+static inline bool cell_grid(CellGrid<R>& g, int n, double rl, const double* box) {
+  bool ok = n >= 512;
+  for (int k = 0; k < 3; ++k) {
+    if (box) {
+      const int nc = (int)std::floor(box[k] / rl);
+      if (nc < 3) ok = false;
+      g.nc[k] = std::max(nc, 1);
+      g.ibox[k] = R(1.0 / box[k]);
+      g.inv[k] = R(g.nc[k] / box[k]);
+    } else {
+      g.nc[k] = 0;
+      g.ibox[k] = R(1);
+      g.inv[k] = R(1.0 / rl);
+    }
+  }
+  return ok;
+}
+
+// The cell table of one build: H slots (the caller decides H and whether the grid is direct-mapped) of the store's bucket
+// capacity, with the site streams or without.  A new layout zeroes the counters; every build counts into the other half.
+template <typename R>
+static inline int cell_table(VerletRows& L, int H, bool sites, hipStream_t st, CellBins& bins) {
+  if (cell_cap_override()) L.cell_bucket_cap = cell_cap_override();
+  const int cap = L.cell_bucket_cap;
+  if (!L.d_cell || H != L.cell_H || cap != L.cell_alloc_bucket_cap || sites != L.cell_sites) {
+    if (int rc = grow_buffer(L.d_cell, L.cell_cap, CellBins::ints(H, cap, sizeof(R), sites))) return rc;
+    MYTHOS_HIP_TRY(hipMemsetAsync(L.d_cell + CellBins::zero_offset(H, cap, sizeof(R), sites), 0, CellBins::zero_ints(H) * sizeof(int), st));
+    L.cell_H = H;
+    L.cell_alloc_bucket_cap = cap;
+    L.cell_sites = sites;
+    L.cell_phase = 0;
+  }
+  bins = CellBins(L.d_cell, H, cap, sizeof(R), L.cell_phase, sites);
+  L.cell_phase ^= 1;
+  return 0;
+}
+
+// Builds the rows of n particles, growing the row stride and the bucket capacity until the build fits (synchronises the
+// stream).  Buckets end up at most half full (fuller ones work, through the spill list, but slowly).  headroom: leave a
+// quarter of spare row length for builds that follow without a chance to grow (inside an MD run, where an overflow halts
+// the launches).  build(): one build into L, 0 or an error code; who: the prefix of the error messages.
+template <class Build>
+static int list_build_until_fit(VerletRows& L, int n, Build&& build, bool headroom, const char* who, hipStream_t st) {
+  for (int attempt = 0; attempt < 6; ++attempt) {
+    MYTHOS_HIP_TRY(hipMemsetAsync(L.d_overflow, 0, kOverflowWords * sizeof(int), st));
+    if (int rc = build()) return rc;
+    int ov[kOverflowWords] = {0, 0, 0};
+    MYTHOS_HIP_TRY(hipMemcpyAsync(ov, L.d_overflow, sizeof(ov), hipMemcpyDeviceToHost, st));
+    MYTHOS_HIP_TRY(hipStreamSynchronize(st));
+    if (ov[1] > 0) {
+      set_error(std::string(who) + ": more than " + std::to_string(kCellSpill) + " particles did not fit the buckets of their cells");
+      return MYTHOS_ERR_OVERFLOW;
+    }
+    const int bucket_demand = cell_cap_override() ? 0 : ov[2];  // a bucket more than half full: double the places
+    if (ov[0] == 0 && bucket_demand == 0) {
+      if (ov[2] > 0) MYTHOS_HIP_TRY(hipMemsetAsync(L.d_overflow + 2, 0, sizeof(int), st));
+      return MYTHOS_OK;
+    }
+    if (ov[0] > 0) {
+      const int want = headroom ? ((ov[0] + ov[0] / 4 + 15) / 16) * 16 : ((ov[0] + 15) / 16) * 16 + 16;
+      if (int rc = rows_reserve(L, n, want)) return rc;
+    }
+    if (bucket_demand > 0) L.cell_bucket_cap = ((2 * bucket_demand + 15) / 16) * 16;  // laid out by the next build
+  }
+  set_error(std::string(who) + ": rows or cell buckets keep overflowing");
+  return MYTHOS_ERR_OVERFLOW;
+}
+
+// longest and mean row of n rows whose lengths are at d_len, less `fixed` slots of each (oxDNA: the bonded ones)
+static inline int row_stats(const int* d_len, int n, int fixed, int* max_row, double* mean_row) {
+  std::vector<int> len(n);
+  MYTHOS_HIP_TRY(hipMemcpy(len.data(), d_len, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  long long tot = 0;
+  int mx = 0;
+  for (int v : len) tot += v - fixed, mx = std::max(mx, v - fixed);
+  if (max_row) *max_row = mx;
+  if (mean_row) *mean_row = double(tot) / std::max(1, n);
+  return MYTHOS_OK;
 }
 
 }  // namespace mythos

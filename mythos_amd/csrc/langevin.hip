@@ -108,8 +108,8 @@ int md_ready(mythos_sim_t* s, const char* who) {
     set_error(std::string(who) + ": parameters and neighbours (or a neighbour policy) must be set first");
     return MYTHOS_ERR_NOT_READY;
   }
-  if (s->rebuild_every > 0 && sys->row_stride == 0)
-    if (int rc = rows_reserve(sys, 64)) return rc;
+  if (s->rebuild_every > 0 && sys->list.stride == 0)
+    if (int rc = rows_reserve(sys->list, sys->n, 64)) return rc;
   if (s->list_epoch != sys->list_epoch) {  // parameters or rows were replaced behind the integrator's back
     s->list_valid = false;
     s->list_epoch = sys->list_epoch;

@@ -40,6 +40,7 @@
 #define MYTHOS_LEAN_MATH 1
 #endif
 
+#include "cell_list.h"
 #include "chunk_order.h"
 #include "md_driver.h"
 #include "oxdna_gather.h"
@@ -1397,7 +1398,7 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
   const bool use_pseq = sys->pseq_terms != 0;
   if (debug_value(MYTHOS_DEBUG_MD_ITEMS_BIG) == 1) sim->items_big = true;  // (tests: the wide instantiations without a crowded system)
   if (use_pseq) pseq.marg = (const R*)sys->d_ps_marg, pseq.unit = sys->d_ps_unit, pseq.bp = (const R*)sys->d_ps_bp, pseq.terms = sys->pseq_terms;
-  int* halt_words = dynamic_list ? sys->d_overflow : nullptr;
+  int* halt_words = dynamic_list ? sys->list.d_overflow : nullptr;
   auto launch_step = [&](int k, const LaunchRow& row) {
     const int cur = row.cur;
     const bool save = row.save;
@@ -1412,8 +1413,8 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
       constexpr int IT = decltype(items_tag)::value;
       auto go = [&](auto lanes_tag) {
         hipExtLaunchKernelGGL((md_step_kernel<R, MODEL, SV, IT, true, false, decltype(lanes_tag)::value>), dim3(grid), dim3(kMdBlock), 0, st, ea, eb, 0,
-                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->d_rows, sys->d_row_len, row_close_of(sys),
-                              sys->row_stride, sys->extra_bonds ? 1 : 0, kick_close, row.do_step, sim->seed, (uint64_t)(sim->step + k), ref,
+                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->list.d_rows, sys->d_row_len, row_close_of(sys),
+                              sys->list.stride, sys->extra_bonds ? 1 : 0, kick_close, row.do_step, sim->seed, (uint64_t)(sim->step + k), ref,
                               ref_off, ref_a1, sim->d_flags, tc, tq, sim->d_epart, sim->d_chunk_order, halt_words, k, 0, prio_on, pseq);
       };
       if (lanes16) go(std::integral_constant<int, 16>{}); else go(std::integral_constant<int, 8>{});
@@ -1425,8 +1426,8 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
       // kernel trace reports), not the time between two markers in the queue
       auto go = [&](auto dense_tag, auto lanes_tag) {
         hipExtLaunchKernelGGL((md_step_kernel<R, MODEL, SV, IT, false, decltype(dense_tag)::value, decltype(lanes_tag)::value>), dim3(grid), dim3(kMdBlock), 0, st, ea, eb, 0,
-                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->d_rows, sys->d_row_len, row_close_of(sys),
-                              sys->row_stride, sys->extra_bonds ? 1 : 0, kick_close, row.do_step, sim->seed, (uint64_t)(sim->step + k), ref,
+                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->list.d_rows, sys->d_row_len, row_close_of(sys),
+                              sys->list.stride, sys->extra_bonds ? 1 : 0, kick_close, row.do_step, sim->seed, (uint64_t)(sim->step + k), ref,
                               ref_off, ref_a1, sim->d_flags, tc, tq, sim->d_epart, sim->d_chunk_order, halt_words, k, 0, prio_on, PseqView<R>{});
       };
       using L8 = std::integral_constant<int, 8>;
@@ -1485,7 +1486,7 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
   d.plain_rows = save_every > 0 && e_trace == nullptr && (traj_center != nullptr || traj_quat != nullptr);
   d.dynamic_list = dynamic_list;
   d.halt_words = halt_words;
-  d.row_stride = &sys->row_stride;
+  d.row_stride = &sys->list.stride;
   d.skin = sim->skin;
   d.st = st;
   return md_drive(*sim, d, launch_step, rebuild, rebuild_until_fit, on_abort);

@@ -397,29 +397,10 @@ using namespace mythos;
 
 namespace mythos {
 
-template <typename R>
-static bool upload_real(void** dst, const double* src, size_t count) {
-  std::vector<R> tmp(std::max<size_t>(count, 1));
-  for (size_t k = 0; k < count; ++k) tmp[k] = R(src[k]);
-  return hipMalloc(dst, tmp.size() * sizeof(R)) == hipSuccess &&
-         hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(R), hipMemcpyHostToDevice) == hipSuccess;
-}
-
 static bool upload_int(int** dst, const std::vector<int>& v) {
   const size_t c = std::max<size_t>(v.size(), 1);
   return hipMalloc((void**)dst, c * sizeof(int)) == hipSuccess &&
          (v.empty() || hipMemcpy(*dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess);
-}
-
-template <typename T>
-static int grow(T*& ptr, size_t& cap, size_t need) {
-  if (need <= cap) return 0;
-  if (ptr) (void)hipFree(ptr);
-  ptr = nullptr;
-  cap = 0;
-  MYTHOS_HIP_TRY(hipMalloc((void**)&ptr, need * sizeof(T)));
-  cap = need;
-  return 0;
 }
 
 template <typename R>
@@ -436,10 +417,10 @@ static int martini_energy_typed(mythos_martini* m, const R* pos, const R* box, i
     int nf = (int)std::min<size_t>(std::min(n_frames - f0, 4096), std::max<size_t>(1, (size_t(512) << 20) / per_frame));
     if (nf > 16) n_js = std::max(1, n_js / 4);  // many frames already fill the GPU
     char* fp = (char*)m->d_fpart;
-    if (int rc = grow(fp, m->fpart_cap, (size_t)nf * (n_js + 1) * n * 3 * sizeof(R))) return rc;
+    if (int rc = grow_buffer(fp, m->fpart_cap, (size_t)nf * (n_js + 1) * n * 3 * sizeof(R))) return rc;
     m->d_fpart = fp;
-    if (int rc = grow(m->d_epart, m->epart_cap, (size_t)nf * n_js * nbx)) return rc;
-    if (int rc = grow(m->d_ebpart, m->ebpart_cap, (size_t)nf * nbb * 2)) return rc;
+    if (int rc = grow_buffer(m->d_epart, m->epart_cap, (size_t)nf * n_js * nbx)) return rc;
+    if (int rc = grow_buffer(m->d_ebpart, m->ebpart_cap, (size_t)nf * nbb * 2)) return rc;
     MartiniConst<R> K{R(m->r_cut * m->r_cut), m->n_types, m->angle_kind};
     const size_t lds = (size_t)3 * m->n_types * m->n_types * sizeof(R) + 3 * kLjBlock * sizeof(R) + kLjBlock * sizeof(int);
     const R* p = pos + (size_t)f0 * n * 3;
@@ -485,7 +466,7 @@ static int martini_pgrad_typed(mythos_martini* m, const R* pos, const R* box, in
     const int n_wg = nbx * n_js;  // workgroups, and partial tables, per frame
     // frames per chunk: at most 256 MB of partial tables
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(4096, (size_t(256) << 20) / ((size_t)n_wg * 2 * tt * sizeof(double))));
-    if (int rc = grow(m->d_ljpart, m->ljpart_cap, (size_t)std::min(chunk, n_frames) * n_wg * 2 * tt)) return rc;
+    if (int rc = grow_buffer(m->d_ljpart, m->ljpart_cap, (size_t)std::min(chunk, n_frames) * n_wg * 2 * tt)) return rc;
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
       const int nf = std::min(n_frames - f0, chunk);
       hipLaunchKernelGGL(martini_lj_pgrad_kernel<R>, dim3(nbx, n_js, nf),
@@ -567,14 +548,9 @@ mythos_martini_t* mythos_martini_create(int n, const int32_t* types, int n_types
   bool ok = upload_int(&m->d_types, ht) && upload_int(&m->d_excl, excl) && upload_int(&m->d_bead_bonds, bb) &&
             upload_int(&m->d_bead_angles, ba) && upload_int(&m->d_bonds, hb) && upload_int(&m->d_angles, ha);
   const size_t tt = (size_t)n_types * n_types;
-  if (dtype == MYTHOS_F32)
-    ok = ok && upload_real<float>(&m->d_sigma, sigma, tt) && upload_real<float>(&m->d_eps, eps, tt) &&
-         upload_real<float>(&m->d_bond_k, bond_k, n_bonds) && upload_real<float>(&m->d_bond_r0, bond_r0, n_bonds) &&
-         upload_real<float>(&m->d_angle_k, angle_k, n_angles) && upload_real<float>(&m->d_angle_t0, angle_t0, n_angles);
-  else
-    ok = ok && upload_real<double>(&m->d_sigma, sigma, tt) && upload_real<double>(&m->d_eps, eps, tt) &&
-         upload_real<double>(&m->d_bond_k, bond_k, n_bonds) && upload_real<double>(&m->d_bond_r0, bond_r0, n_bonds) &&
-         upload_real<double>(&m->d_angle_k, angle_k, n_angles) && upload_real<double>(&m->d_angle_t0, angle_t0, n_angles);
+  ok = ok && upload_real(dtype, &m->d_sigma, sigma, tt) && upload_real(dtype, &m->d_eps, eps, tt) &&
+       upload_real(dtype, &m->d_bond_k, bond_k, n_bonds) && upload_real(dtype, &m->d_bond_r0, bond_r0, n_bonds) &&
+       upload_real(dtype, &m->d_angle_k, angle_k, n_angles) && upload_real(dtype, &m->d_angle_t0, angle_t0, n_angles);
   if (!ok) {
     set_error("mythos_martini_create: device allocation failed");
     mythos_martini_destroy(m);

@@ -2,6 +2,9 @@
 #ifndef MYTHOS_MARTINI_INTERNAL_H
 #define MYTHOS_MARTINI_INTERNAL_H
 
+#include <algorithm>
+#include <vector>
+
 #include "mythos_internal.h"
 
 namespace mythos {
@@ -22,6 +25,18 @@ struct MartiniConst {
 template <typename R>
 __device__ __forceinline__ R wrap(R d, R l, R il) {
   return d - l * m_rint(d * il);
+}
+
+// count doubles -> a new device vector of reals in the system's precision (dtype); at least one element is allocated
+inline bool upload_real(int dtype, void** dst, const double* src, size_t count) {
+  auto up = [&](auto zero) {
+    using R = decltype(zero);
+    std::vector<R> tmp(std::max<size_t>(count, 1), zero);
+    for (size_t k = 0; k < count; ++k) tmp[k] = R(src[k]);
+    return hipMalloc(dst, tmp.size() * sizeof(R)) == hipSuccess &&
+           hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(R), hipMemcpyHostToDevice) == hipSuccess;
+  };
+  return dtype == MYTHOS_F32 ? up(0.0f) : up(0.0);
 }
 
 }  // namespace mythos

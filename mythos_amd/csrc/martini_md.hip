@@ -459,36 +459,7 @@ __global__ __launch_bounds__(256) void mm_build_rows_cells_kernel(
   const int i = blockIdx.x * NG + grp;
   if (i >= n) return;
   const auto pi = pos[i];
-  int cx, cy, cz;
-  cell_of(g, pi.x, pi.y, pi.z, cx, cy, cz);
-  for (int k = l; k < 28; k += G) {
-    int cnt;
-    if (k < 27) {
-      int c[3] = {cx + k % 3 - 1, cy + (k / 3) % 3 - 1, cz + k / 9 - 1};
-#pragma unroll
-      for (int a = 0; a < 3; ++a) c[a] = (c[a] + g.nc[a]) % g.nc[a];
-      const int h = cell_slot(g, c[0], c[1], c[2]);
-      cnt = min(cell_cnt[h], cell_cap);
-      s_st[grp][k] = h * cell_cap;
-      s_c[grp][k][0] = c[0], s_c[grp][k][1] = c[1], s_c[grp][k][2] = c[2];
-    } else {  // the spill list: particles whose bucket was full, candidates for every row
-      cnt = min(cell_cnt[cell_H], kCellSpill);
-    }
-    s_pre[grp][k + 1] = cnt;
-  }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  if (l == 0) {
-    int run = 0;
-    s_pre[grp][0] = 0;
-    for (int k = 1; k <= 28; ++k) {
-      run += s_pre[grp][k];
-      s_pre[grp][k] = run;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  const int total = s_pre[grp][28];
+  const int total = cell_candidates<R, G>(g, pi.x, pi.y, pi.z, cell_cnt, cell_cap, cell_H, s_pre[grp], s_st[grp], s_c[grp], l);
   int ex[kMaxExcl];
 #pragma unroll
   for (int q = 0; q < kMaxExcl; ++q) ex[q] = excl[(size_t)i * kMaxExcl + q];
@@ -623,10 +594,8 @@ struct mythos_martini_sim : mythos::MdRun {
   int* d_bb_partner = nullptr;
   int2* d_ba_partner = nullptr;
   void* d_angle_ref = nullptr;  // per angle: cos(theta0) for the G96 form (once, instead of a cosine per lane and step), theta0 for the harmonic one
-  int *d_rows = nullptr, *d_row_len = nullptr, *d_cell = nullptr, *d_overflow = nullptr;
-  size_t cell_cap = 0;       // ints allocated at d_cell (cell_list.h CellBins: counters [2][H], buckets [H][cap])
-  int cell_H = 0, cell_alloc_bucket_cap = 0, cell_bucket_cap = 64, cell_phase = 0;
-  int row_stride = 256;
+  mythos::VerletRows list{64};  // cell buckets start at 64 places; the rows at a stride of 256 (allocated at create)
+  int* d_row_len = nullptr;
   // pruned rows (martini_md_step_kernel, EMIT): entries of the Verlet rows inside r_c + inner_margin, rewritten every
   // inner_every steps by the step launch itself; inner_margin <= 0 or inner_every < 2: not used
   int *d_rows_in = nullptr, *d_row_len_in = nullptr;
@@ -640,59 +609,29 @@ struct mythos_martini_sim : mythos::MdRun {
 namespace mythos {
 
 template <typename R>
-static bool upload_real_vec(void** dst, const std::vector<double>& src) {
-  std::vector<R> tmp(src.size());
-  for (size_t k = 0; k < src.size(); ++k) tmp[k] = R(src[k]);
-  return hipMalloc(dst, std::max<size_t>(tmp.size(), 1) * sizeof(R)) == hipSuccess &&
-         hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(R), hipMemcpyHostToDevice) == hipSuccess;
-}
-
-template <typename R>
 static int mm_rebuild(mythos_martini_sim* sim, const typename Real4<R>::type* pos, const MmConst<R>& K, const double box[3],
                       hipStream_t st) {
   mythos_martini* m = sim->sys;
+  VerletRows& L = sim->list;
   const int n = m->n;
   const double rl = m->r_cut + sim->skin;
   CellGrid<R> g;
-  bool cells_ok = n >= 512;
-  for (int k = 0; k < 3; ++k) {
-    const int nc = (int)std::floor(box[k] / rl);
-    if (nc < 3) cells_ok = false;
-    g.nc[k] = std::max(nc, 1);
-    g.ibox[k] = R(1.0 / box[k]);
-    g.inv[k] = R(g.nc[k] / box[k]);
+  if (!cell_grid(g, n, rl, box)) {
+    hipLaunchKernelGGL(mm_build_rows_allpairs_kernel<R>, dim3((n + 3) / 4), dim3(256), 0, st, n, pos, K, R(rl * rl), m->d_excl,
+                       L.d_rows, sim->d_row_len, L.stride, L.d_overflow, (typename Real4<R>::type*)sim->ref_pos);
+    return 0;
   }
-  const int wb = (n + 3) / 4;
-  if (!cells_ok) {
-    hipLaunchKernelGGL(mm_build_rows_allpairs_kernel<R>, dim3(wb), dim3(256), 0, st, n, pos, K, R(rl * rl), m->d_excl,
-                       sim->d_rows, sim->d_row_len, sim->row_stride, sim->d_overflow, (typename Real4<R>::type*)sim->ref_pos);
-  } else {
-    // periodic grid: one table slot per cell (no hashing) whenever the grid is not much larger than the system
-    const long long n_cells = (long long)g.nc[0] * g.nc[1] * g.nc[2];
-    g.direct = n_cells <= 8LL * n ? 1 : 0;
-    const int H = g.direct ? (int)n_cells : next_pow2(2 * n);
-    if (cell_cap_override()) sim->cell_bucket_cap = cell_cap_override();
-    const int cap = sim->cell_bucket_cap;
-    const size_t need = CellBins::ints(H, cap, sizeof(R));
-    if (need > sim->cell_cap || H != sim->cell_H || cap != sim->cell_alloc_bucket_cap) {
-      if (sim->d_cell) (void)hipFree(sim->d_cell);
-      sim->d_cell = nullptr;
-      sim->cell_cap = 0;
-      MYTHOS_HIP_TRY(hipMalloc((void**)&sim->d_cell, need * sizeof(int)));
-      MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_cell + CellBins::zero_offset(H, cap, sizeof(R)), 0, CellBins::zero_ints(H) * sizeof(int), st));
-      sim->cell_cap = need;
-      sim->cell_H = H;
-      sim->cell_alloc_bucket_cap = cap;
-      sim->cell_phase = 0;
-    }
-    const CellBins bins(sim->d_cell, H, cap, sizeof(R), sim->cell_phase);
-    sim->cell_phase ^= 1;
-    // buckets sorted by bead index: the row builder copies candidates in bucket order, and rows must not depend on
-    // the order in which the binning atomics landed
-    cell_bins_build<R, true>(n, reinterpret_cast<const R*>(pos), g, bins, sim->d_overflow, true, st);
-hipLaunchKernelGGL((mm_build_rows_cells_kernel<R, kMmRowG>), dim3((n + 256 / kMmRowG - 1) / (256 / kMmRowG)), dim3(256), 0, st, n, pos, K, g, R(rl * rl), m->d_excl,
-                       bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, sim->d_rows, sim->d_row_len, sim->row_stride, sim->d_overflow, (typename Real4<R>::type*)sim->ref_pos);
-  }
+  // one table slot per cell (no hashing) whenever the grid is not much larger than the system
+  const long long n_cells = (long long)g.nc[0] * g.nc[1] * g.nc[2];
+  g.direct = n_cells <= 8LL * n ? 1 : 0;
+  CellBins bins;
+  if (int rc = cell_table<R>(L, g.direct ? (int)n_cells : next_pow2(2 * n), false, st, bins)) return rc;
+  // buckets sorted by bead index: the row builder copies candidates in bucket order, and rows must not depend on
+  // the order in which the binning atomics landed
+  cell_bins_build<R, true>(n, reinterpret_cast<const R*>(pos), g, bins, L.d_overflow, true, st);
+  hipLaunchKernelGGL((mm_build_rows_cells_kernel<R, kMmRowG>), dim3((n + 256 / kMmRowG - 1) / (256 / kMmRowG)), dim3(256), 0, st, n, pos, K, g,
+                     R(rl * rl), m->d_excl, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H,
+                     L.d_rows, sim->d_row_len, L.stride, L.d_overflow, (typename Real4<R>::type*)sim->ref_pos);
   return 0;
 }
 
@@ -752,50 +691,16 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
   const double* box = sim->box;
   V4* fr[2] = {(V4*)sim->frame[0], (V4*)sim->frame[1]};
   V4* vel = (V4*)sim->vel;
-  // A build that may grow: rows until the longest fits with a quarter of headroom, buckets until none is more than
-  // half full (fuller ones work, through the spill list, but slowly).  Used for the first build of an integrator and to
-  // recover from a halt; the scheduled builds inside a call cannot stop to grow.
-  auto build_until_fit = [&](int buf) -> int {
-    for (int attempt = 0;; ++attempt) {
-      MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_overflow, 0, 3 * sizeof(int), st));
-      if (int rc = mm_rebuild<R>(sim, fr[buf], K, box, st)) return rc;
-      int ov0[3] = {0, 0, 0};
-      MYTHOS_HIP_TRY(hipMemcpyAsync(ov0, sim->d_overflow, sizeof(ov0), hipMemcpyDeviceToHost, st));
-      MYTHOS_HIP_TRY(hipStreamSynchronize(st));
-      if (ov0[1] > 0) {
-        set_error("mythos_martini_langevin_run: more than " + std::to_string(kCellSpill) +
-                  " beads did not fit the buckets of their cells during a neighbour rebuild");
-        return MYTHOS_ERR_OVERFLOW;
-      }
-      const int demand = cell_cap_override() ? 0 : ov0[2];  // a bucket more than half full: double the places
-      if (ov0[0] == 0 && demand == 0) {
-        if (ov0[2] > 0) MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_overflow + 2, 0, sizeof(int), st));
-        return 0;
-      }
-      if (attempt == 5) {
-        set_error("mythos_martini_langevin_run: neighbour rows or cell buckets keep overflowing");
-        return MYTHOS_ERR_OVERFLOW;
-      }
-      if (ov0[0] > 0) {
-        const int stride = ((ov0[0] + ov0[0] / 4 + 15) / 16) * 16;
-        (void)hipFree(sim->d_rows);
-        sim->d_rows = nullptr;
-        MYTHOS_HIP_TRY(hipMalloc((void**)&sim->d_rows, (size_t)n * stride * sizeof(int)));
-        sim->row_stride = stride;
-      }
-      if (demand > 0) sim->cell_bucket_cap = ((2 * demand + 15) / 16) * 16;
-    }
-  };
   const bool inner_on = mm_inner_on(sim);
   // the pruned rows share the Verlet rows' stride (a pruned row is a subset of its row: it cannot overflow)
   auto ensure_inner = [&]() -> int {
     if (!inner_on) return 0;
     if (!sim->d_row_len_in) MYTHOS_HIP_TRY(hipMalloc((void**)&sim->d_row_len_in, (size_t)n * sizeof(int)));
-    if (!sim->d_rows_in || sim->rows_in_stride != sim->row_stride) {
+    if (!sim->d_rows_in || sim->rows_in_stride != sim->list.stride) {
       if (sim->d_rows_in) (void)hipFree(sim->d_rows_in);
       sim->d_rows_in = nullptr;
-      MYTHOS_HIP_TRY(hipMalloc((void**)&sim->d_rows_in, (size_t)n * sim->row_stride * sizeof(int)));
-      sim->rows_in_stride = sim->row_stride;
+      MYTHOS_HIP_TRY(hipMalloc((void**)&sim->d_rows_in, (size_t)n * sim->list.stride * sizeof(int)));
+      sim->rows_in_stride = sim->list.stride;
     }
     return 0;
   };
@@ -809,15 +714,15 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
     // pruned rows: the launch d steps after the Verlet rows were built prunes when d is a multiple of inner_every (so
     // the first launch on new rows does) and walks the pruned rows otherwise
     const bool emit = inner_on && ((k - row.built_at) % sim->inner_every == 0);
-    const int* walk_rows = (inner_on && !emit) ? sim->d_rows_in : sim->d_rows;
+    const int* walk_rows = (inner_on && !emit) ? sim->d_rows_in : sim->list.d_rows;
     const int* walk_len = (inner_on && !emit) ? sim->d_row_len_in : sim->d_row_len;
     int* emit_rows = emit ? sim->d_rows_in : nullptr;
     int* emit_len = emit ? sim->d_row_len_in : nullptr;
 #define MM_ARGS                                                                                                    \
-  n, K, (const V4*)fr[cur], fr[cur ^ 1], vel, walk_rows, walk_len, sim->row_stride, (const R*)sim->d_csig2,          \
+  n, K, (const V4*)fr[cur], fr[cur ^ 1], vel, walk_rows, walk_len, sim->list.stride, (const R*)sim->d_csig2,          \
       (const R*)sim->d_ceps, m->d_bead_bonds, m->d_bead_angles, m->d_bonds, (const R*)m->d_bond_k,                      \
       (const R*)m->d_bond_r0, m->d_angles, (const R*)m->d_angle_k, (const R*)sim->d_angle_ref, kick_close, do_step,  \
-      sim->seed, (uint64_t)(sim->step + k), (const V4*)sim->ref_pos, sim->d_flags, tp, sim->d_epart, sim->d_overflow, k, \
+      sim->seed, (uint64_t)(sim->step + k), (const V4*)sim->ref_pos, sim->d_flags, tp, sim->d_epart, sim->list.d_overflow, k, \
       emit_rows, emit_len, sim->d_bb_partner, sim->d_ba_partner
     auto go = [&](auto save_tag, auto emit_tag) {
       constexpr bool SV = decltype(save_tag)::value, EM = decltype(emit_tag)::value;
@@ -842,8 +747,8 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
   d.energy_rows = save_every > 0 && e_trace != nullptr;
   d.plain_rows = save_every > 0 && e_trace == nullptr && traj_pos != nullptr;
   d.dynamic_list = true;
-  d.halt_words = sim->d_overflow;
-  d.row_stride = &sim->row_stride;
+  d.halt_words = sim->list.d_overflow;
+  d.row_stride = &sim->list.stride;
   d.skin = sim->skin;
   if (inner_on)
     d.give_up_hint = ", or the margin of the pruned rows (" + std::to_string(sim->inner_margin) + ") for one pruning in " +
@@ -852,7 +757,8 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
   return md_drive(
       *sim, d, launch_step, [&](int buf) { return mm_rebuild<R>(sim, fr[buf], K, box, st); },
       [&](int buf) -> int {
-        if (int rc = build_until_fit(buf)) return rc;
+        auto build = [&] { return mm_rebuild<R>(sim, fr[buf], K, box, st); };
+        if (int rc = list_build_until_fit(sim->list, n, build, true, "mythos_martini_langevin_run: neighbour build", st)) return rc;
         return ensure_inner();  // (the rows may have grown)
       },
       [] { return 0; });  // (no MARTINI launch aborts)
@@ -876,8 +782,8 @@ extern "C" {
 void mythos_martini_langevin_destroy(mythos_martini_sim_t* s) {
   if (!s) return;
   (void)hipSetDevice(s->sys->device);
-  void* ptrs[] = {s->frame[0], s->frame[1], s->vel, s->ref_pos, s->d_inv_mass, s->d_rows, s->d_row_len,
-                  s->d_cell,   s->d_overflow, s->d_epart, s->d_rows_in, s->d_row_len_in, s->d_angle_ref, s->d_ctypes, s->d_csig2, s->d_ceps, s->d_bb_partner, s->d_ba_partner};
+  void* ptrs[] = {s->frame[0], s->frame[1], s->vel, s->ref_pos, s->d_inv_mass, s->list.d_rows, s->d_row_len,
+                  s->list.d_cell, s->list.d_overflow, s->d_epart, s->d_rows_in, s->d_row_len_in, s->d_angle_ref, s->d_ctypes, s->d_csig2, s->d_ceps, s->d_bb_partner, s->d_ba_partner};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   md_run_destroy(*s);
@@ -912,11 +818,10 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
   const int blocks = (n + kMmPPB - 1) / kMmPPB;
   bool ok = md_run_create(*s) && hipMalloc(&s->frame[0], (size_t)n * 4 * w) == hipSuccess && hipMalloc(&s->frame[1], (size_t)n * 4 * w) == hipSuccess &&
             hipMalloc(&s->vel, (size_t)n * 4 * w) == hipSuccess && hipMalloc(&s->ref_pos, (size_t)n * 4 * w) == hipSuccess &&
-            hipMalloc((void**)&s->d_rows, (size_t)n * s->row_stride * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&s->d_row_len, (size_t)n * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&s->d_overflow, 3 * sizeof(int)) == hipSuccess &&
+            rows_reserve(s->list, n, 256) == 0 && hipMalloc((void**)&s->d_row_len, (size_t)n * sizeof(int)) == hipSuccess &&
+            hipMalloc((void**)&s->list.d_overflow, kOverflowWords * sizeof(int)) == hipSuccess &&
             hipMalloc((void**)&s->d_epart, (size_t)blocks * kMmTrace * sizeof(double)) == hipSuccess;
-  ok = ok && (sys->dtype == MYTHOS_F32 ? upload_real_vec<float>(&s->d_inv_mass, im) : upload_real_vec<double>(&s->d_inv_mass, im));
+  ok = ok && upload_real(sys->dtype, &s->d_inv_mass, im.data(), im.size());
   if (ok) {  // partners per incidence slot
     std::vector<int> bb((size_t)n * kMaxBeadBonds), ba((size_t)n * kMaxBeadAngles), bonds((size_t)2 * std::max(sys->n_bonds, 0)),
         angles((size_t)3 * std::max(sys->n_angles, 0));
@@ -971,8 +876,7 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
       s->n_ctypes = C;
       ok = hipMalloc((void**)&s->d_ctypes, (size_t)n * sizeof(int)) == hipSuccess &&
            hipMemcpy(s->d_ctypes, types.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-           (sys->dtype == MYTHOS_F32 ? upload_real_vec<float>(&s->d_csig2, cs) && upload_real_vec<float>(&s->d_ceps, ce)
-                                     : upload_real_vec<double>(&s->d_csig2, cs) && upload_real_vec<double>(&s->d_ceps, ce));
+           upload_real(sys->dtype, &s->d_csig2, cs.data(), cs.size()) && upload_real(sys->dtype, &s->d_ceps, ce.data(), ce.size());
     }
   }
   {
@@ -988,9 +892,9 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
           for (double& v : ref) v = std::cos(v);
       }
     }
-    ok = ok && (sys->dtype == MYTHOS_F32 ? upload_real_vec<float>(&s->d_angle_ref, ref) : upload_real_vec<double>(&s->d_angle_ref, ref));
+    ok = ok && upload_real(sys->dtype, &s->d_angle_ref, ref.data(), ref.size());
   }
-  ok = ok && hipMemset(s->d_overflow, 0, 3 * sizeof(int)) == hipSuccess;
+  ok = ok && hipMemset(s->list.d_overflow, 0, kOverflowWords * sizeof(int)) == hipSuccess;
   if (!ok) {
     set_error("mythos_martini_langevin_create: device allocation failed");
     mythos_martini_langevin_destroy(s);
@@ -1141,14 +1045,7 @@ int mythos_martini_langevin_neighbor_stats(const mythos_martini_sim_t* s, int* m
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
-  std::vector<int> len(s->sys->n);
-  MYTHOS_HIP_TRY(hipMemcpy(len.data(), s->d_row_len, len.size() * sizeof(int), hipMemcpyDeviceToHost));
-  long long tot = 0;
-  int mx = 0;
-  for (int v : len) tot += v, mx = std::max(mx, v);
-  if (max_row) *max_row = mx;
-  if (mean_row) *mean_row = double(tot) / std::max<size_t>(1, len.size());
-  return MYTHOS_OK;
+  return row_stats(s->d_row_len, s->sys->n, 0, max_row, mean_row);
 }
 
 int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* s, int which, int32_t* rows, int32_t* row_len, int* stride) {
@@ -1156,9 +1053,9 @@ int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* s, int which, i
     set_error("mythos_martini_langevin_get_rows: invalid argument");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  const int* d_rows = which == 0 ? s->d_rows : s->d_rows_in;
+  const int* d_rows = which == 0 ? s->list.d_rows : s->d_rows_in;
   const int* d_len = which == 0 ? s->d_row_len : s->d_row_len_in;
-  if (stride) *stride = s->row_stride;
+  if (stride) *stride = s->list.stride;
   if (!rows && !row_len) return MYTHOS_OK;
   if (!d_rows || !d_len || !s->list_valid) {
     set_error(which == 0 ? "mythos_martini_langevin_get_rows: no list has been built"
@@ -1167,7 +1064,7 @@ int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* s, int which, i
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
   MYTHOS_HIP_TRY(hipDeviceSynchronize());
-  if (rows) MYTHOS_HIP_TRY(hipMemcpy(rows, d_rows, (size_t)s->sys->n * s->row_stride * sizeof(int), hipMemcpyDeviceToHost));
+  if (rows) MYTHOS_HIP_TRY(hipMemcpy(rows, d_rows, (size_t)s->sys->n * s->list.stride * sizeof(int), hipMemcpyDeviceToHost));
   if (row_len) MYTHOS_HIP_TRY(hipMemcpy(row_len, d_len, (size_t)s->sys->n * sizeof(int), hipMemcpyDeviceToHost));
   return MYTHOS_OK;
 }

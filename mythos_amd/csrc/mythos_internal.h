@@ -43,6 +43,40 @@ struct BoxT {
   int on;
 };
 
+// A device buffer that only grows: reallocated, contents not kept, when more than cap elements are needed.
+template <typename T>
+inline int grow_buffer(T*& ptr, size_t& cap, size_t need) {
+  if (need <= cap) return 0;
+  if (ptr) (void)hipFree(ptr);
+  ptr = nullptr;
+  cap = 0;
+  MYTHOS_HIP_TRY(hipMalloc((void**)&ptr, need * sizeof(T)));
+  cap = need;
+  return 0;
+}
+
+// d_overflow words: [0] longest row if over the stride, [1] fullest bucket if over its capacity, [2] fullest bucket if
+// over half its capacity (headroom hint, not an error)
+constexpr int kOverflowWords = 3;
+
+// The Verlet rows of one system (oxDNA: mythos_system, MARTINI: mythos_martini_sim) and what their builds keep from one
+// to the next: the overflow words and the cell table (cell_list.h, which has the host helpers around them).  The row
+// lengths stay with each owner: their layouts differ.
+struct VerletRows {
+  int* d_rows = nullptr;  // [n][stride]
+  size_t rows_cap = 0;    // ints allocated at d_rows
+  int stride = 0;
+  int* d_overflow = nullptr;  // [kOverflowWords] largest demands seen since last cleared (list_build_until_fit)
+  int* d_cell = nullptr;      // cell table (cell_list.h CellBins): counters [2][H], buckets [H][cell_bucket_cap]
+  size_t cell_cap = 0;        // ints allocated at d_cell
+  int cell_H = 0;             // table slots of the current layout
+  int cell_alloc_bucket_cap = 0;  // places per slot the current layout was made for
+  bool cell_sites = false;    // the layout carries the two site streams (cell_list.h CellBins::sites)
+  int cell_bucket_cap;        // places per slot (the owner's default, grown by list_build_until_fit)
+  int cell_phase = 0;         // which counter half the next build counts into
+  explicit VerletRows(int bucket_cap) : cell_bucket_cap(bucket_cap) {}
+};
+
 }  // namespace mythos
 
 struct mythos_obs;
@@ -59,11 +93,10 @@ struct mythos_system {
   // topology (device)
   int* d_meta = nullptr;  // [n] seq | is_end << 2
 
-  // neighbour rows (device)
-  int* d_rows = nullptr;     // [n][row_stride]
+  // neighbour rows: the rows, their overflow words and cell table (cell buckets start at 32 places; the rows reserve a
+  // stride of 64 at first use, rows_build_device)
+  mythos::VerletRows list{32};
   int* d_row_len = nullptr;  // [n] used slots (>= 2) | [2n] bonded partners | [n] end of the "close" segment
-  int row_stride = 0;
-  size_t rows_cap = 0;  // allocated ints in d_rows
   bool nbrs_set = false;
   int list_epoch = 0;  // bumped when parameters or rows are replaced through the ABI (integrators re-validate their list)
   int param_epoch = 0; // bumped when parameters or nucleotide types are replaced (integrators re-derive the site offsets they carry)
@@ -72,14 +105,6 @@ struct mythos_system {
   bool extra_bonds = false;  // some nucleotide uses slot 2 or 3 (circular strands)
 
   // Verlet build scratch
-  int* d_overflow = nullptr;  // [kOverflowWords] largest demands seen since last cleared (see rows_build_until_fit)
-  int* d_cell = nullptr;      // cell table (cell_list.h CellBins): counters [2][H], buckets [H][cell_bucket_cap]
-  size_t cell_cap = 0;        // ints allocated at d_cell
-  int cell_H = 0;             // table slots of the current allocation
-  int cell_alloc_bucket_cap = 0;  // places per slot the allocation was laid out for
-  bool cell_sites = false;    // the allocation carries the two site streams (cell_list.h CellBins::sites)
-  int cell_bucket_cap = 32;   // places per slot
-  int cell_phase = 0;         // which counter half the next build counts into
   void* d_ref_pos = nullptr;  // [n] real4 positions at the last build (MD displacement check)
   void* d_ref_off = nullptr;  // [n] real4 backbone offsets at the last build
   void* d_ref_a1 = nullptr;   // [n] real4 base vectors at the last build
@@ -183,14 +208,11 @@ int oxdna_energy_launch(mythos_system* sys, const void* center, const void* quat
 // neighbors.hip
 int rows_from_pairs(mythos_system* sys, const int32_t* pairs, int n_pairs);
 // backbone_offsets, base_vectors: real4 per nucleotide (MD frames) to select the segments by site distances, or null
-int rows_build_device(mythos_system* sys, const void* center, bool center_is_vec4, double r_cut, double skin,
-                      const void* backbone_offsets, const void* base_vectors, bool write_refs, hipStream_t stream);
 // write_refs: also store the positions / backbone offsets / base vectors the list was built from in
 // d_ref_pos / d_ref_off / d_ref_a1 (the MD kernel's displacement check compares against them)
-int rows_reserve(mythos_system* sys, int stride);
-// d_overflow words: [0] longest row if over row_stride, [1] fullest bucket if over its capacity, [2] fullest
-// bucket if over half its capacity (headroom hint, not an error)
-constexpr int kOverflowWords = 3;
+int rows_build_device(mythos_system* sys, const void* center, bool center_is_vec4, double r_cut, double skin,
+                      const void* backbone_offsets, const void* base_vectors, bool write_refs, hipStream_t stream);
+// rows_build_device inside list_build_until_fit (cell_list.h): grows rows and buckets until the build fits, synchronising
 int rows_build_until_fit(mythos_system* sys, const void* center, bool center_is_vec4, double r_cut, double skin,
                          const void* backbone_offsets, const void* base_vectors, bool write_refs, bool headroom,
                          hipStream_t stream);

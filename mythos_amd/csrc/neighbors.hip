@@ -12,19 +12,6 @@
 
 namespace mythos {
 
-int rows_reserve(mythos_system* sys, int stride) {
-  const size_t need = (size_t)sys->n * stride;
-  if (need > sys->rows_cap) {
-    if (sys->d_rows) (void)hipFree(sys->d_rows);
-    sys->d_rows = nullptr;
-    sys->rows_cap = 0;
-    MYTHOS_HIP_TRY(hipMalloc((void**)&sys->d_rows, need * sizeof(int)));
-    sys->rows_cap = need;
-  }
-  sys->row_stride = stride;
-  return 0;
-}
-
 int rows_from_pairs(mythos_system* sys, const int32_t* pairs, int n_pairs) {
   const int n = sys->n;
   std::vector<int> count(n, 0);
@@ -49,8 +36,8 @@ int rows_from_pairs(mythos_system* sys, const int32_t* pairs, int n_pairs) {
     rows[(size_t)i * stride + len[i]++] = j;               // i plays op_i
     rows[(size_t)j * stride + len[j]++] = i | ROW_ROLE_Q;  // j plays op_j
   }
-  if (int rc = rows_reserve(sys, stride)) return rc;
-  MYTHOS_HIP_TRY(hipMemcpy(sys->d_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (int rc = rows_reserve(sys->list, n, stride)) return rc;
+  MYTHOS_HIP_TRY(hipMemcpy(sys->list.d_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
   MYTHOS_HIP_TRY(hipMemcpy(sys->d_row_len, len.data(), n * sizeof(int), hipMemcpyHostToDevice));
   // a user-supplied pair list carries no distance classes: every entry is in the "close" segment
   MYTHOS_HIP_TRY(hipMemcpy(row_close_of(sys), len.data(), n * sizeof(int), hipMemcpyHostToDevice));
@@ -234,39 +221,7 @@ __global__ __launch_bounds__(256) void build_rows_cells_kernel(int n, const R* _
 #pragma unroll
     for (int a = 0; a < 3; ++a) oi[a] = sc.off[4 * (size_t)i + a], ai[a] = sc.a1[4 * (size_t)i + a];
   }
-  int cx, cy, cz;
-  cell_of(g, ci.x, ci.y, ci.z, cx, cy, cz);
-  // the 27 cells' counters and the spill list's, G at a time, with their running sum (an inclusive scan over the group's
-  // lanes through the cross-lane network; one lane adding up 28 LDS words was 1.5 us of every row's chain)
-  int carry = 0;
-  if (l == 0) s_pre[grp][0] = 0;
-  for (int k0 = 0; k0 < 28; k0 += G) {
-    const int k = k0 + l;
-    int cnt = 0;
-    if (k < 27) {
-      int c[3] = {cx + k % 3 - 1, cy + (k / 3) % 3 - 1, cz + k / 9 - 1};
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-        if (g.nc[a] > 0) c[a] = (c[a] + g.nc[a]) % g.nc[a];
-      const int h = cell_slot(g, c[0], c[1], c[2]);
-      cnt = min(cell_cnt[h], cell_cap);
-      s_st[grp][k] = h * cell_cap;
-      s_c[grp][k][0] = c[0], s_c[grp][k][1] = c[1], s_c[grp][k][2] = c[2];
-    } else if (k == 27) {  // the spill list: particles whose bucket was full, candidates for every row
-      cnt = min(cell_cnt[cell_H], kCellSpill);
-    }
-    int run = cnt;
-#pragma unroll
-    for (int d = 1; d < G; d <<= 1) {
-      const int o = __shfl_up(run, d, G);
-      if (l >= d) run += o;
-    }
-    if (k < 28) s_pre[grp][k + 1] = carry + run;
-    carry += __shfl(run, G - 1, G);
-  }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  const int total = s_pre[grp][28];
+  const int total = cell_candidates<R, G>(g, ci.x, ci.y, ci.z, cell_cnt, cell_cap, cell_H, s_pre[grp], s_st[grp], s_c[grp], l);
   int* row = rows + (size_t)i * row_stride;
   const int* bq = partners + (size_t)ROW_BONDED_SLOTS * i;
   const int4 bp = make_int4(bq[0], bq[1], bq[2], bq[3]);
@@ -396,31 +351,19 @@ static int build_cells_typed(mythos_system* sys, const R* pos, bool vec4, double
     sc.g_ba = R(0.5 * (Pd[GEO_BASE] + Pr[GEO_BASE]));
     sc.g_st = R(0.5 * (Pd[GEO_STACK] + Pr[GEO_STACK]));
   }
+  VerletRows& L = sys->list;
   CellGrid<R> g;
-  bool ok = true;
-  for (int k = 0; k < 3; ++k) {
-    if (sys->has_box) {
-      const int nc = (int)std::floor(sys->box[k] / rl);
-      if (nc < 3) ok = false;
-      g.nc[k] = std::max(nc, 1);
-      g.ibox[k] = R(1.0 / sys->box[k]);
-      g.inv[k] = R(g.nc[k] / sys->box[k]);
-    } else {
-      g.nc[k] = 0;
-      g.ibox[k] = R(1);
-      g.inv[k] = R(1.0 / rl);
-    }
-  }
+  const bool cells = cell_grid(g, n, rl, sys->has_box ? sys->box : nullptr);
   const int blocks_ap = (n * 64 + 255) / 256;
   int* d_partners = sys->d_row_len + n;
   const BoxT<R> box = make_box<R>(sys);
-  if (!ok || n < 512) {  // tiny systems / boxes under three cells: the all-pairs sweep is exact and cheap
+  if (!cells) {  // tiny systems / boxes under three cells: the all-pairs sweep is exact and cheap
     if (vec4)
       hipLaunchKernelGGL((build_rows_allpairs_kernel<R, true>), dim3(blocks_ap), dim3(256), 0, st, n, pos, box,
-                         R(rl * rl), R(rcl * rcl), sc, d_partners, sys->d_rows, sys->d_row_len, d_close, sys->row_stride, sys->d_overflow);
+                         R(rl * rl), R(rcl * rcl), sc, d_partners, L.d_rows, sys->d_row_len, d_close, L.stride, L.d_overflow);
     else
       hipLaunchKernelGGL((build_rows_allpairs_kernel<R, false>), dim3(blocks_ap), dim3(256), 0, st, n, pos, box,
-                         R(rl * rl), R(rcl * rcl), sc, d_partners, sys->d_rows, sys->d_row_len, d_close, sys->row_stride, sys->d_overflow);
+                         R(rl * rl), R(rcl * rcl), sc, d_partners, L.d_rows, sys->d_row_len, d_close, L.stride, L.d_overflow);
     if (write_refs && vec4) {  // the cell-list kernel writes these itself
       const size_t bytes = (size_t)n * 4 * sizeof(R);
       MYTHOS_HIP_TRY(hipMemcpyAsync(ref_pos, pos, bytes, hipMemcpyDeviceToDevice, st));
@@ -431,49 +374,34 @@ static int build_cells_typed(mythos_system* sys, const R* pos, bool vec4, double
     }
     return 0;
   }
-  const int H = next_pow2(2 * n);
-  if (cell_cap_override()) sys->cell_bucket_cap = cell_cap_override();
-  const int cap = sys->cell_bucket_cap;
+  // hashed table, also in a periodic box
   const bool sites = sc.off != nullptr && vec4;  // MD frames: offsets and base vectors ride in the cell table
-  const size_t need = CellBins::ints(H, cap, sizeof(R), sites);
-  if (need > sys->cell_cap || H != sys->cell_H || cap != sys->cell_alloc_bucket_cap || sites != sys->cell_sites) {
-    if (sys->d_cell) (void)hipFree(sys->d_cell);
-    sys->d_cell = nullptr;
-    sys->cell_cap = 0;
-    MYTHOS_HIP_TRY(hipMalloc((void**)&sys->d_cell, need * sizeof(int)));
-    MYTHOS_HIP_TRY(hipMemsetAsync(sys->d_cell + CellBins::zero_offset(H, cap, sizeof(R), sites), 0, CellBins::zero_ints(H) * sizeof(int), st));
-    sys->cell_cap = need;
-    sys->cell_sites = sites;
-    sys->cell_H = H;
-    sys->cell_alloc_bucket_cap = cap;
-    sys->cell_phase = 0;
-  }
-  const CellBins bins(sys->d_cell, H, cap, sizeof(R), sys->cell_phase, sites);
-  sys->cell_phase ^= 1;
-  const size_t site_stride = sites ? (size_t)H * cap : 0;
+  CellBins bins;
+  if (int rc = cell_table<R>(L, next_pow2(2 * n), sites, st, bins)) return rc;
+  const size_t site_stride = sites ? (size_t)bins.H * bins.cap : 0;
   // the row builder orders its rows itself: no bucket sort
   if (vec4)
-    cell_bins_build<R, true>(n, pos, g, bins, sys->d_overflow, false, st, sc.off, sc.a1);
+    cell_bins_build<R, true>(n, pos, g, bins, L.d_overflow, false, st, sc.off, sc.a1);
   else
-    cell_bins_build<R, false>(n, pos, g, bins, sys->d_overflow, false, st);
+    cell_bins_build<R, false>(n, pos, g, bins, L.d_overflow, false, st);
   constexpr int kPerBlock = 256 / kRowG;
   const int wb = (n + kPerBlock - 1) / kPerBlock;
-  const size_t far_lds = (size_t)kPerBlock * 2 * sys->row_stride * sizeof(int);
+  const size_t far_lds = (size_t)kPerBlock * 2 * L.stride * sizeof(int);
   if (vec4)
     hipLaunchKernelGGL((build_rows_cells_kernel<R, true, kRowG>), dim3(wb), dim3(256), far_lds, st, n, pos, box, g, R(rl * rl),
-                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, sys->d_rows, sys->d_row_len, d_close, sys->row_stride,
-                       sys->d_overflow, ref_pos, ref_off, ref_a1);
+                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows, sys->d_row_len, d_close, L.stride,
+                       L.d_overflow, ref_pos, ref_off, ref_a1);
   else
     hipLaunchKernelGGL((build_rows_cells_kernel<R, false, kRowG>), dim3(wb), dim3(256), far_lds, st, n, pos, box, g, R(rl * rl),
-                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, sys->d_rows, sys->d_row_len, d_close, sys->row_stride,
-                       sys->d_overflow, ref_pos, ref_off, ref_a1);
+                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows, sys->d_row_len, d_close, L.stride,
+                       L.d_overflow, ref_pos, ref_off, ref_a1);
   return 0;
 }
 
 int rows_build_device(mythos_system* sys, const void* center, bool center_is_vec4, double r_cut, double skin,
                       const void* backbone_offsets, const void* base_vectors, bool write_refs, hipStream_t stream) {
-  if (sys->row_stride == 0)
-    if (int rc = rows_reserve(sys, 64)) return rc;
+  if (sys->list.stride == 0)
+    if (int rc = rows_reserve(sys->list, sys->n, 64)) return rc;
   const double rl = r_cut + skin;
   int rc;
   if (sys->dtype == MYTHOS_F32)
@@ -486,37 +414,13 @@ int rows_build_device(mythos_system* sys, const void* center, bool center_is_vec
   return 0;
 }
 
-// Builds the rows, growing the row stride and the bucket capacity until the build fits (synchronises the stream).
-// Buckets end up at most half full (fuller ones work, through the spill list, but slowly).  headroom: leave a
-// quarter of spare row length for builds that follow without a chance to grow (inside an MD run, where a row
-// overflow ends the run with an error).
 int rows_build_until_fit(mythos_system* sys, const void* center, bool center_is_vec4, double r_cut, double skin,
                          const void* backbone_offsets, const void* base_vectors, bool write_refs, bool headroom,
                          hipStream_t stream) {
-  for (int attempt = 0; attempt < 6; ++attempt) {
-    MYTHOS_HIP_TRY(hipMemsetAsync(sys->d_overflow, 0, kOverflowWords * sizeof(int), stream));
-    if (int rc = rows_build_device(sys, center, center_is_vec4, r_cut, skin, backbone_offsets, base_vectors, write_refs, stream))
-      return rc;
-    int ov[kOverflowWords] = {0, 0, 0};
-    MYTHOS_HIP_TRY(hipMemcpyAsync(ov, sys->d_overflow, sizeof(ov), hipMemcpyDeviceToHost, stream));
-    MYTHOS_HIP_TRY(hipStreamSynchronize(stream));
-    if (ov[1] > 0) {
-      set_error("neighbour build: more than " + std::to_string(kCellSpill) + " particles did not fit the buckets of their cells");
-      return MYTHOS_ERR_OVERFLOW;
-    }
-    const int bucket_demand = cell_cap_override() ? 0 : ov[2];  // a bucket more than half full: double the places
-    if (ov[0] == 0 && bucket_demand == 0) {
-      if (ov[2] > 0) MYTHOS_HIP_TRY(hipMemsetAsync(sys->d_overflow + 2, 0, sizeof(int), stream));
-      return MYTHOS_OK;
-    }
-    if (ov[0] > 0) {
-      const int want = headroom ? ((ov[0] + ov[0] / 4 + 15) / 16) * 16 : ((ov[0] + 15) / 16) * 16 + 16;
-      if (int rc = rows_reserve(sys, want)) return rc;
-    }
-    if (bucket_demand > 0) sys->cell_bucket_cap = ((2 * bucket_demand + 15) / 16) * 16;  // reallocated by the next build
-  }
-  set_error("neighbour build: rows or cell buckets keep overflowing");
-  return MYTHOS_ERR_OVERFLOW;
+  return list_build_until_fit(
+      sys->list, sys->n,
+      [&] { return rows_build_device(sys, center, center_is_vec4, r_cut, skin, backbone_offsets, base_vectors, write_refs, stream); },
+      headroom, "neighbour build", stream);
 }
 
 }  // namespace mythos

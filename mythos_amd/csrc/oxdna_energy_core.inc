@@ -346,17 +346,6 @@ static void reduce_partials_launch(const double* part, int n_frames, int n_block
                        0, stream, part, n_blocks, width, out, out_width);
 }
 
-template <typename T>
-static int ensure(T*& ptr, size_t& cap, size_t need) {
-  if (need <= cap) return 0;
-  if (ptr) (void)hipFree(ptr);
-  ptr = nullptr;
-  cap = 0;
-  MYTHOS_HIP_TRY(hipMalloc((void**)&ptr, need * sizeof(T)));
-  cap = need;
-  return 0;
-}
-
 template <typename R, int MODEL, int G>
 static int launch_typed(mythos_system* sys, const R* center, const R* quat, int n_frames, double* e_terms,
                         R* dU_dcenter, R* dU_dquat, double* dU_dparams, mythos_obs* oset, double* obs_out, hipStream_t stream) {
@@ -370,9 +359,9 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
   size_t per_frame = (size_t)blocks * (mode >= 2 ? n_out : T_COUNT) * sizeof(double);
   int chunk = (int)std::min<size_t>(65535, std::max<size_t>(1, (size_t(256) << 20) / per_frame));
   chunk = std::min(chunk, n_frames);
-  if (int rc = ensure(sys->d_epart, sys->epart_cap, (size_t)chunk * blocks * T_COUNT)) return rc;
+  if (int rc = grow_buffer(sys->d_epart, sys->epart_cap, (size_t)chunk * blocks * T_COUNT)) return rc;
   if (mode >= 2)
-    if (int rc = ensure(sys->d_pgpart, sys->pgpart_cap, (size_t)chunk * blocks * n_out)) return rc;
+    if (int rc = grow_buffer(sys->d_pgpart, sys->pgpart_cap, (size_t)chunk * blocks * n_out)) return rc;
   const R* P = device_params_of<R>(sys);
   const BoxT<R> box = make_box<R>(sys);
   // centre distance beyond which no site pair of two nucleotides is inside any cut-off: the longest range of a term
@@ -394,7 +383,7 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
     pseq.marg = (const R*)sys->d_ps_marg, pseq.unit = sys->d_ps_unit, pseq.bp = (const R*)sys->d_ps_bp, pseq.terms = sys->pseq_terms;
   }
   // LDS lists of the row walk: a row is walked in segments of list_cap entries (gather_row)
-  int list_cap = std::min(sys->row_stride, kEnergyListCap);
+  int list_cap = std::min(sys->list.stride, kEnergyListCap);
   if (const long long v = debug_value(MYTHOS_DEBUG_ENERGY_LIST_CAP)) {  // test hook: short segments on small systems
     if (v >= 8 && v <= kEnergyListCap) list_cap = std::min(list_cap, (int)v);
   }
@@ -419,11 +408,11 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
     }
     auto launch = [&](auto mode_tag, auto seg_tag) {
       hipLaunchKernelGGL((oxdna_energy_kernel<R, MODEL, decltype(mode_tag)::value, G, decltype(seg_tag)::value>),
-                         grid, dim3(kBlock), (size_t)PPB * 2 * list_cap * sizeof(int), stream, P, box, n, c, q, sys->d_meta, sys->d_rows,
-                         sys->d_row_len, sys->row_stride, sys->d_epart, gc, gq, sys->d_pgpart, rnear2, pseq, list_cap);
+                         grid, dim3(kBlock), (size_t)PPB * 2 * list_cap * sizeof(int), stream, P, box, n, c, q, sys->d_meta, sys->list.d_rows,
+                         sys->d_row_len, sys->list.stride, sys->d_epart, gc, gq, sys->d_pgpart, rnear2, pseq, list_cap);
     };
     auto by_seg = [&](auto mode_tag) {
-      if (sys->row_stride > list_cap) launch(mode_tag, std::true_type{}); else launch(mode_tag, std::false_type{});
+      if (sys->list.stride > list_cap) launch(mode_tag, std::true_type{}); else launch(mode_tag, std::false_type{});
     };
     if (mode == 0) by_seg(std::integral_constant<int, 0>{});
     else if (mode == 1) by_seg(std::integral_constant<int, 1>{});
