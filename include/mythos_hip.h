@@ -397,6 +397,59 @@ int mythos_martini_langevin_neighbor_stats(const mythos_martini_sim_t* sim, int*
  * *stride is set.  Synchronises the device. */
 int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* sim, int which, int32_t* rows, int32_t* row_len, int* stride);
 
+/* ---- MARTINI observables: named bond lengths and triplet angles ------------------------------
+ * Replaces mythos/observables/bond_distances.py:15-17, 51-69 (BondDistances / BondDistancesMapped) and
+ * triplet_angles.py:15-31, 73-92 (TripletAngles / TripletAnglesMapped) with the angle of
+ * mythos/energy/martini/m2/angle.py:35-58 (atan2 of |cross| and dot of the unit vectors): one launch for every group
+ * and every frame.  A group is all bonds, or all angles, that share one topology name.
+ *   beads_per_item  host int32[n_groups]   2 = a group of bonds (i, j), 3 = a group of angles (i, j, k), angle at j
+ *   members         host int32[n_groups]   items of each group
+ *   index           host int32[...]        the bead indices of the groups one after the other, item-major
+ *   pos, box        dev real[n_frames][n][3], dev real[n_frames][3] as for the MARTINI energy entry point; dtype is that of pos / box.
+ *                   Only the per-frame orthorhombic periodic displacement exists (jax_md.space.periodic).
+ *   out             dev double, group-major: group g occupies the (n_frames, members[g]) row-major block that starts
+ *                   at n_frames * (members[0] + ... + members[g-1]).  Arithmetic is double for either dtype. */
+typedef struct mythos_martini_obs mythos_martini_obs_t;
+mythos_martini_obs_t* mythos_martini_obs_create(int n, int n_groups, const int32_t* beads_per_item, const int32_t* members,
+                                                const int32_t* index, int device);
+void mythos_martini_obs_destroy(mythos_martini_obs_t* obs);
+/* items per frame = doubles per frame of the output */
+int64_t mythos_martini_obs_count(const mythos_martini_obs_t* obs);
+int mythos_martini_obs_eval(mythos_martini_obs_t* obs, const void* pos, const void* box, int dtype, int n_frames, double* out,
+                            mythos_stream_t stream);
+
+/* ---- weighted 1-D Wasserstein distance ----------------------------------------------------------
+ * Replaces wasserstein_1d and its callers (mythos/observables/wasserstein.py:42-78): W between the samples u of a group,
+ * weighted per frame, and reference samples v.  The reference sorts u, v and their concatenation on every call and
+ * differentiates through the sorts; here a plan is built once per stored trajectory from a merge order the caller
+ * supplies (one stable sort of concat(u.flatten(), v) per group), and an evaluation is a prefix sum and, for the
+ * gradient, a suffix sum over the plan (csrc/w1.hip).
+ *   n_frames, members  host int32[n_groups]  group g has n_frames[g] x members[g] samples, frame-major
+ *   samples       dev double   the groups' samples one after the other (with one n_frames: the layout of the observables entry point above)
+ *   n_ref         host int64[n_groups];  ref dev double: the groups' reference samples one after the other
+ *   ref_weights   dev double, same layout as ref, or NULL;  has_ref_weights host uint8[n_groups] or NULL: groups
+ *                 without weights take 1 / n_ref (wasserstein.py:24-25).  Weights are masses: a negative or NaN
+ *                 weight fails the call.
+ *   order         dev int64, per group n_frames * members + n_ref indices into concat(u.flatten(), v) in ascending
+ *                 order of the values.  Checked on the device for range and ascent, NOT for being a permutation: that
+ *                 is the caller's duty (a duplicated index leaves the rank of the sample it displaced at entry 0 and
+ *                 the gradient wrong, without an error; memory stays in bounds).  The call synchronises the stream.
+ * The plan borrows nothing: samples, ref and order may be freed after the call.  It owns scratch for one evaluation at
+ * a time (one plan per stream). */
+typedef struct mythos_w1_plan mythos_w1_plan_t;
+mythos_w1_plan_t* mythos_w1_plan_create(int n_groups, const int32_t* n_frames, const int32_t* members, const double* samples,
+                                        const int64_t* n_ref, const double* ref, const double* ref_weights,
+                                        const uint8_t* has_ref_weights, const int64_t* order, int device,
+                                        mythos_stream_t stream);
+void mythos_w1_plan_destroy(mythos_w1_plan_t* plan);
+/* weights  dev double[n_frames] per-frame weights shared by all groups (a frame's weight is spread evenly over its
+ *          members, wasserstein.py:75-77), or NULL for uniform 1 / (n_frames members); with weights every group has
+ *          the same n_frames
+ * w1       dev double[n_groups]
+ * dw1_dweights  dev double[n_groups][max n_frames] or NULL: dW_g/dweights[s], with sign(0) = 0 where the reference
+ *          differentiates jnp.abs.  Bitwise reproducible: fixed summation order, no atomics. */
+int mythos_w1_eval(mythos_w1_plan_t* plan, const double* weights, double* w1, double* dw1_dweights, mythos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

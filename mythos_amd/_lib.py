@@ -107,6 +107,13 @@ def load() -> C.CDLL:
         "mythos_martini_langevin_last_recoveries": (C.c_int, [V, C.POINTER(C.c_int)]),
         "mythos_martini_langevin_neighbor_stats": (C.c_int, [V, C.POINTER(C.c_int), c_double_p]),
         "mythos_martini_langevin_get_rows": (C.c_int, [V, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+        "mythos_martini_obs_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int]),
+        "mythos_martini_obs_destroy": (None, [V]),
+        "mythos_martini_obs_count": (C.c_int64, [V]),
+        "mythos_martini_obs_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V]),
+        "mythos_w1_plan_create": (V, [C.c_int, c_int_p, c_int_p, V, C.POINTER(C.c_int64), V, V, c_uint8_p, V, C.c_int, V]),
+        "mythos_w1_plan_destroy": (None, [V]),
+        "mythos_w1_eval": (C.c_int, [V, V, V, V, V]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header / library mismatch: fail loudly
@@ -177,6 +184,13 @@ DECLARED_SYMBOLS = (
     "mythos_martini_langevin_neighbor_stats",
     "mythos_martini_langevin_get_rows",
     "mythos_martini_langevin_last_recoveries",
+    "mythos_martini_obs_create",
+    "mythos_martini_obs_destroy",
+    "mythos_martini_obs_count",
+    "mythos_martini_obs_eval",
+    "mythos_w1_plan_create",
+    "mythos_w1_plan_destroy",
+    "mythos_w1_eval",
 )
 
 

@@ -36,6 +36,34 @@ __device__ __forceinline__ R group_sum(R v) {
   return v;
 }
 
+// The value a given lane holds, as a wave-uniform (v_readlane: no LDS trip); `lane` must be uniform.
+__device__ __forceinline__ double read_lane(double v, int lane) {
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane);
+  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned int)lo);
+}
+
+// Inclusive prefix sum over the G lanes of a group, G = 16 (one DPP row) or 64 (the wavefront), every lane enabled.
+// Inside a row: row_shr 1 / 2 / 4 / 8, lanes whose source would lie before the row read 0 (bound_ctrl).  Across the
+// four rows of a wavefront: the row totals sit in lanes 15 / 31 / 47 and are added in row order.  The order of the
+// additions is fixed, so the result is reproducible.
+template <int G, typename R>
+__device__ __forceinline__ R group_scan(R v) {
+  static_assert(G == 16 || G == 64, "group_scan: one DPP row or one wavefront");
+  v += dpp_move<0x111>(v);  // row_shr:1
+  v += dpp_move<0x112>(v);  // row_shr:2
+  v += dpp_move<0x114>(v);  // row_shr:4
+  v += dpp_move<0x118>(v);  // row_shr:8
+  if constexpr (G == 64) {
+    const R r0 = read_lane(v, 15), r1 = read_lane(v, 31), r2 = read_lane(v, 47);
+    const int row = (int)(__lane_id() >> 4);
+    const R before = row == 0 ? R(0) : (row == 1 ? r0 : (row == 2 ? r0 + r1 : (r0 + r1) + r2));
+    v += before;
+  }
+  return v;
+}
+
 }  // namespace mythos
 
 #endif  // MYTHOS_WAVE_OPS_H

@@ -336,7 +336,52 @@ class Angle3(Angle):
     angle_kind = 1
 
 
+class MartiniComposedEnergyFunction:
+    """Sum of MARTINI terms: the counterpart of ``ComposedEnergyFunction(energy_fns=..., strict_params=...)`` as the
+    reference's MARTINI workflow builds it (examples/scripts/martini_full_reparameterization.py:147-154).
+    ``with_params`` routes every key to the terms whose configuration holds it."""
+
+    def __init__(self, energy_fns: list, strict_params: bool = True):
+        if not isinstance(energy_fns, list) or not energy_fns or not all(isinstance(f, MartiniEnergyFunction) for f in energy_fns):
+            raise TypeError("energy_fns must be a non-empty list of MartiniEnergyFunction terms")
+        self.energy_fns = energy_fns
+        self.strict_params = strict_params
+
+    def _replace(self, energy_fns: list) -> "MartiniComposedEnergyFunction":
+        return type(self)(energy_fns, strict_params=self.strict_params)
+
+    def with_params(self, *repl_dicts: dict, **repl_kwargs: Any) -> "MartiniComposedEnergyFunction":
+        repl = {k: v for d in repl_dicts for k, v in d.items()}
+        repl.update(repl_kwargs)
+        used, fns = set(), []
+        for fn in self.energy_fns:
+            own = {k: v for k, v in repl.items() if k in fn.params}
+            used.update(own)
+            fns.append(fn.with_params(**own) if own else fn)
+        if self.strict_params and (unused := set(repl) - used):
+            raise ValueError(f"Some parameters were not used in any energy function: {unused}.")
+        return self._replace(fns)
+
+    def with_props(self, **kwargs: Any) -> "MartiniComposedEnergyFunction":
+        return self._replace([fn.with_props(**kwargs) for fn in self.energy_fns])
+
+    def opt_params(self) -> dict:
+        return {k: v for fn in self.energy_fns for k, v in fn.opt_params().items()}
+
+    def params_dict(self, **kw) -> dict:
+        return {k: v for fn in self.energy_fns for k, v in fn.params_dict(**kw).items()}
+
+    def compute_energy(self, trajectory) -> torch.Tensor:
+        total = self.energy_fns[0](trajectory)
+        for fn in self.energy_fns[1:]:
+            total = total + fn(trajectory)
+        return total
+
+    __call__ = compute_energy
+    map = compute_energy
+
+
 __all__ = [
     "Angle", "Angle3", "AngleConfiguration", "Bond", "BondConfiguration", "LJ", "LJConfiguration",
-    "MartiniEnergyConfiguration", "MartiniEnergyFunction", "MartiniTopology",
+    "MartiniComposedEnergyFunction", "MartiniEnergyConfiguration", "MartiniEnergyFunction", "MartiniTopology",
 ]

@@ -1,0 +1,130 @@
+"""What the MARTINI bond-length and triplet-angle observables share: name matching and the one HIP launch that
+evaluates every selected group for every frame (mythos_amd/csrc/martini_obs.hip, ``mythos_martini_obs_eval``).
+
+A group is every bond (or angle) of the topology that carries one name.  The launch writes a packed float64 block,
+group-major: group g with m_g members is the (S, m_g) row-major block at S * (m_0 + ... + m_{g-1}) - the layout
+``WassersteinDistanceMapped`` builds its plan from.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from mythos_amd import _lib
+
+
+def matching(all_names, name: str, kind: str) -> list[int]:
+    """Indices of the topology's bonds / angles called ``name``; the reference's error otherwise
+    (mythos/observables/bond_distances.py:41-49, triplet_angles.py:64-71)."""
+    idx = [i for i, n in enumerate(all_names) if n == name]
+    if not idx:
+        raise ValueError(f"No {kind}s matching '{name}' found in the topology. Available {kind} names: {sorted(set(all_names))}")
+    return idx
+
+
+class GeometrySet:
+    """mythos_martini_obs_t: the index lists of some groups on one device."""
+
+    def __init__(self, n: int, widths, index_lists, device):
+        lib = _lib.load()
+        self.device = torch.device(device)
+        self.members = [int(len(ix)) for ix in index_lists]
+        w = np.ascontiguousarray(widths, dtype=np.int32)
+        m = np.ascontiguousarray(self.members, dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(ix, dtype=np.int32).reshape(-1) for ix in index_lists]), dtype=np.int32)
+        self._h = lib.mythos_martini_obs_create(int(n), len(self.members), w.ctypes.data_as(_lib.c_int_p), m.ctypes.data_as(_lib.c_int_p),
+                                                flat.ctypes.data_as(_lib.c_int_p), self.device.index or 0)
+        if not self._h:
+            raise _lib.MythosHipError(f"mythos_martini_obs_create: {_lib.last_error()}")
+        self._lib = lib
+        self.count = int(lib.mythos_martini_obs_count(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mythos_martini_obs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def eval(self, pos: torch.Tensor, box: torch.Tensor) -> torch.Tensor:
+        """The packed (S * count,) float64 block of (S, n, 3) positions and (S, 3) boxes of one dtype."""
+        s = int(pos.shape[0])
+        out = torch.empty(s * self.count, dtype=torch.float64, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.mythos_martini_obs_eval(self._h, _lib.ptr(pos), _lib.ptr(box), 0 if pos.dtype == torch.float32 else 1,
+                                                     s, _lib.ptr(out), stream), "martini_obs_eval")
+        return out
+
+
+def _frames(trajectory):
+    pos = trajectory.center
+    if getattr(trajectory, "box_size", None) is None:
+        raise ValueError("MARTINI observables need trajectory.box_size (per-frame periodic box)")
+    if not isinstance(pos, torch.Tensor) or pos.device.type != "cuda":
+        raise _lib.MythosHipError("observables are evaluated by the HIP library: the trajectory must live on a GPU "
+                                  "(mythos_amd has no CPU fallback)")
+    if pos.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"unsupported dtype {pos.dtype}")
+    if pos.dim() == 2:
+        pos = pos[None]
+    box = torch.as_tensor(trajectory.box_size, dtype=pos.dtype, device=pos.device).reshape(-1, 3)
+    if box.shape[0] == 1 and pos.shape[0] > 1:
+        box = box.expand(pos.shape[0], 3)
+    if box.shape[0] != pos.shape[0]:
+        raise ValueError(f"box_size has {box.shape[0]} rows for {pos.shape[0]} frames")
+    return pos.contiguous(), box.contiguous()
+
+
+class MappedGeometry:
+    """Base of the ``*Mapped`` observables: ``names`` -> dict of (S, n_matching) float64 device tensors, one launch.
+
+    Only the per-frame orthorhombic periodic displacement (``trajectory.box_size``) is supported - what the MARTINI
+    energy kernels support; there is no ``displacement_fn`` argument."""
+
+    kind = "bond"
+    width = 2
+
+    def _all_names(self):
+        raise NotImplementedError
+
+    def _all_index(self):
+        raise NotImplementedError
+
+    @property
+    def names(self) -> tuple:
+        raise NotImplementedError
+
+    def index_lists(self) -> list:
+        """Per name the (n_matching, width) bead indices; raises the reference's ValueError for an unknown name."""
+        cached = self.__dict__.get("_index_lists")
+        if cached is None:
+            all_names, index = self._all_names(), np.asarray(self._all_index())
+            cached = [index[matching(all_names, n, self.kind)] for n in self.names]
+            self.__dict__["_index_lists"] = cached
+        return cached
+
+    def packed(self, trajectory):
+        """(block, S, members): the packed block of the launch and its layout."""
+        lists = self.index_lists()
+        pos, box = _frames(trajectory)
+        if pos.shape[1] != len(self.topology.atom_names):
+            raise ValueError(f"trajectory has {pos.shape[1]} beads, the topology {len(self.topology.atom_names)}")
+        sets = self.__dict__.setdefault("_sets", {})
+        key = str(pos.device)
+        if key not in sets:
+            sets[key] = GeometrySet(int(pos.shape[1]), [self.width] * len(lists), lists, pos.device)
+        gs = sets[key]
+        return gs.eval(pos, box), int(pos.shape[0]), gs.members
+
+    def __call__(self, trajectory) -> dict:
+        block, s, members = self.packed(trajectory)
+        out, at = {}, 0
+        for name, m in zip(self.names, members):
+            out[name] = block[at:at + s * m].view(s, m)
+            at += s * m
+        return out

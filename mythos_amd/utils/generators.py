@@ -61,6 +61,18 @@ def ideal_duplex(n_bp: int, *, model: int = 2, seed: int = 1234, origin=(0.0, 0.
     return top, np.ascontiguousarray(center), np.ascontiguousarray(quat)
 
 
+def tiled_martini_box(topology, positions, box, reps: int):
+    """A MARTINI box repeated ``reps`` x ``reps`` times in-plane (x, y) -> (tiled topology, positions, box).
+    GROMACS wraps bead by bead, so every molecule is made whole first (each bead's first bond partner has a lower
+    index); otherwise a bond that crossed a face would span a whole tile."""
+    x0, b0 = np.array(positions, dtype=np.float64), np.asarray(box, dtype=np.float64)
+    for i, j in topology.bonded_neighbors:
+        d = x0[j] - x0[i]
+        x0[j] = x0[i] + d - b0 * np.round(d / b0)
+    xt = np.concatenate([x0 + np.array([i * b0[0], j * b0[1], 0.0]) for i in range(reps) for j in range(reps)])
+    return topology.tile(reps * reps), xt, b0 * np.array([reps, reps, 1.0])
+
+
 def duplex_bundle(n_bp: int, n_duplexes: int, spacing: float = 6.0, **kw):
     """Several parallel duplexes on a square lattice (independent molecules in one system)."""
     side = int(np.ceil(np.sqrt(n_duplexes)))
