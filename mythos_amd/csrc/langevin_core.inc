@@ -269,12 +269,6 @@ constexpr int md_prio_digit(int phase) {
 #define MD_PRIO(phase) do { } while (0)
 #endif
 
-// Optimisation barrier on a register value: whatever produced it stays before this point, its uses after.
-template <typename T>
-__device__ __forceinline__ void md_pin(T& v) {
-  asm volatile("" : "+v"(v));
-}
-
 // One MD step (see file header).  kick_close: multiple of dt*F that closes the previous step
 // (0 for the first kernel of a run, 1/2 otherwise); do_step = 0 for the closing-only kernel.
 //
@@ -867,7 +861,7 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   // ---- integrator prologue, early: the wavefront with the coaxial role is the first to leave the angular pass
   //      (few items) and would idle at the barrier; it is also the one that integrates below, so it draws the
   //      thermostat noise and fetches momenta, quaternion and list-reference rows here, off the tail of the kernel
-  //      where nothing else is left to hide their latency.  md_pin keeps the values on this side of the barriers.
+  //      where nothing else is left to hide their latency.  pin_vgpr keeps the values on this side of the barriers.
   const int int_wave = (3 - bid) & 3;  // the wavefront whose role above was 3
   const int il = threadIdx.x & 63;     // nucleotide of this lane in the integrating wave
   const int i_int = bid * PPB + il;
@@ -879,10 +873,10 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     if (do_step && K.skin_half_sq > R(0)) r0 = ref_pos[i_int], f0 = ref_off[i_int], a0 = ref_a1[i_int];
     if (do_step) normals6(seed, (uint32_t)i_int, step, 0u, z);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) md_pin(z[k]);
-    md_pin(pm.x), md_pin(pm.y), md_pin(pm.z);
-    md_pin(lm.x), md_pin(lm.y), md_pin(lm.z);
-    md_pin(qv.x), md_pin(qv.y), md_pin(qv.z), md_pin(qv.w);
+    for (int k = 0; k < 6; ++k) pin_vgpr(z[k]);
+    pin_vgpr(pm.x), pin_vgpr(pm.y), pin_vgpr(pm.z);
+    pin_vgpr(lm.x), pin_vgpr(lm.y), pin_vgpr(lm.z);
+    pin_vgpr(qv.x), pin_vgpr(qv.y), pin_vgpr(qv.z), pin_vgpr(qv.w);
   }
   __syncthreads();
   MD_PRIO(3);

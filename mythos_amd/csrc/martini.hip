@@ -9,7 +9,8 @@
 // over blockIdx.y so small systems still fill 256 CUs; partial forces / energies are combined by a
 // fixed-order reduction (no atomics, reproducible).  Bonded pairs are excluded through a short
 // per-bead list that is consulted only inside the cut-off.  Every pair is visited from both ends
-// (energy weight 1/2).  Bonds and angles are gathered per bead from incidence lists.
+// (energy weight 1/2).  Bonds and angles are gathered per bead from incidence lists.  The terms are martini_terms.h's;
+// the energy and the LJ parameter-gradient kernel run the same sweep (lj_tile_sweep) with their own per-pair work.
 // Roofline: the sweep is ALU/LDS bound, not HBM bound: 16 B per bead per tile pass from L2/HBM versus
 // ~20 flops per pair per lane.
 #include <algorithm>
@@ -19,6 +20,56 @@
 
 namespace mythos {
 
+// The sweep of one thread over its share of the partner tiles (tile js, js + n_js, ...): stages each tile in LDS
+// (s_x: 3 kLjBlock reals and kLjBlock ints behind the caller's tables; the first barrier also publishes those), wraps,
+// tests cut-off and exclusions, and calls pair(tp, dx, dy, dz, r2) for every accepted partner - tp indexes the type-pair
+// tables - and tile_done() behind each tile.
+template <typename R, typename Pair, typename TileDone>
+__device__ __forceinline__ void lj_tile_sweep(int n, const R* __restrict__ p, const R* __restrict__ box,
+                                              const int* __restrict__ types, const int* __restrict__ excl, R rc2,
+                                              int n_types, int n_tiles, R* s_x, Pair pair, TileDone tile_done) {
+  R *s_y = s_x + kLjBlock, *s_z = s_y + kLjBlock;
+  int* s_t = reinterpret_cast<int*>(s_z + kLjBlock);
+  const int js = blockIdx.y, n_js = gridDim.y;
+  const int i = blockIdx.x * kLjBlock + threadIdx.x;
+  const R lx = box[0], ly = box[1], lz = box[2];
+  const R ilx = R(1) / lx, ily = R(1) / ly, ilz = R(1) / lz;
+  R xi = 0, yi = 0, zi = 0;
+  int ti = 0;
+  int ex[kMaxExcl];
+#pragma unroll
+  for (int k = 0; k < kMaxExcl; ++k) ex[k] = -1;
+  if (i < n) {
+    xi = p[3 * i], yi = p[3 * i + 1], zi = p[3 * i + 2];
+    ti = types[i] * n_types;
+#pragma unroll
+    for (int k = 0; k < kMaxExcl; ++k) ex[k] = excl[(size_t)i * kMaxExcl + k];
+  }
+  for (int tile = js; tile < n_tiles; tile += n_js) {
+    __syncthreads();
+    const int j0 = tile * kLjBlock, jl = j0 + threadIdx.x;
+    if (jl < n) {
+      s_x[threadIdx.x] = p[3 * jl], s_y[threadIdx.x] = p[3 * jl + 1], s_z[threadIdx.x] = p[3 * jl + 2];
+      s_t[threadIdx.x] = types[jl];
+    }
+    __syncthreads();
+    const int cnt = min(kLjBlock, n - j0);
+    if (i < n) {
+      for (int k = 0; k < cnt; ++k) {
+        const R dx = wrap(xi - s_x[k], lx, ilx), dy = wrap(yi - s_y[k], ly, ily), dz = wrap(zi - s_z[k], lz, ilz);
+        const R r2 = dx * dx + dy * dy + dz * dz;
+        if (r2 < rc2) {
+          const int j = j0 + k;
+          bool skip = (j == i);
+#pragma unroll
+          for (int q = 0; q < kMaxExcl; ++q) skip = skip || (ex[q] == j);
+          if (!skip) pair(ti + s_t[k], dx, dy, dz, r2);
+        }
+      }
+      tile_done();
+    }
+  }
+}
 
 template <typename R>
 __global__ __launch_bounds__(kLjBlock) void martini_lj_kernel(
@@ -30,72 +81,32 @@ __global__ __launch_bounds__(kLjBlock) void martini_lj_kernel(
   R* s_eps = s_sig + K.n_types * K.n_types;
   R* s_shift = s_eps + K.n_types * K.n_types;  // V(r_c) per type pair
   R* s_x = s_shift + K.n_types * K.n_types;
-  R* s_y = s_x + kLjBlock;
-  R* s_z = s_y + kLjBlock;
-  int* s_t = reinterpret_cast<int*>(s_z + kLjBlock);
   __shared__ double s_e[kLjBlock / 64];
 
   const int frame = blockIdx.z;
   const int js = blockIdx.y, n_js = gridDim.y;
   const int i = blockIdx.x * kLjBlock + threadIdx.x;
-  const R* __restrict__ p = pos + (size_t)frame * n * 3;
-  const R lx = box[frame * 3], ly = box[frame * 3 + 1], lz = box[frame * 3 + 2];
-  const R ilx = R(1) / lx, ily = R(1) / ly, ilz = R(1) / lz;
   const int tt = K.n_types * K.n_types;
   const R irc2 = R(1) / K.rc2;
   for (int k = threadIdx.x; k < tt; k += kLjBlock) {
     const R sg = sigma[k], ep = eps[k];
     s_sig[k] = sg * sg;  // sigma^2
     s_eps[k] = ep;
-    const R s2 = sg * sg * irc2, s6 = s2 * s2 * s2;
+    const R s6 = lj_pow6(sg * sg, irc2);
     s_shift[k] = R(4) * ep * (s6 * s6 - s6);
   }
-  R xi = 0, yi = 0, zi = 0;
-  int ti = 0;
-  int ex[kMaxExcl];
-#pragma unroll
-  for (int k = 0; k < kMaxExcl; ++k) ex[k] = -1;
-  if (i < n) {
-    xi = p[3 * i], yi = p[3 * i + 1], zi = p[3 * i + 2];
-    ti = types[i] * K.n_types;
-#pragma unroll
-    for (int k = 0; k < kMaxExcl; ++k) ex[k] = excl[(size_t)i * kMaxExcl + k];
-  }
   R fx = 0, fy = 0, fz = 0;  // dU/dx_i
+  R et = 0;                  // the energy of one tile in R, the total over tiles in double
   double e = 0.0;
-  for (int tile = js; tile < n_tiles; tile += n_js) {
-    __syncthreads();
-    const int j0 = tile * kLjBlock, jl = j0 + threadIdx.x;
-    if (jl < n) {
-      s_x[threadIdx.x] = p[3 * jl], s_y[threadIdx.x] = p[3 * jl + 1], s_z[threadIdx.x] = p[3 * jl + 2];
-      s_t[threadIdx.x] = types[jl];
-    }
-    __syncthreads();
-    const int cnt = min(kLjBlock, n - j0);
-    if (i < n) {
-      R et = 0;
-      for (int k = 0; k < cnt; ++k) {
-        const R dx = wrap(xi - s_x[k], lx, ilx), dy = wrap(yi - s_y[k], ly, ily), dz = wrap(zi - s_z[k], lz, ilz);
-        const R r2 = dx * dx + dy * dy + dz * dz;
-        if (r2 < K.rc2) {
-          const int j = j0 + k;
-          bool skip = (j == i);
-#pragma unroll
-          for (int q = 0; q < kMaxExcl; ++q) skip = skip || (ex[q] == j);
-          if (!skip) {
-            const int tp = ti + s_t[k];
-            const R ir2 = R(1) / r2;
-            const R s2 = s_sig[tp] * ir2, s6 = s2 * s2 * s2, s12 = s6 * s6;
-            const R ep = s_eps[tp];
-            et += R(4) * ep * (s12 - s6) - s_shift[tp];
-            const R g = R(-24) * ep * (R(2) * s12 - s6) * ir2;  // (dV/dr) / r
-            fx += g * dx, fy += g * dy, fz += g * dz;
-          }
-        }
-      }
-      e += double(et);
-    }
-  }
+  lj_tile_sweep<R>(
+      n, pos + (size_t)frame * n * 3, box + frame * 3, types, excl, K.rc2, K.n_types, n_tiles, s_x,
+      [&](int tp, R dx, R dy, R dz, R r2) {
+        const R ep = s_eps[tp];
+        const LjPair<R> t = lj_pair(s_sig[tp], ep, r2);
+        et += R(4) * ep * (t.s12 - t.s6) - s_shift[tp];
+        fx += t.g * dx, fy += t.g * dy, fz += t.g * dz;
+      },
+      [&] { e += double(et), et = 0; });
   if (i < n) {
     R* o = f_part + (((size_t)frame * (n_js + 1) + js) * n + i) * 3;
     o[0] = fx, o[1] = fy, o[2] = fz;
@@ -138,11 +149,10 @@ __global__ __launch_bounds__(256) void martini_bonded_kernel(
         d[k] = wrap(p[3 * i + k] - p[3 * o + k], l[k], il[k]);
         r2 += d[k] * d[k];
       }
-      const R r = m_sqrt(r2), x = r - bond_r0[b];
-      const R c = bond_k[b] * x / r;
+      const BondTerm<R> t = bond_term(r2, bond_k[b], bond_r0[b]);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) g[k] += c * d[k];
-      if (side == 0) eb += 0.5 * double(bond_k[b]) * double(x) * double(x);
+      for (int k = 0; k < 3; ++k) g[k] += t.c * d[k];
+      if (side == 0) eb += 0.5 * double(bond_k[b]) * double(t.x) * double(t.x);
     }
     for (int s = 0; s < kMaxBeadAngles; ++s) {
       const int ent = bead_angles[(size_t)i * kMaxBeadAngles + s];
@@ -156,35 +166,16 @@ __global__ __launch_bounds__(256) void martini_bonded_kernel(
         v[k] = wrap(p[3 * bk + k] - p[3 * bj + k], l[k], il[k]);
         u2 += u[k] * u[k], v2 += v[k] * v[k], uv += u[k] * v[k];
       }
-      const R iu = R(1) / m_sqrt(u2), iv = R(1) / m_sqrt(v2);
-      const R c = uv * iu * iv;  // cos(theta)
-      // |uhat x vhat| for the atan2 form of the reference (m2/angle.py:49-58)
-      R cr[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-      const R sn = m_sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]) * iu * iv;
-      R dEdc;
-      double en;
+      const AngleGeom<R> ag = angle_geometry(u, v, u2, v2, uv, angle_kind);
+      R ref = angle_t0[a];
       if (angle_kind == 0) {
-        R c0;
-        if constexpr (sizeof(R) == 4) c0 = cosf(angle_t0[a]); else c0 = cos(angle_t0[a]);
-        const R x = c - c0;
-        dEdc = angle_k[a] * x;
-        en = 0.5 * double(angle_k[a]) * double(x) * double(x);
-      } else {
-        R th;
-        if constexpr (sizeof(R) == 4) th = atan2f(sn, c); else th = atan2(sn, c);
-        const R x = th - angle_t0[a];
-        // d(theta)/d(cos) = -1/sin; (theta - pi)/sin(theta) -> -1 at theta = pi
-        dEdc = (sn > R(1e-6)) ? -angle_k[a] * x / sn : angle_k[a];
-        en = 0.5 * double(angle_k[a]) * double(x) * double(x);
+        if constexpr (sizeof(R) == 4) ref = cosf(ref); else ref = cos(ref);
       }
+      const AngleTerm<R> t = angle_term(angle_kind, ag, angle_k[a], ref);
+      const double en = 0.5 * double(angle_k[a]) * double(t.x) * double(t.x);
       if (role == 0) ea += en;
-      // dc/du = (vhat - c uhat)/|u|, dc/dv = (uhat - c vhat)/|v|
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const R du = (v[k] * iv - c * u[k] * iu) * iu, dv = (u[k] * iu - c * v[k] * iv) * iv;
-        const R gk = (role == 0) ? du : ((role == 2) ? dv : -(du + dv));
-        g[k] += dEdc * gk;
-      }
+      for (int k = 0; k < 3; ++k) g[k] += t.dEdc * angle_role_grad(role, ag, u[k], v[k]);
     }
     R* o = f_part + (((size_t)frame * (n_js + 1) + n_js) * n + i) * 3;
     o[0] = g[0], o[1] = g[1], o[2] = g[2];
@@ -231,65 +222,25 @@ __global__ __launch_bounds__(kLjBlock) void martini_lj_pgrad_kernel(
   R* s_sig = reinterpret_cast<R*>(s_tab + (size_t)kLjWaves * 2 * tt);
   R* s_eps = s_sig + K.n_types * K.n_types;
   R* s_x = s_eps + K.n_types * K.n_types;
-  R* s_y = s_x + kLjBlock;
-  R* s_z = s_y + kLjBlock;
-  int* s_t = reinterpret_cast<int*>(s_z + kLjBlock);
 
   const int frame = blockIdx.z;
-  const int js = blockIdx.y, n_js = gridDim.y;
-  const int i = blockIdx.x * kLjBlock + threadIdx.x;
-  const R* __restrict__ p = pos + (size_t)frame * n * 3;
-  const R lx = box[frame * 3], ly = box[frame * 3 + 1], lz = box[frame * 3 + 2];
-  const R ilx = R(1) / lx, ily = R(1) / ly, ilz = R(1) / lz;
   const R irc2 = R(1) / K.rc2;
   for (int k = threadIdx.x; k < tt; k += kLjBlock) {
     s_sig[k] = sigma[k];
     s_eps[k] = eps[k];
   }
   for (int k = threadIdx.x; k < kLjWaves * 2 * tt; k += kLjBlock) s_tab[k] = 0.0;
-  R xi = 0, yi = 0, zi = 0;
-  int ti = 0;
-  int ex[kMaxExcl];
-#pragma unroll
-  for (int k = 0; k < kMaxExcl; ++k) ex[k] = -1;
-  if (i < n) {
-    xi = p[3 * i], yi = p[3 * i + 1], zi = p[3 * i + 2];
-    ti = types[i] * K.n_types;
-#pragma unroll
-    for (int k = 0; k < kMaxExcl; ++k) ex[k] = excl[(size_t)i * kMaxExcl + k];
-  }
-  for (int tile = js; tile < n_tiles; tile += n_js) {
-    __syncthreads();
-    const int j0 = tile * kLjBlock, jl = j0 + threadIdx.x;
-    if (jl < n) {
-      s_x[threadIdx.x] = p[3 * jl], s_y[threadIdx.x] = p[3 * jl + 1], s_z[threadIdx.x] = p[3 * jl + 2];
-      s_t[threadIdx.x] = types[jl];
-    }
-    __syncthreads();
-    const int cnt = min(kLjBlock, n - j0);
-    if (i < n) {
-      for (int k = 0; k < cnt; ++k) {
-        const R dx = wrap(xi - s_x[k], lx, ilx), dy = wrap(yi - s_y[k], ly, ily), dz = wrap(zi - s_z[k], lz, ilz);
-        const R r2 = dx * dx + dy * dy + dz * dz;
-        if (r2 < K.rc2) {
-          const int j = j0 + k;
-          bool skip = (j == i);
-#pragma unroll
-          for (int q = 0; q < kMaxExcl; ++q) skip = skip || (ex[q] == j);
-          if (!skip) {
-            const int tp = ti + s_t[k];
-            const R sg = s_sig[tp], ep = s_eps[tp];
-            const R ir2 = R(1) / r2;
-            const R s2 = sg * sg * ir2, s6 = s2 * s2 * s2, s12 = s6 * s6;
-            const R c2 = sg * sg * irc2, c6 = c2 * c2 * c2, c12 = c6 * c6;
-            // V = 4 eps [(s12 - s6) - (c12 - c6)];  dV/dsigma = 4 eps [12 s12 - 6 s6 - 12 c12 + 6 c6] / sigma
-            atomicAdd(&s_de[tp], 0.5 * double(R(4) * ((s12 - s6) - (c12 - c6))));
-            atomicAdd(&s_ds[tp], 0.5 * double(R(4) * ep * (R(12) * (s12 - c12) - R(6) * (s6 - c6)) / sg));
-          }
-        }
-      }
-    }
-  }
+  lj_tile_sweep<R>(
+      n, pos + (size_t)frame * n * 3, box + frame * 3, types, excl, K.rc2, K.n_types, n_tiles, s_x,
+      [&](int tp, R, R, R, R r2) {
+        const R sg = s_sig[tp], ep = s_eps[tp];
+        const LjPair<R> t = lj_pair(sg * sg, ep, r2);
+        const R c6 = lj_pow6(sg * sg, irc2), c12 = c6 * c6;
+        // V = 4 eps [(s12 - s6) - (c12 - c6)];  dV/dsigma = 4 eps [12 s12 - 6 s6 - 12 c12 + 6 c6] / sigma
+        atomicAdd(&s_de[tp], 0.5 * double(R(4) * ((t.s12 - t.s6) - (c12 - c6))));
+        atomicAdd(&s_ds[tp], 0.5 * double(R(4) * ep * (R(12) * (t.s12 - c12) - R(6) * (t.s6 - c6)) / sg));
+      },
+      [] {});
   __syncthreads();
   // the workgroup's partial tables: the wavefronts' copies added in wavefront order
   double* __restrict__ out = part + ((size_t)frame * gridDim.x * gridDim.y + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * tt;
@@ -313,7 +264,7 @@ __global__ __launch_bounds__(256) void martini_lj_pgrad_reduce_kernel(const doub
   if (k < tt) d_sigma[(size_t)frame * tt + k] = acc; else d_eps[(size_t)frame * tt + (k - tt)] = acc;
 }
 
-// one thread per bond / per angle: dE/dk and dE/dr0 (dE/dtheta0), E as in martini_bonded_kernel
+// one thread per bond / per angle: dE/dk and dE/dr0 (dE/dtheta0), E as in martini_bonded_kernel; double behind the geometry
 template <typename R>
 __global__ void martini_bonded_pgrad_kernel(int n, const R* __restrict__ pos, const R* __restrict__ box, int n_bonds,
                                             const int* __restrict__ bonds, const R* __restrict__ bond_k,
@@ -348,18 +299,15 @@ __global__ void martini_bonded_pgrad_kernel(int n, const R* __restrict__ pos, co
       v[k] = wrap(p[3 * bk + k] - p[3 * bj + k], l[k], il[k]);
       u2 += u[k] * u[k], v2 += v[k] * v[k], uv += u[k] * v[k];
     }
-    const R iu = R(1) / m_sqrt(u2), iv = R(1) / m_sqrt(v2);
-    const R c = uv * iu * iv;
+    const AngleGeom<R> ag = angle_geometry(u, v, u2, v2, uv, angle_kind);
     const double k0 = double(angle_k[t]), t0 = double(angle_t0[t]);
     double dk, dt0;
     if (angle_kind == 0) {
-      const double x = double(c) - cos(t0);
+      const double x = double(ag.c) - cos(t0);
       dk = 0.5 * x * x;
       dt0 = k0 * x * sin(t0);  // d/dtheta0 of 1/2 k (cos theta - cos theta0)^2
     } else {
-      R cr[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-      const R sn = m_sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]) * iu * iv;
-      const double x = atan2(double(sn), double(c)) - t0;
+      const double x = atan2(double(ag.sn), double(ag.c)) - t0;
       dk = 0.5 * x * x;
       dt0 = -k0 * x;
     }

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "martini_terms.h"
 #include "mythos_internal.h"
 
 namespace mythos {
@@ -21,11 +22,6 @@ struct MartiniConst {
   int n_types;
   int angle_kind;  // 0 = G96 cosine, 1 = harmonic
 };
-
-template <typename R>
-__device__ __forceinline__ R wrap(R d, R l, R il) {
-  return d - l * m_rint(d * il);
-}
 
 // count doubles -> a new device vector of reals in the system's precision (dtype); at least one element is allocated
 inline bool upload_real(int dtype, void** dst, const double* src, size_t count) {

@@ -3,8 +3,8 @@
 // The reference has no MARTINI integrator of its own - it drives GROMACS as an external process
 // (mythos/simulators/gromacs/) and only re-evaluates energies (mythos/energy/martini/m2/*.py).  This file
 // is the device-resident counterpart for the same force field: shifted-cut-off Lennard-Jones over a Verlet
-// list, harmonic bonds, G96 / harmonic angles, and the BAOAB Langevin splitting used for oxDNA
-// (langevin_core.inc) specialised to point particles:
+// list, harmonic bonds, G96 / harmonic angles (the terms of martini_terms.h, as in martini.hip), and the BAOAB
+// Langevin splitting used for oxDNA (langevin_core.inc) specialised to point particles:
 //   B  v += h F / m      A  x += h v      O  v = c1 v + sqrt(kT (1 - c1^2) / m) xi,  c1 = exp(-gamma dt)
 // Units are GROMACS': nm, ps, amu, kJ/mol (1 kJ/mol = 1 amu nm^2 / ps^2), kT = 0.0083144626 T.
 //
@@ -70,23 +70,6 @@ struct MmConst {
   R step_max_sq;   // a bead may move (margin / 2) / (inner_every - 1) per step while pruned rows are in use; <= 0: no check
   int n_types, angle_kind;
 };
-
-// Fused multiply-add spelled out.  The squared distance of the row walk decides which entries the pruned rows keep: every
-// instantiation of the step kernel has to round it the same way, whatever contraction the compiler would choose for it
-// (the energy-trace and the plain instantiation disagreed in the last bit of r^2 in fp64, kept different entries at
-// the edge of the pruned range, and the sums behind that entry fell into other lanes).
-__device__ __forceinline__ float mm_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double mm_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-template <typename R>
-__device__ __forceinline__ R mm_wrap(R d, R l, R il) {
-  return mm_fma(-l, m_rint(d * il), d);
-}
-
-// optimisation barrier on a register value: whatever produced it stays before this point, its uses after
-template <typename T>
-__device__ __forceinline__ void mm_pin(T& v) {
-  asm volatile("" : "+v"(v));
-}
 
 // Wave priority by phase (see md_step_kernel, langevin_core.inc): MYTHOS_MM_PRIO_MAP = three decimal digits, the s_setprio
 // level of the row loop, the bonded lists, and everything behind the barrier (0 = no s_setprio)
@@ -203,8 +186,8 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
 #pragma unroll
       for (int u = 0; u < kLjBatch; ++u) {
         const bool have = j[u] >= 0;
-        const R dx = mm_wrap(me.x - o[u].x, K.lx, K.ilx), dy = mm_wrap(me.y - o[u].y, K.ly, K.ily), dz = mm_wrap(me.z - o[u].z, K.lz, K.ilz);
-        const R r2 = mm_fma(dz, dz, mm_fma(dy, dy, dx * dx));
+        const R dx = wrap_fma(me.x - o[u].x, K.lx, K.ilx), dy = wrap_fma(me.y - o[u].y, K.ly, K.ily), dz = wrap_fma(me.z - o[u].z, K.lz, K.ilz);
+        const R r2 = m_fma(dz, dz, m_fma(dy, dy, dx * dx));
         if constexpr (EMIT) {
           const bool keep = have && r2 < K.rin2;
           const unsigned int gm = (unsigned int)(__ballot(keep) >> gshift) & kGroupMask;
@@ -213,15 +196,10 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
         }
         if (have && r2 < K.rc2) {
           const int tp = type_i + (int)o[u].w;
-          const R ir2 = R(1) / r2;
-          const R s2 = s_sig2[tp] * ir2, s6 = s2 * s2 * s2, s12 = s6 * s6;
           const R ep = s_eps[tp];
-          const R g = R(-24) * ep * (R(2) * s12 - s6) * ir2;  // (dV/dr) / r
-          gx += g * dx, gy += g * dy, gz += g * dz;
-          if constexpr (SAVE) {
-            const R c2 = s_sig2[tp] * irc2, c6 = c2 * c2 * c2;
-            e_lj += R(0.5) * R(4) * ep * ((s12 - s6) - (c6 * c6 - c6));
-          }
+          const LjPair<R> t = lj_pair(s_sig2[tp], ep, r2);
+          gx += t.g * dx, gy += t.g * dy, gz += t.g * dz;
+          if constexpr (SAVE) e_lj += R(0.5) * R(4) * ep * lj_shifted(t, lj_pow6(s_sig2[tp], irc2));
         }
       }
     }
@@ -238,11 +216,10 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
       const int b = ent >> 1, side = ent & 1;
       const V4 o = in[partner];
       const R dx = wrap(me.x - o.x, K.lx, K.ilx), dy = wrap(me.y - o.y, K.ly, K.ily), dz = wrap(me.z - o.z, K.lz, K.ilz);
-      const R r = m_sqrt(dx * dx + dy * dy + dz * dz), x = r - bond_r0[b];
-      const R c = bond_k[b] * x / r;
-      gx += c * dx, gy += c * dy, gz += c * dz;
+      const BondTerm<R> t = bond_term(dx * dx + dy * dy + dz * dz, bond_k[b], bond_r0[b]);
+      gx += t.c * dx, gy += t.c * dy, gz += t.c * dz;
       if constexpr (SAVE)
-        if (side == 0) e_b += R(0.5) * bond_k[b] * x * x;
+        if (side == 0) e_b += R(0.5) * bond_k[b] * t.x * t.x;
     }
     for (int s = lane; s < kMaxBeadAngles; s += G) {
       const int ent = (s == lane) ? ent_a0 : bead_angles[(size_t)i * kMaxBeadAngles + s];
@@ -256,31 +233,13 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
       const R v[3] = {wrap(pk.x - pj.x, K.lx, K.ilx), wrap(pk.y - pj.y, K.ly, K.ily), wrap(pk.z - pj.z, K.lz, K.ilz)};
       const R u2 = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], v2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
       const R uv = u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
-      const R iu = R(1) / m_sqrt(u2), iv = R(1) / m_sqrt(v2);
-      const R c = uv * iu * iv;
-      R dEdc, en;
-      if (K.angle_kind == 0) {
-        const R x = c - angle_t0[a];  // (G96: the array holds cos(theta0), mm_angle_ref)
-        dEdc = angle_k[a] * x;
-        en = R(0.5) * angle_k[a] * x * x;
-      } else {
-        const R cr[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-        const R sn = m_sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]) * iu * iv;
-        R th;
-        if constexpr (sizeof(R) == 4) th = atan2f(sn, c); else th = atan2(sn, c);
-        const R x = th - angle_t0[a];
-        dEdc = (sn > R(1e-6)) ? -angle_k[a] * x / sn : angle_k[a];
-        en = R(0.5) * angle_k[a] * x * x;
-      }
+      const AngleGeom<R> ag = angle_geometry(u, v, u2, v2, uv, K.angle_kind);
+      const AngleTerm<R> t = angle_term(K.angle_kind, ag, angle_k[a], angle_t0[a]);  // (d_angle_ref: cos(theta0) for G96)
+      const R en = R(0.5) * angle_k[a] * t.x * t.x;
       if constexpr (SAVE)
         if (role == 0) e_a += en;
-      R gk[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const R du = (v[k] * iv - c * u[k] * iu) * iu, dv = (u[k] * iu - c * v[k] * iv) * iv;
-        gk[k] = (role == 0) ? du : ((role == 2) ? dv : -(du + dv));
-      }
-      gx += dEdc * gk[0], gy += dEdc * gk[1], gz += dEdc * gk[2];
+      const R gk[3] = {angle_role_grad(role, ag, u[0], v[0]), angle_role_grad(role, ag, u[1], v[1]), angle_role_grad(role, ag, u[2], v[2])};
+      gx += t.dEdc * gk[0], gy += t.dEdc * gk[1], gz += t.dEdc * gk[2];
     }
   }
   gx = group_sum<G>(gx);
@@ -302,7 +261,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
   }
   // ---- integrator prologue, before the barrier: the integrating wavefront draws its thermostat noise and fetches
   //      position, velocity and list reference here, so the tail of the kernel behind the barrier is arithmetic only
-  //      (the oxDNA step kernel's arrangement, langevin_core.inc).  mm_pin keeps the values on this side of the barrier.
+  //      (the oxDNA step kernel's arrangement, langevin_core.inc).  pin_vgpr keeps the values on this side of the barrier.
   const int int_wave = (bid >> 2) & (kMmBlock / 64 - 1) & 3;
   const int il = threadIdx.x & 63;
   const int ib = bid * PPB + il;
@@ -314,8 +273,8 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
     vv = vel[ib];
     if (do_step && K.skin_half_sq > R(0)) r0 = ref_pos[ib];
     if (do_step) normals6(seed, (uint32_t)ib, step, 0u, z);
-    mm_pin(z[0]), mm_pin(z[1]), mm_pin(z[2]);
-    mm_pin(x0.x), mm_pin(x0.y), mm_pin(x0.z), mm_pin(vv.x), mm_pin(vv.y), mm_pin(vv.z), mm_pin(vv.w);
+    pin_vgpr(z[0]), pin_vgpr(z[1]), pin_vgpr(z[2]);
+    pin_vgpr(x0.x), pin_vgpr(x0.y), pin_vgpr(x0.z), pin_vgpr(vv.x), pin_vgpr(vv.y), pin_vgpr(vv.z), pin_vgpr(vv.w);
   }
   if (threadIdx.x == 0) s_halt = halt_word;
   __syncthreads();

@@ -6,6 +6,12 @@
 
 namespace mythos {
 
+// Optimisation barrier on a register value: whatever produced it stays before this point, its uses after.
+template <typename T>
+__device__ __forceinline__ void pin_vgpr(T& v) {
+  asm volatile("" : "+v"(v));
+}
+
 // Cross-lane moves inside a 16-lane row as DPP modifiers (full-rate VALU, no trip through the LDS
 // crossbar that __shfl's ds_bpermute takes): quad_perm [1,0,3,2] / [2,3,0,1] exchange with lane^1 /
 // lane^2, row_half_mirror and row_mirror reflect inside 8 / 16 lanes.

@@ -1,12 +1,13 @@
 // C++/OpenMP port of the MARTINI force evaluation + Langevin step  --  TEST INFRASTRUCTURE ONLY.
 //
 // What it is for: bench.py's cpu_baseline leg of BASELINE configs[2] (20 480-bead bilayer; the torch oracle,
-// oracle/martini_oracle.py, sums all M (M - 1) / 2 pairs and cannot step a system of that size), and a third
-// implementation of the step for tests/test_cpu_port.py, which holds it to oracle/martini_oracle.py (pinned to the
-// GROMACS energies the reference ships) and oracle/martini_langevin_oracle.py.
+// oracle/martini_oracle.py, sums all M (M - 1) / 2 pairs and cannot step a system of that size), and the host build of
+// the kernels' term functions (mythos_amd/csrc/martini_terms.h, instantiated at double; <hip/hip_runtime.h> resolves to
+// shim/): tests/test_cpu_port.py holds it to oracle/martini_oracle.py (pinned to the GROMACS energies the reference
+// ships) and oracle/martini_langevin_oracle.py, and runs it under AddressSanitizer + UBSan (selftest.cpp).
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may load it; nothing under mythos_amd/ does.
 //
-// Algorithm (the reference's energy terms, restated): shifted-cut-off Lennard-Jones over the pairs inside r_c that are
+// Algorithm (the reference's energy terms): shifted-cut-off Lennard-Jones over the pairs inside r_c that are
 // not directly bonded (mythos/energy/martini/m2/lj.py:55-88,137-157), harmonic bonds (m2/bond.py:34-40), G96 cosine
 // angles (m2/angle.py:35-93) or harmonic angles (m3/angle.py:8-11), minimum image in an orthorhombic box
 // (martini/base.py:15-17); BAOAB Langevin for point particles as oracle/martini_langevin_oracle.py restates it (the
@@ -20,6 +21,7 @@
 
 #include <omp.h>
 
+#include "martini_terms.h"
 #include "philox.h"
 
 using namespace mythos;
@@ -39,14 +41,13 @@ struct MSys {
   std::vector<int> row_ptr, row;         // Verlet rows
 };
 
-inline double wrap(double d, double l) { return d - l * std::rint(d / l); }
-
 void build_rows(MSys& s, const double* x, const double* box, double r_list) {
   const int n = s.n;
   int nc[3];
   for (int k = 0; k < 3; ++k) nc[k] = std::max(1, (int)std::floor(box[k] / r_list));
   const bool cells = nc[0] >= 3 && nc[1] >= 3 && nc[2] >= 3;
   const double rl2 = r_list * r_list;
+  const double il[3] = {1.0 / box[0], 1.0 / box[1], 1.0 / box[2]};
   std::vector<int> cell_of(n), head, order(n);
   if (cells) {
     const int ncell = nc[0] * nc[1] * nc[2];
@@ -73,8 +74,8 @@ void build_rows(MSys& s, const double* x, const double* box, double r_list) {
       if (j == i) return;
       for (int t = s.excl_ptr[i]; t < s.excl_ptr[i + 1]; ++t)
         if (s.excl[t] == j) return;
-      const double dx = wrap(x[3 * j] - x[3 * i], box[0]), dy = wrap(x[3 * j + 1] - x[3 * i + 1], box[1]),
-                   dz = wrap(x[3 * j + 2] - x[3 * i + 2], box[2]);
+      const double dx = wrap(x[3 * j] - x[3 * i], box[0], il[0]), dy = wrap(x[3 * j + 1] - x[3 * i + 1], box[1], il[1]),
+                   dz = wrap(x[3 * j + 2] - x[3 * i + 2], box[2], il[2]);
       if (dx * dx + dy * dy + dz * dz < rl2) r.push_back(j);
     };
     if (!cells) {
@@ -102,6 +103,7 @@ void build_rows(MSys& s, const double* x, const double* box, double r_list) {
 void forces(const MSys& s, const double* x, const double* box, double* g, double* e3) {
   const int n = s.n, T = s.n_types;
   const double rc2 = s.r_cut * s.r_cut, irc2 = 1.0 / rc2;
+  const double il[3] = {1.0 / box[0], 1.0 / box[1], 1.0 / box[2]};
   const int nt = omp_get_max_threads();
   std::vector<double> e_thr((size_t)nt * 3, 0.0);
 #pragma omp parallel
@@ -109,56 +111,40 @@ void forces(const MSys& s, const double* x, const double* box, double* g, double
     double* et = e_thr.data() + (size_t)omp_get_thread_num() * 3;
 #pragma omp for schedule(static)
     for (int i = 0; i < n; ++i) {
-      double gx = 0, gy = 0, gz = 0, e_lj = 0, e_b = 0, e_a = 0;
-      const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
+      double gi[3] = {0, 0, 0}, e_lj = 0, e_b = 0, e_a = 0, d[3], u[3], v[3];
       const int ti = s.types[i] * T;
+      auto arm = [&](int a, int b, double (&out)[3]) {  // x_a - x_b, minimum image
+        for (int k = 0; k < 3; ++k) out[k] = wrap(x[3 * a + k] - x[3 * b + k], box[k], il[k]);
+      };
+      auto dot = [](const double (&a)[3], const double (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
       for (int t = s.row_ptr[i]; t < s.row_ptr[i + 1]; ++t) {
         const int j = s.row[t];
-        const double dx = wrap(xi - x[3 * j], box[0]), dy = wrap(yi - x[3 * j + 1], box[1]), dz = wrap(zi - x[3 * j + 2], box[2]);
-        const double r2 = dx * dx + dy * dy + dz * dz;
+        arm(i, j, d);
+        const double r2 = dot(d, d);
         if (r2 >= rc2) continue;
         const int tp = ti + s.types[j];
-        const double sg = s.sigma[tp], ep = s.eps[tp];
-        const double ir2 = 1.0 / r2, s2 = sg * sg * ir2, s6 = s2 * s2 * s2, s12 = s6 * s6;
-        const double c = -24.0 * ep * (2.0 * s12 - s6) * ir2;  // (dV/dr) / r
-        gx += c * dx, gy += c * dy, gz += c * dz;
-        const double c2 = sg * sg * irc2, c6 = c2 * c2 * c2;
-        e_lj += 0.5 * 4.0 * ep * ((s12 - s6) - (c6 * c6 - c6));
+        const double sig2 = s.sigma[tp] * s.sigma[tp], ep = s.eps[tp];
+        const LjPair<double> lj = lj_pair(sig2, ep, r2);
+        for (int k = 0; k < 3; ++k) gi[k] += lj.g * d[k];
+        e_lj += 0.5 * 4.0 * ep * lj_shifted(lj, lj_pow6(sig2, irc2));
       }
       for (int t = s.bb_ptr[i]; t < s.bb_ptr[i + 1]; ++t) {
         const int b = s.bb[t] >> 1, side = s.bb[t] & 1, o = s.bonds[2 * b + (1 - side)];
-        const double dx = wrap(xi - x[3 * o], box[0]), dy = wrap(yi - x[3 * o + 1], box[1]), dz = wrap(zi - x[3 * o + 2], box[2]);
-        const double r = std::sqrt(dx * dx + dy * dy + dz * dz), d = r - s.br0[b];
-        const double c = s.bk[b] * d / r;
-        gx += c * dx, gy += c * dy, gz += c * dz;
-        if (side == 0) e_b += 0.5 * s.bk[b] * d * d;
+        arm(i, o, d);
+        const BondTerm<double> bt = bond_term(dot(d, d), s.bk[b], s.br0[b]);
+        for (int k = 0; k < 3; ++k) gi[k] += bt.c * d[k];
+        if (side == 0) e_b += 0.5 * s.bk[b] * bt.x * bt.x;
       }
       for (int t = s.ba_ptr[i]; t < s.ba_ptr[i + 1]; ++t) {
         const int a = s.ba[t] >> 2, role = s.ba[t] & 3;
         const int pi = s.angles[3 * a], pj = s.angles[3 * a + 1], pk = s.angles[3 * a + 2];
-        double u[3], v[3];
-        for (int k = 0; k < 3; ++k) u[k] = wrap(x[3 * pi + k] - x[3 * pj + k], box[k]), v[k] = wrap(x[3 * pk + k] - x[3 * pj + k], box[k]);
-        const double u2 = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], v2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-        const double uv = u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
-        const double iu = 1.0 / std::sqrt(u2), iv = 1.0 / std::sqrt(v2), c = uv * iu * iv;
-        double dEdc, en;
-        if (s.angle_kind == 0) {
-          const double d = c - std::cos(s.at0[a]);
-          dEdc = s.ak[a] * d, en = 0.5 * s.ak[a] * d * d;
-        } else {
-          const double cr[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-          const double sn = std::sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]) * iu * iv;
-          const double d = std::atan2(sn, c) - s.at0[a];
-          dEdc = sn > 1e-12 ? -s.ak[a] * d / sn : s.ak[a], en = 0.5 * s.ak[a] * d * d;
-        }
-        if (role == 0) e_a += en;
-        for (int k = 0; k < 3; ++k) {
-          const double du = (v[k] * iv - c * u[k] * iu) * iu, dv = (u[k] * iu - c * v[k] * iv) * iv;
-          const double gk = role == 0 ? du : (role == 2 ? dv : -(du + dv));
-          (k == 0 ? gx : (k == 1 ? gy : gz)) += dEdc * gk;
-        }
+        arm(pi, pj, u), arm(pk, pj, v);
+        const AngleGeom<double> ag = angle_geometry(u, v, dot(u, u), dot(v, v), dot(u, v), s.angle_kind);
+        const AngleTerm<double> at = angle_term(s.angle_kind, ag, s.ak[a], s.angle_kind == 0 ? std::cos(s.at0[a]) : s.at0[a]);
+        if (role == 0) e_a += 0.5 * s.ak[a] * at.x * at.x;
+        for (int k = 0; k < 3; ++k) gi[k] += at.dEdc * angle_role_grad(role, ag, u[k], v[k]);
       }
-      g[3 * i] = gx, g[3 * i + 1] = gy, g[3 * i + 2] = gz;
+      g[3 * i] = gi[0], g[3 * i + 1] = gi[1], g[3 * i + 2] = gi[2];
       et[0] += e_lj, et[1] += e_b, et[2] += e_a;
     }
   }

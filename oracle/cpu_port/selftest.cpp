@@ -4,6 +4,10 @@
 // clean sanitizer log).  File layout: int32 {model, n, n_bonded, n_params, has_box, n_steps}, then seq int32[n],
 // is_end int32[n], bonded int32[n_bonded][2], box double[3], flat double[n_params], center double[n][3], quat double[n][4],
 // and for model 4 (oxNA; n_params = three vectors) is_rna int32[n].
+// MARTINI (martini_cpu.cpp, which instantiates mythos_amd/csrc/martini_terms.h): int32 {10, n, n_bonds, n_angles, n_types,
+// n_steps}, then types int32[n], bonds int32[n_bonds][2], angles int32[n_angles][3], box double[3], sigma and eps
+// double[n_types][n_types], bond k and r0 double[n_bonds], angle k and theta0 double[n_angles], mass, x and v double[n](,[3]);
+// evaluated and stepped once with G96 and once with harmonic angles.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +24,13 @@ int mythos_cpu_energy(void* h, const double* center, const double* quat, double*
 int mythos_cpu_langevin_run(void* h, double* c, double* q, double* p, double* L, int n_steps, double dt, double kT,
                             double gamma_t, double gamma_r, double mass, const double* inertia, uint64_t seed,
                             int64_t step0, double r_cut, double skin, int rebuild_every, double* e_last);
+void* mythos_cpu_martini_create(int n, const int32_t* types, int n_types, const double* sigma, const double* eps, int n_bonds,
+                                const int32_t* bonds, const double* bk, const double* br0, int n_angles, const int32_t* angles,
+                                const double* ak, const double* at0, int angle_kind, double r_cut, const double* mass);
+void mythos_cpu_martini_destroy(void* h);
+void mythos_cpu_martini_energy(void* h, const double* x, const double* box, double* e3, double* g);
+int mythos_cpu_martini_run(void* h, double* x, double* v, const double* box, int n_steps, double dt, double kT, double gamma,
+                           uint64_t seed, int64_t step0, double skin, int rebuild_every, double* e4);
 }
 
 template <typename T>
@@ -32,12 +43,43 @@ static std::vector<T> rd(FILE* f, size_t n) {
   return v;
 }
 
+static int martini_case(FILE* f, int n, int nb, int na, int nt, int n_steps) {
+  const auto types = rd<int32_t>(f, n);
+  const auto bonds = rd<int32_t>(f, 2 * (size_t)nb);
+  const auto angles = rd<int32_t>(f, 3 * (size_t)na);
+  const auto box = rd<double>(f, 3);
+  const auto sigma = rd<double>(f, (size_t)nt * nt), eps = rd<double>(f, (size_t)nt * nt);
+  const auto bk = rd<double>(f, nb), br0 = rd<double>(f, nb), ak = rd<double>(f, na), at0 = rd<double>(f, na);
+  const auto mass = rd<double>(f, n), x0 = rd<double>(f, 3 * (size_t)n), v0 = rd<double>(f, 3 * (size_t)n);
+  fclose(f);
+  for (int kind = 0; kind < 2; ++kind) {
+    void* h = mythos_cpu_martini_create(n, types.data(), nt, sigma.data(), eps.data(), nb, bonds.data(), bk.data(), br0.data(), na,
+                                        angles.data(), ak.data(), at0.data(), kind, 1.1, mass.data());
+    if (!h) return 3;
+    auto x = x0, v = v0;
+    double e[4];
+    std::vector<double> g(3 * (size_t)n);
+    mythos_cpu_martini_energy(h, x.data(), box.data(), e, g.data());
+    printf("E %.12e %.12e %.12e", e[0], e[1], e[2]);
+    double fs[3] = {0, 0, 0};
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) fs[k] += g[3 * (size_t)i + k];
+    printf("\nFSUM %.3e %.3e %.3e\n", fs[0], fs[1], fs[2]);
+    const int builds = mythos_cpu_martini_run(h, x.data(), v.data(), box.data(), n_steps, 0.02, 2.27, 1.0, 42, 0, 0.2, 3, e);
+    printf("MD builds %d E %.10e %.10e %.10e %.10e", builds, e[0], e[1], e[2], e[3]);
+    printf("\nX %.12e %.12e %.12e\n", x[0], x[3 * (size_t)(n - 1) + 2], v[3 * (size_t)(n / 2)]);
+    mythos_cpu_martini_destroy(h);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
   FILE* f = fopen(argv[1], "rb");
   if (!f) return 2;
   const auto hdr = rd<int32_t>(f, 6);
   const int model = hdr[0], n = hdr[1], nb = hdr[2], np = hdr[3], has_box = hdr[4], n_steps = hdr[5];
+  if (model == 10) return martini_case(f, n, nb, np, has_box, n_steps);
   const auto seq = rd<int32_t>(f, n);
   const auto end32 = rd<int32_t>(f, n);
   const auto bonded = rd<int32_t>(f, 2 * (size_t)nb);

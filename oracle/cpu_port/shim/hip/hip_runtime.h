@@ -1,5 +1,5 @@
 // Host stand-in for <hip/hip_runtime.h>, used ONLY by oracle/cpu_port (the CPU baseline / sanitizer build of the
-// pair-physics templates in mythos_amd/csrc/oxdna_math.h, oxdna_pair.h and philox.h).  TEST INFRASTRUCTURE: nothing
+// physics templates in mythos_amd/csrc/oxdna_math.h, oxdna_pair.h, martini_terms.h and philox.h).  TEST INFRASTRUCTURE: nothing
 // under mythos_amd/ sees this file; the product is compiled by hipcc against the real header.
 #pragma once
 #include <cmath>

@@ -205,10 +205,35 @@ def test_thread_count_does_not_change_results():
 
 def test_sanitizers_are_clean_and_agree_with_the_plain_build(tmp_path):
     """AddressSanitizer + UndefinedBehaviorSanitizer over energy, the cell-list build and 20 Langevin steps with
-    rebuilds (oxDNA1 and oxDNA2; free and periodic): no report, and the same numbers as the optimised build."""
+    rebuilds (oxDNA1 and oxDNA2; free and periodic; oxRNA2, oxNA), and over a small MARTINI system with bonds and both
+    angle kinds, eight steps: no report, and the same numbers as the optimised build."""
     plain, san = cpu_port.BUILD / "md_cpu_selftest", cpu_port.BUILD / "md_cpu_selftest_san"
     if not san.exists():
         subprocess.run(["make", "-C", str(cpu_port.BUILD.parent)], check=True, capture_output=True)
+
+    def run_both(path):
+        env = {"OMP_NUM_THREADS": "4", "ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}
+        a = subprocess.run([str(plain), str(path)], capture_output=True, text=True, env=env, timeout=120)
+        b = subprocess.run([str(san), str(path)], capture_output=True, text=True, env=env, timeout=300)
+        assert a.returncode == 0, a.stderr
+        assert b.returncode == 0, b.stderr[-3000:]
+        assert "ERROR: AddressSanitizer" not in b.stderr and "runtime error" not in b.stderr, b.stderr[-3000:]
+        la, lb = a.stdout.split("\n"), b.stdout.split("\n")
+        assert la[0].startswith("E ") and la[2].startswith("MD builds")
+        for x, y in zip(la, lb):
+            tx, ty = x.split(), y.split()
+            assert len(tx) == len(ty)
+            for u, v in zip(tx, ty):
+                try:
+                    fu, fv = float(u), float(v)
+                except ValueError:
+                    assert u == v
+                    continue
+                assert abs(fu - fv) <= 1e-7 * max(1.0, abs(fu)), (x, y)  # -O1 vs -O3 -mfma: contraction differs
+        fs = [float(t) for t in la[1].split()[1:]]
+        assert max(abs(t) for t in fs) < 1e-8  # Newton's third law
+        return la
+
     for model, box in ((2, None), (1, np.array([40.0, 40.0, 60.0])), (3, np.array([20.0, 20.0, 20.0])), (4, np.array([20.0, 20.0, 20.0]))):
         is_rna = None
         if model == 3:    # oxRNA2: the reference's RNA helix (an ideal B-duplex is outside the FENE well of the RNA geometry)
@@ -232,26 +257,31 @@ def test_sanitizers_are_clean_and_agree_with_the_plain_build(tmp_path):
             q0.astype(np.float64).tofile(f)
             if is_rna is not None:
                 np.asarray(is_rna, np.int32).tofile(f)
-        env = {"OMP_NUM_THREADS": "4", "ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}
-        a = subprocess.run([str(plain), str(path)], capture_output=True, text=True, env=env, timeout=120)
-        b = subprocess.run([str(san), str(path)], capture_output=True, text=True, env=env, timeout=300)
-        assert a.returncode == 0, a.stderr
-        assert b.returncode == 0, b.stderr[-3000:]
-        assert "ERROR: AddressSanitizer" not in b.stderr and "runtime error" not in b.stderr, b.stderr[-3000:]
-        la, lb = a.stdout.split("\n"), b.stdout.split("\n")
-        assert la[0].startswith("E ") and la[2].startswith("MD builds")
-        for x, y in zip(la, lb):
-            tx, ty = x.split(), y.split()
-            assert len(tx) == len(ty)
-            for u, v in zip(tx, ty):
-                try:
-                    fu, fv = float(u), float(v)
-                except ValueError:
-                    assert u == v
-                    continue
-                assert abs(fu - fv) <= 1e-7 * max(1.0, abs(fu)), (x, y)  # -O1 vs -O3 -mfma: contraction differs
-        fs = [float(t) for t in la[1].split()[1:]]
-        assert max(abs(t) for t in fs) < 1e-8  # Newton's third law
+        run_both(path)
+    # MARTINI: 12 bent four-bead chains in a box of three cells per edge, G96 and harmonic angles (martini_terms.h at double)
+    rng = np.random.default_rng(11)
+    starts = np.array([(cx, cy, cz) for cx in (0.2, 2.2) for cy in (0.5, 1.8, 3.1) for cz in (0.7, 2.7)])
+    x = (starts[:, None, :] + np.stack([0.45 * np.arange(4), 0.15 * (np.arange(4) % 2), np.zeros(4)], axis=1)[None]).reshape(-1, 3)
+    x += rng.uniform(-0.04, 0.04, size=x.shape)
+    n, nt = len(x), 3
+    bonds = np.array([(4 * c + k, 4 * c + k + 1) for c in range(12) for k in range(3)], np.int32)
+    angles = np.array([(4 * c + k, 4 * c + k + 1, 4 * c + k + 2) for c in range(12) for k in range(2)], np.int32)
+    sigma = np.full((nt, nt), 0.47) + 0.02 * np.eye(nt)
+    eps = 2.0 + (lambda a: a + a.T)(rng.uniform(0.0, 1.5, size=(nt, nt)))
+    path = tmp_path / "martini.bin"
+    with open(path, "wb") as f:
+        np.array([10, n, len(bonds), len(angles), nt, 8], np.int32).tofile(f)
+        rng.integers(0, nt, size=n).astype(np.int32).tofile(f)
+        bonds.tofile(f)
+        angles.tofile(f)
+        for a in (np.array([4.0, 4.0, 4.0]), sigma, eps, rng.uniform(1000.0, 1500.0, len(bonds)), rng.uniform(0.44, 0.5, len(bonds)),
+                  rng.uniform(20.0, 40.0, len(angles)), rng.uniform(2.2, 2.6, len(angles)), rng.uniform(40.0, 90.0, n), x,
+                  0.3 * rng.standard_normal(x.shape)):
+            np.asarray(a, np.float64).tofile(f)
+    la = run_both(path)
+    assert len(la) >= 8 and la[4].startswith("E ") and la[6].startswith("MD builds 3 ")  # the second angle kind
+    assert la[0] != la[4]
+    assert max(abs(float(t)) for t in la[5].split()[1:]) < 1e-8
 
 
 # ---- MARTINI (oracle/cpu_port/martini_cpu.cpp): bench.py's cpu_baseline of BASELINE configs[2] ------------------
