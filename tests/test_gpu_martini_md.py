@@ -230,6 +230,9 @@ def test_rows_longer_than_the_default_stride_grow_at_the_first_build():
     sysm, *_rest, x0, b0 = _make(torch.float64)
     outs = []
     for skin, every in ((0.3, 5), (1.0, 5)):
+        # which builder (cell_grid, cell_list.h: cells from 512 beads and three cells of the list range per edge on):
+        # two cells fit the 5.7 nm edges at 2.1 nm, so the long rows come from the all-pairs builder, the others from cells
+        assert sysm.n >= 512 and (np.floor(b0 / (1.1 + skin)) >= 3).all() == (skin == 0.3), b0
         integ = MartiniLangevinIntegrator(sysm, dt=0.02, kT=KB * T, gamma=1.0, seed=8)
         integ.set_neighbor_policy(skin, every)
         pos = torch.as_tensor(x0, dtype=torch.float64, device=sysm.device).contiguous()
