@@ -450,6 +450,36 @@ void mythos_w1_plan_destroy(mythos_w1_plan_t* plan);
  *          differentiates jnp.abs.  Bitwise reproducible: fixed summation order, no atomics. */
 int mythos_w1_eval(mythos_w1_plan_t* plan, const double* weights, double* w1, double* dw1_dweights, mythos_stream_t stream);
 
+/* ---- membrane observables: leaflets, thickness, area per lipid ---------------------------------
+ * One launch over the stored frames, one workgroup per frame (csrc/membrane.hip; definitions in DESIGN section 3.5c).
+ * A lipid is a residue that owns beads of the lipid selection; its z is their unweighted mean, the midpoint is the mean
+ * z of all the selection's beads, leaflet +1 is z_lipid > midpoint, -1 otherwise.  Positions in nm, as stored: no
+ * re-wrapping in z.
+ *   lipid_start  host int32[n_lipids + 1]  CSR offsets into lipid_beads, lipid_start[0] = 0, every lipid non-empty
+ *   lipid_beads  host int32[lipid_start[n_lipids]]  the beads of the lipid selection, grouped by lipid
+ *   thick_beads  host int32[n_thick]  the beads of the thickness selection (n_thick = 0: area per lipid only)
+ *   thick_lipid  host int32[n_thick]  the lipid each of them belongs to */
+#define MYTHOS_MEMBRANE_ROW 7 /* doubles per frame of mythos_membrane_eval's out */
+typedef struct mythos_membrane mythos_membrane_t;
+/* Replaces the constructors of lipyphilic.AssignLeaflets / MembThickness / AreaPerLipid in
+ * mythos/observables/membrane_thickness.py:35-42 and area_per_lipid.py:33-40 (selections resolved by the caller). */
+mythos_membrane_t* mythos_membrane_create(int n, int n_lipids, const int32_t* lipid_start, const int32_t* lipid_beads, int n_thick,
+                                          const int32_t* thick_beads, const int32_t* thick_lipid, int device);
+void mythos_membrane_destroy(mythos_membrane_t* mem);
+/* Replaces the n_residues of the lipid selection's AtomGroup (mythos/observables/area_per_lipid.py:37-41, the axis the
+ * mean runs over). */
+int mythos_membrane_n_lipids(const mythos_membrane_t* mem);
+/* Replaces the .run() calls and their results of mythos/observables/membrane_thickness.py:37-43 (leaflets.leaflets,
+ * thicknesses.memb_thickness) and area_per_lipid.py:35-41 (mean over lipids of area_per_lipid.areas).
+ *   pos, box  dev real[n_frames][n][3], dev real[n_frames][3]; dtype is that of both; promoted to double on load
+ *   out       dev double[n_frames][MYTHOS_MEMBRANE_ROW]: thickness (nm; NaN if a leaflet has no lipid or no thickness
+ *             bead), area per lipid Lx Ly (occupied leaflets) / n_lipids (nm^2), midpoint z, lipids in leaflet +1,
+ *             lipids in leaflet -1, mean z of the thickness beads of leaflet +1, of leaflet -1 (NaN if none)
+ *   leaflets  dev int8[n_frames][n_lipids] (+1 / -1) or NULL
+ * Double sums in a fixed order, no atomics: a frame's row has the same bits whatever else is in the launch. */
+int mythos_membrane_eval(mythos_membrane_t* mem, const void* pos, const void* box, int dtype, int n_frames, double* out,
+                         int8_t* leaflets, mythos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

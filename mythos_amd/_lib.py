@@ -114,6 +114,10 @@ def load() -> C.CDLL:
         "mythos_w1_plan_create": (V, [C.c_int, c_int_p, c_int_p, V, C.POINTER(C.c_int64), V, V, c_uint8_p, V, C.c_int, V]),
         "mythos_w1_plan_destroy": (None, [V]),
         "mythos_w1_eval": (C.c_int, [V, V, V, V, V]),
+        "mythos_membrane_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int]),
+        "mythos_membrane_destroy": (None, [V]),
+        "mythos_membrane_n_lipids": (C.c_int, [V]),
+        "mythos_membrane_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V, V]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header / library mismatch: fail loudly
@@ -191,7 +195,14 @@ DECLARED_SYMBOLS = (
     "mythos_w1_plan_create",
     "mythos_w1_plan_destroy",
     "mythos_w1_eval",
+    "mythos_membrane_create",
+    "mythos_membrane_destroy",
+    "mythos_membrane_n_lipids",
+    "mythos_membrane_eval",
 )
+
+
+MEMBRANE_ROW = 7  # MYTHOS_MEMBRANE_ROW of include/mythos_hip.h: doubles per frame of mythos_membrane_eval
 
 
 def last_error() -> str:

@@ -1,0 +1,196 @@
+// Membrane observables of a lipid bilayer: leaflet assignment, thickness and area per lipid of every frame, one launch.
+// Replaces mythos/observables/membrane_thickness.py:33-43 and area_per_lipid.py:31-41 (LiPyphilic's AssignLeaflets,
+// MembThickness and AreaPerLipid at their defaults, n_bins = 1, run on the host through MDAnalysis once per objective
+// per optimisation step).
+//
+// Definitions.  A lipid is a residue that owns beads of the lipid selection; its z is the
+// unweighted mean z of those beads.  The midpoint of a frame is the mean z of ALL beads of the lipid selection (over
+// beads, not over lipids).  Leaflet +1 if z_lipid > midpoint, else -1 (a tie goes to -1).  Thickness is the mean z of the
+// thickness beads whose lipid is in leaflet +1 minus the same mean of leaflet -1, NaN if either is empty; coordinates
+// are used as stored (no re-wrapping in z).  Area per lipid is Lx Ly (occupied leaflets) / n_lipids: the mean of the
+// Voronoi cells of a periodic tessellation, which tile the box.
+//
+// One workgroup per frame, three passes of the workgroup over the index lists: the selection's beads for the midpoint,
+// the lipids for the leaflets, the thickness beads for the two means.  A thickness bead recomputes its lipid's z by the
+// same function the leaflet pass used (same operations in the same order: the same bits), so nothing is kept per
+// lipid and their number has no limit.  Sums are double and in a fixed order: thread-strided partials, the wavefront
+// butterfly of wave_ops.h, the wavefronts' totals in order through LDS.  No atomics: a frame's row depends on that
+// frame only.  The kernel is launch and gather bound (3 - 4 gathered z per lipid and frame).
+#include <vector>
+
+#include "mythos_internal.h"
+#include "wave_ops.h"
+
+struct mythos_membrane {
+  int n = 0, n_lipids = 0, n_sel = 0, n_thick = 0, device = 0;
+  int* d_start = nullptr;        // [n_lipids + 1] CSR offsets into d_sel
+  int* d_sel = nullptr;          // [n_sel] beads of the lipid selection, grouped by lipid
+  int* d_thick = nullptr;        // [n_thick] beads of the thickness selection
+  int* d_thick_lipid = nullptr;  // [n_thick] the lipid of each
+};
+
+namespace mythos {
+
+constexpr int kMemBlock = 256;
+
+// every thread gets the workgroup's sum; s_w: kMemBlock / 64 doubles.  Every thread must call it.
+__device__ __forceinline__ double mem_block_sum(double v, double* s_w) {
+  v = group_sum<64>(v);
+  __syncthreads();  // s_w may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int w = 0; w < kMemBlock / 64; ++w) s += s_w[w];
+  return s;
+}
+
+template <typename R>
+__device__ __forceinline__ double lipid_z(const R* __restrict__ p, const int* __restrict__ start, const int* __restrict__ sel, int l) {
+  const int a = start[l], b = start[l + 1];
+  double s = 0.0;
+  for (int k = a; k < b; ++k) s += double(p[3 * (size_t)sel[k] + 2]);
+  return s / double(b - a);
+}
+
+template <typename R>
+__global__ __launch_bounds__(kMemBlock) void membrane_kernel(int n, int n_lipids, int n_sel, int n_thick,
+                                                             const int* __restrict__ start, const int* __restrict__ sel,
+                                                             const int* __restrict__ thick, const int* __restrict__ thick_lipid,
+                                                             const R* __restrict__ pos, const R* __restrict__ box, int frame0,
+                                                             double* __restrict__ out, int8_t* __restrict__ leaflets) {
+  __shared__ double s_w[kMemBlock / 64];
+  const int frame = frame0 + blockIdx.x;
+  const R* __restrict__ p = pos + (size_t)frame * n * 3;
+  // midpoint: over beads
+  double zs = 0.0;
+  for (int k = threadIdx.x; k < n_sel; k += kMemBlock) zs += double(p[3 * (size_t)sel[k] + 2]);
+  const double mid = mem_block_sum(zs, s_w) / double(n_sel);
+  // leaflets
+  double up = 0.0;
+  for (int l = threadIdx.x; l < n_lipids; l += kMemBlock) {
+    const bool upper = lipid_z(p, start, sel, l) > mid;
+    up += upper ? 1.0 : 0.0;
+    if (leaflets) leaflets[(size_t)frame * n_lipids + l] = upper ? 1 : -1;
+  }
+  const double n_up = mem_block_sum(up, s_w), n_lo = double(n_lipids) - n_up;  // counts: exact in double
+  // thickness beads by the leaflet of their lipid
+  double zu = 0.0, zl = 0.0, cu = 0.0;
+  for (int t = threadIdx.x; t < n_thick; t += kMemBlock) {
+    const double z = double(p[3 * (size_t)thick[t] + 2]);
+    if (lipid_z(p, start, sel, thick_lipid[t]) > mid)
+      zu += z, cu += 1.0;
+    else
+      zl += z;
+  }
+  zu = mem_block_sum(zu, s_w), zl = mem_block_sum(zl, s_w), cu = mem_block_sum(cu, s_w);
+  if (threadIdx.x == 0) {
+    const double cl = double(n_thick) - cu, nan = __builtin_nan("");
+    const double mu = cu > 0.0 ? zu / cu : nan, ml = cl > 0.0 ? zl / cl : nan;
+    const double lx = double(box[(size_t)frame * 3]), ly = double(box[(size_t)frame * 3 + 1]);
+    const double occupied = (n_up > 0.0 ? 1.0 : 0.0) + (n_lo > 0.0 ? 1.0 : 0.0);
+    double* __restrict__ row = out + (size_t)frame * MYTHOS_MEMBRANE_ROW;
+    row[0] = mu - ml;  // NaN if a leaflet has no thickness bead (and with it: no lipid)
+    row[1] = lx * ly * occupied / double(n_lipids);
+    row[2] = mid;
+    row[3] = n_up;
+    row[4] = n_lo;
+    row[5] = mu;
+    row[6] = ml;
+  }
+}
+
+}  // namespace mythos
+
+using namespace mythos;
+
+extern "C" {
+
+mythos_membrane_t* mythos_membrane_create(int n, int n_lipids, const int32_t* lipid_start, const int32_t* lipid_beads, int n_thick,
+                                          const int32_t* thick_beads, const int32_t* thick_lipid, int device) {
+  if (n < 1 || n_lipids < 1 || n_thick < 0 || !lipid_start || !lipid_beads || (n_thick > 0 && (!thick_beads || !thick_lipid))) {
+    set_error("mythos_membrane_create: invalid argument");
+    return nullptr;
+  }
+  if (lipid_start[0] != 0) {
+    set_error("mythos_membrane_create: lipid_start[0] must be 0");
+    return nullptr;
+  }
+  for (int l = 0; l < n_lipids; ++l)
+    if (lipid_start[l + 1] <= lipid_start[l]) {
+      set_error("mythos_membrane_create: every lipid owns at least one bead of the selection");
+      return nullptr;
+    }
+  const int n_sel = lipid_start[n_lipids];
+  for (int k = 0; k < n_sel; ++k)
+    if (lipid_beads[k] < 0 || lipid_beads[k] >= n) {
+      set_error("mythos_membrane_create: bead index out of range");
+      return nullptr;
+    }
+  for (int t = 0; t < n_thick; ++t)
+    if (thick_beads[t] < 0 || thick_beads[t] >= n || thick_lipid[t] < 0 || thick_lipid[t] >= n_lipids) {
+      set_error("mythos_membrane_create: thickness bead or its lipid out of range");
+      return nullptr;
+    }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) {
+    set_error("mythos_membrane_create: no usable HIP device (the HIP path has no CPU fallback)");
+    return nullptr;
+  }
+  auto* h = new mythos_membrane();
+  h->n = n, h->n_lipids = n_lipids, h->n_sel = n_sel, h->n_thick = n_thick, h->device = device;
+  const size_t nt = n_thick > 0 ? (size_t)n_thick : 1;  // no zero-byte allocations
+  bool ok = hipMalloc((void**)&h->d_start, ((size_t)n_lipids + 1) * sizeof(int)) == hipSuccess &&
+            hipMalloc((void**)&h->d_sel, (size_t)n_sel * sizeof(int)) == hipSuccess &&
+            hipMalloc((void**)&h->d_thick, nt * sizeof(int)) == hipSuccess &&
+            hipMalloc((void**)&h->d_thick_lipid, nt * sizeof(int)) == hipSuccess &&
+            hipMemcpy(h->d_start, lipid_start, ((size_t)n_lipids + 1) * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(h->d_sel, lipid_beads, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && n_thick > 0)
+    ok = hipMemcpy(h->d_thick, thick_beads, (size_t)n_thick * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(h->d_thick_lipid, thick_lipid, (size_t)n_thick * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    set_error("mythos_membrane_create: device allocation failed");
+    mythos_membrane_destroy(h);
+    return nullptr;
+  }
+  return h;
+}
+
+void mythos_membrane_destroy(mythos_membrane_t* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->d_start) (void)hipFree(h->d_start);
+  if (h->d_sel) (void)hipFree(h->d_sel);
+  if (h->d_thick) (void)hipFree(h->d_thick);
+  if (h->d_thick_lipid) (void)hipFree(h->d_thick_lipid);
+  delete h;
+}
+
+int mythos_membrane_n_lipids(const mythos_membrane_t* h) { return h ? h->n_lipids : 0; }
+
+int mythos_membrane_eval(mythos_membrane_t* h, const void* pos, const void* box, int dtype, int n_frames, double* out,
+                         int8_t* leaflets, mythos_stream_t stream) {
+  if (!h || !pos || !box || !out || n_frames < 0 || (dtype != MYTHOS_F32 && dtype != MYTHOS_F64)) {
+    set_error("mythos_membrane_eval: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (n_frames == 0) return MYTHOS_OK;
+  MYTHOS_HIP_TRY(hipSetDevice(h->device));
+  constexpr int kFramesPerLaunch = 1 << 20;  // far below the grid limit; the frame index is blockIdx.x + frame0
+  for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
+    const int nf = std::min(n_frames - f0, kFramesPerLaunch);
+    if (dtype == MYTHOS_F32)
+      hipLaunchKernelGGL(membrane_kernel<float>, dim3(nf), dim3(kMemBlock), 0, (hipStream_t)stream, h->n, h->n_lipids, h->n_sel,
+                         h->n_thick, h->d_start, h->d_sel, h->d_thick, h->d_thick_lipid, (const float*)pos, (const float*)box, f0,
+                         out, leaflets);
+    else
+      hipLaunchKernelGGL(membrane_kernel<double>, dim3(nf), dim3(kMemBlock), 0, (hipStream_t)stream, h->n, h->n_lipids, h->n_sel,
+                         h->n_thick, h->d_start, h->d_sel, h->d_thick, h->d_thick_lipid, (const double*)pos, (const double*)box, f0,
+                         out, leaflets);
+  }
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return MYTHOS_OK;
+}
+
+}  // extern "C"

@@ -77,6 +77,9 @@ class MartiniTopology:
     residue_names: tuple
     angles: np.ndarray  # (n_angles, 3)
     bonded_neighbors: np.ndarray  # (n_bonds, 2)
+    # per bead the running number of its residue, non-decreasing (where one residue ends and the next of the same name
+    # begins); None on a topology built without it - the membrane observables then refuse it
+    residue_index: np.ndarray | None = None
 
     @property
     def bond_names(self) -> tuple:
@@ -109,22 +112,26 @@ class MartiniTopology:
                 cur = {"atoms": [], "bonds": [], "angles": []}
                 mols[tok[0]] = cur
             elif section == "atoms" and cur is not None:
-                cur["atoms"].append((tok[1], tok[3], tok[4]))  # type, residue, atom name
+                cur["atoms"].append((tok[1], tok[3], tok[4], int(tok[2])))  # type, residue, atom name, residue number
             elif section == "bonds" and cur is not None:
                 cur["bonds"].append((int(tok[0]) - 1, int(tok[1]) - 1))
             elif section == "angles" and cur is not None:
                 cur["angles"].append((int(tok[0]) - 1, int(tok[1]) - 1, int(tok[2]) - 1))
             elif section == "molecules":
                 order.append((tok[0], int(tok[1])))
-        types, names, res, bonds, angles = [], [], [], [], []
-        base = 0
+        types, names, res, resid, bonds, angles = [], [], [], [], [], []
+        base, running = 0, -1
         for name, count in order:
             mol = mols[name]
             for _ in range(count):
-                for t, r, a in mol["atoms"]:
+                last = None  # a new molecule instance starts a new residue, whatever its residue numbers
+                for t, r, a, nr in mol["atoms"]:
                     types.append(t)
                     res.append(r)
                     names.append(a)
+                    if nr != last:
+                        running, last = running + 1, nr
+                    resid.append(running)
                 bonds += [(base + i, base + j) for i, j in mol["bonds"]]
                 angles += [(base + i, base + j, base + k) for i, j, k in mol["angles"]]
                 base += len(mol["atoms"])
@@ -132,6 +139,7 @@ class MartiniTopology:
             atom_types=tuple(types), atom_names=tuple(names), residue_names=tuple(res),
             angles=np.array(angles, dtype=np.int32).reshape(-1, 3),
             bonded_neighbors=np.array(bonds, dtype=np.int32).reshape(-1, 2),
+            residue_index=np.array(resid, dtype=np.int32),
         )
 
     @classmethod
@@ -140,7 +148,7 @@ class MartiniTopology:
         MDAnalysis.Universe(tpr), mythos/energy/martini/base.py:76-84)."""
         t = read_tpr_topology(path)
         return cls(atom_types=t["atom_types"], atom_names=t["atom_names"], residue_names=t["residue_names"],
-                   angles=t["angles"], bonded_neighbors=t["bonds"])
+                   angles=t["angles"], bonded_neighbors=t["bonds"], residue_index=t["residue_index"])
 
     def tile(self, reps: int) -> "MartiniTopology":
         """The same molecules repeated ``reps`` times (for tiled boxes)."""
@@ -149,6 +157,8 @@ class MartiniTopology:
             atom_types=self.atom_types * reps, atom_names=self.atom_names * reps, residue_names=self.residue_names * reps,
             angles=np.concatenate([self.angles + k * n for k in range(reps)]),
             bonded_neighbors=np.concatenate([self.bonded_neighbors + k * n for k in range(reps)]),
+            residue_index=None if self.residue_index is None else np.concatenate(
+                [np.asarray(self.residue_index, dtype=np.int32) + k * (int(self.residue_index[-1]) + 1) for k in range(reps)]),
         )
 
 
@@ -210,7 +220,7 @@ class _Xdr:
 
 
 def read_tpr_topology(path) -> dict:
-    """Atom types / names / residue names and the bond and angle index lists of a GROMACS ``.tpr``.
+    """Atom types / names / residue names / running residue index and the bond and angle index lists of a GROMACS ``.tpr``.
 
     A narrow reader, written from the layout of GROMACS' tpxio serialisation: single precision, tpx version 137
     (GROMACS 2025), force fields made of bonds, (G96) angles, constraints and LJ tables - what MARTINI lipid systems
@@ -267,9 +277,10 @@ def read_tpr_topology(path) -> dict:
         r.ints(n_excl + 1 + n_excl_a)
         bonds = [tuple(il[k + 1:k + 3]) for ft in (_F_BONDS, _F_G96BONDS, _F_HARMONIC) for il in [ilists[ft]] for k in range(0, len(il), 3)]
         angles = [tuple(il[k + 1:k + 4]) for ft in (_F_ANGLES, _F_G96ANGLES) for il in [ilists[ft]] for k in range(0, len(il), 4)]
-        moltypes.append({"names": names, "types": types, "res": [resnames[k] for k in resind], "bonds": bonds, "angles": angles})
-    out = {"atom_types": [], "atom_names": [], "residue_names": [], "bonds": [], "angles": []}
-    base = 0
+        moltypes.append({"names": names, "types": types, "res": [resnames[k] for k in resind], "resind": resind, "nres": nres,
+                         "bonds": bonds, "angles": angles})
+    out = {"atom_types": [], "atom_names": [], "residue_names": [], "residue_index": [], "bonds": [], "angles": []}
+    base, res_base = 0, 0
     for _ in range(r.i4()):
         mt, nmol, nat_mol = moltypes[r.i4()], r.i4(), r.i4()
         r.i4(), r.i4()  # position-restraint counts
@@ -279,12 +290,15 @@ def read_tpr_topology(path) -> dict:
             out["atom_types"] += mt["types"]
             out["atom_names"] += mt["names"]
             out["residue_names"] += mt["res"]
+            out["residue_index"] += [res_base + k for k in mt["resind"]]
+            res_base += mt["nres"]
             out["bonds"] += [(base + i, base + j) for i, j in mt["bonds"]]
             out["angles"] += [(base + i, base + j, base + k) for i, j, k in mt["angles"]]
             base += nat_mol
     if base != natoms or r.i4() != natoms:
         raise ValueError(f"{path}: {base} atoms in the molecule blocks, {natoms} in the header")
     return {"atom_types": tuple(out["atom_types"]), "atom_names": tuple(out["atom_names"]), "residue_names": tuple(out["residue_names"]),
+            "residue_index": np.array(out["residue_index"], dtype=np.int32),
             "bonds": np.array(out["bonds"], dtype=np.int32).reshape(-1, 2), "angles": np.array(out["angles"], dtype=np.int32).reshape(-1, 3)}
 
 

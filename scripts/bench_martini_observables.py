@@ -9,6 +9,13 @@ Times, alternating in one process, every phase ended by a device synchronise, ea
   (c) mythos_w1_eval, forward + gradient, per optimisation step
   (d) the geometry launch
 and writes them with launch counts and the bytes each kernel must move (from shapes) to profiles/martini_w1.json.
+
+``--membrane`` measures the membrane launch instead (mythos_membrane_eval: leaflets, thickness, area per lipid) at 1 280
+beads and at the 16-fold tiled system, the same number of frames each: time per call by HIP events over back-to-back
+calls, next to the same quantities composed from torch ops on the same device tensors (index_select, means, a
+comparison, masked means - the yardstick, ``torch_membrane`` below), alternating, and writes
+profiles/martini_membrane.json.  ``--kernel-stats CSV`` adds the rows of a rocprofv3 --kernel-trace --stats table of a
+separate run of the same command (``--profile-run``: few repetitions, nothing written) to that file.
 """
 import argparse
 import json
@@ -23,7 +30,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from mythos_amd.hip_system import MartiniLangevinIntegrator, MartiniSystem  # noqa: E402
 from mythos_amd.input import gromacs  # noqa: E402
-from mythos_amd.observables import BondDistancesMapped, TripletAnglesMapped  # noqa: E402
+from mythos_amd.observables import AreaPerLipid, BondDistancesMapped, MembraneThickness, TripletAnglesMapped  # noqa: E402
 from mythos_amd.observables.wasserstein import W1Plan  # noqa: E402
 from mythos_amd.utils.generators import tiled_martini_box  # noqa: E402
 
@@ -79,14 +86,115 @@ def timed(fn, min_s=0.5):
             return (time.perf_counter() - t0) / n, n
 
 
+def torch_membrane(pos, box, sel, per_lipid, thick, thick_lipid):
+    """The membrane launch's quantities from torch ops, for lipids of ``per_lipid`` selected beads each, stored together:
+    (thickness, area per lipid, leaflets).  Eager torch: about a dozen kernels and their temporaries."""
+    z = pos[:, :, 2].double()
+    zs = z.index_select(1, sel)                                   # (S, n_sel)
+    mid = zs.mean(1, keepdim=True)                                # over beads
+    lipid_z = zs.view(zs.shape[0], -1, per_lipid).mean(2)         # (S, n_lipids)
+    up = lipid_z > mid
+    n_up = up.sum(1)
+    zt, tu = z.index_select(1, thick), up.index_select(1, thick_lipid)
+    z_up = (zt * tu).sum(1) / tu.sum(1)
+    z_lo = (zt * ~tu).sum(1) / (~tu).sum(1)
+    occupied = (n_up > 0).double() + (n_up < up.shape[1]).double()
+    area = box[:, 0].double() * box[:, 1].double() * occupied / up.shape[1]
+    return z_up - z_lo, area, torch.where(up, 1, -1).to(torch.int8)
+
+
+def event_ms(fn, calls=None, window_ms=500.0):
+    """Milliseconds per call between two HIP events around back-to-back calls: ``calls`` of them, or as many as fill
+    ``window_ms`` (sized from a first batch of 50)."""
+    def batch(n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n
+
+    fn()
+    torch.cuda.synchronize()
+    if calls is None:
+        calls = max(50, int(window_ms / max(batch(50), 1e-4)))
+    return batch(calls)
+
+
+def stored_frames(dev, reps, n_frames):
+    top, sysm, xt, bt = system(dev, reps)
+    integ = MartiniLangevinIntegrator(sysm, dt=0.02, kT=0.0083144626 * 310.0, gamma=1.0, seed=0)
+    integ.set_neighbor_policy(0.4, 8)
+    integ.load(torch.as_tensor(xt, dtype=torch.float32, device=dev).contiguous(), integ.init_velocities(), bt)
+    integ.advance(200)
+    frames, _ = integ.advance(n_frames * 10, save_every=10, want_energy=False)
+    return top, frames, torch.as_tensor(bt, dtype=torch.float32, device=dev).expand(n_frames, 3).contiguous()
+
+
+def membrane_main(args):
+    dev = torch.device("cuda", 0)
+    calls = 20 if args.profile_run else None
+    result = {"frames": args.frames, "window_ms_per_sample": 500.0, "rounds": args.rounds, "sizes": {}}
+    for reps in (1, args.reps):
+        top, frames, boxes = stored_frames(dev, reps, args.frames)
+
+        class Traj:
+            center = frames
+            box_size = boxes
+
+        thick = MembraneThickness(topology=top, lipid_sel="name GL1 GL2", thickness_sel="name PO4")
+        area = AreaPerLipid(topology=top, lipid_sel="name GL1 GL2")
+        _, start, sel, tb, tl = thick.index_lists()
+        assert np.all(np.diff(start) == 2)
+        idx = [torch.as_tensor(a, dtype=torch.int64, device=dev) for a in (sel, tb, tl)]
+        rows, leaf = thick.rows(Traj), thick.leaflets(Traj)
+        t_ref, a_ref, l_ref = torch_membrane(frames, boxes, idx[0], 2, idx[1], idx[2])
+        agree = {"thickness_max_abs_diff_nm": float((rows[:, 0] - t_ref).abs().max()), "area_max_rel_diff": float((rows[:, 1] / a_ref - 1).abs().max()),
+                 "leaflets_equal": bool(torch.equal(leaf, l_ref)), "upper_leaflet_min_max": [int(rows[:, 3].min()), int(rows[:, 3].max())]}
+        samples = {"hip_rows_ms": [], "hip_rows_and_leaflets_ms": [], "hip_area_only_ms": [], "torch_ms": []}
+        for _ in range(1 if args.profile_run else args.rounds):  # alternate
+            samples["torch_ms"].append(event_ms(lambda: torch_membrane(frames, boxes, idx[0], 2, idx[1], idx[2]), calls))
+            samples["hip_rows_ms"].append(event_ms(lambda: thick.rows(Traj), calls))
+            samples["hip_rows_and_leaflets_ms"].append(event_ms(lambda: thick.leaflets(Traj), calls))
+            samples["hip_area_only_ms"].append(event_ms(lambda: area.rows(Traj), calls))
+        n, n_lip = int(frames.shape[1]), len(start) - 1
+        result["sizes"][str(n)] = {
+            "beads": n, "lipids": n_lip, "median_ms_per_call": {k: float(np.median(v)) for k, v in samples.items()}, "all_ms_per_call": samples,
+            "launches_per_call": {"hip": 1, "torch": "see the kernel-trace summary"},
+            # per frame: the selection's z for the midpoint, again per lipid, the thickness beads' z and their lipids' z again
+            "gathered_z_per_frame": 2 * len(sel) + len(tb) * 3, "agreement_with_torch": agree}
+    if args.profile_run:
+        print(json.dumps(result))
+        return
+    if args.kernel_stats:
+        import csv
+        with open(args.kernel_stats) as f:
+            table = list(csv.DictReader(f))
+        keep = [r for r in table if "membrane_kernel" in r["Name"]] + [r for r in table if "at::native" in r["Name"] or "rocprim" in r["Name"]][:12]
+        result["rocprofv3_kernel_stats"] = {
+            "command": "rocprofv3 --kernel-trace --stats --output-format csv -- python scripts/bench_martini_observables.py --membrane --profile-run",
+            "rows": [{"name": r["Name"][:160], "calls": int(r["Calls"]), "average_ns": float(r["AverageNs"]), "min_ns": int(r["MinNs"]),
+                      "max_ns": int(r["MaxNs"]), "total_ns": int(r["TotalDurationNs"])} for r in keep]}
+    out = Path(args.out or ROOT / "profiles" / "martini_membrane.json")
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--n-ref", type=int, default=100_000)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "martini_w1.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/martini_w1.json, or profiles/martini_membrane.json with --membrane")
+    ap.add_argument("--membrane", action="store_true", help="measure the membrane launch instead (profiles/martini_membrane.json)")
+    ap.add_argument("--profile-run", action="store_true", help="--membrane: a short run for rocprofv3, writes nothing")
+    ap.add_argument("--kernel-stats", default=None, help="--membrane: a rocprofv3 kernel_stats.csv of a --profile-run to record")
     args = ap.parse_args()
+    if args.membrane:
+        return membrane_main(args)
     dev = torch.device("cuda", 0)
     top, sysm, xt, bt = system(dev, args.reps)
     integ = MartiniLangevinIntegrator(sysm, dt=0.02, kT=0.0083144626 * 310.0, gamma=1.0, seed=0)
@@ -160,8 +268,9 @@ def main():
     }
     result["bytes_min"]["c_w1_eval_total"] = sum(result["bytes_min"][k] for k in ("w1_chunk_sum", "w1_scan", "w1_suffix", "w1_frame_sum"))
     result["c_w1_eval_GBps"] = result["bytes_min"]["c_w1_eval_total"] / result["median_s"]["c_w1_eval_s"] / 1e9
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+    out = Path(args.out or ROOT / "profiles" / "martini_w1.json")
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(result, indent=1) + "\n")
     print(json.dumps(result))
 
 
