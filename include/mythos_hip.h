@@ -191,6 +191,8 @@ int mythos_oxdna_energy_obs(mythos_system_t* sys, const void* center, const void
  */
 mythos_sim_t* mythos_langevin_create(mythos_system_t* sys, double dt, double kT, double gamma_t, double gamma_r,
                                      double mass, const double* inertia, uint64_t seed);
+/* Order of destruction: an integrator may be destroyed after the system it was created on, but must not be USED after
+ * it - every other entry point of an integrator reads its system. */
 void mythos_langevin_destroy(mythos_sim_t* sim);
 
 /* neighbour-list policy of the MD loop: rebuild every `every` steps with cut-off r_cut + skin
@@ -360,6 +362,7 @@ int mythos_martini_param_grads(mythos_martini_t* m, const void* pos, const void*
  * Errors and the halt-and-resume protocol as mythos_langevin_run (NUMERIC: NaN). */
 mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, double dt, double kT, double gamma,
                                                      const double* mass, uint64_t seed);
+/* (may be destroyed after its system, but must not be used after it: see mythos_langevin_destroy) */
 void mythos_martini_langevin_destroy(mythos_martini_sim_t* sim);
 int mythos_martini_langevin_set_neighbor_policy(mythos_martini_sim_t* sim, double skin, int rebuild_every);
 /* Pruned rows (round 4; no counterpart in the reference - GROMACS, which runs its MARTINI dynamics, prunes its pair list

@@ -11,6 +11,8 @@ import ctypes as C
 import os
 from pathlib import Path
 
+import torch
+
 _LIB_PATH = Path(__file__).resolve().parent / "lib" / "libmythos_hip.so"
 
 c_int_p = C.POINTER(C.c_int32)
@@ -23,6 +25,86 @@ class MythosHipError(RuntimeError):
 
 
 _lib = None
+
+V = C.c_void_p
+# every prototype of include/mythos_hip.h: name -> (restype, argtypes)
+_SIGS = {
+    "mythos_version": (C.c_char_p, []),
+    "mythos_last_error": (C.c_char_p, []),
+    "mythos_device_count": (C.c_int, []),
+    "mythos_debug_set": (C.c_int, [C.c_int, C.c_int64]),
+    "mythos_debug_get": (C.c_int64, [C.c_int]),
+    "mythos_oxdna_param_count": (C.c_int, []),
+    "mythos_oxdna_param_name": (C.c_char_p, [C.c_int]),
+    "mythos_oxdna_create": (V, [C.c_int, C.c_int, c_int_p, c_uint8_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),
+    "mythos_oxdna_destroy": (None, [V]),
+    "mythos_oxdna_set_params": (C.c_int, [V, c_double_p, C.c_int]),
+    "mythos_oxdna_set_pseq": (C.c_int, [V, c_double_p, c_int_p, C.c_int, c_double_p, C.c_int]),
+    "mythos_oxdna_set_nucleotide_types": (C.c_int, [V, c_uint8_p]),
+    "mythos_oxdna_set_neighbors": (C.c_int, [V, c_int_p, C.c_int]),
+    "mythos_oxdna_build_neighbors": (C.c_int, [V, V, C.c_double, C.c_double, V]),
+    "mythos_oxdna_neighbor_stats": (C.c_int, [V, C.POINTER(C.c_int), c_double_p]),
+    "mythos_oxdna_energy": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V]),
+    "mythos_oxdna_energy_obs": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
+    "mythos_oxdna_energy_dpseq": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
+    "mythos_observables_create": (V, [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, C.c_int, C.c_int]),
+    "mythos_observables_destroy": (None, [V]),
+    "mythos_observables_width": (C.c_int, [V]),
+    "mythos_observables_eval": (C.c_int, [V, V, V, C.c_int, V, V]),
+    "mythos_langevin_create": (V, [V, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, c_double_p, C.c_uint64]),
+    "mythos_langevin_destroy": (None, [V]),
+    "mythos_langevin_set_neighbor_policy": (C.c_int, [V, C.c_double, C.c_double, C.c_int]),
+    "mythos_langevin_init_momenta": (C.c_int, [V, V, V, V]),
+    "mythos_langevin_run": (C.c_int, [V, V, V, V, V, C.c_int, C.c_int, V, V, V, V]),
+    "mythos_langevin_load": (C.c_int, [V, V, V, V, V, V]),
+    "mythos_langevin_advance": (C.c_int, [V, C.c_int, C.c_int, V, V, V, V]),
+    "mythos_langevin_store": (C.c_int, [V, V, V, V, V, V]),
+    "mythos_langevin_get_step": (C.c_int64, [V]),
+    "mythos_langevin_set_step": (C.c_int, [V, C.c_int64]),
+    "mythos_langevin_set_seed": (C.c_int, [V, C.c_uint64]),
+    "mythos_langevin_last_kernel_ms": (C.c_int, [V, c_double_p, c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mythos_langevin_set_option": (C.c_int, [V, C.c_int, C.c_int64]),
+    "mythos_langevin_set_timing": (C.c_int, [V, C.c_int]),
+    "mythos_martini_langevin_set_timing": (C.c_int, [V, C.c_int]),
+    "mythos_langevin_last_recoveries": (C.c_int, [V, C.POINTER(C.c_int)]),
+    "mythos_langevin_last_rebuilds": (C.c_int, [V, C.POINTER(C.c_int)]),
+    "mythos_oxdna_read_trajectory": (C.c_int, [C.c_char_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]),
+    "mythos_oxdna_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int]),
+    "mythos_martini_create": (
+        V,
+        [C.c_int, c_int_p, C.c_int, c_double_p, c_double_p, C.c_int, c_int_p, c_double_p, c_double_p, C.c_int,
+         c_int_p, c_double_p, c_double_p, C.c_int, C.c_double, C.c_int, C.c_int],
+    ),
+    "mythos_martini_destroy": (None, [V]),
+    "mythos_martini_energy": (C.c_int, [V, V, V, C.c_int, V, V, V]),
+    "mythos_martini_param_grads": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
+    "mythos_martini_langevin_create": (V, [V, C.c_double, C.c_double, C.c_double, c_double_p, C.c_uint64]),
+    "mythos_martini_langevin_destroy": (None, [V]),
+    "mythos_martini_langevin_set_neighbor_policy": (C.c_int, [V, C.c_double, C.c_int]),
+    "mythos_martini_langevin_set_inner_list": (C.c_int, [V, C.c_double, C.c_int]),
+    "mythos_martini_langevin_init_velocities": (C.c_int, [V, V, V]),
+    "mythos_martini_langevin_run": (C.c_int, [V, V, V, c_double_p, C.c_int, C.c_int, V, V, V]),
+    "mythos_martini_langevin_load": (C.c_int, [V, V, V, c_double_p, V]),
+    "mythos_martini_langevin_advance": (C.c_int, [V, C.c_int, C.c_int, V, V, V]),
+    "mythos_martini_langevin_store": (C.c_int, [V, V, V, V]),
+    "mythos_martini_langevin_get_step": (C.c_int64, [V]),
+    "mythos_martini_langevin_last_rebuilds": (C.c_int, [V, C.POINTER(C.c_int)]),
+    "mythos_martini_langevin_last_kernel_ms": (C.c_int, [V, c_double_p, c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mythos_martini_langevin_last_recoveries": (C.c_int, [V, C.POINTER(C.c_int)]),
+    "mythos_martini_langevin_neighbor_stats": (C.c_int, [V, C.POINTER(C.c_int), c_double_p]),
+    "mythos_martini_langevin_get_rows": (C.c_int, [V, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "mythos_martini_obs_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int]),
+    "mythos_martini_obs_destroy": (None, [V]),
+    "mythos_martini_obs_count": (C.c_int64, [V]),
+    "mythos_martini_obs_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V]),
+    "mythos_w1_plan_create": (V, [C.c_int, c_int_p, c_int_p, V, C.POINTER(C.c_int64), V, V, c_uint8_p, V, C.c_int, V]),
+    "mythos_w1_plan_destroy": (None, [V]),
+    "mythos_w1_eval": (C.c_int, [V, V, V, V, V]),
+    "mythos_membrane_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int]),
+    "mythos_membrane_destroy": (None, [V]),
+    "mythos_membrane_n_lipids": (C.c_int, [V]),
+    "mythos_membrane_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V, V]),
+}
 
 
 def lib_path() -> Path:
@@ -41,85 +123,7 @@ def load() -> C.CDLL:
             "mythos_amd has no CPU fallback."
         )
     lib = C.CDLL(str(path))
-    V = C.c_void_p
-    sigs = {
-        "mythos_version": (C.c_char_p, []),
-        "mythos_last_error": (C.c_char_p, []),
-        "mythos_device_count": (C.c_int, []),
-        "mythos_debug_set": (C.c_int, [C.c_int, C.c_int64]),
-        "mythos_debug_get": (C.c_int64, [C.c_int]),
-        "mythos_oxdna_param_count": (C.c_int, []),
-        "mythos_oxdna_param_name": (C.c_char_p, [C.c_int]),
-        "mythos_oxdna_create": (V, [C.c_int, C.c_int, c_int_p, c_uint8_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),
-        "mythos_oxdna_destroy": (None, [V]),
-        "mythos_oxdna_set_params": (C.c_int, [V, c_double_p, C.c_int]),
-        "mythos_oxdna_set_pseq": (C.c_int, [V, c_double_p, c_int_p, C.c_int, c_double_p, C.c_int]),
-        "mythos_oxdna_set_nucleotide_types": (C.c_int, [V, c_uint8_p]),
-        "mythos_oxdna_set_neighbors": (C.c_int, [V, c_int_p, C.c_int]),
-        "mythos_oxdna_build_neighbors": (C.c_int, [V, V, C.c_double, C.c_double, V]),
-        "mythos_oxdna_neighbor_stats": (C.c_int, [V, C.POINTER(C.c_int), c_double_p]),
-        "mythos_oxdna_energy": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V]),
-        "mythos_oxdna_energy_obs": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
-        "mythos_oxdna_energy_dpseq": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
-        "mythos_observables_create": (V, [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, C.c_int, C.c_int]),
-        "mythos_observables_destroy": (None, [V]),
-        "mythos_observables_width": (C.c_int, [V]),
-        "mythos_observables_eval": (C.c_int, [V, V, V, C.c_int, V, V]),
-        "mythos_langevin_create": (V, [V, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, c_double_p, C.c_uint64]),
-        "mythos_langevin_destroy": (None, [V]),
-        "mythos_langevin_set_neighbor_policy": (C.c_int, [V, C.c_double, C.c_double, C.c_int]),
-        "mythos_langevin_init_momenta": (C.c_int, [V, V, V, V]),
-        "mythos_langevin_run": (C.c_int, [V, V, V, V, V, C.c_int, C.c_int, V, V, V, V]),
-        "mythos_langevin_load": (C.c_int, [V, V, V, V, V, V]),
-        "mythos_langevin_advance": (C.c_int, [V, C.c_int, C.c_int, V, V, V, V]),
-        "mythos_langevin_store": (C.c_int, [V, V, V, V, V, V]),
-        "mythos_langevin_get_step": (C.c_int64, [V]),
-        "mythos_langevin_set_step": (C.c_int, [V, C.c_int64]),
-        "mythos_langevin_set_seed": (C.c_int, [V, C.c_uint64]),
-        "mythos_langevin_last_kernel_ms": (C.c_int, [V, c_double_p, c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-        "mythos_langevin_set_option": (C.c_int, [V, C.c_int, C.c_int64]),
-        "mythos_langevin_set_timing": (C.c_int, [V, C.c_int]),
-        "mythos_martini_langevin_set_timing": (C.c_int, [V, C.c_int]),
-        "mythos_langevin_last_recoveries": (C.c_int, [V, C.POINTER(C.c_int)]),
-        "mythos_langevin_last_rebuilds": (C.c_int, [V, C.POINTER(C.c_int)]),
-        "mythos_oxdna_read_trajectory": (C.c_int, [C.c_char_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]),
-        "mythos_oxdna_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int]),
-        "mythos_martini_create": (
-            V,
-            [C.c_int, c_int_p, C.c_int, c_double_p, c_double_p, C.c_int, c_int_p, c_double_p, c_double_p, C.c_int,
-             c_int_p, c_double_p, c_double_p, C.c_int, C.c_double, C.c_int, C.c_int],
-        ),
-        "mythos_martini_destroy": (None, [V]),
-        "mythos_martini_energy": (C.c_int, [V, V, V, C.c_int, V, V, V]),
-        "mythos_martini_param_grads": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
-        "mythos_martini_langevin_create": (V, [V, C.c_double, C.c_double, C.c_double, c_double_p, C.c_uint64]),
-        "mythos_martini_langevin_destroy": (None, [V]),
-        "mythos_martini_langevin_set_neighbor_policy": (C.c_int, [V, C.c_double, C.c_int]),
-        "mythos_martini_langevin_set_inner_list": (C.c_int, [V, C.c_double, C.c_int]),
-        "mythos_martini_langevin_init_velocities": (C.c_int, [V, V, V]),
-        "mythos_martini_langevin_run": (C.c_int, [V, V, V, c_double_p, C.c_int, C.c_int, V, V, V]),
-        "mythos_martini_langevin_load": (C.c_int, [V, V, V, c_double_p, V]),
-        "mythos_martini_langevin_advance": (C.c_int, [V, C.c_int, C.c_int, V, V, V]),
-        "mythos_martini_langevin_store": (C.c_int, [V, V, V, V]),
-        "mythos_martini_langevin_get_step": (C.c_int64, [V]),
-        "mythos_martini_langevin_last_rebuilds": (C.c_int, [V, C.POINTER(C.c_int)]),
-        "mythos_martini_langevin_last_kernel_ms": (C.c_int, [V, c_double_p, c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-        "mythos_martini_langevin_last_recoveries": (C.c_int, [V, C.POINTER(C.c_int)]),
-        "mythos_martini_langevin_neighbor_stats": (C.c_int, [V, C.POINTER(C.c_int), c_double_p]),
-        "mythos_martini_langevin_get_rows": (C.c_int, [V, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
-        "mythos_martini_obs_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int]),
-        "mythos_martini_obs_destroy": (None, [V]),
-        "mythos_martini_obs_count": (C.c_int64, [V]),
-        "mythos_martini_obs_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V]),
-        "mythos_w1_plan_create": (V, [C.c_int, c_int_p, c_int_p, V, C.POINTER(C.c_int64), V, V, c_uint8_p, V, C.c_int, V]),
-        "mythos_w1_plan_destroy": (None, [V]),
-        "mythos_w1_eval": (C.c_int, [V, V, V, V, V]),
-        "mythos_membrane_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int]),
-        "mythos_membrane_destroy": (None, [V]),
-        "mythos_membrane_n_lipids": (C.c_int, [V]),
-        "mythos_membrane_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V, V]),
-    }
-    for name, (res, args) in sigs.items():
+    for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name)  # AttributeError here = header / library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args
@@ -127,79 +131,7 @@ def load() -> C.CDLL:
     return lib
 
 
-DECLARED_SYMBOLS = (
-    "mythos_version",
-    "mythos_last_error",
-    "mythos_device_count",
-    "mythos_debug_set",
-    "mythos_debug_get",
-    "mythos_oxdna_param_count",
-    "mythos_oxdna_param_name",
-    "mythos_oxdna_create",
-    "mythos_oxdna_destroy",
-    "mythos_oxdna_set_params",
-    "mythos_oxdna_set_pseq",
-    "mythos_oxdna_set_nucleotide_types",
-    "mythos_oxdna_set_neighbors",
-    "mythos_oxdna_build_neighbors",
-    "mythos_oxdna_neighbor_stats",
-    "mythos_oxdna_energy",
-    "mythos_oxdna_energy_obs",
-    "mythos_oxdna_energy_dpseq",
-    "mythos_observables_create",
-    "mythos_observables_destroy",
-    "mythos_observables_width",
-    "mythos_observables_eval",
-    "mythos_langevin_create",
-    "mythos_langevin_destroy",
-    "mythos_langevin_set_neighbor_policy",
-    "mythos_langevin_init_momenta",
-    "mythos_langevin_run",
-    "mythos_langevin_load",
-    "mythos_langevin_advance",
-    "mythos_langevin_store",
-    "mythos_langevin_get_step",
-    "mythos_langevin_set_step",
-    "mythos_langevin_set_seed",
-    "mythos_langevin_last_kernel_ms",
-    "mythos_langevin_last_recoveries",
-    "mythos_langevin_last_rebuilds",
-    "mythos_langevin_set_option",
-    "mythos_langevin_set_timing",
-    "mythos_martini_langevin_set_timing",
-    "mythos_oxdna_read_trajectory",
-    "mythos_oxdna_write_trajectory",
-    "mythos_martini_create",
-    "mythos_martini_destroy",
-    "mythos_martini_energy",
-    "mythos_martini_param_grads",
-    "mythos_martini_langevin_create",
-    "mythos_martini_langevin_destroy",
-    "mythos_martini_langevin_set_neighbor_policy",
-    "mythos_martini_langevin_set_inner_list",
-    "mythos_martini_langevin_init_velocities",
-    "mythos_martini_langevin_run",
-    "mythos_martini_langevin_load",
-    "mythos_martini_langevin_advance",
-    "mythos_martini_langevin_store",
-    "mythos_martini_langevin_get_step",
-    "mythos_martini_langevin_last_rebuilds",
-    "mythos_martini_langevin_last_kernel_ms",
-    "mythos_martini_langevin_neighbor_stats",
-    "mythos_martini_langevin_get_rows",
-    "mythos_martini_langevin_last_recoveries",
-    "mythos_martini_obs_create",
-    "mythos_martini_obs_destroy",
-    "mythos_martini_obs_count",
-    "mythos_martini_obs_eval",
-    "mythos_w1_plan_create",
-    "mythos_w1_plan_destroy",
-    "mythos_w1_eval",
-    "mythos_membrane_create",
-    "mythos_membrane_destroy",
-    "mythos_membrane_n_lipids",
-    "mythos_membrane_eval",
-)
+DECLARED_SYMBOLS = tuple(_SIGS)
 
 
 MEMBRANE_ROW = 7  # MYTHOS_MEMBRANE_ROW of include/mythos_hip.h: doubles per frame of mythos_membrane_eval
@@ -256,3 +188,52 @@ def ptr(t):
     if hasattr(t, "data_ptr"):
         return C.c_void_p(t.data_ptr())
     return C.c_void_p(t.ctypes.data)
+
+
+def stream(device) -> C.c_void_p:
+    """torch's current stream on ``device`` as the ABI's mythos_stream_t."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def dtype_code(dtype: torch.dtype) -> int:
+    """MYTHOS_F32 / MYTHOS_F64 of include/mythos_hip.h."""
+    if dtype == torch.float32:
+        return 0
+    if dtype == torch.float64:
+        return 1
+    raise ValueError(f"unsupported dtype {dtype}: use torch.float32 or torch.float64")
+
+
+class Handle:
+    """Owner of one handle of the C ABI: ``self._h`` from the named create function (NULL raises with the library's
+    message), given back through the function the subclass names in ``_destroy`` by ``close()`` - any number of times -
+    or when the object goes."""
+
+    _destroy = ""
+    _h = None
+
+    def __init__(self, create: str, *args):
+        self._lib = load()
+        self._h = getattr(self._lib, create)(*args)
+        if not self._h:
+            raise MythosHipError(f"{create}: {last_error()}")
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h:
+            getattr(self._lib, self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def per_device(owner, device, make):
+    """``make()`` once per device for ``owner`` (an observable object, frozen dataclasses included), kept in its ``_sets``."""
+    sets = owner.__dict__.setdefault("_sets", {})
+    key = str(device)
+    if key not in sets:
+        sets[key] = make()
+    return sets[key]

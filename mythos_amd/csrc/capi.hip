@@ -2,6 +2,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <memory>
 
 #include "cell_list.h"
 #include "observables.h"
@@ -72,20 +73,8 @@ mythos_system_t* mythos_oxdna_create(int model, int n, const int32_t* seq, const
     set_error("mythos_oxdna_create: invalid argument");
     return nullptr;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("mythos_oxdna_create: no HIP device visible (the HIP path has no CPU fallback)");
-    return nullptr;
-  }
-  if (device < 0 || device >= ndev) {
-    set_error("mythos_oxdna_create: device index out of range");
-    return nullptr;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    set_error("mythos_oxdna_create: hipSetDevice failed");
-    return nullptr;
-  }
-  auto* s = new mythos_system();
+  if (select_device(device, "mythos_oxdna_create")) return nullptr;
+  auto s = std::make_unique<mythos_system>();
   s->model = model;
   s->n = n;
   s->dtype = dtype;
@@ -96,7 +85,6 @@ mythos_system_t* mythos_oxdna_create(int model, int n, const int32_t* seq, const
     for (int k = 0; k < 3; ++k) s->box[k] = box[k];
     if (!(box[0] > 0 && box[1] > 0 && box[2] > 0)) {
       set_error("mythos_oxdna_create: box lengths must be positive");
-      delete s;
       return nullptr;
     }
   }
@@ -104,18 +92,15 @@ mythos_system_t* mythos_oxdna_create(int model, int n, const int32_t* seq, const
   for (int i = 0; i < n; ++i) {
     if (seq[i] < 0 || seq[i] > 3) {
       set_error("mythos_oxdna_create: sequence entries must be 0..3");
-      delete s;
       return nullptr;
     }
     meta[i] = seq[i] | ((is_end && is_end[i]) ? 4 : 0);
   }
-  s->h_meta = meta;
   s->h_partners.assign((size_t)ROW_BONDED_SLOTS * n, -1);
   for (int b = 0; b < n_bonded; ++b) {
     const int i = bonded[2 * b], j = bonded[2 * b + 1];
     if (i < 0 || j < 0 || i >= n || j >= n || i == j) {
       set_error("mythos_oxdna_create: bonded index out of range");
-      delete s;
       return nullptr;
     }
     int* pi = &s->h_partners[(size_t)ROW_BONDED_SLOTS * i];
@@ -124,48 +109,24 @@ mythos_system_t* mythos_oxdna_create(int model, int n, const int32_t* seq, const
     const int sj = pj[0] == -1 ? 0 : 2;  // j plays nn_j: even slots
     if (pi[si] != -1 || pj[sj] != -1) {
       set_error("mythos_oxdna_create: a nucleotide has more than two bonded partners in one role");
-      delete s;
       return nullptr;
     }
     pi[si] = j;
     pj[sj] = i;
     if (si == 3 || sj == 2) s->extra_bonds = true;
   }
-  bool ok = hipMalloc((void**)&s->d_meta, n * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&s->d_row_len, (size_t)(2 + ROW_BONDED_SLOTS) * n * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&s->list.d_overflow, kOverflowWords * sizeof(int)) == hipSuccess &&
-            hipMemcpy(s->d_meta, meta.data(), n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(s->d_row_len + n, s->h_partners.data(), (size_t)ROW_BONDED_SLOTS * n * sizeof(int), hipMemcpyHostToDevice) ==
-                hipSuccess &&
-            hipMemset(s->list.d_overflow, 0, kOverflowWords * sizeof(int)) == hipSuccess;
-  if (!ok) {
+  s->h_meta = meta;
+  if (s->d_meta.upload(meta) || s->d_row_len.alloc((size_t)(2 + ROW_BONDED_SLOTS) * n) || s->list.d_overflow.alloc(kOverflowWords) ||
+      hipMemcpy(s->d_row_len.get() + n, s->h_partners.data(), (size_t)ROW_BONDED_SLOTS * n * sizeof(int), hipMemcpyHostToDevice) !=
+          hipSuccess ||
+      hipMemset(s->list.d_overflow.get(), 0, kOverflowWords * sizeof(int)) != hipSuccess) {
     set_error("mythos_oxdna_create: device allocation failed");
-    mythos_oxdna_destroy(s);
     return nullptr;
   }
-  return s;
+  return s.release();
 }
 
-void mythos_oxdna_destroy(mythos_system_t* s) {
-  if (!s) return;
-  (void)hipSetDevice(s->device);
-  if (s->d_meta) (void)hipFree(s->d_meta);
-  if (s->list.d_rows) (void)hipFree(s->list.d_rows);
-  if (s->d_row_len) (void)hipFree(s->d_row_len);
-  if (s->list.d_overflow) (void)hipFree(s->list.d_overflow);
-  if (s->list.d_cell) (void)hipFree(s->list.d_cell);
-  if (s->d_ref_pos) (void)hipFree(s->d_ref_pos);
-  if (s->d_ref_off) (void)hipFree(s->d_ref_off);
-  if (s->d_ref_a1) (void)hipFree(s->d_ref_a1);
-  if (s->d_pf) (void)hipFree(s->d_pf);
-  if (s->d_pd) (void)hipFree(s->d_pd);
-  if (s->d_epart) (void)hipFree(s->d_epart);
-  if (s->d_pgpart) (void)hipFree(s->d_pgpart);
-  if (s->d_ps_marg) (void)hipFree(s->d_ps_marg);
-  if (s->d_ps_unit) (void)hipFree(s->d_ps_unit);
-  if (s->d_ps_bp) (void)hipFree(s->d_ps_bp);
-  delete s;
-}
+void mythos_oxdna_destroy(mythos_system_t* s) { delete s; }
 
 int mythos_oxdna_set_params(mythos_system_t* s, const double* flat, int n_params) {
   const int sets = s ? s->param_sets() : 1;
@@ -189,11 +150,11 @@ int mythos_oxdna_set_params(mythos_system_t* s, const double* flat, int n_params
   // device copies for the MD kernel; a blocking copy after a device-wide sync, so no kernel in flight
   // sees a half-written vector
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
-  if (!s->d_pf) MYTHOS_HIP_TRY(hipMalloc((void**)&s->d_pf, total * sizeof(float)));
-  if (!s->d_pd) MYTHOS_HIP_TRY(hipMalloc((void**)&s->d_pd, total * sizeof(double)));
+  if (int rc = s->d_pf.grow(total)) return rc;
+  if (int rc = s->d_pd.grow(total)) return rc;
   MYTHOS_HIP_TRY(hipDeviceSynchronize());
-  MYTHOS_HIP_TRY(hipMemcpy(s->d_pf, pf_sets.data(), total * sizeof(float), hipMemcpyHostToDevice));
-  MYTHOS_HIP_TRY(hipMemcpy(s->d_pd, s->pd_sets.data(), total * sizeof(double), hipMemcpyHostToDevice));
+  MYTHOS_HIP_TRY(hipMemcpy(s->d_pf.get(), pf_sets.data(), total * sizeof(float), hipMemcpyHostToDevice));
+  MYTHOS_HIP_TRY(hipMemcpy(s->d_pd.get(), s->pd_sets.data(), total * sizeof(double), hipMemcpyHostToDevice));
   s->params_set = true;
   ++s->list_epoch;  // cut-offs may have moved: integrators rebuild their list
   ++s->param_epoch; // ... and re-derive the site offsets their resident frames carry
@@ -212,7 +173,7 @@ int mythos_oxdna_set_nucleotide_types(mythos_system_t* s, const uint8_t* is_rna)
   for (int i = 0; i < s->n; ++i) s->h_meta[i] = (s->h_meta[i] & 7) | (is_rna[i] ? 8 : 0);
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
   MYTHOS_HIP_TRY(hipDeviceSynchronize());
-  MYTHOS_HIP_TRY(hipMemcpy(s->d_meta, s->h_meta.data(), s->n * sizeof(int), hipMemcpyHostToDevice));
+  MYTHOS_HIP_TRY(hipMemcpy(s->d_meta.get(), s->h_meta.data(), s->n * sizeof(int), hipMemcpyHostToDevice));
   s->types_set = true;
   ++s->list_epoch;
   ++s->param_epoch;
@@ -286,28 +247,12 @@ int mythos_oxdna_set_pseq(mythos_system_t* s, const double* marginals, const int
         }
     }
   }
-  const size_t word = s->dtype == MYTHOS_F32 ? sizeof(float) : sizeof(double);
-  const int nb = std::max(n_bp, 1);
-  if (!s->d_ps_marg) MYTHOS_HIP_TRY(hipMalloc(&s->d_ps_marg, 4 * (size_t)n * word));
-  if (!s->d_ps_unit) MYTHOS_HIP_TRY(hipMalloc((void**)&s->d_ps_unit, (size_t)n * sizeof(int)));
-  if (nb > s->ps_bp_cap) {
-    if (s->d_ps_bp) (void)hipFree(s->d_ps_bp);
-    s->d_ps_bp = nullptr;
-    s->ps_bp_cap = 0;
-    MYTHOS_HIP_TRY(hipMalloc(&s->d_ps_bp, 4 * (size_t)nb * word));
-    s->ps_bp_cap = nb;
-  }
-  std::vector<double> bp(4 * (size_t)nb, 0.0);
+  // (the tables are replaced whole, behind the device-wide synchronisation above)
+  std::vector<double> bp(4 * (size_t)std::max(n_bp, 1), 0.0);
   if (n_bp > 0) std::copy(bp_probs, bp_probs + 4 * (size_t)n_bp, bp.begin());
-  if (s->dtype == MYTHOS_F32) {
-    std::vector<float> mf(marginals, marginals + 4 * (size_t)n), bf(bp.begin(), bp.end());
-    MYTHOS_HIP_TRY(hipMemcpy(s->d_ps_marg, mf.data(), mf.size() * sizeof(float), hipMemcpyHostToDevice));
-    MYTHOS_HIP_TRY(hipMemcpy(s->d_ps_bp, bf.data(), bf.size() * sizeof(float), hipMemcpyHostToDevice));
-  } else {
-    MYTHOS_HIP_TRY(hipMemcpy(s->d_ps_marg, marginals, 4 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    MYTHOS_HIP_TRY(hipMemcpy(s->d_ps_bp, bp.data(), bp.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  MYTHOS_HIP_TRY(hipMemcpy(s->d_ps_unit, unit, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  if (int rc = s->d_ps_marg.upload_real(s->dtype, marginals, 4 * (size_t)n)) return rc;
+  if (int rc = s->d_ps_bp.upload_real(s->dtype, bp.data(), bp.size())) return rc;
+  if (int rc = s->d_ps_unit.upload(unit, (size_t)n)) return rc;
   s->pseq_terms = terms;
   s->ps_n_bp = n_bp;
   ++s->list_epoch;
@@ -342,7 +287,7 @@ int mythos_oxdna_neighbor_stats(mythos_system_t* s, int* max_row, double* mean_r
     return MYTHOS_ERR_NOT_READY;
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
-  return row_stats(s->d_row_len, s->n, ROW_BONDED_SLOTS, max_row, mean_row);
+  return row_stats(s->d_row_len.get(), s->n, ROW_BONDED_SLOTS, max_row, mean_row);
 }
 
 int mythos_oxdna_energy(mythos_system_t* s, const void* center, const void* quat, int n_frames, double* e_terms,

@@ -320,7 +320,7 @@ __device__ __forceinline__ int cell_candidates(const CellGrid<R>& g, R x, R y, R
 
 // rows of n particles at the given stride; the allocation only grows
 static inline int rows_reserve(VerletRows& L, int n, int stride) {
-  if (int rc = grow_buffer(L.d_rows, L.rows_cap, (size_t)n * stride)) return rc;
+  if (int rc = L.d_rows.grow((size_t)n * stride)) return rc;
   L.stride = stride;
   return 0;
 }
@@ -354,14 +354,14 @@ static inline int cell_table(VerletRows& L, int H, bool sites, hipStream_t st, C
   if (cell_cap_override()) L.cell_bucket_cap = cell_cap_override();
   const int cap = L.cell_bucket_cap;
   if (!L.d_cell || H != L.cell_H || cap != L.cell_alloc_bucket_cap || sites != L.cell_sites) {
-    if (int rc = grow_buffer(L.d_cell, L.cell_cap, CellBins::ints(H, cap, sizeof(R), sites))) return rc;
-    MYTHOS_HIP_TRY(hipMemsetAsync(L.d_cell + CellBins::zero_offset(H, cap, sizeof(R), sites), 0, CellBins::zero_ints(H) * sizeof(int), st));
+    if (int rc = L.d_cell.grow(CellBins::ints(H, cap, sizeof(R), sites))) return rc;
+    MYTHOS_HIP_TRY(hipMemsetAsync(L.d_cell.get() + CellBins::zero_offset(H, cap, sizeof(R), sites), 0, CellBins::zero_ints(H) * sizeof(int), st));
     L.cell_H = H;
     L.cell_alloc_bucket_cap = cap;
     L.cell_sites = sites;
     L.cell_phase = 0;
   }
-  bins = CellBins(L.d_cell, H, cap, sizeof(R), L.cell_phase, sites);
+  bins = CellBins(L.d_cell.get(), H, cap, sizeof(R), L.cell_phase, sites);
   L.cell_phase ^= 1;
   return 0;
 }
@@ -373,10 +373,10 @@ static inline int cell_table(VerletRows& L, int H, bool sites, hipStream_t st, C
 template <class Build>
 static int list_build_until_fit(VerletRows& L, int n, Build&& build, bool headroom, const char* who, hipStream_t st) {
   for (int attempt = 0; attempt < 6; ++attempt) {
-    MYTHOS_HIP_TRY(hipMemsetAsync(L.d_overflow, 0, kOverflowWords * sizeof(int), st));
+    MYTHOS_HIP_TRY(hipMemsetAsync(L.d_overflow.get(), 0, kOverflowWords * sizeof(int), st));
     if (int rc = build()) return rc;
     int ov[kOverflowWords] = {0, 0, 0};
-    MYTHOS_HIP_TRY(hipMemcpyAsync(ov, L.d_overflow, sizeof(ov), hipMemcpyDeviceToHost, st));
+    MYTHOS_HIP_TRY(hipMemcpyAsync(ov, L.d_overflow.get(), sizeof(ov), hipMemcpyDeviceToHost, st));
     MYTHOS_HIP_TRY(hipStreamSynchronize(st));
     if (ov[1] > 0) {
       set_error(std::string(who) + ": more than " + std::to_string(kCellSpill) + " particles did not fit the buckets of their cells");
@@ -384,7 +384,7 @@ static int list_build_until_fit(VerletRows& L, int n, Build&& build, bool headro
     }
     const int bucket_demand = cell_cap_override() ? 0 : ov[2];  // a bucket more than half full: double the places
     if (ov[0] == 0 && bucket_demand == 0) {
-      if (ov[2] > 0) MYTHOS_HIP_TRY(hipMemsetAsync(L.d_overflow + 2, 0, sizeof(int), st));
+      if (ov[2] > 0) MYTHOS_HIP_TRY(hipMemsetAsync(L.d_overflow.get() + 2, 0, sizeof(int), st));
       return MYTHOS_OK;
     }
     if (ov[0] > 0) {

@@ -1,5 +1,7 @@
 // Langevin integrator, translation unit 1 of 2: the fp32 instantiations of langevin_core.inc and the C entry points
 // (mythos_langevin_*).  The fp64 instantiations are in langevin_f64.hip.
+#include <memory>
+
 #include "langevin_core.inc"
 
 MYTHOS_MD_DEFINE_PRECISION(float)
@@ -12,12 +14,10 @@ mythos_sim_t* mythos_langevin_create(mythos_system_t* sys, double dt, double kT,
     set_error("mythos_langevin_create: invalid argument");
     return nullptr;
   }
-  if (hipSetDevice(sys->device) != hipSuccess) {
-    set_error("mythos_langevin_create: hipSetDevice failed");
-    return nullptr;
-  }
-  auto* s = new mythos_sim();
+  if (select_device(sys->device, "mythos_langevin_create")) return nullptr;
+  auto s = std::make_unique<mythos_sim>();
   s->sys = sys;
+  s->device = sys->device;
   s->dt = dt;
   s->kT = kT;
   s->gamma_t = gamma_t;
@@ -28,36 +28,18 @@ mythos_sim_t* mythos_langevin_create(mythos_system_t* sys, double dt, double kT,
   const size_t v4 = (sys->dtype == MYTHOS_F32 ? sizeof(float4) : sizeof(double4)) * (size_t)sys->n;
   bool ok = md_run_create(*s);
   for (int k = 0; k < 2; ++k)
-    for (int a = 0; a < mythos_sim::kFrameArrays; ++a) ok = ok && hipMalloc(&s->frame[k][a], v4) == hipSuccess;
-  ok = ok && hipMalloc(&s->keep_hi, v4) == hipSuccess && hipMalloc(&s->keep_lo, v4) == hipSuccess;
-  // (one row of partials per workgroup of the narrowest launch: 16 lanes per nucleotide)
-  ok = ok && hipMalloc((void**)&s->d_epart, (size_t)((sys->n + 15) / 16) * kTraceWidth * sizeof(double)) == hipSuccess;
-  if (ok && !sys->d_ref_pos) ok = hipMalloc(&sys->d_ref_pos, v4) == hipSuccess;
-  if (ok && !sys->d_ref_off) ok = hipMalloc(&sys->d_ref_off, v4) == hipSuccess;
-  if (ok && !sys->d_ref_a1) ok = hipMalloc(&sys->d_ref_a1, v4) == hipSuccess;
+    for (int a = 0; a < mythos_sim::kFrameArrays; ++a) ok = ok && s->frame[k][a].alloc(v4) == 0;
+  // (d_epart: one row of partials per workgroup of the narrowest launch, 16 lanes per nucleotide)
+  ok = ok && s->keep_hi.alloc(v4) == 0 && s->keep_lo.alloc(v4) == 0 &&
+       s->d_epart.alloc((size_t)((sys->n + 15) / 16) * kTraceWidth) == 0 && sys->reserve_refs() == 0;
   if (!ok) {
     set_error("mythos_langevin_create: device allocation failed");
-    mythos_langevin_destroy(s);
     return nullptr;
   }
-  return s;
+  return s.release();
 }
 
-void mythos_langevin_destroy(mythos_sim_t* s) {
-  if (!s) return;
-  for (int k = 0; k < 2; ++k)
-    for (int a = 0; a < mythos_sim::kFrameArrays; ++a)
-      if (s->frame[k][a]) (void)hipFree(s->frame[k][a]);
-  for (void* u : {s->u_c, s->u_q, s->u_p, s->u_l, s->u_gc, s->u_gq, s->u_ref, (void*)s->u_e})
-    if (u) (void)hipFree(u);
-  if (s->keep_hi) (void)hipFree(s->keep_hi);
-  if (s->keep_lo) (void)hipFree(s->keep_lo);
-  if (s->d_chunk_order) (void)hipFree(s->d_chunk_order);
-  if (s->d_chunk_keys) (void)hipFree(s->d_chunk_keys);
-  if (s->d_epart) (void)hipFree(s->d_epart);
-  md_run_destroy(*s);
-  delete s;
-}
+void mythos_langevin_destroy(mythos_sim_t* s) { delete s; }
 
 int mythos_langevin_set_neighbor_policy(mythos_sim_t* s, double r_cut, double skin, int every) {
   if (!s || (every > 0 && (!(r_cut > 0) || !(skin > 0)))) {
@@ -77,7 +59,7 @@ int mythos_langevin_init_momenta(mythos_sim_t* s, void* p_lin, void* p_ang, myth
     set_error("mythos_langevin_init_momenta: invalid argument");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
   return s->sys->dtype == MYTHOS_F32 ? mythos_md_init_momenta<float>(s, p_lin, p_ang, (hipStream_t)stream)
                                      : mythos_md_init_momenta<double>(s, p_lin, p_ang, (hipStream_t)stream);
 }
@@ -196,7 +178,7 @@ int mythos_langevin_store(mythos_sim_t* s, void* center, void* quat, void* p_lin
   if (s->open) {  // one more launch closes the frame: what a launch needs has to be there (it was, for the advance before)
     if (int rc = md_ready(s, "mythos_langevin_store")) return rc;
   } else {  // a copy: load; store round-trips a state whether or not neighbours were ever set
-    MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
+    MYTHOS_HIP_TRY(hipSetDevice(s->device));
   }
   return md_store(s, center, quat, p_lin, p_ang, (hipStream_t)stream);
 }

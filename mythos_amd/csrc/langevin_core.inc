@@ -1202,30 +1202,31 @@ using namespace mythos;
 
 struct mythos_sim : mythos::MdRun {
   mythos_system* sys = nullptr;
+  int device = 0;  // the system's, copied at create: the integrator may outlive its system, to be destroyed only
   double dt = 0, kT = 0, gamma_t = 0, gamma_r = 0, mass = 1, inertia[3] = {1, 1, 1};
   // neighbour policy (MdRun::rebuild_every: 0 = the system's static rows)
   double r_cut = 0, skin = 0;
   // device state: two ping-pong frames of 8 vec4 arrays each (p0, p1, p2, p3, q, pl, mom, ang)
   static constexpr int kFrameArrays = 8;
-  void* frame[2][kFrameArrays] = {};
+  DeviceBytes frame[2][kFrameArrays];
   int builds = 0;          // scheduled rebuilds so far (the chunk order is refreshed every 64th)
   int list_epoch = 0;      // sys->list_epoch the rows in use belong to
   // centres as the last run handed them out (hi) and the low parts that went with them (fp32 systems)
-  void *keep_hi = nullptr, *keep_lo = nullptr;
+  DeviceBytes keep_hi, keep_lo;
   bool keep_valid = false;
   bool items_big = false;              // the ITEMS = 32 instantiation is in use (a launch of this load found 16 too few)
   bool want_unfused = false;           // mythos_langevin_set_option(MYTHOS_LANGEVIN_UNFUSED): takes effect at the next load
   bool unfused = false;                // the resident state lives in the unfused path's buffers (decided by load)
   int param_epoch = 0;                 // sys->param_epoch the packed site offsets of the resident frames were derived from
   int lanes = kMdG;              // lanes per nucleotide of the step launches of this load (8, or 16 for small systems: md_lanes_for)
-  int chunk_cap = 0;             // chunks d_chunk_order / d_chunk_keys have room for
-  int* d_chunk_order = nullptr;  // [blocks] spatial order of the workgroups' chunks of nucleotides (null: index order)
-  unsigned long long* d_chunk_keys = nullptr;
-  double* d_epart = nullptr;     // [blocks][kTraceWidth] energy-trace partials of a saving launch
+  DeviceBuf<int> d_chunk_order;  // [blocks] spatial order of the workgroups' chunks of nucleotides (null: index order)
+  DeviceBuf<unsigned long long> d_chunk_keys;
+  DeviceBuf<double> d_epart;     // [blocks][kTraceWidth] energy-trace partials of a saving launch
   // oxNA (model 4), unfused path: packed state + gradients of the energy kernel + list reference (see unfused_*)
-  void *u_c = nullptr, *u_q = nullptr, *u_p = nullptr, *u_l = nullptr, *u_gc = nullptr, *u_gq = nullptr, *u_ref = nullptr;
-  double* u_e = nullptr;  // [8] term energies of the last force evaluation + [2] kinetic energies
+  DeviceBytes u_c, u_q, u_p, u_l, u_gc, u_gq, u_ref;
+  DeviceBuf<double> u_e;  // [8] term energies of the last force evaluation + [2] kinetic energies
   bool u_forces_valid = false;
+  ~mythos_sim() { (void)hipSetDevice(device); }  // the members, MdRun's too, free themselves on that device
 };
 
 namespace mythos {
@@ -1271,8 +1272,8 @@ static MdCut<R> make_cut(const mythos_system* sys) {
 template <typename R>
 static Frame<R> frame_of(const mythos_sim* sim, int k) {
   using V4 = typename Vec4T<R>::type;
-  return Frame<R>{(V4*)sim->frame[k][0], (V4*)sim->frame[k][1], (V4*)sim->frame[k][2], (V4*)sim->frame[k][3],
-                  (V4*)sim->frame[k][4], (V4*)sim->frame[k][5], (V4*)sim->frame[k][6], (V4*)sim->frame[k][7]};
+  auto a = [&](int i) { return (V4*)sim->frame[k][i].get(); };
+  return Frame<R>{a(0), a(1), a(2), a(3), a(4), a(5), a(6), a(7)};
 }
 
 // Spatial order of the workgroups' chunks (chunk_order.h): two small kernels on the run's stream, at every load and
@@ -1281,21 +1282,13 @@ static Frame<R> frame_of(const mythos_sim* sim, int k) {
 template <typename R>
 static int update_chunk_order(mythos_sim* sim, const typename Vec4T<R>::type* p0, int blocks, hipStream_t st) {
   if (blocks < 64) {  // (index order; a stale order of another chunk size must not survive a change of lanes)
-    if (sim->d_chunk_order) (void)hipFree(sim->d_chunk_order), sim->d_chunk_order = nullptr;
-    if (sim->d_chunk_keys) (void)hipFree(sim->d_chunk_keys), sim->d_chunk_keys = nullptr;
-    sim->chunk_cap = 0;
+    sim->d_chunk_order.reset(), sim->d_chunk_keys.reset();
     return 0;
   }
-  if (blocks > sim->chunk_cap) {
-    if (sim->d_chunk_order) (void)hipFree(sim->d_chunk_order), sim->d_chunk_order = nullptr;
-    if (sim->d_chunk_keys) (void)hipFree(sim->d_chunk_keys), sim->d_chunk_keys = nullptr;
-    sim->chunk_cap = 0;
-    MYTHOS_HIP_TRY(hipMalloc((void**)&sim->d_chunk_keys, (size_t)blocks * sizeof(unsigned long long)));
-    MYTHOS_HIP_TRY(hipMalloc((void**)&sim->d_chunk_order, (size_t)blocks * sizeof(int)));
-    sim->chunk_cap = blocks;
-  }
-  MYTHOS_HIP_TRY(chunk_order_device(p0, blocks, kMdBlock / sim->lanes, std::max(1.0, sim->r_cut > 0 ? sim->r_cut : 4.0), sim->d_chunk_keys,
-                                    sim->d_chunk_order, st));
+  if (int rc = sim->d_chunk_keys.grow((size_t)blocks)) return rc;
+  if (int rc = sim->d_chunk_order.grow((size_t)blocks)) return rc;
+  MYTHOS_HIP_TRY(chunk_order_device(p0, blocks, kMdBlock / sim->lanes, std::max(1.0, sim->r_cut > 0 ? sim->r_cut : 4.0), sim->d_chunk_keys.get(),
+                                    sim->d_chunk_order.get(), st));
   return 0;
 }
 
@@ -1324,8 +1317,8 @@ static int load_typed(mythos_sim* sim, const R* center, const R* quat, const R* 
   const double* Prna = oxdna_param_set(sys, sys->param_sets() == 1 ? 0 : 1);
   hipLaunchKernelGGL((pack_state_kernel<R, (MODEL == 4 ? 0 : back_axis<MODEL>())>), dim3(tb), dim3(256), 0, st, n, g_k1, g_k2,
                      R(Prna[GEO_BACK_A1]), R(Prna[GEO_BACK_A2]), center, quat, p_lin, p_ang,
-                     sys->d_meta, f0, sim->keep_valid ? (const R*)sim->keep_hi : nullptr,
-                     (const R*)sim->keep_lo);
+                     sys->d_meta.get(), f0, sim->keep_valid ? (const R*)sim->keep_hi.get() : nullptr,
+                     (const R*)sim->keep_lo.get());
   MYTHOS_HIP_TRY(hipGetLastError());
   sim->resident = true;
   sim->list_valid = false;
@@ -1343,7 +1336,7 @@ template <typename R>
 static int unpack_typed(mythos_sim* sim, R* center, R* quat, R* p_lin, R* p_ang, hipStream_t st) {
   const int n = sim->sys->n;
   hipLaunchKernelGGL(unpack_state_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, frame_of<R>(sim, sim->cur),
-                     center, quat, p_lin, p_ang, (R*)sim->keep_hi, (R*)sim->keep_lo);
+                     center, quat, p_lin, p_ang, (R*)sim->keep_hi.get(), (R*)sim->keep_lo.get());
   MYTHOS_HIP_TRY(hipGetLastError());
   sim->keep_valid = true;
   return 0;
@@ -1381,7 +1374,7 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
     const double* Prna = oxdna_param_set(sys, sys->param_sets() == 1 ? 0 : 1);
     hipLaunchKernelGGL((rederive_frame_kernel<R, (MODEL == 4 ? 0 : back_axis<MODEL>())>), dim3((n + 255) / 256), dim3(256), 0, st, n,
                        Ph[GEO_BACK_A1], (MODEL >= 2) ? Ph[GEO_BACK_A2] : R(0), R(Prna[GEO_BACK_A1]), R(Prna[GEO_BACK_A2]),
-                       (const int*)sys->d_meta, fr[sim->cur]);
+                       (const int*)sys->d_meta.get(), fr[sim->cur]);
     MYTHOS_HIP_TRY(hipGetLastError());
     sim->param_epoch = sys->param_epoch;
   }
@@ -1391,25 +1384,25 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
   PseqView<R> pseq;
   const bool use_pseq = sys->pseq_terms != 0;
   if (debug_value(MYTHOS_DEBUG_MD_ITEMS_BIG) == 1) sim->items_big = true;  // (tests: the wide instantiations without a crowded system)
-  if (use_pseq) pseq.marg = (const R*)sys->d_ps_marg, pseq.unit = sys->d_ps_unit, pseq.bp = (const R*)sys->d_ps_bp, pseq.terms = sys->pseq_terms;
-  int* halt_words = dynamic_list ? sys->list.d_overflow : nullptr;
+  if (use_pseq) pseq.marg = (const R*)sys->d_ps_marg.get(), pseq.unit = sys->d_ps_unit.get(), pseq.bp = (const R*)sys->d_ps_bp.get(), pseq.terms = sys->pseq_terms;
+  int* halt_words = dynamic_list ? sys->list.d_overflow.get() : nullptr;
   auto launch_step = [&](int k, const LaunchRow& row) {
     const int cur = row.cur;
     const bool save = row.save;
     const R kick_close = R(row.kick_close);
     R* tc = ((save || row.save_next) && traj_center) ? traj_center + (size_t)row.sidx * n * 3 : nullptr;
     R* tq = ((save || row.save_next) && traj_quat) ? traj_quat + (size_t)row.sidx * n * 4 : nullptr;
-    const V4* ref = (const V4*)sys->d_ref_pos;
-    const V4* ref_off = (const V4*)sys->d_ref_off;
-    const V4* ref_a1 = (const V4*)sys->d_ref_a1;
+    const V4* ref = (const V4*)sys->d_ref_pos.get();
+    const V4* ref_off = (const V4*)sys->d_ref_off.get();
+    const V4* ref_a1 = (const V4*)sys->d_ref_a1.get();
     auto launch_pseq = [&](auto save_tag, auto items_tag, hipEvent_t ea, hipEvent_t eb) {
       constexpr bool SV = decltype(save_tag)::value;
       constexpr int IT = decltype(items_tag)::value;
       auto go = [&](auto lanes_tag) {
         hipExtLaunchKernelGGL((md_step_kernel<R, MODEL, SV, IT, true, false, decltype(lanes_tag)::value>), dim3(grid), dim3(kMdBlock), 0, st, ea, eb, 0,
-                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->list.d_rows, sys->d_row_len, row_close_of(sys),
+                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->list.d_rows.get(), sys->d_row_len.get(), row_close_of(sys),
                               sys->list.stride, sys->extra_bonds ? 1 : 0, kick_close, row.do_step, sim->seed, (uint64_t)(sim->step + k), ref,
-                              ref_off, ref_a1, sim->d_flags, tc, tq, sim->d_epart, sim->d_chunk_order, halt_words, k, 0, prio_on, pseq);
+                              ref_off, ref_a1, sim->d_flags.get(), tc, tq, sim->d_epart.get(), sim->d_chunk_order.get(), halt_words, k, 0, prio_on, pseq);
       };
       if (lanes16) go(std::integral_constant<int, 16>{}); else go(std::integral_constant<int, 8>{});
     };
@@ -1420,9 +1413,9 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
       // kernel trace reports), not the time between two markers in the queue
       auto go = [&](auto dense_tag, auto lanes_tag) {
         hipExtLaunchKernelGGL((md_step_kernel<R, MODEL, SV, IT, false, decltype(dense_tag)::value, decltype(lanes_tag)::value>), dim3(grid), dim3(kMdBlock), 0, st, ea, eb, 0,
-                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->list.d_rows, sys->d_row_len, row_close_of(sys),
+                              Pdev, box, K, cut, n, fr[cur], fr[cur ^ 1], sys->list.d_rows.get(), sys->d_row_len.get(), row_close_of(sys),
                               sys->list.stride, sys->extra_bonds ? 1 : 0, kick_close, row.do_step, sim->seed, (uint64_t)(sim->step + k), ref,
-                              ref_off, ref_a1, sim->d_flags, tc, tq, sim->d_epart, sim->d_chunk_order, halt_words, k, 0, prio_on, PseqView<R>{});
+                              ref_off, ref_a1, sim->d_flags.get(), tc, tq, sim->d_epart.get(), sim->d_chunk_order.get(), halt_words, k, 0, prio_on, PseqView<R>{});
       };
       using L8 = std::integral_constant<int, 8>;
       using L16 = std::integral_constant<int, 16>;
@@ -1452,7 +1445,7 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
       if (sim->items_big) launch(F{}, BigN{}, ea, eb); else launch(F{}, Small{}, ea, eb);
     }
     if (save)
-      hipLaunchKernelGGL(reduce_trace_kernel<kTraceWidth>, dim3(1), dim3(256), 0, st, sim->d_epart, blocks,
+      hipLaunchKernelGGL(reduce_trace_kernel<kTraceWidth>, dim3(1), dim3(256), 0, st, sim->d_epart.get(), blocks,
                          e_trace + (size_t)row.sidx * kTraceWidth);
   };
   auto rebuild = [&](int buf) -> int {
@@ -1580,27 +1573,24 @@ static __global__ void unfused_trace_kernel(const double* __restrict__ e, double
 
 template <typename R>
 static int unfused_alloc(mythos_sim* sim) {
-  if (sim->u_c) return 0;
+  if (sim->u_e) return 0;  // (the last of them: a partly failed attempt is made again)
   const size_t n = (size_t)sim->sys->n;
-  MYTHOS_HIP_TRY(hipMalloc(&sim->u_c, 3 * n * sizeof(R)));
-  MYTHOS_HIP_TRY(hipMalloc(&sim->u_q, 4 * n * sizeof(R)));
-  MYTHOS_HIP_TRY(hipMalloc(&sim->u_p, 3 * n * sizeof(R)));
-  MYTHOS_HIP_TRY(hipMalloc(&sim->u_l, 3 * n * sizeof(R)));
-  MYTHOS_HIP_TRY(hipMalloc(&sim->u_gc, 3 * n * sizeof(R)));
-  MYTHOS_HIP_TRY(hipMalloc(&sim->u_gq, 4 * n * sizeof(R)));
-  MYTHOS_HIP_TRY(hipMalloc(&sim->u_ref, 12 * n * sizeof(R)));
-  MYTHOS_HIP_TRY(hipMalloc((void**)&sim->u_e, kTraceWidth * sizeof(double)));
-  return 0;
+  for (DeviceBytes* b : {&sim->u_c, &sim->u_p, &sim->u_l, &sim->u_gc})
+    if (int rc = b->alloc(3 * n * sizeof(R))) return rc;
+  for (DeviceBytes* b : {&sim->u_q, &sim->u_gq})
+    if (int rc = b->alloc(4 * n * sizeof(R))) return rc;
+  if (int rc = sim->u_ref.alloc(12 * n * sizeof(R))) return rc;
+  return sim->u_e.alloc(kTraceWidth);
 }
 
 template <typename R>
 static int unfused_load(mythos_sim* sim, const R* c, const R* q, const R* p, const R* l, hipStream_t st) {
   if (int rc = unfused_alloc<R>(sim)) return rc;
   const size_t n = (size_t)sim->sys->n;
-  MYTHOS_HIP_TRY(hipMemcpyAsync(sim->u_c, c, 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
-  MYTHOS_HIP_TRY(hipMemcpyAsync(sim->u_q, q, 4 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
-  MYTHOS_HIP_TRY(hipMemcpyAsync(sim->u_p, p, 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
-  MYTHOS_HIP_TRY(hipMemcpyAsync(sim->u_l, l, 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
+  MYTHOS_HIP_TRY(hipMemcpyAsync(sim->u_c.get(), c, 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
+  MYTHOS_HIP_TRY(hipMemcpyAsync(sim->u_q.get(), q, 4 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
+  MYTHOS_HIP_TRY(hipMemcpyAsync(sim->u_p.get(), p, 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
+  MYTHOS_HIP_TRY(hipMemcpyAsync(sim->u_l.get(), l, 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
   sim->resident = true;
   sim->list_valid = false;
   sim->since_build = 0;
@@ -1611,10 +1601,10 @@ static int unfused_load(mythos_sim* sim, const R* c, const R* q, const R* p, con
 template <typename R>
 static int unfused_store(mythos_sim* sim, R* c, R* q, R* p, R* l, hipStream_t st) {
   const size_t n = (size_t)sim->sys->n;
-  MYTHOS_HIP_TRY(hipMemcpyAsync(c, sim->u_c, 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
-  MYTHOS_HIP_TRY(hipMemcpyAsync(q, sim->u_q, 4 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
-  MYTHOS_HIP_TRY(hipMemcpyAsync(p, sim->u_p, 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
-  MYTHOS_HIP_TRY(hipMemcpyAsync(l, sim->u_l, 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
+  MYTHOS_HIP_TRY(hipMemcpyAsync(c, sim->u_c.get(), 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
+  MYTHOS_HIP_TRY(hipMemcpyAsync(q, sim->u_q.get(), 4 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
+  MYTHOS_HIP_TRY(hipMemcpyAsync(p, sim->u_p.get(), 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
+  MYTHOS_HIP_TRY(hipMemcpyAsync(l, sim->u_l.get(), 3 * n * sizeof(R), hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
@@ -1623,8 +1613,8 @@ static int unfused_advance(mythos_sim* sim, int n_steps, int save_every, R* traj
   mythos_system* sys = sim->sys;
   const int n = sys->n, tb = (n + 255) / 256;
   const LangevinConst<R> K = make_const<R>(sim);
-  R *c = (R*)sim->u_c, *q = (R*)sim->u_q, *p = (R*)sim->u_p, *l = (R*)sim->u_l, *gc = (R*)sim->u_gc, *gq = (R*)sim->u_gq;
-  R* ref = (R*)sim->u_ref;
+  R *c = (R*)sim->u_c.get(), *q = (R*)sim->u_q.get(), *p = (R*)sim->u_p.get(), *l = (R*)sim->u_l.get(), *gc = (R*)sim->u_gc.get(), *gq = (R*)sim->u_gq.get();
+  R* ref = (R*)sim->u_ref.get();
   const bool dynamic = sim->rebuild_every > 0;
   sim->last_recoveries = 0;
   // the sum of the offset coefficients of the farthest site, over both geometries (bounds a site's motion under rotation)
@@ -1643,13 +1633,13 @@ static int unfused_advance(mythos_sim* sim, int n_steps, int save_every, R* traj
     return 0;
   };
   auto forces = [&]() -> int {
-    return oxdna_energy_launch(sys, c, q, 1, sim->u_e, gc, gq, nullptr, nullptr, nullptr, st);
+    return oxdna_energy_launch(sys, c, q, 1, sim->u_e.get(), gc, gq, nullptr, nullptr, nullptr, st);
   };
   auto check_flags = [&](const char* when) -> int {
     int fl[2] = {0, 0};
-    MYTHOS_HIP_TRY(hipMemcpyAsync(fl, sim->d_flags, sizeof(fl), hipMemcpyDeviceToHost, st));
+    MYTHOS_HIP_TRY(hipMemcpyAsync(fl, sim->d_flags.get(), sizeof(fl), hipMemcpyDeviceToHost, st));
     MYTHOS_HIP_TRY(hipStreamSynchronize(st));
-    MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_flags, 0, 2 * sizeof(int), st));
+    MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_flags.get(), 0, 2 * sizeof(int), st));
     if (fl[0] & 2) {
       sim->resident = false;
       set_error(std::string("mythos_langevin_run (oxNA, unfused): NaN in the state ") + when);
@@ -1663,7 +1653,7 @@ static int unfused_advance(mythos_sim* sim, int n_steps, int save_every, R* traj
     }
     return 0;
   };
-  MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_flags, 0, mythos_sim::kCtlWords * sizeof(int), st));
+  MYTHOS_HIP_TRY(hipMemsetAsync(sim->d_flags.get(), 0, mythos_sim::kCtlWords * sizeof(int), st));
   if (!sim->list_valid) sim->u_forces_valid = false;  // parameters or rows were replaced since the last force evaluation
   if (dynamic && !sim->list_valid)
     if (int rc = build()) return rc;
@@ -1679,13 +1669,13 @@ static int unfused_advance(mythos_sim* sim, int n_steps, int save_every, R* traj
     if (k == 0 && !do_step) break;  // zero steps: nothing to close
     R* tc = (save && traj_c) ? traj_c + (size_t)saved * n * 3 : nullptr;
     R* tq = (save && traj_q) ? traj_q + (size_t)saved * n * 4 : nullptr;
-    double* ke = save ? sim->u_e + T_COUNT : nullptr;
-    if (save) MYTHOS_HIP_TRY(hipMemsetAsync(sim->u_e + T_COUNT, 0, 2 * sizeof(double), st));
+    double* ke = save ? sim->u_e.get() + T_COUNT : nullptr;
+    if (save) MYTHOS_HIP_TRY(hipMemsetAsync(sim->u_e.get() + T_COUNT, 0, 2 * sizeof(double), st));
     hipLaunchKernelGGL(unfused_integrate_kernel<R>, dim3(tb), dim3(256), 0, st, n, K, c, q, p, l, (const R*)gc, (const R*)gq,
                        R(k > 0 ? 0.5 : 0.0), do_step ? 1 : 0, sim->seed, (uint64_t)(sim->step + k), dynamic ? (const R*)ref : nullptr,
-                       R(reach), sim->d_flags, tc, tq, ke);
+                       R(reach), sim->d_flags.get(), tc, tq, ke);
     if (save) {
-      if (e_trace) hipLaunchKernelGGL(unfused_trace_kernel, dim3(1), dim3(64), 0, st, (const double*)sim->u_e, e_trace + (size_t)saved * kTraceWidth);
+      if (e_trace) hipLaunchKernelGGL(unfused_trace_kernel, dim3(1), dim3(64), 0, st, (const double*)sim->u_e.get(), e_trace + (size_t)saved * kTraceWidth);
       ++saved;
     }
     if (!do_step) break;

@@ -15,6 +15,7 @@
 // ~20 flops per pair per lane.
 #include <algorithm>
 #include <cmath>
+#include <memory>
 
 #include "martini_internal.h"
 
@@ -345,12 +346,6 @@ using namespace mythos;
 
 namespace mythos {
 
-static bool upload_int(int** dst, const std::vector<int>& v) {
-  const size_t c = std::max<size_t>(v.size(), 1);
-  return hipMalloc((void**)dst, c * sizeof(int)) == hipSuccess &&
-         (v.empty() || hipMemcpy(*dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess);
-}
-
 template <typename R>
 static int martini_energy_typed(mythos_martini* m, const R* pos, const R* box, int n_frames, double* e_terms, R* dU,
                                 hipStream_t st) {
@@ -364,25 +359,23 @@ static int martini_energy_typed(mythos_martini* m, const R* pos, const R* box, i
     const size_t per_frame = (size_t)(n_js + 1) * n * 3 * sizeof(R);
     int nf = (int)std::min<size_t>(std::min(n_frames - f0, 4096), std::max<size_t>(1, (size_t(512) << 20) / per_frame));
     if (nf > 16) n_js = std::max(1, n_js / 4);  // many frames already fill the GPU
-    char* fp = (char*)m->d_fpart;
-    if (int rc = grow_buffer(fp, m->fpart_cap, (size_t)nf * (n_js + 1) * n * 3 * sizeof(R))) return rc;
-    m->d_fpart = fp;
-    if (int rc = grow_buffer(m->d_epart, m->epart_cap, (size_t)nf * n_js * nbx)) return rc;
-    if (int rc = grow_buffer(m->d_ebpart, m->ebpart_cap, (size_t)nf * nbb * 2)) return rc;
+    if (int rc = m->d_fpart.grow((size_t)nf * (n_js + 1) * n * 3 * sizeof(R))) return rc;
+    if (int rc = m->d_epart.grow((size_t)nf * n_js * nbx)) return rc;
+    if (int rc = m->d_ebpart.grow((size_t)nf * nbb * 2)) return rc;
     MartiniConst<R> K{R(m->r_cut * m->r_cut), m->n_types, m->angle_kind};
     const size_t lds = (size_t)3 * m->n_types * m->n_types * sizeof(R) + 3 * kLjBlock * sizeof(R) + kLjBlock * sizeof(int);
     const R* p = pos + (size_t)f0 * n * 3;
     const R* b = box + (size_t)f0 * 3;
     MYTHOS_HIP_TRY(hipFuncSetAttribute((const void*)martini_lj_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(martini_lj_kernel<R>, dim3(nbx, n_js, nf), dim3(kLjBlock), lds, st, n, p, b, m->d_types,
-                       (const R*)m->d_sigma, (const R*)m->d_eps, m->d_excl, K, n_tiles, (R*)m->d_fpart, m->d_epart);
-    hipLaunchKernelGGL(martini_bonded_kernel<R>, dim3(nbb, nf), dim3(256), 0, st, n, p, b, m->d_bead_bonds,
-                       m->d_bead_angles, m->d_bonds, (const R*)m->d_bond_k, (const R*)m->d_bond_r0, m->d_angles,
-                       (const R*)m->d_angle_k, (const R*)m->d_angle_t0, m->angle_kind, n_js, (R*)m->d_fpart,
-                       m->d_ebpart);
+    hipLaunchKernelGGL(martini_lj_kernel<R>, dim3(nbx, n_js, nf), dim3(kLjBlock), lds, st, n, p, b, m->d_types.get(),
+                       (const R*)m->d_sigma.get(), (const R*)m->d_eps.get(), m->d_excl.get(), K, n_tiles, (R*)m->d_fpart.get(), m->d_epart.get());
+    hipLaunchKernelGGL(martini_bonded_kernel<R>, dim3(nbb, nf), dim3(256), 0, st, n, p, b, m->d_bead_bonds.get(),
+                       m->d_bead_angles.get(), m->d_bonds.get(), (const R*)m->d_bond_k.get(), (const R*)m->d_bond_r0.get(), m->d_angles.get(),
+                       (const R*)m->d_angle_k.get(), (const R*)m->d_angle_t0.get(), m->angle_kind, n_js, (R*)m->d_fpart.get(),
+                       m->d_ebpart.get());
     hipLaunchKernelGGL(martini_reduce_kernel<R>, dim3((n * 3 + 255) / 256, nf), dim3(256), 0, st, n, n_js + 1,
-                       (const R*)m->d_fpart, dU ? dU + (size_t)f0 * n * 3 : nullptr, m->d_epart, n_js * nbx,
-                       m->d_ebpart, nbb, e_terms + (size_t)f0 * 3);
+                       (const R*)m->d_fpart.get(), dU ? dU + (size_t)f0 * n * 3 : nullptr, m->d_epart.get(), n_js * nbx,
+                       m->d_ebpart.get(), nbb, e_terms + (size_t)f0 * 3);
     MYTHOS_HIP_TRY(hipGetLastError());
     f0 += nf;
   }
@@ -414,14 +407,14 @@ static int martini_pgrad_typed(mythos_martini* m, const R* pos, const R* box, in
     const int n_wg = nbx * n_js;  // workgroups, and partial tables, per frame
     // frames per chunk: at most 256 MB of partial tables
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(4096, (size_t(256) << 20) / ((size_t)n_wg * 2 * tt * sizeof(double))));
-    if (int rc = grow_buffer(m->d_ljpart, m->ljpart_cap, (size_t)std::min(chunk, n_frames) * n_wg * 2 * tt)) return rc;
+    if (int rc = m->d_ljpart.grow((size_t)std::min(chunk, n_frames) * n_wg * 2 * tt)) return rc;
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
       const int nf = std::min(n_frames - f0, chunk);
       hipLaunchKernelGGL(martini_lj_pgrad_kernel<R>, dim3(nbx, n_js, nf),
-                         dim3(kLjBlock), lds, st, n, pos + (size_t)f0 * n * 3, box + (size_t)f0 * 3, m->d_types,
-                         (const R*)m->d_sigma, (const R*)m->d_eps, m->d_excl, K, nbx, m->d_ljpart);
+                         dim3(kLjBlock), lds, st, n, pos + (size_t)f0 * n * 3, box + (size_t)f0 * 3, m->d_types.get(),
+                         (const R*)m->d_sigma.get(), (const R*)m->d_eps.get(), m->d_excl.get(), K, nbx, m->d_ljpart.get());
       hipLaunchKernelGGL(martini_lj_pgrad_reduce_kernel, dim3((unsigned)((2 * tt + 255) / 256), nf), dim3(256), 0, st,
-                         (const double*)m->d_ljpart, n_wg, (int)tt, d_sigma + (size_t)f0 * tt, d_eps + (size_t)f0 * tt);
+                         (const double*)m->d_ljpart.get(), n_wg, (int)tt, d_sigma + (size_t)f0 * tt, d_eps + (size_t)f0 * tt);
     }
   }
   if (d_bk || d_br || d_ak || d_at) {
@@ -430,9 +423,9 @@ static int martini_pgrad_typed(mythos_martini* m, const R* pos, const R* box, in
       const int nf = std::min(n_frames - f0, 4096);
       auto off = [&](double* ptr, int per) { return ptr ? ptr + (size_t)f0 * per : nullptr; };
       hipLaunchKernelGGL(martini_bonded_pgrad_kernel<R>, dim3((cnt + 255) / 256, nf), dim3(256), 0, st, n,
-                         pos + (size_t)f0 * n * 3, box + (size_t)f0 * 3, m->n_bonds, m->d_bonds,
-                         (const R*)m->d_bond_k, (const R*)m->d_bond_r0, m->n_angles, m->d_angles,
-                         (const R*)m->d_angle_k, (const R*)m->d_angle_t0, m->angle_kind, off(d_bk, m->n_bonds),
+                         pos + (size_t)f0 * n * 3, box + (size_t)f0 * 3, m->n_bonds, m->d_bonds.get(),
+                         (const R*)m->d_bond_k.get(), (const R*)m->d_bond_r0.get(), m->n_angles, m->d_angles.get(),
+                         (const R*)m->d_angle_k.get(), (const R*)m->d_angle_t0.get(), m->angle_kind, off(d_bk, m->n_bonds),
                          off(d_br, m->n_bonds), off(d_ak, m->n_angles), off(d_at, m->n_angles));
     }
   }
@@ -455,12 +448,7 @@ mythos_martini_t* mythos_martini_create(int n, const int32_t* types, int n_types
     set_error("mythos_martini_create: invalid argument (1 <= n_types <= 64, angle_kind 0|1)");
     return nullptr;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device < 0 || device >= ndev ||
-      hipSetDevice(device) != hipSuccess) {
-    set_error("mythos_martini_create: no usable HIP device (the HIP path has no CPU fallback)");
-    return nullptr;
-  }
+  if (select_device(device, "mythos_martini_create")) return nullptr;
   std::vector<int> excl((size_t)n * kMaxExcl, -1), bb((size_t)n * kMaxBeadBonds, -1), ba((size_t)n * kMaxBeadAngles, -1);
   std::vector<int> ne(n, 0), nb(n, 0), na(n, 0);
   std::vector<int> hb(bonds, bonds + 2 * (size_t)n_bonds), ha(angles, angles + 3 * (size_t)n_angles), ht(types, types + n);
@@ -490,33 +478,26 @@ mythos_martini_t* mythos_martini_create(int n, const int32_t* types, int n_types
       }
       ba[(size_t)i * kMaxBeadAngles + na[i]++] = 4 * a + r;
     }
-  auto* m = new mythos_martini();
+  auto m = std::make_unique<mythos_martini>();
   m->n = n, m->n_types = n_types, m->n_bonds = n_bonds, m->n_angles = n_angles, m->angle_kind = angle_kind;
   m->dtype = dtype, m->device = device, m->r_cut = r_cut;
-  bool ok = upload_int(&m->d_types, ht) && upload_int(&m->d_excl, excl) && upload_int(&m->d_bead_bonds, bb) &&
-            upload_int(&m->d_bead_angles, ba) && upload_int(&m->d_bonds, hb) && upload_int(&m->d_angles, ha);
   const size_t tt = (size_t)n_types * n_types;
-  ok = ok && upload_real(dtype, &m->d_sigma, sigma, tt) && upload_real(dtype, &m->d_eps, eps, tt) &&
-       upload_real(dtype, &m->d_bond_k, bond_k, n_bonds) && upload_real(dtype, &m->d_bond_r0, bond_r0, n_bonds) &&
-       upload_real(dtype, &m->d_angle_k, angle_k, n_angles) && upload_real(dtype, &m->d_angle_t0, angle_t0, n_angles);
-  if (!ok) {
+  m->h_sigma.assign(sigma, sigma + tt), m->h_eps.assign(eps, eps + tt);
+  m->h_angle_t0.assign(angle_t0, angle_t0 + n_angles);
+  if (m->d_types.upload(ht) || m->d_excl.upload(excl) || m->d_bead_bonds.upload(bb) || m->d_bead_angles.upload(ba) ||
+      m->d_bonds.upload(hb) || m->d_angles.upload(ha) || m->d_sigma.upload_real(dtype, sigma, tt) ||
+      m->d_eps.upload_real(dtype, eps, tt) || m->d_bond_k.upload_real(dtype, bond_k, n_bonds) ||
+      m->d_bond_r0.upload_real(dtype, bond_r0, n_bonds) || m->d_angle_k.upload_real(dtype, angle_k, n_angles) ||
+      m->d_angle_t0.upload_real(dtype, angle_t0, n_angles)) {
     set_error("mythos_martini_create: device allocation failed");
-    mythos_martini_destroy(m);
     return nullptr;
   }
-  return m;
+  m->h_types = std::move(ht), m->h_bead_bonds = std::move(bb), m->h_bead_angles = std::move(ba);
+  m->h_bonds = std::move(hb), m->h_angles = std::move(ha);
+  return m.release();
 }
 
-void mythos_martini_destroy(mythos_martini_t* m) {
-  if (!m) return;
-  (void)hipSetDevice(m->device);
-  void* ptrs[] = {m->d_types, m->d_excl,   m->d_bead_bonds, m->d_bead_angles, m->d_bonds,  m->d_angles, m->d_sigma,
-                  m->d_eps,   m->d_bond_k, m->d_bond_r0,    m->d_angle_k,     m->d_angle_t0, m->d_fpart, m->d_epart,
-                  m->d_ebpart, m->d_ljpart};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  delete m;
-}
+void mythos_martini_destroy(mythos_martini_t* m) { delete m; }
 
 int mythos_martini_energy(mythos_martini_t* m, const void* pos, const void* box, int n_frames, double* e_terms,
                           void* dU_dpos, mythos_stream_t stream) {

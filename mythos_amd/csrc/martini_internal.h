@@ -23,31 +23,20 @@ struct MartiniConst {
   int angle_kind;  // 0 = G96 cosine, 1 = harmonic
 };
 
-// count doubles -> a new device vector of reals in the system's precision (dtype); at least one element is allocated
-inline bool upload_real(int dtype, void** dst, const double* src, size_t count) {
-  auto up = [&](auto zero) {
-    using R = decltype(zero);
-    std::vector<R> tmp(std::max<size_t>(count, 1), zero);
-    for (size_t k = 0; k < count; ++k) tmp[k] = R(src[k]);
-    return hipMalloc(dst, tmp.size() * sizeof(R)) == hipSuccess &&
-           hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(R), hipMemcpyHostToDevice) == hipSuccess;
-  };
-  return dtype == MYTHOS_F32 ? up(0.0f) : up(0.0);
-}
-
 }  // namespace mythos
 
 struct mythos_martini {
   int n = 0, n_types = 0, n_bonds = 0, n_angles = 0, angle_kind = 0, dtype = 0, device = 0;
   double r_cut = 1.1;
-  int *d_types = nullptr, *d_excl = nullptr, *d_bead_bonds = nullptr, *d_bead_angles = nullptr, *d_bonds = nullptr,
-      *d_angles = nullptr;
-  void *d_sigma = nullptr, *d_eps = nullptr, *d_bond_k = nullptr, *d_bond_r0 = nullptr, *d_angle_k = nullptr,
-       *d_angle_t0 = nullptr;
-  void* d_fpart = nullptr;
-  size_t fpart_cap = 0;
-  double *d_epart = nullptr, *d_ebpart = nullptr, *d_ljpart = nullptr;  // d_ljpart: per-workgroup dU/dsigma | dU/deps tables
-  size_t epart_cap = 0, ebpart_cap = 0, ljpart_cap = 0;
+  mythos::DeviceBuf<int> d_types, d_excl, d_bead_bonds, d_bead_angles, d_bonds, d_angles;
+  mythos::DeviceBytes d_sigma, d_eps, d_bond_k, d_bond_r0, d_angle_k, d_angle_t0;  // reals of the system's precision
+  // host copies of what an integrator derives its own tables from (mythos_martini_langevin_create); the reals as the
+  // caller's doubles: what the device holds is these rounded to the system's precision
+  std::vector<int> h_types, h_bead_bonds, h_bead_angles, h_bonds, h_angles;
+  std::vector<double> h_sigma, h_eps, h_angle_t0;
+  mythos::DeviceBytes d_fpart;
+  mythos::DeviceBuf<double> d_epart, d_ebpart, d_ljpart;  // d_ljpart: per-workgroup dU/dsigma | dU/deps tables
+  ~mythos_martini() { (void)hipSetDevice(device); }  // the members free themselves, on the system's device
 };
 
 #endif  // MYTHOS_MARTINI_INTERNAL_H

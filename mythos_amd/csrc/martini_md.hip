@@ -16,6 +16,7 @@
 // 2 x (pos 3 + vel 3) words + 4 B type + 4 B x nbar.
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -541,28 +542,28 @@ struct mythos_martini_sim : mythos::MdRun {
   mythos_martini* sys = nullptr;
   double dt = 0.02, kT = 2.27, gamma = 1.0;
   double skin = 0.2;  // (MdRun::rebuild_every: 10 until set_neighbor_policy)
-  void* frame[2] = {nullptr, nullptr};
-  void *vel = nullptr, *ref_pos = nullptr, *d_inv_mass = nullptr;
+  int device = 0;  // the system's, copied at create: the integrator may outlive its system, to be destroyed only
+  DeviceBytes frame[2], vel, ref_pos, d_inv_mass;
   // Type tables of the step kernel: only the types that occur, renumbered 0 .. n_ctypes - 1 (the DMPC bilayer uses 4 of
   // the force field's 37: every workgroup filled 2 x 37^2 LDS entries per launch, 0.9 us of a 10.6 us kernel), sigma
   // already squared.  d_ctypes: the compact type of every bead (what the frames carry in .w).
   int n_ctypes = 0;
-  int* d_ctypes = nullptr;
-  void *d_csig2 = nullptr, *d_ceps = nullptr;
+  DeviceBuf<int> d_ctypes;
+  DeviceBytes d_csig2, d_ceps;
   // per incidence slot of a bead: the partner of the bond, the two other beads of the angle (see the step kernel)
-  int* d_bb_partner = nullptr;
-  int2* d_ba_partner = nullptr;
-  void* d_angle_ref = nullptr;  // per angle: cos(theta0) for the G96 form (once, instead of a cosine per lane and step), theta0 for the harmonic one
+  DeviceBuf<int> d_bb_partner;
+  DeviceBuf<int2> d_ba_partner;
+  DeviceBytes d_angle_ref;  // per angle: cos(theta0) for the G96 form (once, instead of a cosine per lane and step), theta0 for the harmonic one
   mythos::VerletRows list{64};  // cell buckets start at 64 places; the rows at a stride of 256 (allocated at create)
-  int* d_row_len = nullptr;
+  DeviceBuf<int> d_row_len;
   // pruned rows (martini_md_step_kernel, EMIT): entries of the Verlet rows inside r_c + inner_margin, rewritten every
   // inner_every steps by the step launch itself; inner_margin <= 0 or inner_every < 2: not used
-  int *d_rows_in = nullptr, *d_row_len_in = nullptr;
-  int rows_in_stride = 0;
+  DeviceBuf<int> d_rows_in, d_row_len_in;
   double inner_margin = 0.0;  // off until mythos_martini_langevin_set_inner_list asks for them
   int inner_every = 4;
-  double* d_epart = nullptr;
+  DeviceBuf<double> d_epart;
   double box[3] = {0, 0, 0};  // of the resident state (mythos_martini_langevin_load / advance / store)
+  ~mythos_martini_sim() { (void)hipSetDevice(device); }  // the members, MdRun's too, free themselves on that device
 };
 
 namespace mythos {
@@ -576,8 +577,8 @@ static int mm_rebuild(mythos_martini_sim* sim, const typename Real4<R>::type* po
   const double rl = m->r_cut + sim->skin;
   CellGrid<R> g;
   if (!cell_grid(g, n, rl, box)) {
-    hipLaunchKernelGGL(mm_build_rows_allpairs_kernel<R>, dim3((n + 3) / 4), dim3(256), 0, st, n, pos, K, R(rl * rl), m->d_excl,
-                       L.d_rows, sim->d_row_len, L.stride, L.d_overflow, (typename Real4<R>::type*)sim->ref_pos);
+    hipLaunchKernelGGL(mm_build_rows_allpairs_kernel<R>, dim3((n + 3) / 4), dim3(256), 0, st, n, pos, K, R(rl * rl), m->d_excl.get(),
+                       L.d_rows.get(), sim->d_row_len.get(), L.stride, L.d_overflow.get(), (typename Real4<R>::type*)sim->ref_pos.get());
     return 0;
   }
   // one table slot per cell (no hashing) whenever the grid is not much larger than the system
@@ -587,10 +588,10 @@ static int mm_rebuild(mythos_martini_sim* sim, const typename Real4<R>::type* po
   if (int rc = cell_table<R>(L, g.direct ? (int)n_cells : next_pow2(2 * n), false, st, bins)) return rc;
   // buckets sorted by bead index: the row builder copies candidates in bucket order, and rows must not depend on
   // the order in which the binning atomics landed
-  cell_bins_build<R, true>(n, reinterpret_cast<const R*>(pos), g, bins, L.d_overflow, true, st);
+  cell_bins_build<R, true>(n, reinterpret_cast<const R*>(pos), g, bins, L.d_overflow.get(), true, st);
   hipLaunchKernelGGL((mm_build_rows_cells_kernel<R, kMmRowG>), dim3((n + 256 / kMmRowG - 1) / (256 / kMmRowG)), dim3(256), 0, st, n, pos, K, g,
-                     R(rl * rl), m->d_excl, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H,
-                     L.d_rows, sim->d_row_len, L.stride, L.d_overflow, (typename Real4<R>::type*)sim->ref_pos);
+                     R(rl * rl), m->d_excl.get(), bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H,
+                     L.d_rows.get(), sim->d_row_len.get(), L.stride, L.d_overflow.get(), (typename Real4<R>::type*)sim->ref_pos.get());
   return 0;
 }
 
@@ -624,8 +625,8 @@ static int mm_load_typed(mythos_martini_sim* sim, const R* pos, const R* v, cons
   mythos_martini* m = sim->sys;
   const int n = m->n, tb = (n + 255) / 256;
   for (int k = 0; k < 3; ++k) sim->box[k] = box[k];
-  hipLaunchKernelGGL(mm_pack_kernel<R>, dim3(tb), dim3(256), 0, st, n, pos, v, sim->d_ctypes, (const R*)sim->d_inv_mass,
-                     (V4*)sim->frame[0], (V4*)sim->vel);
+  hipLaunchKernelGGL(mm_pack_kernel<R>, dim3(tb), dim3(256), 0, st, n, pos, v, sim->d_ctypes.get(), (const R*)sim->d_inv_mass.get(),
+                     (V4*)sim->frame[0].get(), (V4*)sim->vel.get());
   MYTHOS_HIP_TRY(hipGetLastError());
   sim->cur = 0;
   sim->resident = true;
@@ -648,20 +649,14 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
   const int blocks = (n + kMmPPB - 1) / kMmPPB, grid = 8 * ((blocks + 7) / 8);
   const MmConst<R> K = mm_const<R>(sim);
   const double* box = sim->box;
-  V4* fr[2] = {(V4*)sim->frame[0], (V4*)sim->frame[1]};
-  V4* vel = (V4*)sim->vel;
+  V4* fr[2] = {(V4*)sim->frame[0].get(), (V4*)sim->frame[1].get()};
+  V4* vel = (V4*)sim->vel.get();
   const bool inner_on = mm_inner_on(sim);
   // the pruned rows share the Verlet rows' stride (a pruned row is a subset of its row: it cannot overflow)
   auto ensure_inner = [&]() -> int {
     if (!inner_on) return 0;
-    if (!sim->d_row_len_in) MYTHOS_HIP_TRY(hipMalloc((void**)&sim->d_row_len_in, (size_t)n * sizeof(int)));
-    if (!sim->d_rows_in || sim->rows_in_stride != sim->list.stride) {
-      if (sim->d_rows_in) (void)hipFree(sim->d_rows_in);
-      sim->d_rows_in = nullptr;
-      MYTHOS_HIP_TRY(hipMalloc((void**)&sim->d_rows_in, (size_t)n * sim->list.stride * sizeof(int)));
-      sim->rows_in_stride = sim->list.stride;
-    }
-    return 0;
+    if (int rc = sim->d_row_len_in.grow((size_t)n)) return rc;
+    return sim->d_rows_in.grow((size_t)n * sim->list.stride);  // (a stride only grows)
   };
   if (int rc = ensure_inner()) return rc;
   const size_t lds = (size_t)2 * sim->n_ctypes * sim->n_ctypes * sizeof(R);
@@ -673,16 +668,17 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
     // pruned rows: the launch d steps after the Verlet rows were built prunes when d is a multiple of inner_every (so
     // the first launch on new rows does) and walks the pruned rows otherwise
     const bool emit = inner_on && ((k - row.built_at) % sim->inner_every == 0);
-    const int* walk_rows = (inner_on && !emit) ? sim->d_rows_in : sim->list.d_rows;
-    const int* walk_len = (inner_on && !emit) ? sim->d_row_len_in : sim->d_row_len;
-    int* emit_rows = emit ? sim->d_rows_in : nullptr;
-    int* emit_len = emit ? sim->d_row_len_in : nullptr;
-#define MM_ARGS                                                                                                    \
-  n, K, (const V4*)fr[cur], fr[cur ^ 1], vel, walk_rows, walk_len, sim->list.stride, (const R*)sim->d_csig2,          \
-      (const R*)sim->d_ceps, m->d_bead_bonds, m->d_bead_angles, m->d_bonds, (const R*)m->d_bond_k,                      \
-      (const R*)m->d_bond_r0, m->d_angles, (const R*)m->d_angle_k, (const R*)sim->d_angle_ref, kick_close, do_step,  \
-      sim->seed, (uint64_t)(sim->step + k), (const V4*)sim->ref_pos, sim->d_flags, tp, sim->d_epart, sim->list.d_overflow, k, \
-      emit_rows, emit_len, sim->d_bb_partner, sim->d_ba_partner
+    const int* walk_rows = (inner_on && !emit) ? sim->d_rows_in.get() : sim->list.d_rows.get();
+    const int* walk_len = (inner_on && !emit) ? sim->d_row_len_in.get() : sim->d_row_len.get();
+    int* emit_rows = emit ? sim->d_rows_in.get() : nullptr;
+    int* emit_len = emit ? sim->d_row_len_in.get() : nullptr;
+#define MM_ARGS                                                                                                           \
+  n, K, (const V4*)fr[cur], fr[cur ^ 1], vel, walk_rows, walk_len, sim->list.stride, (const R*)sim->d_csig2.get(),        \
+      (const R*)sim->d_ceps.get(), m->d_bead_bonds.get(), m->d_bead_angles.get(), m->d_bonds.get(),                       \
+      (const R*)m->d_bond_k.get(), (const R*)m->d_bond_r0.get(), m->d_angles.get(), (const R*)m->d_angle_k.get(),         \
+      (const R*)sim->d_angle_ref.get(), kick_close, do_step, sim->seed, (uint64_t)(sim->step + k),                        \
+      (const V4*)sim->ref_pos.get(), sim->d_flags.get(), tp, sim->d_epart.get(), sim->list.d_overflow.get(), k,           \
+      emit_rows, emit_len, sim->d_bb_partner.get(), sim->d_ba_partner.get()
     auto go = [&](auto save_tag, auto emit_tag) {
       constexpr bool SV = decltype(save_tag)::value, EM = decltype(emit_tag)::value;
       if (row.ea) {
@@ -694,7 +690,7 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
 #undef MM_ARGS
     if (row.save) {
       if (emit) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{});
-      hipLaunchKernelGGL(reduce_trace_kernel<kMmTrace>, dim3(1), dim3(256), 0, st, sim->d_epart, blocks,
+      hipLaunchKernelGGL(reduce_trace_kernel<kMmTrace>, dim3(1), dim3(256), 0, st, sim->d_epart.get(), blocks,
                          e_trace + (size_t)row.sidx * kMmTrace);
     } else {
       if (emit) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{});
@@ -706,7 +702,7 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
   d.energy_rows = save_every > 0 && e_trace != nullptr;
   d.plain_rows = save_every > 0 && e_trace == nullptr && traj_pos != nullptr;
   d.dynamic_list = true;
-  d.halt_words = sim->list.d_overflow;
+  d.halt_words = sim->list.d_overflow.get();
   d.row_stride = &sim->list.stride;
   d.skin = sim->skin;
   if (inner_on)
@@ -729,7 +725,7 @@ static int mm_store_typed(mythos_martini_sim* sim, R* pos, R* v, hipStream_t st)
   using V4 = typename Real4<R>::type;
   const int n = sim->sys->n;
   const int rc = sim->open ? mm_advance_typed<R>(sim, 0, 0, true, nullptr, nullptr, st) : MYTHOS_OK;
-  hipLaunchKernelGGL(mm_unpack_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const V4*)sim->frame[sim->cur], (const V4*)sim->vel, pos, v);
+  hipLaunchKernelGGL(mm_unpack_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const V4*)sim->frame[sim->cur].get(), (const V4*)sim->vel.get(), pos, v);
   MYTHOS_HIP_TRY(hipGetLastError());
   return rc;
 }
@@ -738,16 +734,7 @@ static int mm_store_typed(mythos_martini_sim* sim, R* pos, R* v, hipStream_t st)
 
 extern "C" {
 
-void mythos_martini_langevin_destroy(mythos_martini_sim_t* s) {
-  if (!s) return;
-  (void)hipSetDevice(s->sys->device);
-  void* ptrs[] = {s->frame[0], s->frame[1], s->vel, s->ref_pos, s->d_inv_mass, s->list.d_rows, s->d_row_len,
-                  s->list.d_cell, s->list.d_overflow, s->d_epart, s->d_rows_in, s->d_row_len_in, s->d_angle_ref, s->d_ctypes, s->d_csig2, s->d_ceps, s->d_bb_partner, s->d_ba_partner};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  md_run_destroy(*s);
-  delete s;
-}
+void mythos_martini_langevin_destroy(mythos_martini_sim_t* s) { delete s; }
 
 mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, double dt, double kT, double gamma,
                                                      const double* mass, uint64_t seed) {
@@ -755,111 +742,71 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
     set_error("mythos_martini_langevin_create: invalid argument");
     return nullptr;
   }
-  if (hipSetDevice(sys->device) != hipSuccess) {
-    set_error("mythos_martini_langevin_create: hipSetDevice failed");
-    return nullptr;
-  }
-  auto* s = new mythos_martini_sim();
-  s->sys = sys, s->dt = dt, s->kT = kT, s->gamma = gamma, s->seed = seed;
+  if (select_device(sys->device, "mythos_martini_langevin_create")) return nullptr;
+  auto s = std::make_unique<mythos_martini_sim>();
+  s->sys = sys, s->device = sys->device, s->dt = dt, s->kT = kT, s->gamma = gamma, s->seed = seed;
   s->rebuild_every = 10;
-  const int n = sys->n;
-  const size_t w = sys->dtype == MYTHOS_F32 ? sizeof(float) : sizeof(double);
+  const int n = sys->n, dtype = sys->dtype;
+  const size_t w = dtype == MYTHOS_F32 ? sizeof(float) : sizeof(double);
   std::vector<double> im(n);
   for (int i = 0; i < n; ++i) {
     const double mi = mass ? mass[i] : 72.0;  // MARTINI's standard bead mass (amu)
     if (!(mi > 0)) {
       set_error("mythos_martini_langevin_create: masses must be positive");
-      delete s;
       return nullptr;
     }
     im[i] = 1.0 / mi;
   }
+  // partners per incidence slot
+  const std::vector<int>&bb = sys->h_bead_bonds, &ba = sys->h_bead_angles;
+  std::vector<int> pb(bb.size(), -1);
+  std::vector<int2> pa(ba.size(), int2{-1, -1});
+  for (size_t k = 0; k < bb.size(); ++k)
+    if (bb[k] >= 0) pb[k] = sys->h_bonds[2 * (size_t)(bb[k] >> 1) + (1 - (bb[k] & 1))];
+  for (size_t k = 0; k < ba.size(); ++k)
+    if (ba[k] >= 0) {
+      const int* t = &sys->h_angles[3 * (size_t)(ba[k] >> 2)];
+      const int role = ba[k] & 3;
+      pa[k] = role == 0 ? int2{t[1], t[2]} : (role == 1 ? int2{t[0], t[2]} : int2{t[0], t[1]});
+    }
+  // The tables below derive from the system's reals AS THE DEVICE HOLDS THEM: the caller's doubles rounded to the
+  // system's precision.
+  auto rounded = [dtype](double v) { return dtype == MYTHOS_F32 ? double(float(v)) : v; };
+  // the compact type tables
+  const int T = sys->n_types;
+  std::vector<int> types = sys->h_types, cmap(T, -1), used;
+  for (int t : types)
+    if (t >= 0 && t < T && cmap[t] < 0) cmap[t] = 0;
+  for (int t = 0; t < T; ++t)
+    if (cmap[t] == 0) cmap[t] = (int)used.size(), used.push_back(t);
+  const int C = std::max<int>(1, (int)used.size());
+  std::vector<double> cs((size_t)C * C, 0.0), ce((size_t)C * C, 0.0);
+  for (size_t p = 0; p < used.size(); ++p)
+    for (size_t q = 0; q < used.size(); ++q) {
+      // (squared in the kernel's own precision, as the kernel did)
+      const double sg = rounded(sys->h_sigma[(size_t)used[p] * T + used[q]]);
+      cs[p * C + q] = dtype == MYTHOS_F32 ? double(float(sg) * float(sg)) : sg * sg;
+      ce[p * C + q] = rounded(sys->h_eps[(size_t)used[p] * T + used[q]]);
+    }
+  for (int& t : types) t = (t >= 0 && t < T) ? cmap[t] : 0;
+  s->n_ctypes = C;
+  std::vector<double> ref(sys->h_angle_t0.size());
+  for (size_t a = 0; a < ref.size(); ++a) {
+    const double t0 = rounded(sys->h_angle_t0[a]);
+    ref[a] = sys->angle_kind == 0 ? std::cos(t0) : t0;
+  }
   const int blocks = (n + kMmPPB - 1) / kMmPPB;
-  bool ok = md_run_create(*s) && hipMalloc(&s->frame[0], (size_t)n * 4 * w) == hipSuccess && hipMalloc(&s->frame[1], (size_t)n * 4 * w) == hipSuccess &&
-            hipMalloc(&s->vel, (size_t)n * 4 * w) == hipSuccess && hipMalloc(&s->ref_pos, (size_t)n * 4 * w) == hipSuccess &&
-            rows_reserve(s->list, n, 256) == 0 && hipMalloc((void**)&s->d_row_len, (size_t)n * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&s->list.d_overflow, kOverflowWords * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&s->d_epart, (size_t)blocks * kMmTrace * sizeof(double)) == hipSuccess;
-  ok = ok && upload_real(sys->dtype, &s->d_inv_mass, im.data(), im.size());
-  if (ok) {  // partners per incidence slot
-    std::vector<int> bb((size_t)n * kMaxBeadBonds), ba((size_t)n * kMaxBeadAngles), bonds((size_t)2 * std::max(sys->n_bonds, 0)),
-        angles((size_t)3 * std::max(sys->n_angles, 0));
-    ok = hipMemcpy(bb.data(), sys->d_bead_bonds, bb.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(ba.data(), sys->d_bead_angles, ba.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
-         (bonds.empty() || hipMemcpy(bonds.data(), sys->d_bonds, bonds.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) &&
-         (angles.empty() || hipMemcpy(angles.data(), sys->d_angles, angles.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess);
-    std::vector<int> pb(bb.size(), -1);
-    std::vector<int2> pa(ba.size(), int2{-1, -1});
-    for (size_t k = 0; ok && k < bb.size(); ++k)
-      if (bb[k] >= 0) pb[k] = bonds[2 * (size_t)(bb[k] >> 1) + (1 - (bb[k] & 1))];
-    for (size_t k = 0; ok && k < ba.size(); ++k)
-      if (ba[k] >= 0) {
-        const int* t = &angles[3 * (size_t)(ba[k] >> 2)];
-        const int role = ba[k] & 3;
-        pa[k] = role == 0 ? int2{t[1], t[2]} : (role == 1 ? int2{t[0], t[2]} : int2{t[0], t[1]});
-      }
-    ok = ok && hipMalloc((void**)&s->d_bb_partner, std::max<size_t>(pb.size(), 1) * sizeof(int)) == hipSuccess &&
-         hipMalloc((void**)&s->d_ba_partner, std::max<size_t>(pa.size(), 1) * sizeof(int2)) == hipSuccess &&
-         hipMemcpy(s->d_bb_partner, pb.data(), pb.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(s->d_ba_partner, pa.data(), pa.size() * sizeof(int2), hipMemcpyHostToDevice) == hipSuccess;
-  }
-  if (ok) {  // the compact type tables
-    const int T = sys->n_types;
-    std::vector<int> types(n), cmap(T, -1), used;
-    ok = hipMemcpy(types.data(), sys->d_types, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-    std::vector<double> sig((size_t)T * T), ep((size_t)T * T);
-    if (sys->dtype == MYTHOS_F32) {
-      std::vector<float> a((size_t)T * T), b((size_t)T * T);
-      ok = ok && hipMemcpy(a.data(), sys->d_sigma, a.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(b.data(), sys->d_eps, b.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
-      for (size_t k = 0; k < a.size(); ++k) sig[k] = a[k], ep[k] = b[k];
-    } else {
-      ok = ok && hipMemcpy(sig.data(), sys->d_sigma, sig.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(ep.data(), sys->d_eps, ep.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    if (ok) {
-      for (int t : types)
-        if (t >= 0 && t < T && cmap[t] < 0) cmap[t] = 0;
-      for (int t = 0; t < T; ++t)
-        if (cmap[t] == 0) cmap[t] = (int)used.size(), used.push_back(t);
-      const int C = std::max<int>(1, (int)used.size());
-      std::vector<double> cs((size_t)C * C, 0.0), ce((size_t)C * C, 0.0);
-      for (size_t p = 0; p < used.size(); ++p)
-        for (size_t q = 0; q < used.size(); ++q) {
-          // (squared in the kernel's own precision, as the kernel did)
-          const double sg = sig[(size_t)used[p] * T + used[q]];
-          cs[p * C + q] = sys->dtype == MYTHOS_F32 ? double(float(sg) * float(sg)) : sg * sg;
-          ce[p * C + q] = ep[(size_t)used[p] * T + used[q]];
-        }
-      for (int& t : types) t = (t >= 0 && t < T) ? cmap[t] : 0;
-      s->n_ctypes = C;
-      ok = hipMalloc((void**)&s->d_ctypes, (size_t)n * sizeof(int)) == hipSuccess &&
-           hipMemcpy(s->d_ctypes, types.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-           upload_real(sys->dtype, &s->d_csig2, cs.data(), cs.size()) && upload_real(sys->dtype, &s->d_ceps, ce.data(), ce.size());
-    }
-  }
-  {
-    std::vector<double> ref((size_t)std::max(sys->n_angles, 0));
-    if (ok && sys->n_angles > 0) {
-      if (sys->dtype == MYTHOS_F32) {
-        std::vector<float> t0(ref.size());
-        ok = hipMemcpy(t0.data(), sys->d_angle_t0, t0.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
-        for (size_t a = 0; a < ref.size(); ++a) ref[a] = sys->angle_kind == 0 ? std::cos(double(t0[a])) : double(t0[a]);
-      } else {
-        ok = hipMemcpy(ref.data(), sys->d_angle_t0, ref.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
-        if (sys->angle_kind == 0)
-          for (double& v : ref) v = std::cos(v);
-      }
-    }
-    ok = ok && upload_real(sys->dtype, &s->d_angle_ref, ref.data(), ref.size());
-  }
-  ok = ok && hipMemset(s->list.d_overflow, 0, kOverflowWords * sizeof(int)) == hipSuccess;
-  if (!ok) {
+  if (!md_run_create(*s) || s->frame[0].alloc((size_t)n * 4 * w) || s->frame[1].alloc((size_t)n * 4 * w) || s->vel.alloc((size_t)n * 4 * w) ||
+      s->ref_pos.alloc((size_t)n * 4 * w) || rows_reserve(s->list, n, 256) || s->d_row_len.alloc((size_t)n) ||
+      s->list.d_overflow.alloc(kOverflowWords) || s->d_epart.alloc((size_t)blocks * kMmTrace) ||
+      s->d_inv_mass.upload_real(dtype, im.data(), im.size()) || s->d_bb_partner.upload(pb) || s->d_ba_partner.upload(pa) ||
+      s->d_ctypes.upload(types) || s->d_csig2.upload_real(dtype, cs.data(), cs.size()) ||
+      s->d_ceps.upload_real(dtype, ce.data(), ce.size()) || s->d_angle_ref.upload_real(dtype, ref.data(), ref.size()) ||
+      hipMemset(s->list.d_overflow.get(), 0, kOverflowWords * sizeof(int)) != hipSuccess) {
     set_error("mythos_martini_langevin_create: device allocation failed");
-    mythos_martini_langevin_destroy(s);
     return nullptr;
   }
-  return s;
+  return s.release();
 }
 
 int mythos_martini_langevin_set_neighbor_policy(mythos_martini_sim_t* s, double skin, int rebuild_every) {
@@ -890,13 +837,13 @@ int mythos_martini_langevin_init_velocities(mythos_martini_sim_t* s, void* vel, 
     set_error("mythos_martini_langevin_init_velocities: invalid argument");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
   if (s->sys->dtype == MYTHOS_F32)
     hipLaunchKernelGGL(mm_init_velocities_kernel<float>, dim3(1), dim3(256), 0, (hipStream_t)stream, s->sys->n, float(s->kT),
-                       (const float*)s->d_inv_mass, s->seed, (float*)vel);
+                       (const float*)s->d_inv_mass.get(), s->seed, (float*)vel);
   else
     hipLaunchKernelGGL(mm_init_velocities_kernel<double>, dim3(1), dim3(256), 0, (hipStream_t)stream, s->sys->n, s->kT,
-                       (const double*)s->d_inv_mass, s->seed, (double*)vel);
+                       (const double*)s->d_inv_mass.get(), s->seed, (double*)vel);
   MYTHOS_HIP_TRY(hipGetLastError());
   return MYTHOS_OK;
 }
@@ -937,7 +884,7 @@ int mythos_martini_langevin_run(mythos_martini_sim_t* s, void* pos, void* vel, c
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   if (int rc = mm_check_box(s, box, "mythos_martini_langevin_run")) return rc;
-  MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
   if (int rc = mm_load(s, pos, vel, box, st)) return rc;
   const int rc = mm_advance(s, n_steps, save_every, true, traj_pos, e_trace, st);
@@ -955,7 +902,7 @@ int mythos_martini_langevin_load(mythos_martini_sim_t* s, const void* pos, const
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   if (int rc = mm_check_box(s, box, "mythos_martini_langevin_load")) return rc;
-  MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
   return mm_load(s, pos, vel, box, (hipStream_t)stream);
 }
 
@@ -970,7 +917,7 @@ int mythos_martini_langevin_advance(mythos_martini_sim_t* s, int n_steps, int sa
               "numeric error drops its state)");
     return MYTHOS_ERR_NOT_READY;
   }
-  MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
   return mm_advance(s, n_steps, save_every, false, traj_pos, e_trace, (hipStream_t)stream);
 }
 
@@ -983,7 +930,7 @@ int mythos_martini_langevin_store(mythos_martini_sim_t* s, void* pos, void* vel,
     set_error("mythos_martini_langevin_store: no resident state");
     return MYTHOS_ERR_NOT_READY;
   }
-  MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
   return mm_store(s, pos, vel, (hipStream_t)stream);
 }
 
@@ -1003,8 +950,8 @@ int mythos_martini_langevin_neighbor_stats(const mythos_martini_sim_t* s, int* m
     set_error("mythos_martini_langevin_neighbor_stats: invalid argument");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
-  return row_stats(s->d_row_len, s->sys->n, 0, max_row, mean_row);
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
+  return row_stats(s->d_row_len.get(), s->sys->n, 0, max_row, mean_row);
 }
 
 int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* s, int which, int32_t* rows, int32_t* row_len, int* stride) {
@@ -1012,8 +959,8 @@ int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* s, int which, i
     set_error("mythos_martini_langevin_get_rows: invalid argument");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  const int* d_rows = which == 0 ? s->list.d_rows : s->d_rows_in;
-  const int* d_len = which == 0 ? s->d_row_len : s->d_row_len_in;
+  const int* d_rows = which == 0 ? s->list.d_rows.get() : s->d_rows_in.get();
+  const int* d_len = which == 0 ? s->d_row_len.get() : s->d_row_len_in.get();
   if (stride) *stride = s->list.stride;
   if (!rows && !row_len) return MYTHOS_OK;
   if (!d_rows || !d_len || !s->list_valid) {
@@ -1021,7 +968,7 @@ int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* s, int which, i
                          : "mythos_martini_langevin_get_rows: no pruned rows (switched off, or no step taken yet)");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  MYTHOS_HIP_TRY(hipSetDevice(s->sys->device));
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
   MYTHOS_HIP_TRY(hipDeviceSynchronize());
   if (rows) MYTHOS_HIP_TRY(hipMemcpy(rows, d_rows, (size_t)s->sys->n * s->list.stride * sizeof(int), hipMemcpyDeviceToHost));
   if (row_len) MYTHOS_HIP_TRY(hipMemcpy(row_len, d_len, (size_t)s->sys->n * sizeof(int), hipMemcpyDeviceToHost));

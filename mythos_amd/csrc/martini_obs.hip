@@ -9,6 +9,7 @@
 // Output, dev double, group-major: group g with m_g members occupies the (S, m_g) row-major block that starts at
 // S * (m_0 + ... + m_{g-1}) - the layout the distribution plan of w1.hip reads.
 // Arithmetic is always double: fp32 positions and boxes are promoted on load.
+#include <memory>
 #include <vector>
 
 #include "mythos_internal.h"
@@ -16,8 +17,9 @@
 struct mythos_martini_obs {
   int n = 0, n_groups = 0, device = 0;
   long long n_items = 0;    // sum of the groups' members
-  int4* d_beads = nullptr;  // [n_items] i, j, k (k = -1: a bond)
-  int4* d_place = nullptr;  // [n_items] members before this group, members of this group, column inside the group
+  mythos::DeviceBuf<int4> d_beads;  // [n_items] i, j, k (k = -1: a bond)
+  mythos::DeviceBuf<int4> d_place;  // [n_items] members before this group, members of this group, column inside the group
+  ~mythos_martini_obs() { (void)hipSetDevice(device); }  // the members free themselves, on the set's device
 };
 
 namespace mythos {
@@ -100,31 +102,17 @@ mythos_martini_obs_t* mythos_martini_obs_create(int n, int n_groups, const int32
       return nullptr;
     }
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) {
-    set_error("mythos_martini_obs_create: no usable HIP device (the HIP path has no CPU fallback)");
-    return nullptr;
-  }
-  auto* h = new mythos_martini_obs();
+  if (select_device(device, "mythos_martini_obs_create")) return nullptr;
+  auto h = std::make_unique<mythos_martini_obs>();
   h->n = n, h->n_groups = n_groups, h->device = device, h->n_items = before;
-  const size_t bytes = beads.size() * sizeof(int4);
-  if (hipMalloc((void**)&h->d_beads, bytes) != hipSuccess || hipMalloc((void**)&h->d_place, bytes) != hipSuccess ||
-      hipMemcpy(h->d_beads, beads.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->d_place, place.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+  if (h->d_beads.upload(beads) || h->d_place.upload(place)) {
     set_error("mythos_martini_obs_create: device allocation failed");
-    mythos_martini_obs_destroy(h);
     return nullptr;
   }
-  return h;
+  return h.release();
 }
 
-void mythos_martini_obs_destroy(mythos_martini_obs_t* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->d_beads) (void)hipFree(h->d_beads);
-  if (h->d_place) (void)hipFree(h->d_place);
-  delete h;
-}
+void mythos_martini_obs_destroy(mythos_martini_obs_t* h) { delete h; }
 
 int64_t mythos_martini_obs_count(const mythos_martini_obs_t* h) { return h ? (int64_t)h->n_items : 0; }
 
@@ -141,10 +129,10 @@ int mythos_martini_obs_eval(mythos_martini_obs_t* h, const void* pos, const void
     const int nf = std::min(n_frames - f0, 32768);
     if (dtype == MYTHOS_F32)
       hipLaunchKernelGGL(martini_obs_kernel<float>, dim3(nbx, nf), dim3(kObsBlock), 0, (hipStream_t)stream, h->n, h->n_items,
-                         h->d_beads, h->d_place, (const float*)pos, (const float*)box, f0, n_frames, out);
+                         h->d_beads.get(), h->d_place.get(), (const float*)pos, (const float*)box, f0, n_frames, out);
     else
       hipLaunchKernelGGL(martini_obs_kernel<double>, dim3(nbx, nf), dim3(kObsBlock), 0, (hipStream_t)stream, h->n, h->n_items,
-                         h->d_beads, h->d_place, (const double*)pos, (const double*)box, f0, n_frames, out);
+                         h->d_beads.get(), h->d_place.get(), (const double*)pos, (const double*)box, f0, n_frames, out);
   }
   MYTHOS_HIP_TRY(hipGetLastError());
   return MYTHOS_OK;

@@ -27,7 +27,7 @@ struct MdRun {
   int timing_samples = 0;   // dispatches per run timed with their own event pair (set_timing; ~8 us each)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;  // bracket a whole run
   hipEvent_t sa[kMaxSamples] = {}, sb[kMaxSamples] = {};
-  int* d_flags = nullptr;
+  DeviceBuf<int> d_flags;
   // control words as the device published them at the end of a segment: [0..3] d_flags, [4..6] the list builder's
   // overflow words.  Pinned host memory the publishing kernel writes directly: one stream synchronisation per segment
   // and no copy commands.
@@ -38,12 +38,25 @@ struct MdRun {
   int last_launches = 0, last_samples = 0;
   int last_recoveries = 0;  // halts of the last run that were rebuilt and resumed
   int last_rebuilds = 0;    // scheduled list rebuilds inside the last advance (the first build of a list not counted)
+
+  MdRun() = default;
+  MdRun(const MdRun&) = delete;
+  MdRun& operator=(const MdRun&) = delete;
+  // (the owner's destructor has selected the device; what md_run_create did not get to is null)
+  ~MdRun() {
+    if (h_ctl) (void)hipHostFree(h_ctl);
+    for (hipEvent_t e : {ev0, ev1})
+      if (e) (void)hipEventDestroy(e);
+    for (int k = 0; k < kMaxSamples; ++k) {
+      if (sa[k]) (void)hipEventDestroy(sa[k]);
+      if (sb[k]) (void)hipEventDestroy(sb[k]);
+    }
+  }
 };
 
-// events, control words (cleared) and their pinned host copy; false on failure (md_run_destroy frees what was made)
+// events, control words (cleared) and their pinned host copy; false on failure (the destructor frees what was made)
 inline bool md_run_create(MdRun& r) {
-  bool ok = hipMalloc((void**)&r.d_flags, MdRun::kCtlWords * sizeof(int)) == hipSuccess &&
-            hipMemset(r.d_flags, 0, MdRun::kCtlWords * sizeof(int)) == hipSuccess &&
+  bool ok = r.d_flags.alloc(MdRun::kCtlWords) == 0 && hipMemset(r.d_flags.get(), 0, MdRun::kCtlWords * sizeof(int)) == hipSuccess &&
             hipHostMalloc((void**)&r.h_ctl, 8 * sizeof(int), hipHostMallocDefault) == hipSuccess &&
             hipHostGetDevicePointer((void**)&r.d_ctl, r.h_ctl, 0) == hipSuccess &&
             hipEventCreate(&r.ev0) == hipSuccess && hipEventCreate(&r.ev1) == hipSuccess;
@@ -51,17 +64,6 @@ inline bool md_run_create(MdRun& r) {
   for (int k = 0; ok && k < MdRun::kMaxSamples; ++k)
     ok = hipEventCreate(&r.sa[k]) == hipSuccess && hipEventCreate(&r.sb[k]) == hipSuccess;
   return ok;
-}
-
-inline void md_run_destroy(MdRun& r) {
-  if (r.d_flags) (void)hipFree(r.d_flags);
-  if (r.h_ctl) (void)hipHostFree(r.h_ctl);
-  for (hipEvent_t e : {r.ev0, r.ev1})
-    if (e) (void)hipEventDestroy(e);
-  for (int k = 0; k < MdRun::kMaxSamples; ++k) {
-    if (r.sa[k]) (void)hipEventDestroy(r.sa[k]);
-    if (r.sb[k]) (void)hipEventDestroy(r.sb[k]);
-  }
 }
 
 // End of a segment: hand the control words to the host (pinned memory) and clear the ones a later segment starts
@@ -174,7 +176,7 @@ static int md_drive(MdRun& run, const MdDrive& d, Launch&& launch, Rebuild&& reb
     run.since_build = 0;
     run.last_recoveries = recoveries;
     run.last_rebuilds = scheduled;
-    (void)hipMemsetAsync(run.d_flags + 1, 0, 3 * sizeof(int), st);
+    (void)hipMemsetAsync(run.d_flags.get() + 1, 0, 3 * sizeof(int), st);
     if (d.halt_words) (void)hipMemsetAsync(d.halt_words, 0, kOverflowWords * sizeof(int), st);
   };
   // ... and the state that kernels 0 .. ran - 1 left: positions after the last step that counted, momenta short of its
@@ -231,7 +233,7 @@ static int md_drive(MdRun& run, const MdDrive& d, Launch&& launch, Rebuild&& reb
       cur ^= 1;
     }
     if (timing && k >= n_launch) MYTHOS_HIP_TRY(hipEventRecord(run.ev1, st));
-    hipLaunchKernelGGL(publish_ctl_kernel, dim3(1), dim3(1), 0, st, run.d_flags, (const int*)d.halt_words, run.d_ctl);
+    hipLaunchKernelGGL(publish_ctl_kernel, dim3(1), dim3(1), 0, st, run.d_flags.get(), (const int*)d.halt_words, run.d_ctl);
     MYTHOS_HIP_TRY(hipGetLastError());
     MYTHOS_HIP_TRY(hipStreamSynchronize(st));
     const int* ctl = run.h_ctl;
@@ -265,7 +267,7 @@ static int md_drive(MdRun& run, const MdDrive& d, Launch&& launch, Rebuild&& reb
     cur = cur0 ^ (ran & 1);
     k = ran;
     seg_len = std::max(std::min(256, kSegment), seg_len / 4);
-    MYTHOS_HIP_TRY(hipMemsetAsync(run.d_flags + 1, 0, 3 * sizeof(int), st));
+    MYTHOS_HIP_TRY(hipMemsetAsync(run.d_flags.get() + 1, 0, 3 * sizeof(int), st));
     if (d.dynamic_list) {
       if (int rc = rebuild_until_fit(cur)) return fail(ran, rc);
       built_at = k;

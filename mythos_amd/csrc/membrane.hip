@@ -16,6 +16,7 @@
 // lipid and their number has no limit.  Sums are double and in a fixed order: thread-strided partials, the wavefront
 // butterfly of wave_ops.h, the wavefronts' totals in order through LDS.  No atomics: a frame's row depends on that
 // frame only.  The kernel is launch and gather bound (3 - 4 gathered z per lipid and frame).
+#include <memory>
 #include <vector>
 
 #include "mythos_internal.h"
@@ -23,10 +24,11 @@
 
 struct mythos_membrane {
   int n = 0, n_lipids = 0, n_sel = 0, n_thick = 0, device = 0;
-  int* d_start = nullptr;        // [n_lipids + 1] CSR offsets into d_sel
-  int* d_sel = nullptr;          // [n_sel] beads of the lipid selection, grouped by lipid
-  int* d_thick = nullptr;        // [n_thick] beads of the thickness selection
-  int* d_thick_lipid = nullptr;  // [n_thick] the lipid of each
+  mythos::DeviceBuf<int> d_start;        // [n_lipids + 1] CSR offsets into d_sel
+  mythos::DeviceBuf<int> d_sel;          // [n_sel] beads of the lipid selection, grouped by lipid
+  mythos::DeviceBuf<int> d_thick;        // [n_thick] beads of the thickness selection
+  mythos::DeviceBuf<int> d_thick_lipid;  // [n_thick] the lipid of each
+  ~mythos_membrane() { (void)hipSetDevice(device); }  // the members free themselves, on the set's device
 };
 
 namespace mythos {
@@ -132,40 +134,18 @@ mythos_membrane_t* mythos_membrane_create(int n, int n_lipids, const int32_t* li
       set_error("mythos_membrane_create: thickness bead or its lipid out of range");
       return nullptr;
     }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) {
-    set_error("mythos_membrane_create: no usable HIP device (the HIP path has no CPU fallback)");
-    return nullptr;
-  }
-  auto* h = new mythos_membrane();
+  if (select_device(device, "mythos_membrane_create")) return nullptr;
+  auto h = std::make_unique<mythos_membrane>();
   h->n = n, h->n_lipids = n_lipids, h->n_sel = n_sel, h->n_thick = n_thick, h->device = device;
-  const size_t nt = n_thick > 0 ? (size_t)n_thick : 1;  // no zero-byte allocations
-  bool ok = hipMalloc((void**)&h->d_start, ((size_t)n_lipids + 1) * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&h->d_sel, (size_t)n_sel * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&h->d_thick, nt * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&h->d_thick_lipid, nt * sizeof(int)) == hipSuccess &&
-            hipMemcpy(h->d_start, lipid_start, ((size_t)n_lipids + 1) * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(h->d_sel, lipid_beads, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && n_thick > 0)
-    ok = hipMemcpy(h->d_thick, thick_beads, (size_t)n_thick * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(h->d_thick_lipid, thick_lipid, (size_t)n_thick * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
+  if (h->d_start.upload(lipid_start, (size_t)n_lipids + 1) || h->d_sel.upload(lipid_beads, (size_t)n_sel) ||
+      h->d_thick.upload(thick_beads, (size_t)n_thick) || h->d_thick_lipid.upload(thick_lipid, (size_t)n_thick)) {
     set_error("mythos_membrane_create: device allocation failed");
-    mythos_membrane_destroy(h);
     return nullptr;
   }
-  return h;
+  return h.release();
 }
 
-void mythos_membrane_destroy(mythos_membrane_t* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->d_start) (void)hipFree(h->d_start);
-  if (h->d_sel) (void)hipFree(h->d_sel);
-  if (h->d_thick) (void)hipFree(h->d_thick);
-  if (h->d_thick_lipid) (void)hipFree(h->d_thick_lipid);
-  delete h;
-}
+void mythos_membrane_destroy(mythos_membrane_t* h) { delete h; }
 
 int mythos_membrane_n_lipids(const mythos_membrane_t* h) { return h ? h->n_lipids : 0; }
 
@@ -182,11 +162,11 @@ int mythos_membrane_eval(mythos_membrane_t* h, const void* pos, const void* box,
     const int nf = std::min(n_frames - f0, kFramesPerLaunch);
     if (dtype == MYTHOS_F32)
       hipLaunchKernelGGL(membrane_kernel<float>, dim3(nf), dim3(kMemBlock), 0, (hipStream_t)stream, h->n, h->n_lipids, h->n_sel,
-                         h->n_thick, h->d_start, h->d_sel, h->d_thick, h->d_thick_lipid, (const float*)pos, (const float*)box, f0,
+                         h->n_thick, h->d_start.get(), h->d_sel.get(), h->d_thick.get(), h->d_thick_lipid.get(), (const float*)pos, (const float*)box, f0,
                          out, leaflets);
     else
       hipLaunchKernelGGL(membrane_kernel<double>, dim3(nf), dim3(kMemBlock), 0, (hipStream_t)stream, h->n, h->n_lipids, h->n_sel,
-                         h->n_thick, h->d_start, h->d_sel, h->d_thick, h->d_thick_lipid, (const double*)pos, (const double*)box, f0,
+                         h->n_thick, h->d_start.get(), h->d_sel.get(), h->d_thick.get(), h->d_thick_lipid.get(), (const double*)pos, (const double*)box, f0,
                          out, leaflets);
   }
   MYTHOS_HIP_TRY(hipGetLastError());

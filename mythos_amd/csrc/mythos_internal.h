@@ -9,21 +9,15 @@
 #include <vector>
 
 #include "../../include/mythos_hip.h"
+#include "device_buf.h"
 #include "oxdna_math.h"
 
 namespace mythos {
 
-void set_error(const std::string& msg);
-int hip_fail(hipError_t e, const char* what);
+// (set_error, hip_fail and MYTHOS_HIP_TRY: device_buf.h)
 // test / diagnostic switches (mythos_debug_set): process-wide, 0 = default
 long long debug_value(int key);
 void debug_clear(int key);
-
-#define MYTHOS_HIP_TRY(expr)                                   \
-  do {                                                         \
-    hipError_t _e = (expr);                                    \
-    if (_e != hipSuccess) return ::mythos::hip_fail(_e, #expr); \
-  } while (0)
 
 // Row entry encoding of the per-nucleotide neighbour rows:
 //   slot 0 : bonded partner on the 3' side  (bond (j, self): self plays nn_j)   or -1
@@ -43,18 +37,6 @@ struct BoxT {
   int on;
 };
 
-// A device buffer that only grows: reallocated, contents not kept, when more than cap elements are needed.
-template <typename T>
-inline int grow_buffer(T*& ptr, size_t& cap, size_t need) {
-  if (need <= cap) return 0;
-  if (ptr) (void)hipFree(ptr);
-  ptr = nullptr;
-  cap = 0;
-  MYTHOS_HIP_TRY(hipMalloc((void**)&ptr, need * sizeof(T)));
-  cap = need;
-  return 0;
-}
-
 // d_overflow words: [0] longest row if over the stride, [1] fullest bucket if over its capacity, [2] fullest bucket if
 // over half its capacity (headroom hint, not an error)
 constexpr int kOverflowWords = 3;
@@ -63,12 +45,10 @@ constexpr int kOverflowWords = 3;
 // to the next: the overflow words and the cell table (cell_list.h, which has the host helpers around them).  The row
 // lengths stay with each owner: their layouts differ.
 struct VerletRows {
-  int* d_rows = nullptr;  // [n][stride]
-  size_t rows_cap = 0;    // ints allocated at d_rows
+  DeviceBuf<int> d_rows;  // [n][stride]
   int stride = 0;
-  int* d_overflow = nullptr;  // [kOverflowWords] largest demands seen since last cleared (list_build_until_fit)
-  int* d_cell = nullptr;      // cell table (cell_list.h CellBins): counters [2][H], buckets [H][cell_bucket_cap]
-  size_t cell_cap = 0;        // ints allocated at d_cell
+  DeviceBuf<int> d_overflow;  // [kOverflowWords] largest demands seen since last cleared (list_build_until_fit)
+  DeviceBuf<int> d_cell;      // cell table (cell_list.h CellBins): counters [2][H], buckets [H][cell_bucket_cap]
   int cell_H = 0;             // table slots of the current layout
   int cell_alloc_bucket_cap = 0;  // places per slot the current layout was made for
   bool cell_sites = false;    // the layout carries the two site streams (cell_list.h CellBins::sites)
@@ -91,12 +71,12 @@ struct mythos_system {
   double box[3] = {0, 0, 0};
 
   // topology (device)
-  int* d_meta = nullptr;  // [n] seq | is_end << 2
+  mythos::DeviceBuf<int> d_meta;  // [n] seq | is_end << 2
 
   // neighbour rows: the rows, their overflow words and cell table (cell buckets start at 32 places; the rows reserve a
   // stride of 64 at first use, rows_build_device)
   mythos::VerletRows list{32};
-  int* d_row_len = nullptr;  // [n] used slots (>= 2) | [2n] bonded partners | [n] end of the "close" segment
+  mythos::DeviceBuf<int> d_row_len;  // [n] used slots (>= 2) | [2n] bonded partners | [n] end of the "close" segment
   bool nbrs_set = false;
   int list_epoch = 0;  // bumped when parameters or rows are replaced through the ABI (integrators re-validate their list)
   int param_epoch = 0; // bumped when parameters or nucleotide types are replaced (integrators re-derive the site offsets they carry)
@@ -104,10 +84,17 @@ struct mythos_system {
   std::vector<int> h_partners;
   bool extra_bonds = false;  // some nucleotide uses slot 2 or 3 (circular strands)
 
-  // Verlet build scratch
-  void* d_ref_pos = nullptr;  // [n] real4 positions at the last build (MD displacement check)
-  void* d_ref_off = nullptr;  // [n] real4 backbone offsets at the last build
-  void* d_ref_a1 = nullptr;   // [n] real4 base vectors at the last build
+  // Verlet build scratch of an MD run (neighbors.hip writes it): allocated by reserve_refs, which an integrator's
+  // create calls
+  mythos::DeviceBytes d_ref_pos;  // [n] real4 positions at the last build (MD displacement check)
+  mythos::DeviceBytes d_ref_off;  // [n] real4 backbone offsets at the last build
+  mythos::DeviceBytes d_ref_a1;   // [n] real4 base vectors at the last build
+  int reserve_refs() {
+    const size_t v4 = (dtype == MYTHOS_F32 ? sizeof(float4) : sizeof(double4)) * (size_t)n;
+    for (mythos::DeviceBytes* b : {&d_ref_pos, &d_ref_off, &d_ref_a1})
+      if (int rc = b->grow(v4)) return rc;
+    return 0;
+  }
 
   // parameters
   bool params_set = false;
@@ -118,24 +105,24 @@ struct mythos_system {
   int param_sets() const { return model == 4 ? 3 : 1; }
   bool types_set = false;  // model 4: mythos_oxdna_set_nucleotide_types has run
   std::vector<int> h_meta;  // seq | is_end << 2 | is_rna << 3, as uploaded to d_meta
-  float* d_pf = nullptr;   // the same vectors in device memory (read by the MD kernel as scalar loads)
-  double* d_pd = nullptr;
+  mythos::DeviceBuf<float> d_pf;   // the same vectors in device memory (read by the MD kernel as scalar loads)
+  mythos::DeviceBuf<double> d_pd;
 
   // probabilistic sequence (mythos_oxdna_set_pseq); pseq_terms == 0: discrete sequence
-  void* d_ps_marg = nullptr;  // [n][4] real: marginal base probabilities
-  int* d_ps_unit = nullptr;   // [n] 2 * base pair + member, or -1
-  void* d_ps_bp = nullptr;    // [max(n_bp, 1)][4] real: base-pair type probabilities
-  int ps_bp_cap = 0;
+  mythos::DeviceBytes d_ps_marg;  // [n][4] real: marginal base probabilities
+  mythos::DeviceBuf<int> d_ps_unit;   // [n] 2 * base pair + member, or -1
+  mythos::DeviceBytes d_ps_bp;    // [max(n_bp, 1)][4] real: base-pair type probabilities
   int pseq_terms = 0;         // bit 0 stacking, bit 1 hydrogen bonding
   int ps_n_bp = 0;            // constrained base pairs of the distribution
   double* ps_gmarg = nullptr; // caller's dU/d(marginals) and dU/d(type probabilities) buffers, set for the duration of
   double* ps_gbp = nullptr;   // one mythos_oxdna_energy_dpseq call
 
   // energy-pass scratch
-  double* d_epart = nullptr;  // [frames_chunk][blocks][8]
-  size_t epart_cap = 0;
-  double* d_pgpart = nullptr;  // [frames_chunk][blocks][OXP_COUNT]
-  size_t pgpart_cap = 0;
+  mythos::DeviceBuf<double> d_epart;   // [frames_chunk][blocks][8]
+  mythos::DeviceBuf<double> d_pgpart;  // [frames_chunk][blocks][OXP_COUNT]
+
+  // the members free themselves, on the system's device
+  ~mythos_system() { (void)hipSetDevice(device); }
 };
 
 namespace mythos {
@@ -160,14 +147,14 @@ inline const OxParams<double>& params_of<double>(const mythos_system* s) { retur
 template <typename R>
 const R* device_params_of(const mythos_system* s);
 template <>
-inline const float* device_params_of<float>(const mythos_system* s) { return s->d_pf; }
+inline const float* device_params_of<float>(const mythos_system* s) { return s->d_pf.get(); }
 template <>
-inline const double* device_params_of<double>(const mythos_system* s) { return s->d_pd; }
+inline const double* device_params_of<double>(const mythos_system* s) { return s->d_pd.get(); }
 
 // d_row_len holds three arrays back to back: row length [n] | bonded partners [n][ROW_BONDED_SLOTS] | end of the
 // "close" segment of the row [n]
 static_assert(ROW_BONDED_SLOTS == 4, "the row builders copy four partner slots");
-inline int* row_close_of(const mythos_system* sys) { return sys->d_row_len + (size_t)(1 + ROW_BONDED_SLOTS) * sys->n; }
+inline int* row_close_of(const mythos_system* sys) { return sys->d_row_len.get() + (size_t)(1 + ROW_BONDED_SLOTS) * sys->n; }
 
 // Largest centre-centre distance at which anything other than the backbone-backbone terms (excluded
 // volume between base / backbone sites, H-bond, cross- and coaxial stacking) can act.  Rows keep the

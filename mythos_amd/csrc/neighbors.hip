@@ -37,8 +37,8 @@ int rows_from_pairs(mythos_system* sys, const int32_t* pairs, int n_pairs) {
     rows[(size_t)j * stride + len[j]++] = i | ROW_ROLE_Q;  // j plays op_j
   }
   if (int rc = rows_reserve(sys->list, n, stride)) return rc;
-  MYTHOS_HIP_TRY(hipMemcpy(sys->list.d_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
-  MYTHOS_HIP_TRY(hipMemcpy(sys->d_row_len, len.data(), n * sizeof(int), hipMemcpyHostToDevice));
+  MYTHOS_HIP_TRY(hipMemcpy(sys->list.d_rows.get(), rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+  MYTHOS_HIP_TRY(hipMemcpy(sys->d_row_len.get(), len.data(), n * sizeof(int), hipMemcpyHostToDevice));
   // a user-supplied pair list carries no distance classes: every entry is in the "close" segment
   MYTHOS_HIP_TRY(hipMemcpy(row_close_of(sys), len.data(), n * sizeof(int), hipMemcpyHostToDevice));
   sys->nbrs_set = true;
@@ -321,9 +321,9 @@ __global__ __launch_bounds__(256) void build_rows_cells_kernel(int n, const R* _
 template <typename R>
 static int build_cells_typed(mythos_system* sys, const R* pos, bool vec4, double rl, double skin, const R* off,
                              const R* a1, bool write_refs, hipStream_t st) {
-  R* ref_pos = write_refs ? (R*)sys->d_ref_pos : nullptr;
-  R* ref_off = write_refs ? (R*)sys->d_ref_off : nullptr;
-  R* ref_a1 = write_refs ? (R*)sys->d_ref_a1 : nullptr;
+  R* ref_pos = write_refs ? (R*)sys->d_ref_pos.get() : nullptr;
+  R* ref_off = write_refs ? (R*)sys->d_ref_off.get() : nullptr;
+  R* ref_a1 = write_refs ? (R*)sys->d_ref_a1.get() : nullptr;
   const int n = sys->n;
   // classification radius of the leading "close" segment (everything is close until parameters exist)
   const double rcl = sys->params_set ? std::min(rl, oxdna_close_range(sys) + skin) : rl;
@@ -355,15 +355,15 @@ static int build_cells_typed(mythos_system* sys, const R* pos, bool vec4, double
   CellGrid<R> g;
   const bool cells = cell_grid(g, n, rl, sys->has_box ? sys->box : nullptr);
   const int blocks_ap = (n * 64 + 255) / 256;
-  int* d_partners = sys->d_row_len + n;
+  int* d_partners = sys->d_row_len.get() + n;
   const BoxT<R> box = make_box<R>(sys);
   if (!cells) {  // tiny systems / boxes under three cells: the all-pairs sweep is exact and cheap
     if (vec4)
       hipLaunchKernelGGL((build_rows_allpairs_kernel<R, true>), dim3(blocks_ap), dim3(256), 0, st, n, pos, box,
-                         R(rl * rl), R(rcl * rcl), sc, d_partners, L.d_rows, sys->d_row_len, d_close, L.stride, L.d_overflow);
+                         R(rl * rl), R(rcl * rcl), sc, d_partners, L.d_rows.get(), sys->d_row_len.get(), d_close, L.stride, L.d_overflow.get());
     else
       hipLaunchKernelGGL((build_rows_allpairs_kernel<R, false>), dim3(blocks_ap), dim3(256), 0, st, n, pos, box,
-                         R(rl * rl), R(rcl * rcl), sc, d_partners, L.d_rows, sys->d_row_len, d_close, L.stride, L.d_overflow);
+                         R(rl * rl), R(rcl * rcl), sc, d_partners, L.d_rows.get(), sys->d_row_len.get(), d_close, L.stride, L.d_overflow.get());
     if (write_refs && vec4) {  // the cell-list kernel writes these itself
       const size_t bytes = (size_t)n * 4 * sizeof(R);
       MYTHOS_HIP_TRY(hipMemcpyAsync(ref_pos, pos, bytes, hipMemcpyDeviceToDevice, st));
@@ -381,20 +381,20 @@ static int build_cells_typed(mythos_system* sys, const R* pos, bool vec4, double
   const size_t site_stride = sites ? (size_t)bins.H * bins.cap : 0;
   // the row builder orders its rows itself: no bucket sort
   if (vec4)
-    cell_bins_build<R, true>(n, pos, g, bins, L.d_overflow, false, st, sc.off, sc.a1);
+    cell_bins_build<R, true>(n, pos, g, bins, L.d_overflow.get(), false, st, sc.off, sc.a1);
   else
-    cell_bins_build<R, false>(n, pos, g, bins, L.d_overflow, false, st);
+    cell_bins_build<R, false>(n, pos, g, bins, L.d_overflow.get(), false, st);
   constexpr int kPerBlock = 256 / kRowG;
   const int wb = (n + kPerBlock - 1) / kPerBlock;
   const size_t far_lds = (size_t)kPerBlock * 2 * L.stride * sizeof(int);
   if (vec4)
     hipLaunchKernelGGL((build_rows_cells_kernel<R, true, kRowG>), dim3(wb), dim3(256), far_lds, st, n, pos, box, g, R(rl * rl),
-                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows, sys->d_row_len, d_close, L.stride,
-                       L.d_overflow, ref_pos, ref_off, ref_a1);
+                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows.get(), sys->d_row_len.get(), d_close, L.stride,
+                       L.d_overflow.get(), ref_pos, ref_off, ref_a1);
   else
     hipLaunchKernelGGL((build_rows_cells_kernel<R, false, kRowG>), dim3(wb), dim3(256), far_lds, st, n, pos, box, g, R(rl * rl),
-                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows, sys->d_row_len, d_close, L.stride,
-                       L.d_overflow, ref_pos, ref_off, ref_a1);
+                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows.get(), sys->d_row_len.get(), d_close, L.stride,
+                       L.d_overflow.get(), ref_pos, ref_off, ref_a1);
   return 0;
 }
 

@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "device_buf.h"
 #include "oxdna_math.h"
 
 namespace mythos {
@@ -142,10 +143,9 @@ __device__ __forceinline__ void frame_observables(const ObsView& v, const R* __r
 struct mythos_obs {
   int n = 0, dtype = 0, device = 0;
   mythos::ObsView view;     // device pointers filled in; view.axis is (re)allocated per call
-  int* d_bps = nullptr;
-  int* d_quartets = nullptr;
-  double* d_axis = nullptr;
-  size_t axis_cap = 0;      // doubles
+  mythos::DeviceBuf<int> d_bps, d_quartets;
+  mythos::DeviceBuf<double> d_axis;
+  ~mythos_obs() { (void)hipSetDevice(device); }  // the members free themselves, on the set's device
 };
 
 namespace mythos {

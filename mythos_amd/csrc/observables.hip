@@ -2,6 +2,8 @@
 // reference defines it.  One workgroup per frame; mythos_oxdna_energy_obs (oxdna_kernels.hip) queues the same kernel behind its energy launch.
 #include "observables.h"
 
+#include <memory>
+
 #include "mythos_internal.h"
 
 namespace mythos {
@@ -16,14 +18,8 @@ __global__ __launch_bounds__(256) void observables_kernel(const ObsView v, int n
 
 int obs_view_for(mythos_obs* o, int n_frames, ObsView* out) {
   const size_t need = (size_t)std::max(n_frames, 1) * std::max(o->view.n_q, 1) * 3;
-  if (need > o->axis_cap) {
-    if (o->d_axis) (void)hipFree(o->d_axis);
-    o->d_axis = nullptr;
-    o->axis_cap = 0;
-    MYTHOS_HIP_TRY(hipMalloc((void**)&o->d_axis, need * sizeof(double)));
-    o->axis_cap = need;
-  }
-  o->view.axis = o->d_axis;
+  if (int rc = o->d_axis.grow(need)) return rc;
+  o->view.axis = o->d_axis.get();
   *out = o->view;
   return 0;
 }
@@ -68,11 +64,8 @@ mythos_obs_t* mythos_observables_create(int model, int n, const double* geometry
       set_error("mythos_observables_create: quartet index out of range");
       return nullptr;
     }
-  if (hipSetDevice(device) != hipSuccess) {
-    set_error("mythos_observables_create: hipSetDevice failed");
-    return nullptr;
-  }
-  auto* o = new mythos_obs();
+  if (select_device(device, "mythos_observables_create")) return nullptr;
+  auto o = std::make_unique<mythos_obs>();
   o->n = n, o->dtype = dtype, o->device = device;
   ObsView& v = o->view;
   v.n_bp = n_bp, v.n_q = n_quartets;
@@ -85,32 +78,16 @@ mythos_obs_t* mythos_observables_create(int model, int n, const double* geometry
     v.box_on = 1;
     for (int k = 0; k < 3; ++k) v.box[k] = box[k];
   }
-  bool ok = true;
-  if (n_bp > 0) {
-    ok = ok && hipMalloc((void**)&o->d_bps, 2 * (size_t)n_bp * sizeof(int)) == hipSuccess &&
-         hipMemcpy(o->d_bps, base_pairs, 2 * (size_t)n_bp * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-  }
-  if (ok && n_quartets > 0) {
-    ok = hipMalloc((void**)&o->d_quartets, 4 * (size_t)n_quartets * sizeof(int)) == hipSuccess &&
-         hipMemcpy(o->d_quartets, quartets, 4 * (size_t)n_quartets * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-  }
-  if (!ok) {
+  if ((n_bp > 0 && o->d_bps.upload(base_pairs, 2 * (size_t)n_bp)) ||
+      (n_quartets > 0 && o->d_quartets.upload(quartets, 4 * (size_t)n_quartets))) {
     set_error("mythos_observables_create: device allocation failed");
-    mythos_observables_destroy(o);
     return nullptr;
   }
-  v.bps = o->d_bps, v.quartets = o->d_quartets;
-  return o;
+  v.bps = o->d_bps.get(), v.quartets = o->d_quartets.get();
+  return o.release();
 }
 
-void mythos_observables_destroy(mythos_obs_t* o) {
-  if (!o) return;
-  (void)hipSetDevice(o->device);
-  if (o->d_bps) (void)hipFree(o->d_bps);
-  if (o->d_quartets) (void)hipFree(o->d_quartets);
-  if (o->d_axis) (void)hipFree(o->d_axis);
-  delete o;
-}
+void mythos_observables_destroy(mythos_obs_t* o) { delete o; }
 
 int mythos_observables_width(const mythos_obs_t* o) { return o ? o->view.width : -1; }
 

@@ -359,9 +359,9 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
   size_t per_frame = (size_t)blocks * (mode >= 2 ? n_out : T_COUNT) * sizeof(double);
   int chunk = (int)std::min<size_t>(65535, std::max<size_t>(1, (size_t(256) << 20) / per_frame));
   chunk = std::min(chunk, n_frames);
-  if (int rc = grow_buffer(sys->d_epart, sys->epart_cap, (size_t)chunk * blocks * T_COUNT)) return rc;
+  if (int rc = sys->d_epart.grow((size_t)chunk * blocks * T_COUNT)) return rc;
   if (mode >= 2)
-    if (int rc = grow_buffer(sys->d_pgpart, sys->pgpart_cap, (size_t)chunk * blocks * n_out)) return rc;
+    if (int rc = sys->d_pgpart.grow((size_t)chunk * blocks * n_out)) return rc;
   const R* P = device_params_of<R>(sys);
   const BoxT<R> box = make_box<R>(sys);
   // centre distance beyond which no site pair of two nucleotides is inside any cut-off: the longest range of a term
@@ -380,7 +380,7 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
   const R rnear2 = R(rnear * rnear);
   PseqView<R> pseq;
   if (sys->pseq_terms != 0) {
-    pseq.marg = (const R*)sys->d_ps_marg, pseq.unit = sys->d_ps_unit, pseq.bp = (const R*)sys->d_ps_bp, pseq.terms = sys->pseq_terms;
+    pseq.marg = (const R*)sys->d_ps_marg.get(), pseq.unit = sys->d_ps_unit.get(), pseq.bp = (const R*)sys->d_ps_bp.get(), pseq.terms = sys->pseq_terms;
   }
   // LDS lists of the row walk: a row is walked in segments of list_cap entries (gather_row)
   int list_cap = std::min(sys->list.stride, kEnergyListCap);
@@ -394,7 +394,7 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
   for (int f0 = 0; f0 < n_frames; f0 += chunk) {
     const int nf = std::min(chunk, n_frames - f0);
     dim3 grid(blocks, nf);
-    if (obs.width > 0) obs.axis = oset->d_axis + (size_t)f0 * obs.n_q * 3;
+    if (obs.width > 0) obs.axis = oset->d_axis.get() + (size_t)f0 * obs.n_q * 3;
     const R* c = center + (size_t)f0 * n * 3;
     const R* q = quat + (size_t)f0 * n * 4;
     R* gc = dU_dcenter ? dU_dcenter + (size_t)f0 * n * 3 : nullptr;
@@ -408,8 +408,8 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
     }
     auto launch = [&](auto mode_tag, auto seg_tag) {
       hipLaunchKernelGGL((oxdna_energy_kernel<R, MODEL, decltype(mode_tag)::value, G, decltype(seg_tag)::value>),
-                         grid, dim3(kBlock), (size_t)PPB * 2 * list_cap * sizeof(int), stream, P, box, n, c, q, sys->d_meta, sys->list.d_rows,
-                         sys->d_row_len, sys->list.stride, sys->d_epart, gc, gq, sys->d_pgpart, rnear2, pseq, list_cap);
+                         grid, dim3(kBlock), (size_t)PPB * 2 * list_cap * sizeof(int), stream, P, box, n, c, q, sys->d_meta.get(), sys->list.d_rows.get(),
+                         sys->d_row_len.get(), sys->list.stride, sys->d_epart.get(), gc, gq, sys->d_pgpart.get(), rnear2, pseq, list_cap);
     };
     auto by_seg = [&](auto mode_tag) {
       if (sys->list.stride > list_cap) launch(mode_tag, std::true_type{}); else launch(mode_tag, std::false_type{});
@@ -427,8 +427,8 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
       if (int rc = observables_launch(oset, obs, c, q, nf, obs_out + (size_t)f0 * obs.width, stream)) return rc;
     }
     MYTHOS_HIP_TRY(hipGetLastError());
-    reduce_partials_launch(sys->d_epart, nf, blocks, (int)T_COUNT, e_terms + (size_t)f0 * T_COUNT, (int)T_COUNT, stream);
-    if (mode >= 2) reduce_partials_launch(sys->d_pgpart, nf, blocks, oxp_used<MODEL>(), dU_dparams + (size_t)f0 * n_out, n_out, stream);
+    reduce_partials_launch(sys->d_epart.get(), nf, blocks, (int)T_COUNT, e_terms + (size_t)f0 * T_COUNT, (int)T_COUNT, stream);
+    if (mode >= 2) reduce_partials_launch(sys->d_pgpart.get(), nf, blocks, oxp_used<MODEL>(), dU_dparams + (size_t)f0 * n_out, n_out, stream);
     MYTHOS_HIP_TRY(hipGetLastError());
   }
   return 0;

@@ -27,6 +27,7 @@
 // per-frame gradient gathers through rank instead of scattering dW/da to sample order and summing rows: 8-B accesses at
 // sorted positions either way (uncoalesced reads here, uncoalesced writes there), plain coalesced stores in w1_suffix,
 // and nothing is written through an index.  DESIGN.md 3.5b has what w1_frame_sum costs.
+#include <memory>
 #include <vector>
 
 #include "mythos_internal.h"
@@ -55,14 +56,15 @@ struct W1Group {
 struct mythos_w1_plan {
   int n_groups = 0, max_frames = 0, max_members = 0, device = 0, n_chunks = 0;
   long long n_u_total = 0;
-  mythos::W1Group* d_groups = nullptr;
-  int* d_chunk_group = nullptr;  // [n_chunks]
-  double* d_dx = nullptr;        // [n_chunks * kW1Chunk]
-  long long* d_src = nullptr;    // [n_chunks * kW1Chunk]
-  int* d_rank = nullptr;         // [n_u_total]
-  double* d_g = nullptr;         // [n_chunks * kW1Chunk] dx sign(D), then dW/da
-  double* d_part = nullptr;      // [3][n_chunks]: chunk totals of a | of dx |D| | of dx sign(D)
-  int* d_flag = nullptr;
+  mythos::DeviceBuf<mythos::W1Group> d_groups;
+  mythos::DeviceBuf<int> d_chunk_group;  // [n_chunks]
+  mythos::DeviceBuf<double> d_dx;        // [n_chunks * kW1Chunk]
+  mythos::DeviceBuf<long long> d_src;    // [n_chunks * kW1Chunk]
+  mythos::DeviceBuf<int> d_rank;         // [n_u_total]
+  mythos::DeviceBuf<double> d_g;         // [n_chunks * kW1Chunk] dx sign(D), then dW/da
+  mythos::DeviceBuf<double> d_part;      // [3][n_chunks]: chunk totals of a | of dx |D| | of dx sign(D)
+  mythos::DeviceBuf<int> d_flag;
+  ~mythos_w1_plan() { (void)hipSetDevice(device); }  // the members free themselves, on the plan's device
 };
 
 namespace mythos {
@@ -317,35 +319,23 @@ mythos_w1_plan_t* mythos_w1_plan_create(int n_groups, const int32_t* n_frames, c
     max_frames = std::max(max_frames, n_frames[g]);
     max_members = std::max(max_members, members[g]);
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) {
-    set_error("mythos_w1_plan_create: no usable HIP device (the HIP path has no CPU fallback)");
-    return nullptr;
-  }
-  auto* p = new mythos_w1_plan();
+  if (select_device(device, "mythos_w1_plan_create")) return nullptr;
+  auto p = std::make_unique<mythos_w1_plan>();
   p->n_groups = n_groups, p->max_frames = max_frames, p->max_members = max_members, p->device = device, p->n_chunks = (int)chunks;
   p->n_u_total = u_off;
   const size_t padded = (size_t)chunks * kW1Chunk;
   hipStream_t st = (hipStream_t)stream;
-  bool ok = hipMalloc((void**)&p->d_groups, groups.size() * sizeof(W1Group)) == hipSuccess &&
-            hipMalloc((void**)&p->d_chunk_group, chunk_group.size() * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&p->d_dx, padded * sizeof(double)) == hipSuccess &&
-            hipMalloc((void**)&p->d_src, padded * sizeof(long long)) == hipSuccess &&
-            hipMalloc((void**)&p->d_rank, (size_t)p->n_u_total * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&p->d_g, padded * sizeof(double)) == hipSuccess &&
-            hipMalloc((void**)&p->d_part, (size_t)3 * chunks * sizeof(double)) == hipSuccess &&
-            hipMalloc((void**)&p->d_flag, sizeof(int)) == hipSuccess;
-  ok = ok && hipMemcpy(p->d_groups, groups.data(), groups.size() * sizeof(W1Group), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(p->d_chunk_group, chunk_group.data(), chunk_group.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-       // a merge order that is no permutation leaves ranks unwritten: they then point at entry 0, not anywhere
-       hipMemsetAsync(p->d_rank, 0, (size_t)p->n_u_total * sizeof(int), st) == hipSuccess &&
-       hipMemsetAsync(p->d_flag, 0, sizeof(int), st) == hipSuccess;
+  bool ok = !(p->d_groups.upload(groups) || p->d_chunk_group.upload(chunk_group) || p->d_dx.alloc(padded) || p->d_src.alloc(padded) ||
+              p->d_rank.alloc((size_t)p->n_u_total) || p->d_g.alloc(padded) || p->d_part.alloc((size_t)3 * chunks) || p->d_flag.alloc(1));
+  // a merge order that is no permutation leaves ranks unwritten: they then point at entry 0, not anywhere
+  ok = ok && hipMemsetAsync(p->d_rank.get(), 0, (size_t)p->n_u_total * sizeof(int), st) == hipSuccess &&
+       hipMemsetAsync(p->d_flag.get(), 0, sizeof(int), st) == hipSuccess;
   int flag = 0;
   if (ok) {
-    hipLaunchKernelGGL(w1_plan_kernel, dim3((unsigned)(chunks * kW1Per)), dim3(kW1Block), 0, st, p->d_groups, p->d_chunk_group,
-                       samples, ref, ref_weights, (const long long*)order, p->d_dx, p->d_src, p->d_rank, p->d_flag);
+    hipLaunchKernelGGL(w1_plan_kernel, dim3((unsigned)(chunks * kW1Per)), dim3(kW1Block), 0, st, p->d_groups.get(), p->d_chunk_group.get(),
+                       samples, ref, ref_weights, (const long long*)order, p->d_dx.get(), p->d_src.get(), p->d_rank.get(), p->d_flag.get());
     ok = hipGetLastError() == hipSuccess &&
-         hipMemcpyAsync(&flag, p->d_flag, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipMemcpyAsync(&flag, p->d_flag.get(), sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
          hipStreamSynchronize(st) == hipSuccess;
   }
   if (!ok || flag != 0) {
@@ -353,20 +343,12 @@ mythos_w1_plan_t* mythos_w1_plan_create(int n_groups, const int32_t* n_frames, c
                   : (flag == 1 ? "mythos_w1_plan_create: the merge order holds an index outside its group"
                      : flag == 3 ? "mythos_w1_plan_create: a reference weight is negative or NaN"
                                  : "mythos_w1_plan_create: the merge order is not ascending (or a sample is NaN)"));
-    mythos_w1_plan_destroy(p);
     return nullptr;
   }
-  return p;
+  return p.release();
 }
 
-void mythos_w1_plan_destroy(mythos_w1_plan_t* p) {
-  if (!p) return;
-  (void)hipSetDevice(p->device);
-  void* ptrs[] = {p->d_groups, p->d_chunk_group, p->d_dx, p->d_src, p->d_rank, p->d_g, p->d_part, p->d_flag};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  delete p;
-}
+void mythos_w1_plan_destroy(mythos_w1_plan_t* p) { delete p; }
 
 int mythos_w1_eval(mythos_w1_plan_t* p, const double* weights, double* w1, double* dw1_dweights, mythos_stream_t stream) {
   if (!p || !w1) {
@@ -376,20 +358,20 @@ int mythos_w1_eval(mythos_w1_plan_t* p, const double* weights, double* w1, doubl
   MYTHOS_HIP_TRY(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
   const int nc = p->n_chunks;
-  double *a_tot = p->d_part, *w_tot = p->d_part + nc, *g_tot = p->d_part + 2 * (size_t)nc;
-  hipLaunchKernelGGL(w1_chunk_sum_kernel, dim3(nc), dim3(kW1Block), 0, st, p->d_groups, p->d_chunk_group, p->d_src, weights, a_tot);
-  hipLaunchKernelGGL(w1_scan_kernel, dim3(nc), dim3(kW1Block), 0, st, p->d_groups, p->d_chunk_group, p->d_dx, p->d_src, weights,
-                     a_tot, dw1_dweights ? p->d_g : nullptr, w_tot, g_tot);
+  double *a_tot = p->d_part.get(), *w_tot = p->d_part.get() + nc, *g_tot = p->d_part.get() + 2 * (size_t)nc;
+  hipLaunchKernelGGL(w1_chunk_sum_kernel, dim3(nc), dim3(kW1Block), 0, st, p->d_groups.get(), p->d_chunk_group.get(), p->d_src.get(), weights, a_tot);
+  hipLaunchKernelGGL(w1_scan_kernel, dim3(nc), dim3(kW1Block), 0, st, p->d_groups.get(), p->d_chunk_group.get(), p->d_dx.get(), p->d_src.get(), weights,
+                     a_tot, dw1_dweights ? p->d_g.get() : nullptr, w_tot, g_tot);
   if (dw1_dweights) {
-    hipLaunchKernelGGL(w1_suffix_kernel, dim3(nc), dim3(kW1Block), 0, st, p->d_groups, p->d_chunk_group, g_tot, p->d_g);
+    hipLaunchKernelGGL(w1_suffix_kernel, dim3(nc), dim3(kW1Block), 0, st, p->d_groups.get(), p->d_chunk_group.get(), g_tot, p->d_g.get());
     if (p->max_members >= 512)
       hipLaunchKernelGGL(w1_frame_sum_kernel<kW1Block / 64>, dim3((unsigned)p->max_frames, p->n_groups), dim3(kW1Block), 0, st,
-                         p->d_groups, p->d_rank, p->d_g, p->max_frames, dw1_dweights);
+                         p->d_groups.get(), p->d_rank.get(), p->d_g.get(), p->max_frames, dw1_dweights);
     else
       hipLaunchKernelGGL(w1_frame_sum_kernel<1>, dim3((unsigned)((p->max_frames + kW1Block / 64 - 1) / (kW1Block / 64)), p->n_groups),
-                         dim3(kW1Block), 0, st, p->d_groups, p->d_rank, p->d_g, p->max_frames, dw1_dweights);
+                         dim3(kW1Block), 0, st, p->d_groups.get(), p->d_rank.get(), p->d_g.get(), p->max_frames, dw1_dweights);
   }
-  hipLaunchKernelGGL(w1_total_kernel, dim3(p->n_groups), dim3(64), 0, st, p->d_groups, w_tot, w1);
+  hipLaunchKernelGGL(w1_total_kernel, dim3(p->n_groups), dim3(64), 0, st, p->d_groups.get(), w_tot, w1);
   MYTHOS_HIP_TRY(hipGetLastError());
   return MYTHOS_OK;
 }

@@ -31,23 +31,12 @@ TERM_NAMES = (
 )
 
 
-def _stream(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _dtype_code(dtype: torch.dtype) -> int:
-    if dtype == torch.float32:
-        return 0
-    if dtype == torch.float64:
-        return 1
-    raise ValueError(f"unsupported dtype {dtype}: use torch.float32 or torch.float64")
-
-
-class OxdnaSystem:
+class OxdnaSystem(_lib.Handle):
     """One oxDNA system on one GPU."""
 
+    _destroy = "mythos_oxdna_destroy"
+
     def __init__(self, model: int, seq, is_end, bonded, box=None, dtype=torch.float32, device=None, is_rna=None):
-        lib = _lib.load()
         if _lib.device_count() == 0 or not torch.cuda.is_available():
             raise _lib.MythosHipError("no HIP device visible: the mythos_amd HIP path has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -61,7 +50,8 @@ class OxdnaSystem:
         bonded = np.ascontiguousarray(bonded, dtype=np.int32).reshape(-1, 2)
         box_arr = None if box is None else np.ascontiguousarray(np.broadcast_to(np.asarray(box, np.float64), (3,)))
         self.box = box_arr
-        self._h = lib.mythos_oxdna_create(
+        super().__init__(
+            "mythos_oxdna_create",
             self.model,
             self.n,
             seq.ctypes.data_as(_lib.c_int_p),
@@ -69,34 +59,20 @@ class OxdnaSystem:
             int(bonded.shape[0]),
             bonded.ctypes.data_as(_lib.c_int_p),
             None if box_arr is None else box_arr.ctypes.data_as(_lib.c_double_p),
-            _dtype_code(dtype),
+            _lib.dtype_code(dtype),
             self.device.index or 0,
         )
-        if not self._h:
-            raise _lib.MythosHipError(f"mythos_oxdna_create: {_lib.last_error()}")
-        self._lib = lib
         self._pseq_n_bp = 0
         self._pseq_terms = 0
         # oxNA (model 4): three vectors - oxDNA2, oxRNA2, hybrid - one after the other; dU/dparams rows likewise
-        self.n_params = lib.mythos_oxdna_param_count() * (3 if self.model == 4 else 1)
+        self.n_params = self._lib.mythos_oxdna_param_count() * (3 if self.model == 4 else 1)
         if self.model == 4:
             if is_rna is None:
                 raise ValueError("an oxNA system (model 4) needs is_rna, the type of every nucleotide")
             t = np.ascontiguousarray(is_rna, dtype=np.uint8)
             if t.shape != (self.n,):
                 raise ValueError(f"is_rna must have shape ({self.n},)")
-            _lib.check(lib.mythos_oxdna_set_nucleotide_types(self._h, t.ctypes.data_as(_lib.c_uint8_p)), "set_nucleotide_types")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mythos_oxdna_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
+            _lib.check(self._lib.mythos_oxdna_set_nucleotide_types(self._h, t.ctypes.data_as(_lib.c_uint8_p)), "set_nucleotide_types")
 
     # ---- parameters / neighbours -------------------------------------------------------------
     def set_params(self, flat) -> None:
@@ -139,7 +115,7 @@ class OxdnaSystem:
     def build_neighbors(self, center: torch.Tensor, r_cut: float, skin: float) -> None:
         c = self._check(center, (self.n, 3), "center")
         _lib.check(
-            self._lib.mythos_oxdna_build_neighbors(self._h, _lib.ptr(c), float(r_cut), float(skin), _stream(self.device)),
+            self._lib.mythos_oxdna_build_neighbors(self._h, _lib.ptr(c), float(r_cut), float(skin), _lib.stream(self.device)),
             "build_neighbors",
         )
 
@@ -186,7 +162,7 @@ class OxdnaSystem:
             _lib.check(
                 self._lib.mythos_oxdna_energy_dpseq(
                     self._h, _lib.ptr(c), _lib.ptr(q), nf, _lib.ptr(e), _lib.ptr(gc), _lib.ptr(gq), _lib.ptr(gp), _lib.ptr(gm),
-                    _lib.ptr(gb), _stream(self.device),
+                    _lib.ptr(gb), _lib.stream(self.device),
                 ),
                 "energy_dpseq",
             )
@@ -197,7 +173,7 @@ class OxdnaSystem:
             _lib.check(
                 self._lib.mythos_oxdna_energy(
                     self._h, _lib.ptr(c), _lib.ptr(q), nf, _lib.ptr(e), _lib.ptr(gc), _lib.ptr(gq), _lib.ptr(gp),
-                    _stream(self.device),
+                    _lib.stream(self.device),
                 ),
                 "energy",
             )
@@ -207,7 +183,7 @@ class OxdnaSystem:
             _lib.check(
                 self._lib.mythos_oxdna_energy_obs(
                     self._h, _lib.ptr(c), _lib.ptr(q), nf, _lib.ptr(e), _lib.ptr(gc), _lib.ptr(gq), _lib.ptr(gp),
-                    observables._h, _lib.ptr(rows), _stream(self.device),
+                    observables._h, _lib.ptr(rows), _lib.stream(self.device),
                 ),
                 "energy_obs",
             )
@@ -229,25 +205,20 @@ def _touched(*tensors) -> None:
             torch.autograd.graph.increment_version(t)
 
 
-class _MdIntegrator:
+class _MdIntegrator(_lib.Handle):
     """What the two Langevin integrators share: a handle of the C ABI whose entry points are named ``<_prefix>_*``
-    (mythos_langevin_* / mythos_martini_langevin_*) - its destruction, the step counter and the figures of the last run."""
+    (mythos_langevin_* / mythos_martini_langevin_*) - its creation on a system, the step counter and the figures of the
+    last run.  The system is kept alive with it; closing the system first is allowed, using the integrator afterwards is not."""
 
     _prefix = ""
+    _destroy = property(lambda self: f"{self._prefix}_destroy")
+
+    def __init__(self, system, *args):
+        self.system = system
+        super().__init__(f"{self._prefix}_create", system._h, *args)
 
     def _fn(self, name):
         return getattr(self._lib, f"{self._prefix}_{name}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._fn("destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
 
     @property
     def step(self) -> int:
@@ -283,15 +254,9 @@ class LangevinIntegrator(_MdIntegrator):
     _prefix = "mythos_langevin"
 
     def __init__(self, system: OxdnaSystem, dt, kT, gamma_t, gamma_r, mass=1.0, inertia=(1.0, 1.0, 1.0), seed=0):
-        self.system = system
-        self._lib = system._lib
         inertia = np.ascontiguousarray(inertia, dtype=np.float64)
-        self._h = self._lib.mythos_langevin_create(
-            system._h, float(dt), float(kT), float(gamma_t), float(gamma_r), float(mass),
-            inertia.ctypes.data_as(_lib.c_double_p), C.c_uint64(int(seed) & (2**64 - 1)),
-        )
-        if not self._h:
-            raise _lib.MythosHipError(f"mythos_langevin_create: {_lib.last_error()}")
+        super().__init__(system, float(dt), float(kT), float(gamma_t), float(gamma_r), float(mass),
+                         inertia.ctypes.data_as(_lib.c_double_p), C.c_uint64(int(seed) & (2**64 - 1)))
         self.dt, self.kT = float(dt), float(kT)
 
     def set_neighbor_policy(self, r_cut: float, skin: float, every: int) -> None:
@@ -309,7 +274,7 @@ class LangevinIntegrator(_MdIntegrator):
         s = self.system
         p = torch.empty((s.n, 3), dtype=s.dtype, device=s.device)
         ang = torch.empty((s.n, 3), dtype=s.dtype, device=s.device)
-        _lib.check(self._lib.mythos_langevin_init_momenta(self._h, _lib.ptr(p), _lib.ptr(ang), _stream(s.device)), "init_momenta")
+        _lib.check(self._lib.mythos_langevin_init_momenta(self._h, _lib.ptr(p), _lib.ptr(ang), _lib.stream(s.device)), "init_momenta")
         return p, ang
 
     def run(self, center, quat, p_lin, p_ang, n_steps: int, save_every: int = 0, want_energy: bool = True):
@@ -324,7 +289,7 @@ class LangevinIntegrator(_MdIntegrator):
         et = torch.zeros((n_save, TRACE_WIDTH), dtype=torch.float64, device=s.device) if (n_save and want_energy) else None
         rc = self._lib.mythos_langevin_run(
             self._h, _lib.ptr(center), _lib.ptr(quat), _lib.ptr(p_lin), _lib.ptr(p_ang), int(n_steps),
-            int(save_every), _lib.ptr(tc), _lib.ptr(tq), _lib.ptr(et), _stream(s.device),
+            int(save_every), _lib.ptr(tc), _lib.ptr(tq), _lib.ptr(et), _lib.stream(s.device),
         )
         _touched(center, quat, p_lin, p_ang)  # (a run that fails still hands back the state of its last valid step)
         _lib.check(rc, "langevin_run")
@@ -340,7 +305,7 @@ class LangevinIntegrator(_MdIntegrator):
 
     def load(self, center, quat, p_lin, p_ang) -> None:
         """Copy a state into the integrator (mythos_langevin_load); ``advance`` then steps it in place."""
-        _lib.check(self._lib.mythos_langevin_load(self._h, *self._state_ptrs(center, quat, p_lin, p_ang), _stream(self.system.device)), "langevin_load")
+        _lib.check(self._lib.mythos_langevin_load(self._h, *self._state_ptrs(center, quat, p_lin, p_ang), _lib.stream(self.system.device)), "langevin_load")
 
     def advance(self, n_steps: int, save_every: int = 0, want_energy: bool = True, out=None):
         """``n_steps`` on the resident state; the neighbour list and its rebuild schedule carry over between calls.
@@ -358,7 +323,7 @@ class LangevinIntegrator(_MdIntegrator):
             tq = torch.empty((n_save, s.n, 4), dtype=s.dtype, device=s.device) if n_save else None
         et = torch.zeros((n_save, TRACE_WIDTH), dtype=torch.float64, device=s.device) if (n_save and want_energy) else None
         _lib.check(
-            self._lib.mythos_langevin_advance(self._h, int(n_steps), int(save_every), _lib.ptr(tc), _lib.ptr(tq), _lib.ptr(et), _stream(s.device)),
+            self._lib.mythos_langevin_advance(self._h, int(n_steps), int(save_every), _lib.ptr(tc), _lib.ptr(tq), _lib.ptr(et), _lib.stream(s.device)),
             "langevin_advance",
         )
         if out is not None and n_save:
@@ -367,7 +332,7 @@ class LangevinIntegrator(_MdIntegrator):
 
     def store(self, center, quat, p_lin, p_ang) -> None:
         """Copy the resident state out (mythos_langevin_store, asynchronous on the current stream)."""
-        rc = self._lib.mythos_langevin_store(self._h, *self._state_ptrs(center, quat, p_lin, p_ang), _stream(self.system.device))
+        rc = self._lib.mythos_langevin_store(self._h, *self._state_ptrs(center, quat, p_lin, p_ang), _lib.stream(self.system.device))
         _touched(center, quat, p_lin, p_ang)  # (the arrays are written even when closing an open frame failed)
         _lib.check(rc, "langevin_store")
 
@@ -380,14 +345,14 @@ class LangevinIntegrator(_MdIntegrator):
         _lib.check(self._lib.mythos_langevin_set_seed(self._h, C.c_uint64(int(seed) & (2**64 - 1))), "set_seed")
 
 
-class MartiniSystem:
+class MartiniSystem(_lib.Handle):
     """One MARTINI system on one GPU (mythos_martini_t): LJ type tables, bonds, angles."""
 
     N_TERMS = 3  # lj, bond, angle
+    _destroy = "mythos_martini_destroy"
 
     def __init__(self, types, sigma, eps, bonds, bond_k, bond_r0, angles, angle_k, angle_t0, angle_kind=0, r_cut=1.1,
                  dtype=torch.float32, device=None):
-        lib = _lib.load()
         if _lib.device_count() == 0 or not torch.cuda.is_available():
             raise _lib.MythosHipError("no HIP device visible: the mythos_amd HIP path has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -403,26 +368,12 @@ class MartiniSystem:
         f = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
         bond_k, bond_r0, angle_k, angle_t0 = f(bond_k), f(bond_r0), f(angle_k), f(angle_t0)
         dp = lambda a: a.ctypes.data_as(_lib.c_double_p)  # noqa: E731
-        self._h = lib.mythos_martini_create(
-            self.n, types.ctypes.data_as(_lib.c_int_p), n_types, dp(sigma), dp(eps), int(bonds.shape[0]),
+        super().__init__(
+            "mythos_martini_create", self.n, types.ctypes.data_as(_lib.c_int_p), n_types, dp(sigma), dp(eps), int(bonds.shape[0]),
             bonds.ctypes.data_as(_lib.c_int_p), dp(bond_k), dp(bond_r0), int(angles.shape[0]),
             angles.ctypes.data_as(_lib.c_int_p), dp(angle_k), dp(angle_t0), int(angle_kind), float(r_cut),
-            _dtype_code(dtype), self.device.index or 0,
+            _lib.dtype_code(dtype), self.device.index or 0,
         )
-        if not self._h:
-            raise _lib.MythosHipError(f"mythos_martini_create: {_lib.last_error()}")
-        self._lib = lib
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mythos_martini_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     def energy(self, pos: torch.Tensor, box: torch.Tensor, grads: bool = False):
         """pos (F, N, 3) or (N, 3); box (F, 3) or (3,) -> (e_terms (F, 3) float64, dU/dpos or None)."""
@@ -440,7 +391,7 @@ class MartiniSystem:
         e = torch.empty((nf, 3), dtype=torch.float64, device=self.device)
         g = torch.empty_like(pos) if grads else None
         _lib.check(
-            self._lib.mythos_martini_energy(self._h, _lib.ptr(pos), _lib.ptr(box), nf, _lib.ptr(e), _lib.ptr(g), _stream(self.device)),
+            self._lib.mythos_martini_energy(self._h, _lib.ptr(pos), _lib.ptr(box), nf, _lib.ptr(e), _lib.ptr(g), _lib.stream(self.device)),
             "martini_energy",
         )
         return (e[0], g[0] if grads else None) if single else (e, g)
@@ -469,7 +420,7 @@ class MartiniSystem:
             self._lib.mythos_martini_param_grads(
                 self._h, _lib.ptr(pos), _lib.ptr(box), nf, _lib.ptr(out["sigma"]), _lib.ptr(out["eps"]),
                 _lib.ptr(out["bond_k"]), _lib.ptr(out["bond_r0"]), _lib.ptr(out["angle_k"]), _lib.ptr(out["angle_t0"]),
-                _stream(self.device)),
+                _lib.stream(self.device)),
             "martini_param_grads",
         )
         return out
@@ -483,17 +434,13 @@ class MartiniLangevinIntegrator(_MdIntegrator):
     _prefix = "mythos_martini_langevin"
 
     def __init__(self, system: MartiniSystem, dt, kT, gamma, mass=None, seed=0):
-        self.system = system
-        self._lib = system._lib
         mptr = None
         if mass is not None:
             mass = np.ascontiguousarray(mass, dtype=np.float64)
             if mass.shape != (system.n,):
                 raise ValueError(f"mass must have shape ({system.n},)")
             mptr = mass.ctypes.data_as(_lib.c_double_p)
-        self._h = self._lib.mythos_martini_langevin_create(system._h, float(dt), float(kT), float(gamma), mptr, int(seed))
-        if not self._h:
-            raise _lib.MythosHipError(f"mythos_martini_langevin_create: {_lib.last_error()}")
+        super().__init__(system, float(dt), float(kT), float(gamma), mptr, int(seed))
 
     def set_neighbor_policy(self, skin: float, every: int) -> None:
         _lib.check(self._lib.mythos_martini_langevin_set_neighbor_policy(self._h, float(skin), int(every)), "set_neighbor_policy")
@@ -505,7 +452,7 @@ class MartiniLangevinIntegrator(_MdIntegrator):
 
     def init_velocities(self) -> torch.Tensor:
         v = torch.empty((self.system.n, 3), dtype=self.system.dtype, device=self.system.device)
-        _lib.check(self._lib.mythos_martini_langevin_init_velocities(self._h, _lib.ptr(v), _stream(self.system.device)), "init_velocities")
+        _lib.check(self._lib.mythos_martini_langevin_init_velocities(self._h, _lib.ptr(v), _lib.stream(self.system.device)), "init_velocities")
         return v
 
     def _check_state(self, pos, vel):
@@ -530,7 +477,7 @@ class MartiniLangevinIntegrator(_MdIntegrator):
         traj, et = self._rows(n_steps, save_every, want_energy)
         rc = self._lib.mythos_martini_langevin_run(
             self._h, _lib.ptr(pos), _lib.ptr(vel), box.ctypes.data_as(_lib.c_double_p), int(n_steps), int(save_every),
-            _lib.ptr(traj), _lib.ptr(et), _stream(s.device))
+            _lib.ptr(traj), _lib.ptr(et), _lib.stream(s.device))
         _touched(pos, vel)
         _lib.check(rc, "martini_langevin_run")
         return traj, et
@@ -540,18 +487,18 @@ class MartiniLangevinIntegrator(_MdIntegrator):
         self._check_state(pos, vel)
         box = np.ascontiguousarray(np.asarray(box, dtype=np.float64).reshape(3))
         _lib.check(self._lib.mythos_martini_langevin_load(self._h, _lib.ptr(pos), _lib.ptr(vel), box.ctypes.data_as(_lib.c_double_p),
-                                                          _stream(self.system.device)), "martini_langevin_load")
+                                                          _lib.stream(self.system.device)), "martini_langevin_load")
 
     def advance(self, n_steps: int, save_every: int = 0, want_energy: bool = True):
         """``n_steps`` on the resident state: n launches, the frame stays open; the list and its schedule carry over."""
         traj, et = self._rows(n_steps, save_every, want_energy)
         _lib.check(self._lib.mythos_martini_langevin_advance(self._h, int(n_steps), int(save_every), _lib.ptr(traj), _lib.ptr(et),
-                                                             _stream(self.system.device)), "martini_langevin_advance")
+                                                             _lib.stream(self.system.device)), "martini_langevin_advance")
         return traj, et
 
     def store(self, pos, vel) -> None:
         self._check_state(pos, vel)
-        rc = self._lib.mythos_martini_langevin_store(self._h, _lib.ptr(pos), _lib.ptr(vel), _stream(self.system.device))
+        rc = self._lib.mythos_martini_langevin_store(self._h, _lib.ptr(pos), _lib.ptr(vel), _lib.stream(self.system.device))
         _touched(pos, vel)
         _lib.check(rc, "martini_langevin_store")
 

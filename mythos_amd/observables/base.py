@@ -9,8 +9,6 @@ dU/dtheta of the frames (``mythos_oxdna_energy_obs``), so a DiffTRe iteration re
 
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -40,11 +38,12 @@ def _geometry3(geometry: dict, model: int) -> np.ndarray:
     return np.array([float(geometry["com_to_hb"]), float(geometry["com_to_backbone"]), 0.0])
 
 
-class ObservableSet:
+class ObservableSet(_lib.Handle):
     """mythos_obs_t: the index lists of up to one propeller-twist list and one quartet list on the device."""
 
+    _destroy = "mythos_observables_destroy"
+
     def __init__(self, n: int, model: int, geometry: dict | None, box, base_pairs, quartets, skip_ends: bool, dtype, device):
-        lib = _lib.load()
         self.n, self.model, self.dtype, self.device = int(n), int(model), dtype, torch.device(device)
         bps = np.ascontiguousarray(np.asarray(base_pairs if base_pairs is not None else np.zeros((0, 2)), dtype=np.int32).reshape(-1, 2))
         qs = np.ascontiguousarray(np.asarray(quartets if quartets is not None else np.zeros((0, 2, 2)), dtype=np.int32).reshape(-1, 2, 2))
@@ -52,34 +51,19 @@ class ObservableSet:
             raise ValueError("rise, pitch and persistence length need the [geometry] section (site offsets)")
         g3 = _geometry3(geometry, model) if geometry is not None else np.zeros(3)
         box_arr = None if box is None else np.ascontiguousarray(np.broadcast_to(np.asarray(box, np.float64), (3,)))
-        self._h = lib.mythos_observables_create(
-            self.model, self.n, g3.ctypes.data_as(_lib.c_double_p), None if box_arr is None else box_arr.ctypes.data_as(_lib.c_double_p),
+        super().__init__(
+            "mythos_observables_create", self.model, self.n, g3.ctypes.data_as(_lib.c_double_p), None if box_arr is None else box_arr.ctypes.data_as(_lib.c_double_p),
             int(bps.shape[0]), bps.ctypes.data_as(_lib.c_int_p), int(qs.shape[0]), qs.ctypes.data_as(_lib.c_int_p), int(bool(skip_ends)),
-            0 if dtype == torch.float32 else 1, self.device.index or 0)
-        if not self._h:
-            raise _lib.MythosHipError(f"mythos_observables_create: {_lib.last_error()}")
-        self._lib = lib
-        self.width = int(lib.mythos_observables_width(self._h))
+            _lib.dtype_code(dtype), self.device.index or 0)
+        self.width = int(self._lib.mythos_observables_width(self._h))
         self.n_corr = self.width - COL_CORR
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mythos_observables_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
 
     def eval(self, center: torch.Tensor, quat: torch.Tensor) -> torch.Tensor:
         """(S, width) float64 rows for (S, n, 3) / (S, n, 4) frames - the stand-alone launch."""
         c, q = center.contiguous(), quat.contiguous()
         out = torch.empty((c.shape[0], self.width), dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._lib.mythos_observables_eval(self._h, _lib.ptr(c), _lib.ptr(q), int(c.shape[0]), _lib.ptr(out), stream),
-                   "observables_eval")
+        _lib.check(self._lib.mythos_observables_eval(self._h, _lib.ptr(c), _lib.ptr(q), int(c.shape[0]), _lib.ptr(out),
+                                                     _lib.stream(self.device)), "observables_eval")
         return out
 
 

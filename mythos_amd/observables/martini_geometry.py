@@ -23,41 +23,27 @@ def matching(all_names, name: str, kind: str) -> list[int]:
     return idx
 
 
-class GeometrySet:
+class GeometrySet(_lib.Handle):
     """mythos_martini_obs_t: the index lists of some groups on one device."""
 
+    _destroy = "mythos_martini_obs_destroy"
+
     def __init__(self, n: int, widths, index_lists, device):
-        lib = _lib.load()
         self.device = torch.device(device)
         self.members = [int(len(ix)) for ix in index_lists]
         w = np.ascontiguousarray(widths, dtype=np.int32)
         m = np.ascontiguousarray(self.members, dtype=np.int32)
         flat = np.ascontiguousarray(np.concatenate([np.asarray(ix, dtype=np.int32).reshape(-1) for ix in index_lists]), dtype=np.int32)
-        self._h = lib.mythos_martini_obs_create(int(n), len(self.members), w.ctypes.data_as(_lib.c_int_p), m.ctypes.data_as(_lib.c_int_p),
-                                                flat.ctypes.data_as(_lib.c_int_p), self.device.index or 0)
-        if not self._h:
-            raise _lib.MythosHipError(f"mythos_martini_obs_create: {_lib.last_error()}")
-        self._lib = lib
-        self.count = int(lib.mythos_martini_obs_count(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mythos_martini_obs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
+        super().__init__("mythos_martini_obs_create", int(n), len(self.members), w.ctypes.data_as(_lib.c_int_p),
+                         m.ctypes.data_as(_lib.c_int_p), flat.ctypes.data_as(_lib.c_int_p), self.device.index or 0)
+        self.count = int(self._lib.mythos_martini_obs_count(self._h))
 
     def eval(self, pos: torch.Tensor, box: torch.Tensor) -> torch.Tensor:
         """The packed (S * count,) float64 block of (S, n, 3) positions and (S, 3) boxes of one dtype."""
         s = int(pos.shape[0])
         out = torch.empty(s * self.count, dtype=torch.float64, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.mythos_martini_obs_eval(self._h, _lib.ptr(pos), _lib.ptr(box), 0 if pos.dtype == torch.float32 else 1,
-                                                     s, _lib.ptr(out), stream), "martini_obs_eval")
+        _lib.check(self._lib.mythos_martini_obs_eval(self._h, _lib.ptr(pos), _lib.ptr(box), _lib.dtype_code(pos.dtype), s, _lib.ptr(out),
+                                                     _lib.stream(self.device)), "martini_obs_eval")
         return out
 
 
@@ -114,11 +100,7 @@ class MappedGeometry:
         pos, box = _frames(trajectory)
         if pos.shape[1] != len(self.topology.atom_names):
             raise ValueError(f"trajectory has {pos.shape[1]} beads, the topology {len(self.topology.atom_names)}")
-        sets = self.__dict__.setdefault("_sets", {})
-        key = str(pos.device)
-        if key not in sets:
-            sets[key] = GeometrySet(int(pos.shape[1]), [self.width] * len(lists), lists, pos.device)
-        gs = sets[key]
+        gs = _lib.per_device(self, pos.device, lambda: GeometrySet(int(pos.shape[1]), [self.width] * len(lists), lists, pos.device))
         return gs.eval(pos, box), int(pos.shape[0]), gs.members
 
     def __call__(self, trajectory) -> dict:

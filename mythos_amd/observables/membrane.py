@@ -81,40 +81,26 @@ def select(topology: MartiniTopology, selection) -> np.ndarray:
     return mask
 
 
-class MembraneSet:
+class MembraneSet(_lib.Handle):
     """mythos_membrane_t: the index lists of one pair of selections on one device."""
 
+    _destroy = "mythos_membrane_destroy"
+
     def __init__(self, n, start, sel, thick, thick_lipid, device):
-        lib = _lib.load()
         self.device = torch.device(device)
         arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (start, sel, thick, thick_lipid)]
-        self._h = lib.mythos_membrane_create(int(n), len(arrs[0]) - 1, arrs[0].ctypes.data_as(_lib.c_int_p), arrs[1].ctypes.data_as(_lib.c_int_p),
-                                             len(arrs[2]), arrs[2].ctypes.data_as(_lib.c_int_p), arrs[3].ctypes.data_as(_lib.c_int_p),
-                                             self.device.index or 0)
-        if not self._h:
-            raise _lib.MythosHipError(f"mythos_membrane_create: {_lib.last_error()}")
-        self._lib = lib
-        self.n_lipids = int(lib.mythos_membrane_n_lipids(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mythos_membrane_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
+        super().__init__("mythos_membrane_create", int(n), len(arrs[0]) - 1, arrs[0].ctypes.data_as(_lib.c_int_p),
+                         arrs[1].ctypes.data_as(_lib.c_int_p), len(arrs[2]), arrs[2].ctypes.data_as(_lib.c_int_p),
+                         arrs[3].ctypes.data_as(_lib.c_int_p), self.device.index or 0)
+        self.n_lipids = int(self._lib.mythos_membrane_n_lipids(self._h))
 
     def eval(self, pos: torch.Tensor, box: torch.Tensor, want_leaflets: bool = False):
         """-> ((S, MEMBRANE_ROW) float64 rows, (S, n_lipids) int8 leaflets or None)."""
         s = int(pos.shape[0])
         out = torch.empty((s, _lib.MEMBRANE_ROW), dtype=torch.float64, device=self.device)
         leaf = torch.empty((s, self.n_lipids), dtype=torch.int8, device=self.device) if want_leaflets else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.mythos_membrane_eval(self._h, _lib.ptr(pos), _lib.ptr(box), 0 if pos.dtype == torch.float32 else 1,
-                                                  s, _lib.ptr(out), _lib.ptr(leaf), stream), "membrane_eval")
+        _lib.check(self._lib.mythos_membrane_eval(self._h, _lib.ptr(pos), _lib.ptr(box), _lib.dtype_code(pos.dtype), s, _lib.ptr(out),
+                                                  _lib.ptr(leaf), _lib.stream(self.device)), "membrane_eval")
         return out, leaf
 
 
@@ -159,11 +145,7 @@ class _Membrane:
         pos, box = _frames(trajectory)
         if pos.shape[1] != len(self.topology.atom_names):
             raise ValueError(f"trajectory has {pos.shape[1]} beads, the topology {len(self.topology.atom_names)}")
-        sets = self.__dict__.setdefault("_sets", {})
-        key = str(pos.device)
-        if key not in sets:
-            sets[key] = MembraneSet(int(pos.shape[1]), *lists[1:], pos.device)
-        return sets[key].eval(pos, box, want_leaflets)
+        return _lib.per_device(self, pos.device, lambda: MembraneSet(int(pos.shape[1]), *lists[1:], pos.device)).eval(pos, box, want_leaflets)
 
     def rows(self, trajectory) -> torch.Tensor:
         """The launch's (S, 7) float64 rows in nm: thickness, area per lipid, midpoint z, lipids in leaflet +1 and -1,

@@ -63,14 +63,15 @@ def _check_mass(sum_u: float, sum_v: float) -> None:
         raise ValueError(f"u_weights and v_weights must sum to the same total mass; got {sum_u} and {sum_v}.")
 
 
-class W1Plan:
+class W1Plan(_lib.Handle):
     """mythos_w1_plan_t plus the sample block it was built from.  ``values``: per group a float64 device tensor
     whose first axis is the frame axis; ``refs`` / ``ref_weights``: per group a flat float64 device tensor (weights
     may be None)."""
 
+    _destroy = "mythos_w1_plan_destroy"
+
     def __init__(self, block: torch.Tensor, frames: list, members: list, refs: list, ref_weights: list):
         global _PLANS_BUILT
-        lib = _lib.load()
         self.device = block.device
         self.block, self.frames, self.members = block, list(frames), list(members)
         self.n_groups, self.max_frames = len(frames), max(frames)
@@ -88,27 +89,16 @@ class W1Plan:
         fr = np.ascontiguousarray(frames, dtype=np.int32)
         mem = np.ascontiguousarray(members, dtype=np.int32)
         nref = np.ascontiguousarray([int(v.numel()) for v in refs], dtype=np.int64)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._h = lib.mythos_w1_plan_create(
-            self.n_groups, fr.ctypes.data_as(_lib.c_int_p), mem.ctypes.data_as(_lib.c_int_p), _lib.ptr(block),
+        super().__init__(
+            "mythos_w1_plan_create", self.n_groups, fr.ctypes.data_as(_lib.c_int_p), mem.ctypes.data_as(_lib.c_int_p), _lib.ptr(block),
             nref.ctypes.data_as(C.POINTER(C.c_int64)), _lib.ptr(ref), _lib.ptr(vw),
-            has.ctypes.data_as(_lib.c_uint8_p) if vw is not None else None, _lib.ptr(order), self.device.index or 0, stream)
-        if not self._h:
-            raise _lib.MythosHipError(f"mythos_w1_plan_create: {_lib.last_error()}")
-        self._lib = lib
+            has.ctypes.data_as(_lib.c_uint8_p) if vw is not None else None, _lib.ptr(order), self.device.index or 0,
+            _lib.stream(self.device))
         _PLANS_BUILT += 1
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mythos_w1_plan_destroy(self._h)
-            self._h = None
+        super().close()
         self.block = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
 
     def same_block(self, block, frames, members) -> torch.Tensor | None:
         """Device bool: ``block`` equals, bit for bit, the block this plan was built from (None: another layout)."""
@@ -120,8 +110,7 @@ class W1Plan:
         """(w1 (G,), dw1/dweights (G, max frames) or None) for float64 device weights (S,) or None."""
         w1 = torch.empty(self.n_groups, dtype=torch.float64, device=self.device)
         dw = torch.zeros((self.n_groups, self.max_frames), dtype=torch.float64, device=self.device) if want_grad else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.mythos_w1_eval(self._h, _lib.ptr(weights), _lib.ptr(w1), _lib.ptr(dw), stream), "w1_eval")
+        _lib.check(self._lib.mythos_w1_eval(self._h, _lib.ptr(weights), _lib.ptr(w1), _lib.ptr(dw), _lib.stream(self.device)), "w1_eval")
         return w1, dw
 
 

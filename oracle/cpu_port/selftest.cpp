@@ -8,10 +8,26 @@
 // n_steps}, then types int32[n], bonds int32[n_bonds][2], angles int32[n_angles][3], box double[3], sigma and eps
 // double[n_types][n_types], bond k and r0 double[n_bonds], angle k and theta0 double[n_angles], mass, x and v double[n](,[3]);
 // evaluated and stepped once with G96 and once with harmonic angles.
+// `--device-buf` instead of a file: the owning buffer type of the library (mythos_amd/csrc/device_buf.h) over the shim's
+// malloc-backed runtime; prints what was read back and, after every scope, the live allocations (the test wants 0).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
+#include <utility>
 #include <vector>
+
+#include "device_buf.h"
+
+namespace mythos {
+static std::string g_error;
+void set_error(const std::string& msg) { g_error = msg; }
+int hip_fail(hipError_t e, const char* what) {
+  g_error = std::string("HIP error: ") + hipGetErrorString(e) + " in " + what;
+  return MYTHOS_ERR_HIP;
+}
+}  // namespace mythos
 
 extern "C" {
 void* mythos_cpu_create(int model, int n, const int32_t* seq, const uint8_t* is_end, int n_bonded, const int32_t* bonded,
@@ -73,8 +89,99 @@ static int martini_case(FILE* f, int n, int nb, int na, int nt, int n_steps) {
   return 0;
 }
 
+static void live(const char* scope) { printf("DEVBUF %s live %ld\n", scope, shim_live_allocations()); }
+
+struct FourBuffers {
+  mythos::DeviceBuf<int> a, b;
+  mythos::DeviceBytes c;
+  mythos::DeviceBuf<double> d;
+  int create() {  // as a *_create of the library: the first failure ends it, the destructor cleans up
+    if (int rc = a.alloc(8)) return rc;
+    if (int rc = b.alloc(8)) return rc;
+    if (int rc = c.alloc(64)) return rc;
+    return d.alloc(8);
+  }
+};
+
+static int device_buf_case() {
+  using mythos::DeviceBuf;
+  using mythos::DeviceBytes;
+  {
+    DeviceBuf<int> b;
+    const std::vector<int> v = {3, 1, 4, 1, 5, 9, 2, 6};
+    int back[8] = {};
+    if (b.alloc(5) || b.capacity() != 5 || b.upload(v) || b.capacity() != 8) return 10;
+    hipMemcpy(back, b.get(), sizeof(back), hipMemcpyDeviceToHost);
+    printf("DEVBUF upload %d %d %d cap %zu\n", back[0], back[4], back[7], b.capacity());
+    if (b.upload(v.data(), 3) || b.capacity() != 3) return 11;
+    hipMemcpy(back, b.get(), 3 * sizeof(int), hipMemcpyDeviceToHost);
+    printf("DEVBUF upload3 %d %d cap %zu\n", back[0], back[2], b.capacity());
+  }
+  live("upload");
+  {
+    DeviceBuf<double> g;
+    if (g.grow(0) || g.get() != nullptr) return 20;  // nothing needed, nothing allocated
+    if (g.grow(16)) return 21;
+    const double* p0 = g.get();
+    if (g.grow(16) || g.grow(7) || g.get() != p0 || g.capacity() != 16) return 22;  // at or below capacity: untouched
+    if (g.grow(17) || g.capacity() != 17) return 23;
+    hipMemset(g.get(), 0, 17 * sizeof(double));  // (the sanitizer build checks the extent)
+    printf("DEVBUF grow cap %zu held %ld\n", g.capacity(), shim_live_allocations());
+  }
+  live("grow");
+  {
+    DeviceBuf<int> a;
+    if (a.alloc(4)) return 30;
+    int* pa = a.get();
+    DeviceBuf<int> b(std::move(a));
+    if (a.get() != nullptr || a.capacity() != 0 || b.get() != pa || b.capacity() != 4) return 31;
+    DeviceBuf<int> c;
+    if (c.alloc(2)) return 32;
+    c = std::move(b);  // frees c's own allocation
+    if (b.get() != nullptr || c.get() != pa || c.capacity() != 4) return 33;
+    printf("DEVBUF moved held %ld\n", shim_live_allocations());
+    c.reset();
+    if (c.get() != nullptr || c.capacity() != 0 || c) return 34;
+    c.reset();  // twice: nothing to do
+    printf("DEVBUF reset held %ld\n", shim_live_allocations());
+  }
+  live("move");
+  {
+    DeviceBuf<int> z;
+    DeviceBytes r;
+    if (z.alloc(0) || !z.get() || z.capacity() != 1) return 40;  // never a zero-byte allocation
+    if (z.upload(nullptr, 0) || !z.get() || z.capacity() != 1) return 41;
+    if (r.upload_real(MYTHOS_F32, nullptr, 0) || !r.get() || r.capacity() != 1) return 42;
+    const double src[3] = {0.1, 2.0, -1.0 / 3.0};
+    float f[3];
+    double d[3];
+    if (r.upload_real(MYTHOS_F32, src, 3) || r.capacity() != 3 * sizeof(float)) return 43;
+    hipMemcpy(f, r.get(), sizeof(f), hipMemcpyDeviceToHost);
+    if (r.upload_real(MYTHOS_F64, src, 3) || r.capacity() != 3 * sizeof(double)) return 44;
+    hipMemcpy(d, r.get(), sizeof(d), hipMemcpyDeviceToHost);
+    printf("DEVBUF real %.9e %.9e %.17e %.17e\n", (double)f[0], (double)f[2], d[0], d[2]);
+    if (f[0] != float(src[0]) || f[2] != float(src[2]) || memcmp(d, src, sizeof(d)) != 0) return 45;
+  }
+  live("zero");
+  {
+    FourBuffers h;
+    shim_fail_allocation_in() = 3;
+    const int rc = h.create();
+    printf("DEVBUF partial rc %d a %d b %d c %d d %d held %ld: %s\n", rc, h.a ? 1 : 0, h.b ? 1 : 0, h.c ? 1 : 0, h.d ? 1 : 0,
+           shim_live_allocations(), mythos::g_error.c_str());
+    if (rc != MYTHOS_ERR_HIP || h.c || h.d) return 50;
+  }
+  live("partial");
+  {
+    const int ok = mythos::select_device(0, "selftest"), bad = mythos::select_device(3, "selftest");
+    printf("DEVBUF select %d %d: %s\n", ok, bad, mythos::g_error.c_str());
+  }
+  return shim_live_allocations() == 0 ? 0 : 60;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
+  if (std::string(argv[1]) == "--device-buf") return device_buf_case();
   FILE* f = fopen(argv[1], "rb");
   if (!f) return 2;
   const auto hdr = rd<int32_t>(f, 6);

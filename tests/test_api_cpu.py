@@ -360,3 +360,58 @@ def test_units_as_the_reference_defines_them():
         units.get_kt_from_string("300")
     sim, _ = defaults.default_configs_for("dna2")
     assert sim["kT"] == pytest.approx(units.get_kt(296.15))
+
+
+def test_handle_base_owns_one_handle(monkeypatch):
+    """_lib.Handle on a stub in place of the library: NULL from create raises with last_error(), close() twice destroys
+    once, and __del__ is silent - after a failed __init__, without any __init__, and when destroy itself raises."""
+    calls = []
+
+    class Stub:
+        def __init__(self, handle, destroy_raises=False):
+            self.handle, self.destroy_raises = handle, destroy_raises
+
+        def stub_create(self, *args):
+            calls.append(("create", args))
+            return self.handle
+
+        def stub_destroy(self, h):
+            calls.append(("destroy", h))
+            if self.destroy_raises:
+                raise RuntimeError("destroy failed")
+
+        def mythos_last_error(self):
+            return b"stub says no"
+
+    class Thing(_lib.Handle):
+        _destroy = "stub_destroy"
+
+    def destroyed():
+        return [c[1] for c in calls if c[0] == "destroy"]
+
+    monkeypatch.setattr(_lib, "_lib", Stub(None))  # create returns NULL
+    with pytest.raises(_lib.MythosHipError, match="^stub_create: stub says no$"):
+        Thing("stub_create", 1, 2)
+    assert calls == [("create", (1, 2))]
+    failed = Thing.__new__(Thing)
+    with pytest.raises(_lib.MythosHipError):
+        failed.__init__("stub_create")
+    failed.__del__()
+    failed.close()
+    Thing.__new__(Thing).__del__()  # (__init__ never ran: there is not even a library to ask)
+    assert destroyed() == []
+
+    monkeypatch.setattr(_lib, "_lib", Stub(41))
+    t = Thing("stub_create", 7)
+    assert t._h == 41
+    t.close()
+    assert t._h is None
+    t.close()
+    t.__del__()
+    assert destroyed() == [41]
+
+    monkeypatch.setattr(_lib, "_lib", Stub(42, destroy_raises=True))
+    t = Thing("stub_create")
+    t.__del__()  # swallows the error; the handle is not offered a second time
+    t.__del__()
+    assert destroyed() == [41, 42]

@@ -206,7 +206,9 @@ def test_thread_count_does_not_change_results():
 def test_sanitizers_are_clean_and_agree_with_the_plain_build(tmp_path):
     """AddressSanitizer + UndefinedBehaviorSanitizer over energy, the cell-list build and 20 Langevin steps with
     rebuilds (oxDNA1 and oxDNA2; free and periodic; oxRNA2, oxNA), and over a small MARTINI system with bonds and both
-    angle kinds, eight steps: no report, and the same numbers as the optimised build."""
+    angle kinds, eight steps: no report, and the same numbers as the optimised build.  And over the library's owning
+    device-buffer type (mythos_amd/csrc/device_buf.h on a malloc-backed runtime): the same lines from both builds, no
+    allocation alive after any scope - a struct whose third allocation fails included - and a clean log."""
     plain, san = cpu_port.BUILD / "md_cpu_selftest", cpu_port.BUILD / "md_cpu_selftest_san"
     if not san.exists():
         subprocess.run(["make", "-C", str(cpu_port.BUILD.parent)], check=True, capture_output=True)
@@ -282,6 +284,21 @@ def test_sanitizers_are_clean_and_agree_with_the_plain_build(tmp_path):
     assert len(la) >= 8 and la[4].startswith("E ") and la[6].startswith("MD builds 3 ")  # the second angle kind
     assert la[0] != la[4]
     assert max(abs(float(t)) for t in la[5].split()[1:]) < 1e-8
+    # device_buf.h: alloc / upload / read back, grow below and above capacity, moves, reset, a count of 0, partial construction
+    env = {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}
+    a = subprocess.run([str(plain), "--device-buf"], capture_output=True, text=True, env=env, timeout=60)
+    b = subprocess.run([str(san), "--device-buf"], capture_output=True, text=True, env=env, timeout=60)
+    assert a.returncode == 0, (a.stdout, a.stderr)
+    assert b.returncode == 0, (b.stdout, b.stderr[-3000:])
+    assert a.stdout == b.stdout
+    assert b.stderr.strip() == "", b.stderr[-3000:]  # no AddressSanitizer / LeakSanitizer / UBSan report
+    lines = a.stdout.splitlines()
+    live = [ln for ln in lines if " live " in ln]
+    assert [ln.split()[1] for ln in live] == ["upload", "grow", "move", "zero", "partial"]
+    assert all(ln.split()[-1] == "0" for ln in live), live
+    assert "DEVBUF upload 3 5 6 cap 8" in lines and "DEVBUF grow cap 17 held 1" in lines
+    partial = next(ln for ln in lines if ln.startswith("DEVBUF partial rc"))
+    assert partial.startswith("DEVBUF partial rc -2 a 1 b 1 c 0 d 0 held 2: HIP error: out of memory")
 
 
 # ---- MARTINI (oracle/cpu_port/martini_cpu.cpp): bench.py's cpu_baseline of BASELINE configs[2] ------------------

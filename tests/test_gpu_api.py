@@ -306,3 +306,114 @@ def test_sequence_dependent_energy_function_from_the_references_file():
     assert e.shape == (25,) and np.abs(e - split.sum(1)).max() <= 3e-5, np.abs(e - split.sum(1)).max()
     plain = dna2.create_default_energy_fn(top, disp).with_params(half_charged_ends=False).map(body).cpu().numpy() / top.n_nucleotides
     assert np.abs(plain - split.sum(1)).max() > 1e-3  # (the average-sequence model is a different function)
+
+
+# ---- handle lifetime: an integrator may be destroyed after its system; close() is idempotent ------------------------
+DEV = "cuda:0"
+
+
+def _oxdna_pair():
+    """A 16-nt oxDNA2 duplex (fp32) with its integrator, and the two steps every pair takes."""
+    from mythos_amd import _lib
+    from mythos_amd.energy import flat_params as fp
+    from mythos_amd.hip_system import LangevinIntegrator, OxdnaSystem
+    from mythos_amd.input import defaults
+    from mythos_amd.utils import generators
+
+    top, c0, q0 = generators.ideal_duplex(8, model=2, seed=3)
+    sim, cfg = defaults.default_configs_for("dna2")
+    flat = fp.pack_flat(fp.derive_flat(2, cfg, kt=sim["kT"], half_charged_ends=False), _lib.param_names())
+    s = OxdnaSystem(2, top.seq, top.is_end, top.bonded_neighbors, dtype=torch.float32, device=DEV)
+    s.set_params(flat)
+    integ = LangevinIntegrator(s, dt=sim["dt"], kT=sim["kT"], gamma_t=sim["kT"] / 2.5, gamma_r=sim["kT"] / 7.5, seed=11)
+    integ.set_neighbor_policy(3.25, 0.3, 5)
+
+    def two_steps():
+        c, q = torch.tensor(c0, dtype=torch.float32, device=DEV), torch.tensor(q0, dtype=torch.float32, device=DEV)
+        p, ang = integ.init_momenta()
+        integ.run(c, q, p, ang, 2)
+        return [t.cpu().numpy() for t in (c, q, p, ang)]
+
+    return s, integ, two_steps
+
+
+def _martini_pair():
+    """Two bent four-bead chains (8 beads, two types, fp32) with their integrator, and the two steps every pair takes."""
+    from mythos_amd.hip_system import MartiniLangevinIntegrator, MartiniSystem
+
+    x0 = np.array([[0.5 + 0.45 * k, 1.0 + 0.15 * (k % 2), 1.0 + 1.5 * c] for c in range(2) for k in range(4)])
+    bonds = [(4 * c + k, 4 * c + k + 1) for c in range(2) for k in range(3)]
+    angles = [(4 * c + k, 4 * c + k + 1, 4 * c + k + 2) for c in range(2) for k in range(2)]
+    s = MartiniSystem([0, 1, 1, 0, 1, 0, 0, 1], np.array([[0.47, 0.43], [0.43, 0.47]]), np.array([[3.5, 2.7], [2.7, 4.5]]), bonds,
+                      np.full(6, 1250.0), np.full(6, 0.47), angles, np.full(4, 25.0), np.full(4, 2.4), dtype=torch.float32, device=DEV)
+    integ = MartiniLangevinIntegrator(s, dt=0.01, kT=2.27, gamma=1.0, seed=11)
+
+    def two_steps():
+        x = torch.tensor(x0, dtype=torch.float32, device=DEV)
+        v = integ.init_velocities()
+        integ.run(x, v, [4.0, 4.0, 4.0], 2)
+        return [t.cpu().numpy() for t in (x, v)]
+
+    return s, integ, two_steps
+
+
+@pytest.mark.parametrize("make", [_oxdna_pair, _martini_pair], ids=["oxdna-16nt", "martini-8beads"])
+def test_integrator_and_system_close_in_either_order(make):
+    """The system closed before its integrator, then a fresh pair the other way round; a third pair with the same seed
+    then reproduces the first pair's two steps bit for bit.  close() after close() does nothing."""
+    s, integ, two_steps = make()
+    first = two_steps()
+    s.close()
+    integ.close()
+    s.close()
+    integ.close()
+    assert s._h is None and integ._h is None
+    s, integ, two_steps = make()
+    two_steps()
+    integ.close()
+    s.close()
+    integ.close()
+    s.close()
+    s, integ, two_steps = make()
+    third = two_steps()
+    assert all(np.isfinite(a).all() for a in first) and not np.array_equal(first[0], first[0] * 0)
+    for a, b in zip(first, third):
+        assert a.tobytes() == b.tobytes()
+
+
+def test_close_is_idempotent_for_every_handle_class():
+    """Each class of mythos_amd that owns a handle of the C ABI: the second close() does not reach the library."""
+    from mythos_amd import _lib
+    from mythos_amd.observables.base import ObservableSet
+    from mythos_amd.observables.martini_geometry import GeometrySet
+    from mythos_amd.observables.membrane import MembraneSet
+    from mythos_amd.observables.wasserstein import W1Plan
+
+    class Counting:
+        def __init__(self, lib):
+            self.lib, self.destroyed = lib, []
+
+        def __getattr__(self, name):
+            fn = getattr(self.lib, name)
+            if not name.endswith("_destroy"):
+                return fn
+            return lambda h: (self.destroyed.append(name), fn(h))[1]
+
+    sx, ix, _ = _oxdna_pair()
+    sm, im, _ = _martini_pair()
+    samples = torch.tensor([0.3, 0.1, 0.2], dtype=torch.float64, device=DEV)
+    handles = [ix, sx, im, sm,
+               ObservableSet(16, 2, None, None, [[0, 15], [1, 14]], None, True, torch.float32, DEV),
+               GeometrySet(8, [2, 3], [np.array([[0, 1], [2, 3]]), np.array([[0, 1, 2]])], DEV),
+               MembraneSet(8, [0, 1, 2], [0, 4], [1, 5], [0, 1], DEV),
+               W1Plan(samples, [3], [1], [torch.tensor([0.15, 0.25], dtype=torch.float64, device=DEV)], [None])]
+    owners = {c for c in _lib.Handle.__subclasses__() if c.__module__.startswith("mythos_amd.") and not c.__name__.startswith("_")}
+    assert {type(h) for h in handles} >= owners and len(owners) == 6
+    for h in handles:
+        assert isinstance(h, _lib.Handle) and h._h
+        spy = h._lib = Counting(h._lib)
+        h.close()
+        assert h._h is None and len(spy.destroyed) == 1, type(h).__name__
+        h.close()
+        h.__del__()
+        assert len(spy.destroyed) == 1, type(h).__name__
