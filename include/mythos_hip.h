@@ -252,6 +252,26 @@ int mythos_langevin_set_step(mythos_sim_t* sim, int64_t step);
  * run(opt_params, init_state, n_steps, key) is (mythos/simulators/jax_md/jaxmd.py:60-68), without a new integrator */
 int mythos_langevin_set_seed(mythos_sim_t* sim, uint64_t seed);
 
+/* Constant external forces: oxDNA's external force of `type = string` with `rate = 0` (the reference ships the
+ * experiment as data/templates/force-ext/: a 220-nt duplex and eight force files, +-z on the two end pairs), a constant
+ * force on the centre of mass of each listed nucleotide, no torque.
+ *   index   host int32[count]     nucleotides, each in [0, n) and listed once (a caller with repeats sums them first)
+ *   force   host double[count][3] stored on the device in the system's precision
+ *   count = 0 clears the forces; a run without forces issues exactly the launches it issued before this entry existed.
+ * With forces set every step launch is preceded by one small launch that kicks the listed momenta by the multiple of
+ * dt F_ext the step launch itself applies of dt F (1/2 on the first launch of a closed frame and on a closing-only one,
+ * 1 otherwise): a kick by a constant force commutes with the kick by the interaction force, so the pair is BAOAB with
+ * the total force.  The kick follows the halt / abort / resume protocol of the step launches (it skips when they skip
+ * and is applied once however often a launch is repeated).
+ * MYTHOS_ERR_INVALID_ARGUMENT while the resident frame is open (after mythos_langevin_advance: the pending closing half
+ * kick would mix two forces) - valid before mythos_langevin_load and after mythos_langevin_store; also for an index out
+ * of range or listed twice.  mythos_langevin_run / _advance refuse to step with forces on the unfused oxNA path
+ * (MYTHOS_LANGEVIN_UNFUSED); the fused oxNA kernel is supported.
+ * The energy-trace rows stay what they are: the external potential -sum F.x is not part of them (it does not depend on
+ * the model parameters and cancels in DiffTRe weights), and the kinetic energies of a row are taken after the external
+ * kick of that launch, i.e. with the external part of the NEXT step's opening half kick already in the momenta. */
+int mythos_langevin_set_external_forces(mythos_sim_t* sim, int count, const int32_t* index, const double* force);
+
 /* Integrator options.  MYTHOS_LANGEVIN_UNFUSED (oxNA systems only, value 0 / 1): step through the two-launch path -
  * the energy kernel's forces launch + a one-thread-per-nucleotide integrator - instead of the fused step kernel.  A
  * second implementation of the same map (same Philox stream), kept as the cross-check of the fused oxNA instantiation;
@@ -482,6 +502,36 @@ int mythos_membrane_n_lipids(const mythos_membrane_t* mem);
  * Double sums in a fixed order, no atomics: a frame's row has the same bits whatever else is in the launch. */
 int mythos_membrane_eval(mythos_membrane_t* mem, const void* pos, const void* box, int dtype, int n_frames, double* out,
                          int8_t* leaflets, mythos_stream_t stream);
+
+/* ---- duplex-mechanics observables: backbone distance, extension, twist, RMSD -------------------
+ * What the reference's force-extension and stretch-torsion workflows measure per state, one launch over the stored
+ * frames, one workgroup per frame (csrc/duplex_obs.hip).  Replaces the per-state parts of
+ * mythos/observables/diameter.py:23-46, stretch_torsion.py:16-35 and 77-95, rmse.py:19-67.
+ *   geometry, box   as mythos_observables_create (site offsets of the model; periodic box of the displacement, or NULL)
+ *   base_pairs      host int32[n_bp][2]     hydrogen-bonded pairs of the backbone distance
+ *   quartets        host int32[n_q][2][2]   adjacent base pairs ((a1, b1), (a2, b2)) of the twist
+ *   end_pairs       host int32[4] a1, b1, a2, b2: the two base pairs of the extension, or NULL
+ *   target_center   host double[n][3] target of the RMSD, CENTRED by the caller (rmse.py:110-113), or NULL
+ * Output row per frame, MYTHOS_DUPLEX_ROW doubles, oxDNA length units and radians; a column that was not asked for
+ * (empty list, NULL) is 0:
+ *   [0] mean over base_pairs of the distance between the two backbone sites (diameter.py:37-41; sigma_backbone and the
+ *       Angstrom factor are the caller's: they may carry a gradient)
+ *   [1] |z| of disp(m2, m1), m = c_a + disp(c_b, c_a) / 2 of the two end pairs (stretch_torsion.py:84-95)
+ *   [2] sum over quartets of acos(clamp(b1 . b2)), b = disp(base_b, base_a) with z dropped, then normalised
+ *       (stretch_torsion.py:19-35); NaN if a pair's x-y projection vanishes, as the reference's division
+ *   [3] sqrt(mean_i |R (x_i - mean x) - t_i|^2) with R the proper rotation that minimises it (rmse.py:29-47: SVD with
+ *       the reflection fix; here Horn's quaternion by Jacobi sweeps, then a second pass over the residuals); raw
+ *       coordinates, no minimum image (rmse.py:61-65)
+ * center dev real[n_frames][n][3], quat dev real[n_frames][n][4] of precision dtype, read as they are; arithmetic in
+ * double, sums in a fixed order, no atomics: a frame's row has the same bits whatever else is in the launch. */
+#define MYTHOS_DUPLEX_ROW 4
+typedef struct mythos_duplex_obs mythos_duplex_obs_t;
+mythos_duplex_obs_t* mythos_duplex_obs_create(int model, int n, const double* geometry, const double* box, int n_bp,
+                                              const int32_t* base_pairs, int n_quartets, const int32_t* quartets,
+                                              const int32_t* end_pairs, const double* target_center, int device);
+void mythos_duplex_obs_destroy(mythos_duplex_obs_t* obs);
+int mythos_duplex_obs_eval(mythos_duplex_obs_t* obs, const void* center, const void* quat, int dtype, int n_frames, double* out,
+                           mythos_stream_t stream);
 
 #ifdef __cplusplus
 }

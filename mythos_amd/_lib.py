@@ -62,6 +62,7 @@ _SIGS = {
     "mythos_langevin_get_step": (C.c_int64, [V]),
     "mythos_langevin_set_step": (C.c_int, [V, C.c_int64]),
     "mythos_langevin_set_seed": (C.c_int, [V, C.c_uint64]),
+    "mythos_langevin_set_external_forces": (C.c_int, [V, C.c_int, c_int_p, c_double_p]),
     "mythos_langevin_last_kernel_ms": (C.c_int, [V, c_double_p, c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mythos_langevin_set_option": (C.c_int, [V, C.c_int, C.c_int64]),
     "mythos_langevin_set_timing": (C.c_int, [V, C.c_int]),
@@ -104,6 +105,9 @@ _SIGS = {
     "mythos_membrane_destroy": (None, [V]),
     "mythos_membrane_n_lipids": (C.c_int, [V]),
     "mythos_membrane_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V, V]),
+    "mythos_duplex_obs_create": (V, [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, c_double_p, C.c_int]),
+    "mythos_duplex_obs_destroy": (None, [V]),
+    "mythos_duplex_obs_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V]),
 }
 
 

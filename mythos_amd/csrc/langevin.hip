@@ -1,6 +1,7 @@
 // Langevin integrator, translation unit 1 of 2: the fp32 instantiations of langevin_core.inc and the C entry points
 // (mythos_langevin_*).  The fp64 instantiations are in langevin_f64.hip.
 #include <memory>
+#include <vector>
 
 #include "langevin_core.inc"
 
@@ -109,6 +110,11 @@ int md_load(mythos_sim_t* s, void* c, void* q, void* p, void* l, hipStream_t st)
 }
 
 int md_advance(mythos_sim_t* s, int n_steps, int save_every, bool close, void* tc, void* tq, double* e_trace, hipStream_t st) {
+  if (s->ext_count > 0 && s->unfused) {
+    set_error("mythos_langevin_run / advance: external forces are not applied on the unfused oxNA path "
+              "(MYTHOS_LANGEVIN_UNFUSED); clear them or step through the fused kernel");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
   // quaternion rows are written as one 4-vector per nucleotide
   const size_t q_align = s->sys->dtype == MYTHOS_F32 ? sizeof(float4) : sizeof(double4);
   if (save_every > 0 && tq && (reinterpret_cast<uintptr_t>(tq) % q_align) != 0) {
@@ -191,6 +197,56 @@ int mythos_langevin_set_step(mythos_sim_t* s, int64_t step) {
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   s->step = step;
+  s->ext_stamp_stale = true;  // (the stamp of the last external kick names a step index)
+  return MYTHOS_OK;
+}
+
+int mythos_langevin_set_external_forces(mythos_sim_t* s, int count, const int32_t* index, const double* force) {
+  const char* who = "mythos_langevin_set_external_forces";
+  if (!s || count < 0 || (count > 0 && (!index || !force))) {
+    set_error(std::string(who) + ": invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (s->resident && s->open) {
+    set_error(std::string(who) + ": the resident frame is open (its pending closing half kick would mix two forces); call "
+              "mythos_langevin_store first");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  const int n = s->sys->n;
+  std::vector<char> seen((size_t)n, 0);
+  for (int e = 0; e < count; ++e) {
+    if (index[e] < 0 || index[e] >= n) {
+      set_error(std::string(who) + ": nucleotide index " + std::to_string(index[e]) + " out of range [0, " + std::to_string(n) + ")");
+      return MYTHOS_ERR_INVALID_ARGUMENT;
+    }
+    if (seen[index[e]]) {
+      set_error(std::string(who) + ": nucleotide " + std::to_string(index[e]) + " is listed twice (sum its forces first)");
+      return MYTHOS_ERR_INVALID_ARGUMENT;
+    }
+    seen[index[e]] = 1;
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(force[3 * (size_t)e + k])) {
+        set_error(std::string(who) + ": a force component is not finite");
+        return MYTHOS_ERR_INVALID_ARGUMENT;
+      }
+  }
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
+  s->ext_stamp_stale = true;
+  if (count == 0) {
+    s->ext_count = 0;
+    return MYTHOS_OK;
+  }
+  // an earlier advance may still be reading the old list on its stream: wait before replacing it
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());
+  std::vector<double> f4((size_t)count * 4, 0.0);
+  for (int e = 0; e < count; ++e)
+    for (int k = 0; k < 3; ++k) f4[4 * (size_t)e + k] = force[3 * (size_t)e + k];
+  s->ext_count = 0;  // (nothing half replaced counts)
+  if (int rc = s->d_ext_index.upload(index, (size_t)count)) return rc;
+  if (int rc = s->d_ext_force.upload_real(s->sys->dtype, f4.data(), f4.size())) return rc;
+  if (!s->d_ext_stamp)
+    if (int rc = s->d_ext_stamp.alloc(1)) return rc;
+  s->ext_count = count;
   return MYTHOS_OK;
 }
 

@@ -1196,6 +1196,42 @@ __global__ void init_momenta_kernel(int n, R sd_t, R sd_r0, R sd_r1, R sd_r2, ui
   }
 }
 
+// Constant external forces (mythos_langevin_set_external_forces; oxDNA's `string` force with rate = 0): the kick
+// p_i += c dt F_ext,i on the frame step launch k is about to read, c = kick_close + do_step / 2 - the multiple of dt F
+// that launch applies itself.  A kick by a constant force commutes with the kick by the interaction force (both translate
+// momenta at fixed positions), so the launch that follows is BAOAB with the total force.  One workgroup, entries strided
+// (indices are distinct: the host checked), queued in front of the step launch and behind the scheduled list rebuild.
+// It honours the driver's protocol (md_driver.h):
+//   - it skips exactly when step launch k skips: the test of md_step_kernel on flags[1], flags[3] and the list
+//     builder's overflow words;
+//   - it is idempotent per launch.  The kick is in place, so the frames' invariant - a launch never modifies the state it
+//     read, which is what lets an aborted launch run again wider from intact inputs - holds only if a second application
+//     is a no-op: `stamp` holds 2 (step + k) + (kick_close != 0) + 1 of the last kick applied, every thread reads it in
+//     front of a barrier, and a workgroup that finds its own stamp there returns.  The closed / open bit tells a
+//     closing-only launch from the first launch of the next call, which carries the same step index;
+//   - it writes the momenta and the stamp, nothing else; never the control words.
+template <typename R>
+__global__ __launch_bounds__(256) void ext_kick_kernel(int count, const int* __restrict__ index,
+                                                       const typename Vec4T<R>::type* __restrict__ force, R c_dt,
+                                                       typename Vec4T<R>::type* __restrict__ mom, const int* __restrict__ flags,
+                                                       const int* __restrict__ list_overflow, int k_index,
+                                                       unsigned long long this_stamp, unsigned long long* __restrict__ stamp) {
+  const int hw = flags[1], aw = flags[3];
+  const int halt = ((hw != 0 && hw <= k_index) ? 1 : 0) | ((aw != 0 && aw <= k_index) ? 1 : 0) |
+                   (list_overflow ? (list_overflow[0] | list_overflow[1]) : 0);
+  const unsigned long long seen = *stamp;
+  __syncthreads();  // everybody has read the stamp before thread 0 replaces it
+  if (halt != 0 || seen == this_stamp) return;
+  for (int e = threadIdx.x; e < count; e += blockDim.x) {
+    const int i = index[e];
+    const auto f = force[e];
+    auto p = mom[i];
+    p.x += c_dt * f.x, p.y += c_dt * f.y, p.z += c_dt * f.z;
+    mom[i] = p;
+  }
+  if (threadIdx.x == 0) *stamp = this_stamp;
+}
+
 }  // namespace mythos
 
 using namespace mythos;
@@ -1226,6 +1262,12 @@ struct mythos_sim : mythos::MdRun {
   DeviceBytes u_c, u_q, u_p, u_l, u_gc, u_gq, u_ref;
   DeviceBuf<double> u_e;  // [8] term energies of the last force evaluation + [2] kinetic energies
   bool u_forces_valid = false;
+  // constant external forces (mythos_langevin_set_external_forces), in the system's precision
+  int ext_count = 0;
+  DeviceBuf<int> d_ext_index;                  // [ext_count] distinct nucleotides
+  DeviceBytes d_ext_force;                     // [ext_count] Vec4T<R>: (F, 0)
+  DeviceBuf<unsigned long long> d_ext_stamp;   // [1] the last kick applied (ext_kick_kernel)
+  bool ext_stamp_stale = true;                 // load / set_step / set_external_forces: cleared in front of the next kick
   ~mythos_sim() { (void)hipSetDevice(device); }  // the members, MdRun's too, free themselves on that device
 };
 
@@ -1325,6 +1367,7 @@ static int load_typed(mythos_sim* sim, const R* center, const R* quat, const R* 
   sim->since_build = 0;
   sim->items_big = false;
   sim->open = false;
+  sim->ext_stamp_stale = true;
   sim->param_epoch = sys->param_epoch;
   sim->lanes = md_lanes_for(sys);
   const int ppb = kMdBlock / sim->lanes;
@@ -1427,6 +1470,17 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
         go(std::false_type{}, L8{});
       }
     };
+    if (sim->ext_count > 0) {  // the external kick of this launch (ext_kick_kernel); outside the dispatch's event pair
+      if (sim->ext_stamp_stale) {
+        (void)hipMemsetAsync(sim->d_ext_stamp.get(), 0, sizeof(unsigned long long), st);
+        sim->ext_stamp_stale = false;
+      }
+      const double c = double(row.kick_close) + 0.5 * row.do_step;
+      const unsigned long long stamp = 2ull * (unsigned long long)(sim->step + k) + (row.kick_close != 0.0f ? 1ull : 0ull) + 1ull;
+      hipLaunchKernelGGL(ext_kick_kernel<R>, dim3(1), dim3(256), 0, st, sim->ext_count, (const int*)sim->d_ext_index.get(),
+                         (const V4*)sim->d_ext_force.get(), R(c * sim->dt), fr[cur].mom, (const int*)sim->d_flags.get(),
+                         (const int*)halt_words, k, stamp, sim->d_ext_stamp.get());
+    }
     using T = std::true_type;
     using F = std::false_type;
     using Small = std::integral_constant<int, kMdItems>;

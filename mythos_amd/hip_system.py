@@ -169,6 +169,9 @@ class OxdnaSystem(_lib.Handle):
             if single:
                 return e[0], (gc[0] if grads else None), (gq[0] if grads else None), gp[0], gm[0], gb[0]
             return e, gc, gq, gp, gm, gb
+        if observables is not None and not getattr(observables, "fusable", True):
+            raise ValueError(f"{type(observables).__name__} is not evaluated in the energy call (the fused energy + observables "
+                             "path takes an ObservableSet of propeller twist / rise / pitch / persistence length)")
         if observables is None:
             _lib.check(
                 self._lib.mythos_oxdna_energy(
@@ -258,6 +261,7 @@ class LangevinIntegrator(_MdIntegrator):
         super().__init__(system, float(dt), float(kT), float(gamma_t), float(gamma_r), float(mass),
                          inertia.ctypes.data_as(_lib.c_double_p), C.c_uint64(int(seed) & (2**64 - 1)))
         self.dt, self.kT = float(dt), float(kT)
+        self.external_forces = (np.zeros(0, np.int32), np.zeros((0, 3), np.float64))
 
     def set_neighbor_policy(self, r_cut: float, skin: float, every: int) -> None:
         _lib.check(
@@ -269,6 +273,22 @@ class LangevinIntegrator(_MdIntegrator):
         """oxNA systems: step through the two-launch path (forces launch + integrator launch) from the next load / run
         on - the second implementation the fused oxNA step kernel is checked against (mythos_langevin_set_option)."""
         _lib.check(self._lib.mythos_langevin_set_option(self._h, 0, 1 if on else 0), "set_option(unfused)")
+
+    def set_external_forces(self, index=None, force=None) -> None:
+        """Constant forces on the centres of mass of the listed nucleotides (oxDNA's ``string`` force with ``rate = 0``;
+        mythos_langevin_set_external_forces): ``index`` (m,), ``force`` (m, 3); a nucleotide listed more than once gets the
+        sum.  No arguments, or empty lists, clear them.  Refused between ``advance`` and ``store`` (an open frame).
+        ``external_forces`` keeps what was handed to the library."""
+        from mythos_amd.input.external_forces import sum_repeated
+
+        if index is None or len(index) == 0:
+            idx, f = np.zeros(0, np.int32), np.zeros((0, 3), np.float64)
+        else:
+            idx, f = sum_repeated(torch.as_tensor(index).detach().cpu().numpy(), torch.as_tensor(force).detach().cpu().numpy())
+        idx, f = np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(f, dtype=np.float64)
+        _lib.check(self._lib.mythos_langevin_set_external_forces(self._h, int(idx.shape[0]), idx.ctypes.data_as(_lib.c_int_p),
+                                                                 f.ctypes.data_as(_lib.c_double_p)), "set_external_forces")
+        self.external_forces = (idx, f)
 
     def init_momenta(self):
         s = self.system

@@ -42,6 +42,7 @@ class ObservableSet(_lib.Handle):
     """mythos_obs_t: the index lists of up to one propeller-twist list and one quartet list on the device."""
 
     _destroy = "mythos_observables_destroy"
+    fusable = True  # the handle mythos_oxdna_energy_obs takes
 
     def __init__(self, n: int, model: int, geometry: dict | None, box, base_pairs, quartets, skip_ends: bool, dtype, device):
         self.n, self.model, self.dtype, self.device = int(n), int(model), dtype, torch.device(device)
@@ -149,4 +150,70 @@ class HipObservable:
         key = (int(c.shape[1]), c.dtype, str(c.device))
         if key not in cache:
             cache[key] = self.make_set(int(c.shape[1]), c.dtype, c.device)
+        return cache[key].eval(c, q)
+
+
+# output row of mythos_duplex_obs_eval (MYTHOS_DUPLEX_ROW of include/mythos_hip.h)
+DUPLEX_ROW = 4
+COL_BACKBONE_DISTANCE, COL_EXTENSION, COL_TWIST, COL_RMSD = 0, 1, 2, 3
+
+
+class DuplexSet(ObservableSet):
+    """mythos_duplex_obs_t: the lists of the duplex-mechanics observables on one device (any of them may be absent: its
+    column is then 0).  An observable set like its base - index lists on the device, ``eval(center, quat)`` -> rows, owned and
+    given back the same way - over its own handle type, row layout and entry points."""
+
+    width = DUPLEX_ROW
+    fusable = False  # its rows do not come out of mythos_oxdna_energy_obs: OxdnaSystem.energy(observables=...) refuses it
+
+    _destroy = "mythos_duplex_obs_destroy"
+
+    def __init__(self, n: int, model: int, geometry: dict | None, box, base_pairs=None, quartets=None, end_pairs=None, target=None, device=None):
+        self.n, self.model, self.device = int(n), int(model), torch.device(device)
+        bps = np.ascontiguousarray(np.asarray(base_pairs if base_pairs is not None else np.zeros((0, 2)), dtype=np.int32).reshape(-1, 2))
+        qs = np.ascontiguousarray(np.asarray(quartets if quartets is not None else np.zeros((0, 2, 2)), dtype=np.int32).reshape(-1, 2, 2))
+        ends = None if end_pairs is None else np.ascontiguousarray(np.asarray(end_pairs, dtype=np.int32).reshape(4))
+        tgt = None if target is None else np.ascontiguousarray(np.asarray(target, dtype=np.float64).reshape(-1, 3))
+        if tgt is not None and tgt.shape[0] != self.n:
+            raise ValueError(f"the target has {tgt.shape[0]} nucleotides, the trajectory {self.n}")
+        if (bps.shape[0] > 0 or qs.shape[0] > 0) and geometry is None:
+            raise ValueError("backbone distance and twist need the [geometry] section (site offsets)")
+        g3 = _geometry3(geometry, model) if geometry is not None else np.zeros(3)
+        box_arr = None if box is None else np.ascontiguousarray(np.broadcast_to(np.asarray(box, np.float64), (3,)))
+        _lib.Handle.__init__(
+            self, "mythos_duplex_obs_create", self.model, self.n, g3.ctypes.data_as(_lib.c_double_p), None if box_arr is None else box_arr.ctypes.data_as(_lib.c_double_p),
+            int(bps.shape[0]), bps.ctypes.data_as(_lib.c_int_p), int(qs.shape[0]), qs.ctypes.data_as(_lib.c_int_p),
+            None if ends is None else ends.ctypes.data_as(_lib.c_int_p), None if tgt is None else tgt.ctypes.data_as(_lib.c_double_p),
+            self.device.index or 0)
+
+    def eval(self, center: torch.Tensor, quat: torch.Tensor) -> torch.Tensor:
+        """(S, 4) float64 rows for (S, n, 3) / (S, n, 4) frames."""
+        c, q = center.contiguous(), quat.contiguous()
+        if int(c.shape[1]) != self.n:
+            raise ValueError(f"the trajectory has {int(c.shape[1])} nucleotides, the observable set {self.n}")
+        out = torch.empty((c.shape[0], DUPLEX_ROW), dtype=torch.float64, device=self.device)
+        _lib.check(self._lib.mythos_duplex_obs_eval(self._h, _lib.ptr(c), _lib.ptr(q), _lib.dtype_code(c.dtype), int(c.shape[0]), _lib.ptr(out),
+                                                    _lib.stream(self.device)), "duplex_obs_eval")
+        return out
+
+
+class DuplexObservable:
+    """What Diameter, TwistXY, ExtensionZ and RMSE share: the description of their lists and one ``DuplexSet`` per
+    (object, number of nucleotides, device)."""
+
+    base_pairs = None
+    quartets = None
+    end_pairs = None
+    target = None
+    geometry: dict | None = None
+    model: int = 2
+    displacement_fn = None
+
+    def rows(self, trajectory) -> torch.Tensor:
+        c, q = _frames(trajectory)
+        cache = self.__dict__.setdefault("_sets", {})
+        key = (int(c.shape[1]), str(c.device))
+        if key not in cache:
+            box = getattr(self.displacement_fn, "box", None)
+            cache[key] = DuplexSet(int(c.shape[1]), self.model, self.geometry, box, self.base_pairs, self.quartets, self.end_pairs, self.target, c.device)
         return cache[key].eval(c, q)

@@ -193,6 +193,10 @@ class HipMDSimulator(Simulator):
     # system, not 64 steps.  Every nucleotide has its own Philox stream, so replicas are statistically independent.
     # The reference runs replicas as separate simulator instances (mythos/simulators/base.py MultiSimulator, Ray).
     n_replicas: int = 1
+    # Constant external forces (oxDNA's ``string`` force with ``rate = 0``): ``(index (m,), force (m, 3))`` or the path of an
+    # oxDNA external-force file (mythos_amd.input.external_forces).  With replicas the list is repeated per replica at
+    # ``index + r * n``.  None: no forces, and exactly the launches of a simulator that never had any.
+    external_forces: Any = None
     # device-side objects kept between calls: {key: (OxdnaSystem, LangevinIntegrator, pinned python objects)}
     _resident: dict = dc.field(default_factory=dict, init=False, repr=False, compare=False)
 
@@ -314,6 +318,20 @@ class HipMDSimulator(Simulator):
             integ.set_seed(int(key))
             integ.step = 0  # a run starts its noise stream at (key, step 0), as a new integrator would
             had_pseq = system._pseq_terms != 0
+        if self.external_forces is None:
+            if integ.external_forces[0].size:
+                integ.set_external_forces()
+        else:
+            ext = self.external_forces
+            if isinstance(ext, (str, bytes)) or hasattr(ext, "__fspath__"):
+                from mythos_amd.input.external_forces import read_external_forces
+
+                ext = read_external_forces(ext, n_one)
+            e_idx = np.asarray(ext[0], dtype=np.int64).reshape(-1)
+            e_f = np.asarray(ext[1], dtype=np.float64).reshape(-1, 3)
+            if e_idx.size and (e_idx.min() < 0 or e_idx.max() >= n_one):
+                raise ValueError(f"external_forces: nucleotide index out of range [0, {n_one})")
+            integ.set_external_forces(np.concatenate([e_idx + r * n_one for r in range(n_rep)]), np.tile(e_f, (n_rep, 1)))
         if pseq is not None:
             marg, unit, bp, terms = pseq
             if n_rep > 1:  # every replica its own copy of the base pairs
