@@ -25,8 +25,6 @@ from typing import Any, Callable
 import numpy as np
 import torch
 
-from mythos_amd import _lib
-from mythos_amd.energy import flat_params as fp
 from mythos_amd.energy.configuration import BaseConfiguration
 
 ERR_PARAM_NOT_FOUND = "Parameter '{key}' not found in {class_name}"
@@ -128,29 +126,34 @@ def _pairs_2xP(unbonded, n: int) -> np.ndarray:
     return np.ascontiguousarray(u, dtype=np.int32)
 
 
-def _get_system(model, seq, is_end, bonded, unbonded, box, dtype, device, is_rna=None):
+def topology_key(model, seq, is_end, bonded, is_rna, box, dtype, device) -> tuple:
+    """Everything a system handle is built from, by content: the key of the system cache and of a simulator's kept entries."""
+    bts = lambda a, t: None if a is None else np.ascontiguousarray(a, dtype=t).tobytes()  # noqa: E731
+    return (model, bts(seq, np.int32), bts(is_end, np.uint8), bts(bonded, np.int32), bts(is_rna, np.uint8),
+            None if box is None else tuple(np.asarray(box, dtype=np.float64).reshape(-1).tolist()), dtype, str(device))
+
+
+def pair_tag(pairs: np.ndarray) -> tuple:
+    """What identifies a pair list as ``_pairs_2xP`` returns it.  Content, never identity: ids are reused after garbage
+    collection and arrays are mutated in place."""
+    return (pairs.shape, pairs.tobytes() if pairs.size < 65_536 else hashlib.blake2b(pairs.data, digest_size=16).digest())
+
+
+def _get_system(low, dtype, device):
+    """The cached system handle of a lowered energy function (lowering.Lowered), with its pair list in place."""
     from mythos_amd.hip_system import OxdnaSystem
 
-    seq = np.ascontiguousarray(seq, dtype=np.int32)
-    bonded = np.ascontiguousarray(bonded, dtype=np.int32)
-    is_end_b = None if is_end is None else np.ascontiguousarray(is_end, dtype=np.uint8)
-    is_rna_b = None if is_rna is None else np.ascontiguousarray(is_rna, dtype=np.uint8)
-    key = (
-        model, seq.tobytes(), bonded.tobytes(), None if is_end_b is None else is_end_b.tobytes(),
-        None if box is None else tuple(np.asarray(box, dtype=np.float64).tolist()), dtype, str(device),
-        None if is_rna_b is None else is_rna_b.tobytes(),
-    )
+    key = topology_key(low.model, low.seq, low.is_end, low.bonded, low.is_rna, low.box, dtype, device)
     entry = _SYSTEMS.get(key)
     if entry is None:
-        entry = {"sys": OxdnaSystem(model, seq, is_end_b, bonded, box=box, dtype=dtype, device=device, is_rna=is_rna_b), "pairs": None,
-                 "flat": None, "pseq": None}
+        entry = {"sys": OxdnaSystem(low.model, low.seq, low.is_end, low.bonded, box=low.box, dtype=dtype, device=device, is_rna=low.is_rna),
+                 "pairs": None, "flat": None, "pseq": None}
         _SYSTEMS[key] = entry
         if len(_SYSTEMS) > 16:
             _SYSTEMS.pop(next(iter(_SYSTEMS)))
-    if unbonded is not None:
-        pairs = _pairs_2xP(unbonded, seq.shape[0])
-        # content, never identity: ids are reused after garbage collection and arrays are mutated in place
-        tag = (pairs.shape, pairs.tobytes() if pairs.size < 65_536 else hashlib.blake2b(pairs.data, digest_size=16).digest())
+    if low.unbonded is not None:
+        pairs = _pairs_2xP(low.unbonded, low.seq.shape[0])
+        tag = pair_tag(pairs)
         if entry["pairs"] != tag:
             entry["sys"].set_neighbors(pairs)
             entry["pairs"] = tag
@@ -190,43 +193,6 @@ def pseq_tensors(energy_fns):
                 return kernel_tables_torch(pseq, fn.params["pseq_constraints"])
             return None
     return None
-
-
-def na1_flat_and_types(energy_fns, weights, geom, kt_default=None):
-    """The three flat vectors (one tensor, oxDNA2 | oxRNA2 | hybrid) and ``is_rna`` of a composed oxNA function, plus
-    the term weights and columns: what the energy path and the simulator both hand to an oxNA system."""
-    from mythos_amd.energy import terms as _terms
-    from mythos_amd.input.topology import NucleotideType
-
-    sets = {which: {"geometry": geom.params[which]} if which in geom.params else {} for which in fp.NA1_SETS}
-    term_w, cols = [0.0] * 8, []
-    w_user = weights if weights is not None else torch.ones(len(energy_fns), dtype=torch.float64)
-    kt = salt = hce = nt_type = None
-    for fn, w in zip(energy_fns, w_user):
-        k = TERM_ORDER.index(fn.term)
-        if k in cols:
-            raise ValueError(f"term '{fn.term}' appears twice in one composed energy function")
-        for which, sec in fn.params.sections().items():
-            sets[which][fn.term] = sec
-        term_w[k] = float(w)
-        cols.append(k)
-        t = np.asarray(_np(fn.params["nt_type"]))
-        if nt_type is not None and not np.array_equal(nt_type, t):
-            raise ValueError("the terms of an oxNA energy function carry different nt_type arrays")
-        nt_type = t
-        if "kt" in fn.params and kt is None:
-            kt = fn.params["kt"]
-        if fn.term == "debye":
-            salt, hce = fn.params["salt_conc"], bool(fn.params["half_charged_ends"])
-    _terms.fill_missing_sections_na1(sets)
-    if kt is None:
-        kt = _terms.default_kt() if kt_default is None else kt_default
-    named = fp.derive_flat_na1(sets["dna"], sets["rna"], sets["drh"], kt=kt, salt_conc=0.5 if salt is None else salt,
-                               half_charged_ends=False if hce is None else hce, term_weights=term_w, numbers_ok=True)
-    flat = fp.pack_flat_na1(named, _lib.param_names())
-    if nt_type.shape != (int(_np(energy_fns[0].seq).shape[0]),):
-        raise ValueError("nt_type must have one entry per nucleotide")
-    return flat, nt_type == int(NucleotideType.RNA), term_w, cols
 
 
 def _apply_pseq(entry, request) -> None:
@@ -575,80 +541,24 @@ class ComposedEnergyFunction(EnergyFunction):
     # -- evaluation -----------------------------------------------------------------------------------
     def _evaluate(self, body: RigidBody):
         """One launch: (weighted total per frame, raw (.., 8) term energies, per-fn term columns)."""
-        if not self.energy_fns:
-            raise ValueError("ComposedEnergyFunction has no energy functions")
-        first = self.energy_fns[0]
-        geom = next((fn.transform_fn for fn in self.energy_fns if fn.transform_fn is not None), None)
-        if geom is None:
-            raise ValueError("transform_fn (site geometry) must be provided")
-        model = geom.model  # the site geometry decides oxDNA1 vs oxDNA2 (shared term classes exist in both)
-        from mythos_amd.energy import terms as _terms
+        from mythos_amd.energy.lowering import lower  # (not at module level: lowering needs the term classes, which need this module)
 
-        _terms.check_term_models(model, self.energy_fns)
-        if model == 4:
-            return self._evaluate_na1(body, geom)
-        sections = {"geometry": geom.params}
-        term_w = [0.0] * 8
-        cols = []
-        w_user = self.weights if self.weights is not None else torch.ones(len(self.energy_fns), dtype=torch.float64)
-
-        for fn, w in zip(self.energy_fns, w_user):
-            k = TERM_ORDER.index(fn.term)
-            if fn.term in sections:
-                raise ValueError(f"term '{fn.term}' appears twice in one composed energy function")
-            sections[fn.term] = {n: fn.params[n] for n in (*type(fn.params).required_params, *type(fn.params).optional_params)
-                                 if n not in ("pseq", "pseq_constraints")}
-            term_w[k] = float(w)
-            cols.append(k)
-        kt = salt = hce = None
-        for fn in self.energy_fns:
-            if "kt" in fn.params:
-                kt = fn.params["kt"] if kt is None else kt
-            if fn.term == "debye":
-                salt, hce = fn.params["salt_conc"], bool(fn.params["half_charged_ends"])
-        _terms.fill_missing_sections(model, sections)
-        if kt is None:
-            kt = _terms.default_kt()
-        flat_named = fp.derive_flat(model, sections, kt=kt, salt_conc=0.5 if salt is None else salt,
-                                    half_charged_ends=True if hce is None else hce, term_weights=term_w, numbers_ok=True)
-        flat = fp.pack_flat(flat_named, _lib.param_names())
+        low = lower(self.energy_fns, self.weights)
         center, quat = body.center, body.orientation.vec
-        box = getattr(first.displacement_fn, "box", None)
-        entry = _get_system(model, _np(first.seq), _np(first.is_end) if first.is_end is not None else None,
-                            _np(first.bonded_neighbors), first.unbonded_neighbors, box, center.dtype, center.device)
-        _apply_pseq(entry, pseq_request(self.energy_fns))
+        entry = _get_system(low, center.dtype, center.device)
+        _apply_pseq(entry, low.pseq)
+        # d<U>/d(distribution) wanted: its own entry point (mythos_oxdna_energy_dpseq), without the observables
+        pseq_leaves = pseq_tensors(self.energy_fns)
         entry["observe"] = None
-        if getattr(self, "observables", None) and center.dim() == 3 and center.device.type == "cuda":
+        if (low.model != 4 and pseq_leaves is None and getattr(self, "observables", None) and center.dim() == 3
+                and center.device.type == "cuda"):
             oset, served = _fused_observables(self.observables, int(center.shape[1]), center.dtype, center.device)
             entry["observe"] = None if oset is None else (oset, served)
-        pseq_leaves = pseq_tensors(self.energy_fns)
         try:
-            if pseq_leaves is not None:
-                entry["observe"] = None  # the distribution gradient comes from its own entry point, without the observables
-                total, terms = _EnergyOp.apply(center, quat, flat, entry, term_w, *pseq_leaves)
-            else:
-                total, terms = _EnergyOp.apply(center, quat, flat, entry, term_w)
+            total, terms = _EnergyOp.apply(center, quat, low.flat, entry, low.term_weights, *(pseq_leaves or ()))
         finally:
             entry["observe"] = None
-        return total, terms, cols
-
-    def _evaluate_na1(self, body: RigidBody, geom):
-        """oxNA (mythos/energy/na1/): every term carries three parameter sets and the types of the nucleotides; the
-        kernels take three flat vectors - oxDNA2, oxRNA2, hybrid - and ``is_rna``."""
-        first = self.energy_fns[0]
-        flat, is_rna, term_w, cols = na1_flat_and_types(self.energy_fns, self.weights, geom)
-        center, quat = body.center, body.orientation.vec
-        entry = _get_system(4, _np(first.seq), _np(first.is_end) if first.is_end is not None else None, _np(first.bonded_neighbors),
-                            first.unbonded_neighbors, getattr(first.displacement_fn, "box", None), center.dtype, center.device,
-                            is_rna=is_rna)
-        _apply_pseq(entry, pseq_request(self.energy_fns))  # hydrogen bonding only (na1/hydrogen_bonding.py:127-128)
-        entry["observe"] = None
-        pseq_leaves = pseq_tensors(self.energy_fns)  # d<U>/d(distribution) wanted: mythos_oxdna_energy_dpseq
-        if pseq_leaves is not None:
-            total, terms = _EnergyOp.apply(center, quat, flat, entry, term_w, *pseq_leaves)
-        else:
-            total, terms = _EnergyOp.apply(center, quat, flat, entry, term_w)
-        return total, terms, cols
+        return total, terms, low.cols
 
     def compute_terms(self, body: RigidBody) -> torch.Tensor:
         """Energy of each composed function, shape (n_fns,) or (n_states, n_fns) (base.py:312-314)."""
@@ -673,8 +583,3 @@ class QualifiedComposedEnergyFunction(ComposedEnergyFunction):
     def _rename_param_from_fn(self, param: str, fn) -> str:
         return f"{type(fn).__qualname__}.{param}"
 
-
-def _np(x):
-    if isinstance(x, torch.Tensor):
-        return x.detach().cpu().numpy()
-    return np.asarray(x)

@@ -299,38 +299,25 @@ class LangevinIntegrator(_MdIntegrator):
 
     def run(self, center, quat, p_lin, p_ang, n_steps: int, save_every: int = 0, want_energy: bool = True):
         """Advance in place; returns (traj_center, traj_quat, e_trace) or Nones when save_every == 0."""
-        s = self.system
-        for t, tail, name in ((center, (s.n, 3), "center"), (quat, (s.n, 4), "quat"), (p_lin, (s.n, 3), "p_lin"), (p_ang, (s.n, 3), "p_ang")):
-            if s._check(t, tail, name).data_ptr() != t.data_ptr():
-                raise ValueError(f"{name} must be contiguous (it is updated in place)")
-        n_save = n_steps // save_every if save_every > 0 else 0
-        tc = torch.empty((n_save, s.n, 3), dtype=s.dtype, device=s.device) if n_save else None
-        tq = torch.empty((n_save, s.n, 4), dtype=s.dtype, device=s.device) if n_save else None
-        et = torch.zeros((n_save, TRACE_WIDTH), dtype=torch.float64, device=s.device) if (n_save and want_energy) else None
+        state = self._state_ptrs(center, quat, p_lin, p_ang)
+        tc, tq, et = self._rows(n_steps, save_every, want_energy)
         rc = self._lib.mythos_langevin_run(
-            self._h, _lib.ptr(center), _lib.ptr(quat), _lib.ptr(p_lin), _lib.ptr(p_ang), int(n_steps),
-            int(save_every), _lib.ptr(tc), _lib.ptr(tq), _lib.ptr(et), _lib.stream(s.device),
+            self._h, *state, int(n_steps), int(save_every), _lib.ptr(tc), _lib.ptr(tq), _lib.ptr(et), _lib.stream(self.system.device),
         )
         _touched(center, quat, p_lin, p_ang)  # (a run that fails still hands back the state of its last valid step)
         _lib.check(rc, "langevin_run")
         return tc, tq, et
 
-    # ---- resident form: the state stays in the integrator's layout on the device between calls ----------
     def _state_ptrs(self, center, quat, p_lin, p_ang):
         s = self.system
         for t, tail, name in ((center, (s.n, 3), "center"), (quat, (s.n, 4), "quat"), (p_lin, (s.n, 3), "p_lin"), (p_ang, (s.n, 3), "p_ang")):
             if s._check(t, tail, name).data_ptr() != t.data_ptr():
-                raise ValueError(f"{name} must be contiguous")
+                raise ValueError(f"{name} must be contiguous (the library reads and writes it in place)")
         return _lib.ptr(center), _lib.ptr(quat), _lib.ptr(p_lin), _lib.ptr(p_ang)
 
-    def load(self, center, quat, p_lin, p_ang) -> None:
-        """Copy a state into the integrator (mythos_langevin_load); ``advance`` then steps it in place."""
-        _lib.check(self._lib.mythos_langevin_load(self._h, *self._state_ptrs(center, quat, p_lin, p_ang), _lib.stream(self.system.device)), "langevin_load")
-
-    def advance(self, n_steps: int, save_every: int = 0, want_energy: bool = True, out=None):
-        """``n_steps`` on the resident state; the neighbour list and its rebuild schedule carry over between calls.
-        Returns (traj_center, traj_quat, e_trace) or Nones when save_every == 0.  ``out = (traj_center, traj_quat)``:
-        rows written into the caller's tensors ((n_steps // save_every, n, 3 | 4), contiguous) instead of new ones."""
+    def _rows(self, n_steps: int, save_every: int, want_energy: bool, out=None):
+        """Rows for the saved steps: (traj_center, traj_quat, e_trace), Nones where there is nothing to save.
+        ``out = (traj_center, traj_quat)``: the caller's tensors, checked, instead of new ones."""
         s = self.system
         n_save = n_steps // save_every if save_every > 0 else 0
         if out is not None and n_save:
@@ -342,11 +329,24 @@ class LangevinIntegrator(_MdIntegrator):
             tc = torch.empty((n_save, s.n, 3), dtype=s.dtype, device=s.device) if n_save else None
             tq = torch.empty((n_save, s.n, 4), dtype=s.dtype, device=s.device) if n_save else None
         et = torch.zeros((n_save, TRACE_WIDTH), dtype=torch.float64, device=s.device) if (n_save and want_energy) else None
+        return tc, tq, et
+
+    # ---- resident form: the state stays in the integrator's layout on the device between calls ----------
+    def load(self, center, quat, p_lin, p_ang) -> None:
+        """Copy a state into the integrator (mythos_langevin_load); ``advance`` then steps it in place."""
+        _lib.check(self._lib.mythos_langevin_load(self._h, *self._state_ptrs(center, quat, p_lin, p_ang), _lib.stream(self.system.device)), "langevin_load")
+
+    def advance(self, n_steps: int, save_every: int = 0, want_energy: bool = True, out=None):
+        """``n_steps`` on the resident state; the neighbour list and its rebuild schedule carry over between calls.
+        Returns (traj_center, traj_quat, e_trace) or Nones when save_every == 0.  ``out = (traj_center, traj_quat)``:
+        rows written into the caller's tensors ((n_steps // save_every, n, 3 | 4), contiguous) instead of new ones."""
+        s = self.system
+        tc, tq, et = self._rows(n_steps, save_every, want_energy, out)
         _lib.check(
             self._lib.mythos_langevin_advance(self._h, int(n_steps), int(save_every), _lib.ptr(tc), _lib.ptr(tq), _lib.ptr(et), _lib.stream(s.device)),
             "langevin_advance",
         )
-        if out is not None and n_save:
+        if out is not None and tc is not None:
             _touched(tc, tq)
         return tc, tq, et
 
@@ -395,18 +395,21 @@ class MartiniSystem(_lib.Handle):
             _lib.dtype_code(dtype), self.device.index or 0,
         )
 
-    def energy(self, pos: torch.Tensor, box: torch.Tensor, grads: bool = False):
-        """pos (F, N, 3) or (N, 3); box (F, 3) or (3,) -> (e_terms (F, 3) float64, dU/dpos or None)."""
-        single = pos.dim() == 2
-        if single:
+    def _frames(self, pos, box):
+        """pos (F, N, 3) or (N, 3), box (F, 3), (1, 3) or (3,) -> contiguous (F, N, 3) and (F, 3) on the device."""
+        if pos.dim() == 2:
             pos, box = pos[None], torch.as_tensor(box).reshape(1, 3)
         if pos.device != self.device or pos.dtype != self.dtype or tuple(pos.shape[1:]) != (self.n, 3):
             raise ValueError(f"pos must be a {self.dtype} tensor of shape (F, {self.n}, 3) on {self.device}")
-        pos = pos.contiguous()
         box = torch.as_tensor(box, dtype=self.dtype, device=self.device).reshape(-1, 3)
         if box.shape[0] == 1 and pos.shape[0] > 1:
             box = box.expand(pos.shape[0], 3)
-        box = box.contiguous()
+        return pos.contiguous(), box.contiguous()
+
+    def energy(self, pos: torch.Tensor, box: torch.Tensor, grads: bool = False):
+        """pos (F, N, 3) or (N, 3); box (F, 3) or (3,) -> (e_terms (F, 3) float64, dU/dpos or None)."""
+        single = pos.dim() == 2
+        pos, box = self._frames(pos, box)
         nf = pos.shape[0]
         e = torch.empty((nf, 3), dtype=torch.float64, device=self.device)
         g = torch.empty_like(pos) if grads else None
@@ -419,15 +422,7 @@ class MartiniSystem(_lib.Handle):
     def param_grads(self, pos: torch.Tensor, box: torch.Tensor, lj: bool = True, bonds: bool = True, angles: bool = True):
         """Per-frame parameter gradients (float64, on the device): dict with ``sigma``/``eps`` (F, T, T) for the
         ordered type pair, ``bond_k``/``bond_r0`` (F, n_bonds), ``angle_k``/``angle_t0`` (F, n_angles)."""
-        if pos.dim() == 2:
-            pos, box = pos[None], torch.as_tensor(box).reshape(1, 3)
-        if pos.device != self.device or pos.dtype != self.dtype or tuple(pos.shape[1:]) != (self.n, 3):
-            raise ValueError(f"pos must be a {self.dtype} tensor of shape (F, {self.n}, 3) on {self.device}")
-        pos = pos.contiguous()
-        box = torch.as_tensor(box, dtype=self.dtype, device=self.device).reshape(-1, 3)
-        if box.shape[0] == 1 and pos.shape[0] > 1:
-            box = box.expand(pos.shape[0], 3)
-        box = box.contiguous()
+        pos, box = self._frames(pos, box)
         nf = pos.shape[0]
 
         def buf(on, *shape):

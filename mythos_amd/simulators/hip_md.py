@@ -27,13 +27,13 @@ from typing import Any, Callable
 import numpy as np
 import torch
 
-from mythos_amd import _lib
-from mythos_amd.energy import flat_params as fp
-from mythos_amd.energy.base import ComposedEnergyFunction, EnergyFunction, Quaternion, RigidBody, _np
-from mythos_amd.energy import terms as _terms
+from mythos_amd.energy.base import ComposedEnergyFunction, EnergyFunction, Quaternion, RigidBody, _pairs_2xP, pair_tag, topology_key
+from mythos_amd.energy.lowering import lower
 from mythos_amd.hip_system import LangevinIntegrator, OxdnaSystem
+from mythos_amd.input.external_forces import read_external_forces
 from mythos_amd.simulators.base import Simulator, SimulatorOutput
 from mythos_amd.simulators.io import SimulatorTrajectory
+from mythos_amd.simulators.replicas import ReplicaLayout
 from mythos_amd.simulators.neighbors import NoNeighborList, VerletNeighborList  # noqa: F401  (NoNeighborList: re-exported, the docstring's example)
 
 
@@ -87,8 +87,8 @@ class NVTLangevin:
     (``simulator_init``, mythos/simulators/jax_md/utils.py:19-28; call sites jaxmd.py:73-92) on the fused HIP kernel.
 
     ``init_fn(key, R, mass=..., **kw) -> state`` draws the momenta at kT from ``key`` and loads the state into the
-    integrator; ``step_fn(state, **kw) -> state`` advances ONE step (one launch) and reads the frames back, so that every
-    state is a value as it is in JAX: stepping the newest state continues the resident frames, stepping an older one
+    integrator; ``step_fn(state, **kw) -> state`` advances ONE step (the step launch, then a second force launch that closes
+    the frame so that it can be read) and reads the frames back, so that every state is a value as it is in JAX: stepping the newest state continues the resident frames, stepping an older one
     reloads it first and reproduces what it produced before to rounding (the noise of a step is a function of key, step and
     nucleotide; a reloaded state's closing half kick and the next opening one are two additions where the resident frames
     have one).  This is the reference's calling shape, at one C-ABI call and four small copies per step; the loop the
@@ -197,7 +197,7 @@ class HipMDSimulator(Simulator):
     # oxDNA external-force file (mythos_amd.input.external_forces).  With replicas the list is repeated per replica at
     # ``index + r * n``.  None: no forces, and exactly the launches of a simulator that never had any.
     external_forces: Any = None
-    # device-side objects kept between calls: {key: (OxdnaSystem, LangevinIntegrator, pinned python objects)}
+    # device-side objects kept between calls: {key: (OxdnaSystem, LangevinIntegrator, ReplicaLayout)}
     _resident: dict = dc.field(default_factory=dict, init=False, repr=False, compare=False)
 
     def __getstate__(self):  # (the reference's simulators travel through Ray: handles stay behind)
@@ -209,12 +209,63 @@ class HipMDSimulator(Simulator):
             object.__setattr__(self, k, v)
         object.__setattr__(self, "_resident", {})
 
+    @staticmethod
+    def _close_entry(entry) -> None:
+        system, integ, _ = entry
+        integ.close()
+        system.close()
+
     def release(self) -> None:
         """Free the device-side objects kept from earlier runs."""
-        for system, integ, _ in self._resident.values():
-            integ.close()
-            system.close()
+        for entry in self._resident.values():
+            self._close_entry(entry)
         self._resident.clear()
+
+    def _integrator_constants(self) -> dict:
+        sp = self.simulator_params
+        mass, inertia = _pair(sp.mass)
+        gamma_t, gamma_r = _pair(sp.gamma)
+        return {"dt": float(sp.dt), "kT": float(sp.kT), "gamma_t": float(gamma_t), "gamma_r": float(gamma_r),
+                "mass": float(np.asarray(mass).reshape(-1)[0]),
+                "inertia": tuple(np.asarray(inertia, dtype=np.float64).reshape(-1)[:3].tolist())}
+
+    def _entry_key(self, low, topo, pairs, n_rep, dev) -> tuple:
+        """Everything the kept objects are built from, by content."""
+        nb = self.neighbors
+        nbr_key = ("verlet", float(nb.r_cutoff), float(nb.dr_threshold), int(nb.rebuild_every)) if pairs is None else ("pairs", pair_tag(pairs))
+        return (topology_key(low.model, *topo, low.box, self.dtype, dev), n_rep, nbr_key, *self._integrator_constants().values())
+
+    def _entry(self, key_res, low, topo, pairs, layout, dev, seed):
+        """The kept (system, integrator) of this key, or a new pair; -> (system, integrator, whether it is new)."""
+        entry = self._resident.get(key_res)
+        if entry is not None:
+            return entry[0], entry[1], False
+        seq, is_end, bonded, is_rna = topo
+        system = OxdnaSystem(low.model, seq, is_end, bonded, box=low.box, dtype=self.dtype, device=dev, is_rna=is_rna)
+        integ = LangevinIntegrator(system, **self._integrator_constants(), seed=int(seed))
+        if pairs is None:
+            nb = self.neighbors
+            integ.set_neighbor_policy(nb.r_cutoff, nb.dr_threshold, nb.rebuild_every)
+        else:
+            system.set_neighbors(layout.pairs(pairs))
+        while len(self._resident) >= 4:  # (a simulator serves one system; a few variants at most)
+            self._close_entry(self._resident.pop(next(iter(self._resident))))
+        self._resident[key_res] = (system, integ, layout)
+        return system, integ, True
+
+    def _apply_external_forces(self, integ, layout) -> None:
+        ext = self.external_forces
+        if ext is None:
+            if integ.external_forces[0].size:
+                integ.set_external_forces()
+            return
+        if isinstance(ext, (str, bytes)) or hasattr(ext, "__fspath__"):
+            ext = read_external_forces(ext, layout.n_one)
+        index = np.asarray(ext[0], dtype=np.int64).reshape(-1)
+        force = np.asarray(ext[1], dtype=np.float64).reshape(-1, 3)
+        if index.size and (index.min() < 0 or index.max() >= layout.n_one):
+            raise ValueError(f"external_forces: nucleotide index out of range [0, {layout.n_one})")
+        integ.set_external_forces(*layout.forces(index, force))
 
     def _prepare(self, opt_params, key, state_device):
         """The device-side objects of this simulator at ``opt_params``: (system, integrator, device, replicas, nucleotides
@@ -222,126 +273,30 @@ class HipMDSimulator(Simulator):
         ef = self.energy_fn.with_params(opt_params) if opt_params else self.energy_fn
         if not isinstance(ef, ComposedEnergyFunction):
             ef = ComposedEnergyFunction(energy_fns=[ef])
-        first = ef.energy_fns[0]
-        from mythos_amd.energy.base import pseq_request
-
-        # a probabilistic sequence rides along into the dynamics, as it does in the reference - there the stacking /
-        # hydrogen-bonding configurations carry pseq into whatever energy function a simulator steps with
-        # (dna1/stacking.py:284-285, hydrogen_bonding.py:330-331)
-        pseq = pseq_request(ef.energy_fns)
-        geom = next(fn.transform_fn for fn in ef.energy_fns if fn.transform_fn is not None)
-        model = geom.model
-        _terms.check_term_models(model, ef.energy_fns)
-        is_rna = None
-        sections = {"geometry": geom.params} if model != 4 else None
-        tw = [0.0] * 8
-        w_user = ef.weights if ef.weights is not None else torch.ones(len(ef.energy_fns), dtype=torch.float64)
-        kt_e = salt = hce = None
-        from mythos_amd.energy.base import TERM_ORDER
-
-        for fn, w in zip(ef.energy_fns if model != 4 else [], w_user):
-            sections[fn.term] = {n: fn.params[n] for n in (*type(fn.params).required_params, *type(fn.params).optional_params)
-                                 if n not in ("pseq", "pseq_constraints")}
-            tw[TERM_ORDER.index(fn.term)] = float(w)
-            if "kt" in fn.params and kt_e is None:
-                kt_e = fn.params["kt"]
-            if fn.term == "debye":
-                salt, hce = fn.params["salt_conc"], bool(fn.params["half_charged_ends"])
-        sp = self.simulator_params
-        if model == 4:
-            # oxNA: three flat vectors and the nucleotide types (the step kernel's MODEL 4 instantiation)
-            from mythos_amd.energy.base import na1_flat_and_types
-
-            flat, is_rna, _, _ = na1_flat_and_types(ef.energy_fns, ef.weights, geom, kt_default=sp.kT)
-        else:
-            _terms.fill_missing_sections(model, sections)
-        flat = flat if model == 4 else fp.pack_flat(
-            fp.derive_flat(model, sections, kt=sp.kT if kt_e is None else kt_e, salt_conc=0.5 if salt is None else salt,
-                           half_charged_ends=True if hce is None else hce, term_weights=tw, numbers_ok=True),
-            _lib.param_names(),
-        )
+        # a term without a temperature of its own is stepped at the thermostat's
+        low = lower(ef.energy_fns, ef.weights, kt_default=self.simulator_params.kT)
         dev = torch.device(self.device) if self.device is not None else state_device
         if dev.type != "cuda":
             dev = torch.device("cuda", torch.cuda.current_device())
-        box = getattr(first.displacement_fn, "box", None)
-        n_rep = int(self.n_replicas)
-        n_one = int(_np(first.seq).shape[0])
-        seq_a, end_a, bonded_a = _np(first.seq), None if first.is_end is None else _np(first.is_end), _np(first.bonded_neighbors)
-        if n_rep > 1:
-            if box is not None:
-                raise ValueError("HipMDSimulator: replicas are batched in free space; the energy function has a periodic box")
-            bonded_2 = np.asarray(bonded_a).reshape(-1, 2)
-            seq_a = np.tile(np.asarray(seq_a), n_rep)
-            end_a = None if end_a is None else np.tile(np.asarray(end_a), n_rep)
-            bonded_a = np.concatenate([bonded_2 + r * n_one for r in range(n_rep)], axis=0)
-        if n_rep > 1 and is_rna is not None:
-            is_rna = np.tile(np.asarray(is_rna), n_rep)
-        mass, inertia = _pair(sp.mass)
-        gamma_t, gamma_r = _pair(sp.gamma)
-        mass_f = float(np.asarray(mass).reshape(-1)[0])
-        inertia_a = np.asarray(inertia, dtype=np.float64).reshape(-1)[:3]
-        nb = self.neighbors
-        pairs_obj = None if isinstance(nb, VerletNeighborList) else (nb.idx if nb is not None else first.unbonded_neighbors)
-        bts = lambda a: None if a is None else np.ascontiguousarray(a).tobytes()  # noqa: E731
-        key_res = (
-            model, n_rep, self.dtype, str(dev), bts(np.asarray(seq_a, dtype=np.int32)), bts(None if end_a is None else np.asarray(end_a, dtype=np.uint8)),
-            bts(np.asarray(bonded_a, dtype=np.int32)), None if box is None else tuple(np.asarray(box, dtype=np.float64).reshape(-1).tolist()),
-            bts(None if is_rna is None else np.asarray(is_rna, dtype=np.uint8)),
-            ("verlet", float(nb.r_cutoff), float(nb.dr_threshold), int(nb.rebuild_every)) if pairs_obj is None else ("pairs", id(pairs_obj)),
-            float(sp.dt), float(sp.kT), float(gamma_t), float(gamma_r), mass_f, tuple(inertia_a.tolist()),
-        )
-        entry = self._resident.get(key_res)
-        if entry is None:
-            system = OxdnaSystem(model, seq_a, end_a, bonded_a, box=box, dtype=self.dtype, device=dev, is_rna=is_rna)
-            integ = LangevinIntegrator(system, dt=sp.dt, kT=sp.kT, gamma_t=float(gamma_t), gamma_r=float(gamma_r), mass=mass_f,
-                                       inertia=inertia_a, seed=int(key))
-            system.set_params(flat.detach())
-            if pairs_obj is None:
-                integ.set_neighbor_policy(nb.r_cutoff, nb.dr_threshold, nb.rebuild_every)
-            else:
-                from mythos_amd.energy.base import _pairs_2xP
-
-                p2 = _pairs_2xP(pairs_obj, n_one)
-                if n_rep > 1:
-                    p2 = np.concatenate([np.asarray(p2).reshape(-1, 2) + r * n_one for r in range(n_rep)], axis=0)
-                system.set_neighbors(p2)
-            while len(self._resident) >= 4:  # (a simulator serves one system; a few variants at most)
-                old_system, old_integ, _ = self._resident.pop(next(iter(self._resident)))
-                old_integ.close()
-                old_system.close()
-            # (pairs_obj is pinned: its id is part of the key)
-            self._resident[key_res] = (system, integ, pairs_obj)
-            had_pseq = False
-        else:
-            system, integ, _ = entry
-            system.set_params(flat.detach())  # 2 KB; everything derived from it on the device follows (param_epoch)
+        layout = ReplicaLayout(int(self.n_replicas), int(low.seq.shape[0]))
+        topo = layout.topology(low.seq, low.is_end, low.bonded, low.is_rna, box=low.box)
+        nb = self.neighbors  # an explicit pair list, the energy function's own, or (pairs None) a Verlet list built on the device
+        pairs = None if isinstance(nb, VerletNeighborList) else _pairs_2xP(nb.idx if nb is not None else low.unbonded, layout.n_one)
+        key_res = self._entry_key(low, topo, pairs, layout.n_rep, dev)
+        system, integ, new = self._entry(key_res, low, topo, pairs, layout, dev, key)
+        system.set_params(low.flat.detach())  # 2 KB; everything derived from it on the device follows (param_epoch)
+        if not new:
             integ.set_seed(int(key))
             integ.step = 0  # a run starts its noise stream at (key, step 0), as a new integrator would
-            had_pseq = system._pseq_terms != 0
-        if self.external_forces is None:
-            if integ.external_forces[0].size:
-                integ.set_external_forces()
-        else:
-            ext = self.external_forces
-            if isinstance(ext, (str, bytes)) or hasattr(ext, "__fspath__"):
-                from mythos_amd.input.external_forces import read_external_forces
-
-                ext = read_external_forces(ext, n_one)
-            e_idx = np.asarray(ext[0], dtype=np.int64).reshape(-1)
-            e_f = np.asarray(ext[1], dtype=np.float64).reshape(-1, 3)
-            if e_idx.size and (e_idx.min() < 0 or e_idx.max() >= n_one):
-                raise ValueError(f"external_forces: nucleotide index out of range [0, {n_one})")
-            integ.set_external_forces(np.concatenate([e_idx + r * n_one for r in range(n_rep)]), np.tile(e_f, (n_rep, 1)))
-        if pseq is not None:
-            marg, unit, bp, terms = pseq
-            if n_rep > 1:  # every replica its own copy of the base pairs
-                n_bp = int(bp.shape[0]) if (unit >= 0).any() else 0
-                unit = np.concatenate([np.where(unit >= 0, unit + 2 * n_bp * r, -1) for r in range(n_rep)])
-                marg, bp = np.tile(marg, (n_rep, 1)), (np.tile(bp, (n_rep, 1)) if n_bp > 0 else bp)
-            system.set_pseq(marg, unit, bp, terms)
-        elif had_pseq:
+        self._apply_external_forces(integ, layout)
+        # a probabilistic sequence rides along into the dynamics, as it does in the reference - there the stacking /
+        # hydrogen-bonding configurations carry pseq into whatever energy function a simulator steps with
+        # (dna1/stacking.py:284-285, hydrogen_bonding.py:330-331)
+        if low.pseq is not None:
+            system.set_pseq(*layout.pseq(*low.pseq))
+        elif system._pseq_terms:
             system.set_pseq()
-        return system, integ, dev, n_rep, n_one
+        return system, integ, dev, layout.n_rep, layout.n_one
 
     def run(self, opt_params: dict, init_state: RigidBody | None = None, n_steps: int | None = None, key: int | None = None,
             **_) -> SimulatorOutput:
@@ -356,37 +311,13 @@ class HipMDSimulator(Simulator):
         sp, nb = self.simulator_params, self.neighbors
         c = init_state.center.to(device=dev, dtype=self.dtype).contiguous().clone()
         q = init_state.orientation.vec.to(device=dev, dtype=self.dtype).contiguous().clone()
-        offsets = None
-        if n_rep > 1:
-            # (n, 3) initial state: every replica starts from it; (R, n, 3): one start per replica
-            c = (c if c.dim() == 3 else c[None].expand(n_rep, -1, -1)).reshape(n_rep, n_one, 3).clone()
-            q = (q if q.dim() == 3 else q[None].expand(n_rep, -1, -1)).reshape(n_rep, n_one, 4).clone()
-            # every replica is centred on its grid node for the run (free space: a translation changes nothing) and gets
-            # its own centre of mass back afterwards, so drift accumulated over earlier runs never eats into the spacing
-            com = c.mean(dim=1, keepdim=True)
-            extent = float((c - com).norm(dim=-1).max())
-            r_list = (nb.r_cutoff + nb.dr_threshold) if isinstance(nb, VerletNeighborList) else 4.0
-            spacing = 2.0 * extent + 8.0 * r_list + 64.0  # out of each other's list range for as long as a run diffuses
-            side = int(np.ceil(n_rep ** (1.0 / 3.0)))
-            grid = torch.as_tensor([[r % side, (r // side) % side, r // (side * side)] for r in range(n_rep)], dtype=self.dtype, device=dev)
-            offsets = (grid * spacing)[:, None, :] - com
-            c = (c + offsets).reshape(n_rep * n_one, 3).contiguous()
-            q = q.reshape(n_rep * n_one, 4).contiguous()
+        r_list = (nb.r_cutoff + nb.dr_threshold) if isinstance(nb, VerletNeighborList) else 4.0
+        layout = ReplicaLayout(n_rep, n_one)
+        c, q, offsets = layout.place(c, q, r_list)
         p, ang = integ.init_momenta()
         tc, tq, et = integ.run(c, q, p, ang, int(n_steps), save_every=self.save_every, want_energy=self.trace_energy)
-        if n_rep > 1:
-            # states of all replicas, replica-major: (R * S, n, .); the offsets of the grid come off again
-            def unbatch(t, width, off):
-                t = t.reshape(t.shape[0], n_rep, n_one, width)
-                if off is not None:
-                    t = t - off[None]
-                return t.transpose(0, 1).reshape(-1, n_one, width)
-
-            tc = None if tc is None else unbatch(tc, 3, offsets)
-            tq = None if tq is None else unbatch(tq, 4, None)
-            et = None  # the fused trace sums over the whole launch; per-replica energies come from energy_fn
-            c = c.reshape(n_rep, n_one, 3) - offsets
-            q = q.reshape(n_rep, n_one, 4)
+        tc, tq, et = layout.unplace_rows(tc, tq, et, offsets)
+        c, q = layout.unplace_state(c, q, offsets)
         n_saved = 0 if tc is None else tc.shape[0]
         traj = SimulatorTrajectory(
             center=tc if tc is not None else c[None][:0],

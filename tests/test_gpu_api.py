@@ -289,6 +289,63 @@ def test_simulator_batches_independent_replicas_in_one_launch():
         dc.replace(sim, energy_fn=mod.create_default_energy_fn(top, box_disp), space=(box_disp, box_shift)).run({}, init, 5, key=1)
 
 
+def _helix_simulator(pairs, ef=None):
+    """fp64 simulator of the 16-nt oxDNA2 helix on an explicit pair list, and its initial state."""
+    from mythos_amd.simulators.hip_md import HipMDSimulator, StaticSimulatorParams, nvt_langevin
+    from mythos_amd.simulators.neighbors import NoNeighborList
+
+    top, traj, _, _, mod, _, _, _ = _setup(2, "simple-helix")
+    disp, shift = space.free()
+    params = StaticSimulatorParams(seq=top.seq, mass=(1.0, (1.0, 1.0, 1.0)), gamma=(KT / 2.5, KT / 7.5),
+                                   bonded_neighbors=top.bonded_neighbors, checkpoint_every=0, dt=5e-3, kT=KT)
+    sim = HipMDSimulator(energy_fn=mod.create_default_energy_fn(top, disp) if ef is None else ef, simulator_params=params, space=(disp, shift),
+                         simulator_init=nvt_langevin, neighbors=NoNeighborList(unbonded_nbrs=pairs), dtype=torch.float64)
+    return sim, _states(traj)[0]
+
+
+def _four_steps(sim, init):
+    tr = sim.run({}, init, 4, key=7).observables[0]
+    return tr.center, tr.orientation.vec
+
+
+def test_equal_pair_lists_share_one_kept_entry():
+    """The simulator keys an explicit pair list by content: a second, equal array finds the kept system and integrator."""
+    pairs = np.array(H.load_golden(2, "simple-helix")[0].unbonded_neighbors)
+    sim, init = _helix_simulator(pairs)
+    _four_steps(sim, init)
+    sim.neighbors.unbonded_nbrs = pairs.copy()
+    second = _four_steps(sim, init)
+    assert len(sim._resident) == 1
+    fresh = _four_steps(_helix_simulator(pairs.copy())[0], init)
+    assert torch.equal(second[0], fresh[0]) and torch.equal(second[1], fresh[1])
+
+
+def test_pair_list_mutated_in_place_is_seen():
+    """Base pair (3, 12) leaves the list in place (an entry past the last nucleotide is padding): the next run steps on the
+    new list, not on the rows kept from the old one."""
+    top = H.load_golden(2, "simple-helix")[0]
+    pairs = np.array(top.unbonded_neighbors)
+    sim, init = _helix_simulator(pairs)
+    before = _four_steps(sim, init)
+    drop = ((pairs[:, 0] == 3) & (pairs[:, 1] == 12)) | ((pairs[:, 0] == 12) & (pairs[:, 1] == 3))
+    assert drop.sum() == 1
+    pairs[drop] = top.n_nucleotides
+    mutated = _four_steps(sim, init)
+    fresh = _four_steps(_helix_simulator(pairs[~drop])[0], init)
+    assert torch.equal(mutated[0], fresh[0]) and torch.equal(mutated[1], fresh[1])
+    assert not torch.equal(mutated[0], before[0])
+
+
+def test_simulator_refuses_a_repeated_term_before_any_launch():
+    top, _, _, _, mod, _, _, _ = _setup(2, "simple-helix")
+    ef = mod.create_default_energy_fn(top, space.free()[0])
+    twice = ef + ef.energy_fns[2]
+    sim, init = _helix_simulator(np.array(top.unbonded_neighbors), ef=twice)
+    with pytest.raises(ValueError, match="appears twice"):
+        sim.run({}, init, 4, key=7)
+    assert sim._resident == {}
+
+
 def test_sequence_dependent_energy_function_from_the_references_file():
     """The drop-in route to sequence-dependent weights, as a user of the reference takes it: `read_ss_weights(file)` into
     `with_params` of the default oxDNA2 energy function (mythos/input/sequence_dependence.py:12-51), evaluated with `map` over
