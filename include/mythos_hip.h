@@ -153,6 +153,23 @@ int mythos_oxdna_neighbor_stats(mythos_system_t* sys, int* max_row, double* mean
 int mythos_oxdna_energy(mythos_system_t* sys, const void* center, const void* quat, int n_frames, double* e_terms,
                         void* dU_dcenter, void* dU_dquat, double* dU_dparams, mythos_stream_t stream);
 
+/* Debye-Hueckel energy of n_frames configurations at n_kt temperatures: the part of a temperature sweep of the energy
+ * that is not a host-side scale of one ordinary energy call.  Replaces the Debye term of the reference's
+ * vmap(lambda kt: energy_fn.with_params(kt=kt).map(trajectory)) (mythos/observables/melting_temp.py:127-140,
+ * mythos/energy/dna2/debye.py:47-110): every backbone-backbone distance is computed once and the n_kt constant sets are
+ * evaluated on it.  Uses the system's current neighbour rows, box, precision, end flags and DH_HALF_CHARGED_ENDS; the
+ * term weight is not applied (row t at the system's own constants equals e_terms[:, 7] of mythos_oxdna_energy).
+ *   center, quat  as mythos_oxdna_energy
+ *   dh_consts     host double[n_kt][MYTHOS_DEBYE_SWEEP_CONSTS]: DH_KAPPA, DH_PREFACTOR, DH_BSMOOTH, DH_RCUT, DH_RHIGH
+ *   e_dh          dev double[n_kt][n_frames]
+ *   de_dconsts    dev double[n_kt][n_frames][MYTHOS_DEBYE_SWEEP_CONSTS] or NULL: partials with respect to the constants
+ *                 (the DH_* columns of dU_dparams at each temperature, without the term weight)
+ * Models 2 (oxDNA2) and 3 (oxRNA2); model 1 has no such term and model 4 (oxNA: three constant sets per temperature) is
+ * refused with MYTHOS_ERR_INVALID_ARGUMENT.  n_frames = 0 or n_kt = 0 returns MYTHOS_OK.  Reproducible bit for bit. */
+#define MYTHOS_DEBYE_SWEEP_CONSTS 5
+int mythos_oxdna_debye_sweep(mythos_system_t* sys, const void* center, const void* quat, int n_frames, int n_kt,
+                             const double* dh_consts, double* e_dh, double* de_dconsts, mythos_stream_t stream);
+
 /* ---- per-frame structural observables ------------------------------------------------------------
  * Replaces mythos/observables/propeller.py:19-71, pitch.py:33-102, rise.py:21-80 and the per-state part of
  * persistence_length.py:47-91, 168-185 (base.py:24-66 for the local helical axis and the quartets).

@@ -120,6 +120,9 @@ struct mythos_system {
   // energy-pass scratch
   mythos::DeviceBuf<double> d_epart;   // [frames_chunk][blocks][8]
   mythos::DeviceBuf<double> d_pgpart;  // [frames_chunk][blocks][OXP_COUNT]
+  // temperature-sweep scratch (debye_sweep.hip)
+  mythos::DeviceBuf<double> d_sweep_consts;  // [n_kt][5] the caller's constant table
+  mythos::DeviceBuf<double> d_sweep_part;    // [frames_chunk][tiles][n_kt_chunk][1 or 6]
 
   // the members free themselves, on the system's device
   ~mythos_system() { (void)hipSetDevice(device); }

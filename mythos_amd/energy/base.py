@@ -311,6 +311,85 @@ class _EnergyOp(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------
+# temperature sweep: E_t(f) of every frame at every kT of a range (ComposedEnergyFunction.map_kt)
+# ---------------------------------------------------------------------------------------------
+_K_STCK, _K_DH = TERM_ORDER.index("stacking"), TERM_ORDER.index("debye")
+LAST_MAP_KT: dict = {}  # what the last map_kt call did: path, reason, sweep_launch
+
+
+def _sweep_columns(names):
+    """Columns of the flat vector by how a change of kT reaches them: (STCK_* shape entries, STCK_EPS_ij, the Debye
+    constants of the sweep's table in its order)."""
+    from mythos_amd.energy.flat_params import DEBYE_KT_NAMES
+
+    shape = [i for i, n in enumerate(names) if n.startswith("STCK_") and not n.startswith("STCK_EPS_")]
+    eps = [names.index(f"STCK_EPS_{i}{j}") for i in range(4) for j in range(4)]
+    return shape, eps, [names.index(n) for n in DEBYE_KT_NAMES]
+
+
+class _SweepOp(torch.autograd.Function):
+    """(flat at the function's own kT, STCK_EPS at every kT (T, 16), Debye constants at every kT (T, 5)) -> E (T, F).
+
+    kT enters an oxDNA energy through the stacking strength - one scalar factor of the whole term - and the Debye-Hueckel
+    constants, so  E_t = [the other terms at kT_0] + rho_t stacking_0 + Debye_t  with rho_t = eps_stack(kT_t) / eps_stack(kT_0):
+    one ordinary energy launch (with dU/dparams when a gradient is wanted) and one sweep launch (debye_sweep.hip).
+    Backward hands autograd dE/d(flat) for the entries kT does not reach, and dE/d(STCK_EPS_t), dE/d(Debye constants_t) per
+    temperature; the graphs of those three inputs (flat_params) carry them to the parameters."""
+
+    @staticmethod
+    def forward(ctx, flat, eps_all, consts_all, center, quat, entry, weights, rho, table, model):
+        system = entry["sys"]
+        flat_np = flat.detach().cpu().to(torch.float64)
+        tag = flat_np.numpy().tobytes()
+        if entry["flat"] != tag:
+            system.set_params(flat_np)
+            entry["flat"] = tag
+        need_p = any(t is not None and t.requires_grad for t in (flat, eps_all, consts_all))
+        w = torch.as_tensor(weights, dtype=torch.float64)
+        sweep = model in (2, 3) and float(w[_K_DH]) != 0.0
+        e_dh = de = None
+        if sweep:
+            e_dh, de = system.debye_sweep(center, quat, table, const_grads=need_p)
+        e, _, _, gp = system.energy(center, quat, grads=False, param_grads=need_p)
+        w_rest = w.clone()
+        w_rest[_K_STCK] = w_rest[_K_DH] = 0.0
+        dev = e.device
+        rho_d = torch.as_tensor(rho, dtype=torch.float64, device=dev)
+        total = (e @ w_rest.to(dev))[None, :] + (float(w[_K_STCK]) * rho_d)[:, None] * e[:, _K_STCK][None, :]
+        if sweep:
+            total = total + float(w[_K_DH]) * e_dh
+        ctx.save_for_backward(*(t for t in (gp, de, rho_d) if t is not None))
+        ctx.flags = (need_p, de is not None, float(w[_K_DH]), flat.device, eps_all is not None, consts_all is not None)
+        LAST_MAP_KT["sweep_launch"] = sweep
+        return total
+
+    @staticmethod
+    def backward(ctx, g):
+        need_p, has_de, w_dh, fdev, has_eps, has_consts = ctx.flags
+        if not need_p:
+            return (None,) * 10
+        saved = list(ctx.saved_tensors)
+        gp = saved.pop(0)
+        de = saved.pop(0) if has_de else None
+        rho_d = saved.pop(0)
+        from mythos_amd import _lib
+
+        shape, eps, dh = _sweep_columns(_lib.param_names())
+        g = g.to(gp.dtype)
+        # dU/dflat carries the term weights (the kernel multiplies them in); the stacking term's shape entries scale with rho_t
+        g_flat = g.sum(0) @ gp
+        g_flat[shape] = ((rho_d[:, None] * g).sum(0) @ gp)[shape]
+        g_eps = g @ gp[:, eps] if has_eps else None  # the energy is linear in STCK_EPS_ij: the same partial at every kT
+        g_flat[eps] = 0.0
+        g_flat[dh] = 0.0
+        g_consts = None
+        if has_consts:
+            g_consts = w_dh * (g[:, :, None] * de).sum(1) if has_de else torch.zeros((g.shape[0], 5), dtype=gp.dtype)
+        return (g_flat.to(fdev), None if g_eps is None else g_eps.cpu(), None if g_consts is None else g_consts.cpu(),
+                None, None, None, None, None, None, None)
+
+
+# ---------------------------------------------------------------------------------------------
 # protocol
 # ---------------------------------------------------------------------------------------------
 class EnergyFunction(ABC):
@@ -559,6 +638,75 @@ class ComposedEnergyFunction(EnergyFunction):
         finally:
             entry["observe"] = None
         return total, terms, low.cols
+
+    # -- temperature sweep ----------------------------------------------------------------------------
+    def map_kt_plan(self, body_sequence: RigidBody, low=None) -> tuple[str, str]:
+        """Which way ``map_kt(..., sweep=None)`` evaluates these frames, and why: ("fused" | "per_temperature", reason)."""
+        from mythos_amd.energy.flat_params import _wants_graph, kt_sweep_tables
+        from mythos_amd.energy.lowering import lower
+
+        low = lower(self.energy_fns, self.weights) if low is None else low
+        if low.model == 4:
+            return "per_temperature", "oxNA carries three stacking strengths and three Debye-Hueckel constant sets per temperature"
+        if pseq_tensors(self.energy_fns) is not None:
+            return "per_temperature", "the probabilistic sequence requires a gradient"
+        if body_sequence.center.requires_grad or body_sequence.orientation.vec.requires_grad:
+            return "per_temperature", "the coordinates require a gradient"
+        if _wants_graph(low.sections["geometry"]):
+            return "per_temperature", "the site geometry requires a gradient (its partials are not separable by term)"
+        if low.term_weights[_K_STCK] != 0.0:
+            rho, _ = kt_sweep_tables(low.model, low.sections, [1.0], kt=low.kt, salt_conc=low.salt_conc)
+            if not np.isfinite(rho).all():
+                return "per_temperature", "the stacking strength is zero at the function's own kT"
+        if low.model == 1 or low.term_weights[_K_DH] == 0.0:
+            return "fused", "stacking scale only: no Debye-Hueckel term to sweep"
+        return "fused", "stacking scale and Debye-Hueckel sweep"
+
+    def map_kt(self, body_sequence: RigidBody, kts, *, sweep: str | None = None) -> torch.Tensor:
+        """Energies of every frame at every temperature of ``kts`` (T,), shape (T, n_states), float64: what the reference
+        gets from ``vmap(lambda kt: self.with_params(kt=kt).map(trajectory))(kts)`` (mythos/observables/melting_temp.py:127-140).
+        Differentiable with respect to the parameter tensors the function holds.
+
+        ``sweep="per_temperature"``: that loop, T energy calls.  ``sweep="fused"``: one energy call at the function's own
+        kT, the stacking term scaled per temperature and one launch for the Debye-Hueckel term at all temperatures
+        (``_SweepOp``); refused where the decomposition does not apply, and without gradients with respect to coordinates.
+        ``sweep=None``: fused where it applies (``map_kt_plan``).  ``LAST_MAP_KT`` records what ran."""
+        from mythos_amd.energy.flat_params import _wants_graph, kt_sweep_tables
+        from mythos_amd.energy.lowering import lower
+
+        if sweep not in (None, "fused", "per_temperature"):
+            raise ValueError("sweep must be None, 'fused' or 'per_temperature'")
+        kt_list = [k for k in (kts if isinstance(kts, torch.Tensor) else np.asarray(kts, dtype=np.float64).reshape(-1))]
+        center, quat = body_sequence.center, body_sequence.orientation.vec
+        if center.dim() != 3:
+            raise ValueError("map_kt takes a trajectory: center (n_states, N, 3)")
+        path, reason = sweep, "asked for"
+        low = None
+        if sweep != "per_temperature":
+            low = lower(self.energy_fns, self.weights)
+            planned, why = self.map_kt_plan(body_sequence, low)
+            if sweep == "fused" and planned != "fused":
+                if center.requires_grad or quat.requires_grad:
+                    raise NotImplementedError("map_kt(sweep='fused') has no gradient with respect to coordinates")
+                raise ValueError(f"map_kt(sweep='fused') does not apply: {why}")
+            path, reason = planned, why
+        LAST_MAP_KT.clear()
+        LAST_MAP_KT.update(path=path, reason=reason, sweep_launch=False)
+        if path == "per_temperature":
+            if not kt_list:
+                return torch.zeros((0, center.shape[0]), dtype=torch.float64, device=center.device)
+            return torch.stack([self.with_params(kt=kt).map(body_sequence) for kt in kt_list])
+        entry = _get_system(low, center.dtype, center.device)
+        _apply_pseq(entry, low.pseq)
+        kw = dict(kt=low.kt, salt_conc=low.salt_conc)
+        rho, table = kt_sweep_tables(low.model, low.sections, kts, **kw)
+        eps_all = consts_all = None
+        if _wants_graph(low.sections["stacking"], low.sections.get("debye"), low.kt, low.salt_conc, kts):
+            eps_all, consts_all = kt_sweep_tables(low.model, low.sections, kts, graph=True, **kw)
+            eps_all = eps_all if eps_all.requires_grad else None
+            consts_all = consts_all if (consts_all is not None and consts_all.requires_grad) else None
+        return _SweepOp.apply(low.flat, eps_all, consts_all, center.detach().contiguous(), quat.detach().contiguous(), entry,
+                              low.term_weights, rho, table, low.model)
 
     def compute_terms(self, body: RigidBody) -> torch.Tensor:
         """Energy of each composed function, shape (n_fns,) or (n_states, n_fns) (base.py:312-314)."""

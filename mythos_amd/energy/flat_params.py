@@ -157,6 +157,63 @@ HB_WEIGHTS_SA = torch.tensor(
 )
 
 
+# ---------------------------------------------------------------------------------------------
+# The two places kT enters an oxDNA energy, stated once: ``derive_flat`` uses them for its one temperature and the
+# temperature sweep (``kt_sweep_tables``, ComposedEnergyFunction.map_kt) for many - both broadcast over an array of kT.
+# ---------------------------------------------------------------------------------------------
+def stack_kt_factor(st: dict, st_kt):
+    """s(kT) of the stacking strength eps_stack = s(kT) * table: the table is all ones and s = eps_stack_base +
+    eps_stack_kt_coeff kT (dna1/stacking.py:163-165), or the table is ``ss_stack_weights`` and s = 1 - c + 9 c kT
+    (sequence-specific weights, fitted at kT = 0.1)."""
+    if st.get("ss_stack_weights") is None:
+        return st["eps_stack_base"] + st["eps_stack_kt_coeff"] * st_kt
+    return 1.0 - st["eps_stack_kt_coeff"] + (st_kt * 9.0 * st["eps_stack_kt_coeff"])
+
+
+DEBYE_KT_NAMES = ("DH_KAPPA", "DH_PREFACTOR", "DH_BSMOOTH", "DH_RCUT", "DH_RHIGH")  # column order of the sweep's constant table
+
+
+def debye_constants(d: dict, d_kt, d_salt, xp=_Torch) -> dict:
+    """The Debye-Hueckel constants of one temperature, or of an array of them (dna2/debye.py:47-64)."""
+    lam = d["lambda_factor"] * xp.sqrt(d_kt / 0.1) / xp.sqrt(d_salt)
+    r_high = 3.0 * lam
+    pref = d["prefactor_coeff"] * d["q_eff"] ** 2
+    v = pref * xp.exp(-r_high / lam) / r_high
+    dv = -v * (1.0 / lam + 1.0 / r_high)
+    bsm, r_cut = c1_match(r_high, v, dv)
+    return dict(DH_KAPPA=1.0 / lam, DH_PREFACTOR=pref, DH_BSMOOTH=bsm, DH_RCUT=r_cut, DH_RHIGH=r_high)
+
+
+def kt_sweep_tables(model: int, sections: dict, kts, *, kt, salt_conc=0.5, graph: bool = False):
+    """What a sweep of the energy over the temperatures ``kts`` (T,) needs besides one evaluation at the function's own
+    temperature: ``(rho, table)`` with rho[t] = s(kts[t]) / s(kT_0) the ratio of the stacking strengths (kT_0: the
+    stacking section's own ``kt``, else ``kt``) and table[t] the five Debye-Hueckel constants at kts[t] in the order
+    ``DEBYE_KT_NAMES`` (None for oxDNA1).  ``sections``, ``kt``, ``salt_conc`` as ``derive_flat`` takes them.
+    ``graph=False``: numpy float64 arrays.  ``graph=True``: instead ``(eps, table)`` as torch tensors that carry the
+    autograd graph of the parameters - eps (T, 16) the stacking strengths STCK_EPS_ij at every temperature."""
+    xp = _Torch if graph else _Numpy
+    conv = lambda sec: {k: (xp.t(v) if v is not None else None) for k, v in sections[sec].items()}  # noqa: E731
+    kts = xp.t(kts)
+    st = conv("stacking")
+    st_kt0 = st.get("kt")
+    st_kt0 = xp.t(kt) if st_kt0 is None else st_kt0
+    s_t = stack_kt_factor(st, kts)
+    if graph:
+        w = _t(STACK_WEIGHTS_SA) if st.get("ss_stack_weights") is None else st["ss_stack_weights"]
+        first = (s_t * torch.ones_like(kts))[:, None] * w.reshape(1, 16)
+    else:
+        first = s_t / stack_kt_factor(st, st_kt0) * np.ones_like(kts)
+    table = None
+    if model in (2, 3):
+        d = conv("debye")
+        d_salt = d.get("salt_conc")
+        d_salt = xp.t(salt_conc) if d_salt is None else d_salt
+        named = debye_constants(d, kts, d_salt, xp)
+        cols = [named[n] * (torch.ones_like(kts) if graph else np.ones_like(kts)) for n in DEBYE_KT_NAMES]
+        table = torch.stack(cols, dim=1) if graph else np.stack(cols, axis=1)
+    return first, table
+
+
 TERM_WEIGHT_NAMES = ("TW_FENE", "TW_BEXC", "TW_STCK", "TW_NEXC", "TW_HB", "TW_CRST", "TW_CXST", "TW_DH")
 
 
@@ -246,10 +303,7 @@ def derive_flat(
             _f4_block(f"STCK_TH{k}", zero, _t(0.5), _t(1.0), out)
     for k in (1, 2):
         _f5_block(f"STCK_PHI{k}", st[f"neg_cos_phi{k}_star_stack"], st[f"a_stack_{k}"], out)
-    if st.get("ss_stack_weights") is None:
-        eps_stack = (st["eps_stack_base"] + st["eps_stack_kt_coeff"] * st_kt) * _t(STACK_WEIGHTS_SA)
-    else:
-        eps_stack = st["ss_stack_weights"] * (1.0 - st["eps_stack_kt_coeff"] + (st_kt * 9.0 * st["eps_stack_kt_coeff"]))
+    eps_stack = stack_kt_factor(st, st_kt) * (_t(STACK_WEIGHTS_SA) if st.get("ss_stack_weights") is None else st["ss_stack_weights"])
 
     # hydrogen bonding (dna1/hydrogen_bonding.py:148-223)
     hb = S["hydrogen_bonding"]
@@ -292,16 +346,7 @@ def derive_flat(
         d_salt = _t(salt_conc) if d_salt is None else d_salt
         hce = d.get("half_charged_ends")
         hce = half_charged_ends if hce is None else bool(hce)
-        lam = d["lambda_factor"] * xp.sqrt(d_kt / 0.1) / xp.sqrt(d_salt)
-        r_high = 3.0 * lam
-        pref = d["prefactor_coeff"] * d["q_eff"] ** 2
-        v = pref * xp.exp(-r_high / lam) / r_high
-        dv = -v * (1.0 / lam + 1.0 / r_high)
-        bsm, r_cut = c1_match(r_high, v, dv)
-        out.update(
-            DH_KAPPA=1.0 / lam, DH_PREFACTOR=pref, DH_BSMOOTH=bsm, DH_RCUT=r_cut, DH_RHIGH=r_high,
-            DH_HALF_CHARGED_ENDS=_t(1.0 if hce else 0.0),
-        )
+        out.update(debye_constants(d, d_kt, d_salt, xp), DH_HALF_CHARGED_ENDS=_t(1.0 if hce else 0.0))
     else:
         out.update(
             DH_KAPPA=_t(1.0), DH_PREFACTOR=zero, DH_BSMOOTH=zero, DH_RCUT=zero, DH_RHIGH=zero,

@@ -38,6 +38,10 @@ class Lowered:
     is_rna: np.ndarray | None  # oxNA only
     box: np.ndarray | None
     pseq: tuple | None  # pseq_request: (marginals, unit, bp_probs, terms)
+    # what the flat vector was derived from (a temperature sweep derives its kT-dependent entries again, map_kt)
+    sections: dict | None = None  # derive_flat's sections, defaults filled in; None for oxNA (three sets)
+    kt: Any = None  # of a section that carries none of its own
+    salt_conc: Any = None
 
 
 def lower(energy_fns, weights, *, kt_default=None) -> Lowered:
@@ -94,4 +98,5 @@ def lower(energy_fns, weights, *, kt_default=None) -> Lowered:
     return Lowered(model=model, flat=flat, term_weights=term_w, cols=cols, seq=seq,
                    is_end=None if first.is_end is None else _np(first.is_end), bonded=_np(first.bonded_neighbors),
                    unbonded=first.unbonded_neighbors, is_rna=nt_type == int(NucleotideType.RNA) if na1 else None,
-                   box=getattr(first.displacement_fn, "box", None), pseq=pseq_request(energy_fns))
+                   box=getattr(first.displacement_fn, "box", None), pseq=pseq_request(energy_fns), sections=sections, kt=kt,
+                   salt_conc=kw["salt_conc"])

@@ -200,6 +200,31 @@ class OxdnaSystem(_lib.Handle):
         return e, gc, gq, gp
 
 
+    def debye_sweep(self, center, quat, table, *, const_grads=False):
+        """Debye-Hueckel energy of every frame at every row of ``table`` (T, 5) [kappa, prefactor, bsmooth, rcut, rhigh]
+        (mythos_oxdna_debye_sweep): (e_dh (T, F) float64, de/dconstants (T, F, 5) or None).  oxDNA2 and oxRNA2 systems."""
+        c = self._check(center, (self.n, 3), "center")
+        q = self._check(quat, (self.n, 4), "quat")
+        if c.dim() == 2:
+            c, q = c[None], q[None]
+        nf = c.shape[0]
+        if q.shape[0] != nf:
+            raise ValueError("center and quat disagree on the number of frames")
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] != 5:
+            raise ValueError("table must have shape (T, 5)")
+        nt = int(table.shape[0])
+        e = torch.empty((nt, nf), dtype=torch.float64, device=self.device)
+        de = torch.empty((nt, nf, 5), dtype=torch.float64, device=self.device) if const_grads else None
+        self._sweep_table = table  # (kept until the next call: the library copies it in stream order)
+        _lib.check(
+            self._lib.mythos_oxdna_debye_sweep(self._h, _lib.ptr(c), _lib.ptr(q), nf, nt, table.ctypes.data_as(_lib.c_double_p),
+                                               _lib.ptr(e), _lib.ptr(de), _lib.stream(self.device)),
+            "debye_sweep",
+        )
+        return e, de
+
+
 def _touched(*tensors) -> None:
     """The library has just written into these caller tensors through raw pointers: bump torch's version counters, so that
     anything keyed on them (the fused-observable rows of mythos_amd/observables/base.py) sees the change."""
