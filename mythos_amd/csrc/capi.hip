@@ -195,7 +195,7 @@ int mythos_oxdna_set_pseq(mythos_system_t* s, const double* marginals, const int
   MYTHOS_HIP_TRY(hipDeviceSynchronize());  // no kernel in flight reads a half-written table
   if (terms == 0) {
     s->pseq_terms = 0;
-    ++s->list_epoch;  // integrators drop forces cached from the old distribution (the unfused oxNA path keeps some)
+    ++s->list_epoch;  // integrators drop forces cached from the old distribution (the unfused oxNA path keeps some: UnfusedState::forces_valid)
     return MYTHOS_OK;
   }
   const int n = s->n;

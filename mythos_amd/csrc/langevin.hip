@@ -5,7 +5,10 @@
 
 #include "langevin_core.inc"
 
-MYTHOS_MD_DEFINE_PRECISION(float)
+namespace {
+// the entry points of the system's precision: this unit's own, or langevin_f64.hip's
+MdEntries md_entries_of(const mythos_sim* s) { return s->sys->dtype == MYTHOS_F32 ? md_entries<float>() : md_entries_f64(); }
+}  // namespace
 
 extern "C" {
 
@@ -61,8 +64,7 @@ int mythos_langevin_init_momenta(mythos_sim_t* s, void* p_lin, void* p_ang, myth
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
-  return s->sys->dtype == MYTHOS_F32 ? mythos_md_init_momenta<float>(s, p_lin, p_ang, (hipStream_t)stream)
-                                     : mythos_md_init_momenta<double>(s, p_lin, p_ang, (hipStream_t)stream);
+  return md_entries_of(s).init_momenta(s, p_lin, p_ang, (hipStream_t)stream);
 }
 
 namespace {
@@ -105,12 +107,12 @@ int md_ready(mythos_sim_t* s, const char* who) {
 // the tests hold the first to.  The choice is made when a state is loaded and holds while that state is resident.
 
 int md_load(mythos_sim_t* s, void* c, void* q, void* p, void* l, hipStream_t st) {
-  s->unfused = s->want_unfused && s->sys->model == 4;
-  return s->sys->dtype == MYTHOS_F32 ? mythos_md_load<float>(s, c, q, p, l, st) : mythos_md_load<double>(s, c, q, p, l, st);
+  s->unfused.active = s->unfused.want && s->sys->model == 4;
+  return md_entries_of(s).load(s, c, q, p, l, st);
 }
 
 int md_advance(mythos_sim_t* s, int n_steps, int save_every, bool close, void* tc, void* tq, double* e_trace, hipStream_t st) {
-  if (s->ext_count > 0 && s->unfused) {
+  if (s->ext_count > 0 && s->unfused.active) {
     set_error("mythos_langevin_run / advance: external forces are not applied on the unfused oxNA path "
               "(MYTHOS_LANGEVIN_UNFUSED); clear them or step through the fused kernel");
     return MYTHOS_ERR_INVALID_ARGUMENT;
@@ -121,12 +123,11 @@ int md_advance(mythos_sim_t* s, int n_steps, int save_every, bool close, void* t
     set_error("mythos_langevin_run / advance: traj_quat must be aligned to 4 elements (" + std::to_string(q_align) + " bytes)");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  return s->sys->dtype == MYTHOS_F32 ? mythos_md_advance<float>(s, n_steps, save_every, close, tc, tq, e_trace, st)
-                                     : mythos_md_advance<double>(s, n_steps, save_every, close, tc, tq, e_trace, st);
+  return md_entries_of(s).advance(s, n_steps, save_every, close, tc, tq, e_trace, st);
 }
 
 int md_store(mythos_sim_t* s, void* c, void* q, void* p, void* l, hipStream_t st) {
-  return s->sys->dtype == MYTHOS_F32 ? mythos_md_store<float>(s, c, q, p, l, st) : mythos_md_store<double>(s, c, q, p, l, st);
+  return md_entries_of(s).store(s, c, q, p, l, st);
 }
 
 }  // namespace
@@ -281,7 +282,7 @@ int mythos_langevin_set_option(mythos_sim_t* s, int option, int64_t value) {
     set_error("mythos_langevin_set_option: the unfused path exists for oxNA systems (model 4) only");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  s->want_unfused = value == 1;
+  s->unfused.want = value == 1;
   return MYTHOS_OK;
 }
 

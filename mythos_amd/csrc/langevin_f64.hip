@@ -2,4 +2,6 @@
 // precision).  Compiled without machine LICM (Makefile: LANGEVIN_F64_FLAGS), which the fp32 unit keeps.
 #include "langevin_core.inc"
 
-MYTHOS_MD_DEFINE_PRECISION(double)
+namespace mythos {
+MdEntries md_entries_f64() { return md_entries<double>(); }
+}

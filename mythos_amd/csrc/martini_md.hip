@@ -4,7 +4,7 @@
 // (mythos/simulators/gromacs/) and only re-evaluates energies (mythos/energy/martini/m2/*.py).  This file
 // is the device-resident counterpart for the same force field: shifted-cut-off Lennard-Jones over a Verlet
 // list, harmonic bonds, G96 / harmonic angles (the terms of martini_terms.h, as in martini.hip), and the BAOAB
-// Langevin splitting used for oxDNA (langevin_core.inc) specialised to point particles:
+// Langevin splitting used for oxDNA (langevin_step.h) specialised to point particles:
 //   B  v += h F / m      A  x += h v      O  v = c1 v + sqrt(kT (1 - c1^2) / m) xi,  c1 = exp(-gamma dt)
 // Units are GROMACS': nm, ps, amu, kJ/mol (1 kJ/mol = 1 amu nm^2 / ps^2), kT = 0.0083144626 T.
 //
@@ -72,7 +72,7 @@ struct MmConst {
   int n_types, angle_kind;
 };
 
-// Wave priority by phase (see md_step_kernel, langevin_core.inc): MYTHOS_MM_PRIO_MAP = three decimal digits, the s_setprio
+// Wave priority by phase (see md_step_kernel, langevin_step.h): MYTHOS_MM_PRIO_MAP = three decimal digits, the s_setprio
 // level of the row loop, the bonded lists, and everything behind the barrier (0 = no s_setprio)
 // (20 480 beads: 64.7 k -> 65.3 k steps/s with 310)
 #ifndef MYTHOS_MM_PRIO_MAP
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
   }
   // ---- integrator prologue, before the barrier: the integrating wavefront draws its thermostat noise and fetches
   //      position, velocity and list reference here, so the tail of the kernel behind the barrier is arithmetic only
-  //      (the oxDNA step kernel's arrangement, langevin_core.inc).  pin_vgpr keeps the values on this side of the barrier.
+  //      (the oxDNA step kernel's arrangement, langevin_step.h).  pin_vgpr keeps the values on this side of the barrier.
   const int int_wave = (bid >> 2) & (kMmBlock / 64 - 1) & 3;
   const int il = threadIdx.x & 63;
   const int ib = bid * PPB + il;
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
     vel[ib] = V4{v[0], v[1], v[2], im};
     if constexpr (!SAVE) {
       // positions-only trajectory (e_trace == NULL): the launch that produces x_{k+1} writes it to the caller's row too
-      // (md_step_kernel does the same, langevin_core.inc) - no energy-trace instantiation, no reduction, no closing launch
+      // (md_step_kernel does the same, langevin_step.h) - no energy-trace instantiation, no reduction, no closing launch
       if (traj) traj[3 * (size_t)ib] = x[0], traj[3 * (size_t)ib + 1] = x[1], traj[3 * (size_t)ib + 2] = x[2];
     }
   }

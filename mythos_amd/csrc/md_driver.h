@@ -1,5 +1,5 @@
 // The host loop that drives a Langevin step kernel over the resident state, shared by the oxDNA integrator
-// (langevin_core.inc) and the MARTINI one (martini_md.hip): per-run state, the segmented launch loop with its
+// (advance_typed, langevin_core.inc) and the MARTINI one (martini_md.hip): per-run state, the segmented launch loop with its
 // halt / rebuild / resume protocol, HIP-event timing, and the two small kernels behind it.
 #ifndef MYTHOS_MD_DRIVER_H
 #define MYTHOS_MD_DRIVER_H

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mythos_hip.h"
@@ -153,6 +154,23 @@ template <>
 inline const float* device_params_of<float>(const mythos_system* s) { return s->d_pf.get(); }
 template <>
 inline const double* device_params_of<double>(const mythos_system* s) { return s->d_pd.get(); }
+
+// A run-time model number, or a run-time switch, as the compile-time tag a kernel template takes: f is a generic lambda and
+// is called with std::integral_constant<int, M>, M = 1 ... 4 (the entry points checked the range; 2 otherwise), or with
+// std::true_type / std::false_type.
+template <class F>
+auto with_model(int model, F&& f) {
+  switch (model) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 2>{});
+  }
+}
+template <class F>
+auto with_bool(bool on, F&& f) {
+  return on ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // d_row_len holds three arrays back to back: row length [n] | bonded partners [n][ROW_BONDED_SLOTS] | end of the
 // "close" segment of the row [n]

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kBlock, (energy_blocks_per_cu<R, MODE, MODEL>())) v
   // fp64 with parameter partials: the radial sums are parked in LDS across the angular stage (gather_row, PARK)
   constexpr bool kPark = sizeof(R) == 8 && MODE >= (MODEL == 4 ? MYTHOS_EN_PARK_FROM_NA1 : MYTHOS_EN_PARK_FROM);
   __shared__ R park_lds[kPark ? PPB : 1][kParkWidth];
-  // parameters through the constant address space: scalar loads at the point of use (langevin_core.inc has the
+  // parameters through the constant address space: scalar loads at the point of use (langevin_step.h has the
   // measurements: by value in the kernel-argument segment they were spilled to scratch, from LDS they cost VGPRs)
   // (+ the probabilistic sequence, if one is set: a uniform branch at the two sequence-weight lookups)
   // (oxNA, MODEL 4: three vectors one after the other - oxDNA2, oxRNA2, hybrid; a probabilistic sequence reaches the
@@ -434,33 +434,21 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
   return 0;
 }
 
-// per-precision entry point: defined (explicitly specialised) in the translation unit of its precision
+// Per-precision entry point: a template here, used by name in the translation unit of its precision alone
+// (oxdna_kernels.hip: float, oxdna_kernels_f64.hip: double, as oxdna_energy_launch_f64), so neither unit holds a kernel of
+// the other's.
+// 8 lanes per nucleotide = 32 nucleotides per workgroup (half the wavefronts of 16 lanes for the same rows, and the
+// short angular lists fill 8 lanes better than 16).  Rows of any length: the walk is segmented (gather_row), so the
+// reference's all-pairs lists of a 1 000-nt system (997 entries per row) go through the same kernel.
 template <typename R>
-int oxdna_energy_launch_typed(mythos_system* sys, const void* center, const void* quat, int n_frames, double* e_terms, void* dU_dcenter,
-                              void* dU_dquat, double* dU_dparams, mythos_obs* oset, double* obs_out, hipStream_t stream);
-
-#define MYTHOS_ENERGY_DEFINE_PRECISION(R)                                                                                       \
-  template <>                                                                                                                    \
-  int oxdna_energy_launch_typed<R>(mythos_system * sys, const void* center, const void* quat, int n_frames, double* e_terms,     \
-                                   void* dU_dcenter, void* dU_dquat, double* dU_dparams, mythos_obs* oset, double* obs_out,      \
-                                   hipStream_t stream) {                                                                         \
-    /* 8 lanes per nucleotide = 32 nucleotides per workgroup (half the wavefronts of 16 lanes for the same rows, and the */     \
-    /* short angular lists fill 8 lanes better than 16).  Rows of any length: the walk is segmented (gather_row), so the */     \
-    /* reference's all-pairs lists of a 1 000-nt system (997 entries per row) go through the same kernel.               */     \
-    switch (sys->model) {                                                                                                        \
-      case 1:                                                                                                                    \
-        return launch_typed<R, 1, 8>(sys, (const R*)center, (const R*)quat, n_frames, e_terms, (R*)dU_dcenter, (R*)dU_dquat,     \
-                                     dU_dparams, oset, obs_out, stream);                                                         \
-      case 3:                                                                                                                    \
-        return launch_typed<R, 3, 8>(sys, (const R*)center, (const R*)quat, n_frames, e_terms, (R*)dU_dcenter, (R*)dU_dquat,     \
-                                     dU_dparams, oset, obs_out, stream);                                                         \
-      case 4:                                                                                                                    \
-        return launch_typed<R, 4, 8>(sys, (const R*)center, (const R*)quat, n_frames, e_terms, (R*)dU_dcenter, (R*)dU_dquat,     \
-                                     dU_dparams, oset, obs_out, stream);                                                         \
-      default:                                                                                                                   \
-        return launch_typed<R, 2, 8>(sys, (const R*)center, (const R*)quat, n_frames, e_terms, (R*)dU_dcenter, (R*)dU_dquat,     \
-                                     dU_dparams, oset, obs_out, stream);                                                         \
-    }                                                                                                                            \
-  }
+static int oxdna_energy_launch_typed(mythos_system* sys, const void* center, const void* quat, int n_frames, double* e_terms, void* dU_dcenter,
+                                     void* dU_dquat, double* dU_dparams, mythos_obs* oset, double* obs_out, hipStream_t stream) {
+  return with_model(sys->model, [&](auto m) {
+    return launch_typed<R, decltype(m)::value, 8>(sys, (const R*)center, (const R*)quat, n_frames, e_terms, (R*)dU_dcenter, (R*)dU_dquat,
+                                                  dU_dparams, oset, obs_out, stream);
+  });
+}
+int oxdna_energy_launch_f64(mythos_system* sys, const void* center, const void* quat, int n_frames, double* e_terms, void* dU_dcenter,
+                            void* dU_dquat, double* dU_dparams, mythos_obs* oset, double* obs_out, hipStream_t stream);  // oxdna_kernels_f64.hip
 
 }  // namespace mythos

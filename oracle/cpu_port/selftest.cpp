@@ -10,6 +10,8 @@
 // evaluated and stepped once with G96 and once with harmonic angles.
 // `--device-buf` instead of a file: the owning buffer type of the library (mythos_amd/csrc/device_buf.h) over the shim's
 // malloc-backed runtime; prints what was read back and, after every scope, the live allocations (the test wants 0).
+// `--md-plan`: the launch plan of the oxDNA step kernel (mythos_amd/csrc/md_plan.h) for a fixed table of systems, one line
+// each: lanes per nucleotide, then nucleotides per workgroup, workgroups, grid, the DENSE choice and the priority switch.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +21,7 @@
 #include <vector>
 
 #include "device_buf.h"
+#include "md_plan.h"
 
 namespace mythos {
 static std::string g_error;
@@ -179,9 +182,36 @@ static int device_buf_case() {
   return shim_live_allocations() == 0 ? 0 : 60;
 }
 
+// md_plan.h at the sizes where a choice changes (the thresholds are in workgroups per CU, so they move with `cus`)
+static int md_plan_case() {
+  struct Row {
+    int n, cus, real_bytes, debug_lanes, debug_dense;
+  };
+  const Row rows[] = {
+      // lanes: 16 up to 6 144 nt on 256 CUs, the override wins at either size
+      {6144, 256, 4, 0, 0}, {6145, 256, 4, 0, 0}, {6144, 256, 4, 8, 0}, {6145, 256, 4, 16, 0}, {64, 256, 4, 0, 0},
+      // DENSE: fp32, 8 lanes, more than four workgroups per CU; forced and forbidden; never fp64, never 16 lanes
+      {32768, 256, 4, 0, 0}, {32769, 256, 4, 0, 0}, {32769, 256, 8, 0, 0}, {64, 256, 4, 8, 1}, {32769, 256, 4, 0, 2},
+      {64, 256, 4, 16, 1}, {32769, 256, 4, 16, 0}, {32769, 256, 8, 0, 1},
+      // priority: off for fp64 grids of more than three workgroups per CU
+      {24000, 256, 8, 0, 0}, {24577, 256, 8, 0, 0}, {24577, 256, 4, 0, 0},
+      // another device: 304 CUs move every threshold
+      {6145, 304, 4, 0, 0}, {7296, 304, 4, 0, 0}, {7297, 304, 4, 0, 0}, {32769, 304, 4, 0, 0}, {38913, 304, 4, 0, 0},
+      {24577, 304, 8, 0, 0}, {29185, 304, 8, 0, 0},
+  };
+  for (const Row& r : rows) {
+    const int lanes = mythos::md_lanes_for(r.n, r.cus, r.debug_lanes);
+    const mythos::MdPlan p = mythos::md_plan_for(r.n, lanes, r.cus, (size_t)r.real_bytes, r.debug_dense);
+    printf("MDPLAN n %d cus %d fp%d dbg_lanes %d dbg_dense %d -> lanes %d ppb %d blocks %d grid %d dense %d prio %d\n", r.n, r.cus,
+           8 * r.real_bytes, r.debug_lanes, r.debug_dense, lanes, p.ppb, p.blocks, p.grid, p.dense_grid ? 1 : 0, p.prio_on);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
   if (std::string(argv[1]) == "--device-buf") return device_buf_case();
+  if (std::string(argv[1]) == "--md-plan") return md_plan_case();
   FILE* f = fopen(argv[1], "rb");
   if (!f) return 2;
   const auto hdr = rd<int32_t>(f, 6);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""dev: the oxNA MD loop alone (for rocprofv3 --kernel-trace --stats; MYTHOS_NA1_UNFUSED=1 for the two-launch path): 1 500
+"""dev: the oxNA MD loop alone (for rocprofv3 --kernel-trace --stats; LangevinIntegrator.set_unfused() selects the two-launch path): 1 500
 replicas of the DNA-RNA golden helix."""
 import sys
 import time

@@ -301,6 +301,52 @@ def test_sanitizers_are_clean_and_agree_with_the_plain_build(tmp_path):
     assert partial.startswith("DEVBUF partial rc -2 a 1 b 1 c 0 d 0 held 2: HIP error: out of memory")
 
 
+def test_md_launch_plan_boundaries():
+    """Which md_step_kernel instantiation a launch takes (mythos_amd/csrc/md_plan.h: lanes per nucleotide, grid, DENSE, wave
+    priority) at the sizes where the choice changes.  All instantiations compute the same numbers, so a wrong choice fails
+    no parity test and only loses speed; these lines are what holds the policy.  Printed by the stand-alone programs, the
+    plain and the sanitizer build alike.  Expected values by hand from the thresholds: 16 lanes while 2 ceil(n / 16) <= 3 CUs;
+    DENSE (fp32, 8 lanes only) above 4 workgroups per CU; priority off for fp64 above 3 per CU; grid = workgroups padded to 8."""
+    plain, san = cpu_port.BUILD / "md_cpu_selftest", cpu_port.BUILD / "md_cpu_selftest_san"
+    if not san.exists():
+        subprocess.run(["make", "-C", str(cpu_port.BUILD.parent)], check=True, capture_output=True)
+    want = {  # (n, cus, fp bits, debug lanes, debug dense): (lanes, nucleotides per workgroup, workgroups, grid, dense, prio)
+        (6144, 256, 32, 0, 0): (16, 16, 384, 384, 0, 1),
+        (6145, 256, 32, 0, 0): (8, 32, 193, 200, 0, 1),
+        (6144, 256, 32, 8, 0): (8, 32, 192, 192, 0, 1),  # the override wins at either size
+        (6145, 256, 32, 16, 0): (16, 16, 385, 392, 0, 1),
+        (64, 256, 32, 0, 0): (16, 16, 4, 8, 0, 1),
+        (32768, 256, 32, 0, 0): (8, 32, 1024, 1024, 0, 1),
+        (32769, 256, 32, 0, 0): (8, 32, 1025, 1032, 1, 1),
+        (32769, 256, 64, 0, 0): (8, 32, 1025, 1032, 0, 0),  # fp64: never dense
+        (64, 256, 32, 8, 1): (8, 32, 2, 8, 1, 1),  # forced
+        (32769, 256, 32, 0, 2): (8, 32, 1025, 1032, 0, 1),  # forbidden
+        (64, 256, 32, 16, 1): (16, 16, 4, 8, 0, 1),  # 16 lanes: never dense, even forced
+        (32769, 256, 32, 16, 0): (16, 16, 2049, 2056, 0, 1),
+        (32769, 256, 64, 0, 1): (8, 32, 1025, 1032, 0, 0),
+        (24000, 256, 64, 0, 0): (8, 32, 750, 752, 0, 1),
+        (24577, 256, 64, 0, 0): (8, 32, 769, 776, 0, 0),
+        (24577, 256, 32, 0, 0): (8, 32, 769, 776, 0, 1),
+        (6145, 304, 32, 0, 0): (16, 16, 385, 392, 0, 1),  # 304 CUs: every threshold moves
+        (7296, 304, 32, 0, 0): (16, 16, 456, 456, 0, 1),
+        (7297, 304, 32, 0, 0): (8, 32, 229, 232, 0, 1),
+        (32769, 304, 32, 0, 0): (8, 32, 1025, 1032, 0, 1),
+        (38913, 304, 32, 0, 0): (8, 32, 1217, 1224, 1, 1),
+        (24577, 304, 64, 0, 0): (8, 32, 769, 776, 0, 1),
+        (29185, 304, 64, 0, 0): (8, 32, 913, 920, 0, 0),
+    }
+    lines = [
+        f"MDPLAN n {n} cus {cus} fp{bits} dbg_lanes {dl} dbg_dense {dd} -> lanes {v[0]} ppb {v[1]} blocks {v[2]} grid {v[3]} dense {v[4]} prio {v[5]}"
+        for (n, cus, bits, dl, dd), v in want.items()
+    ]
+    env = {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}
+    for exe in (plain, san):
+        r = subprocess.run([str(exe), "--md-plan"], capture_output=True, text=True, env=env, timeout=60)
+        assert r.returncode == 0, (r.stdout, r.stderr[-3000:])
+        assert r.stderr.strip() == "", r.stderr[-3000:]
+        assert r.stdout.splitlines() == lines
+
+
 # ---- MARTINI (oracle/cpu_port/martini_cpu.cpp): bench.py's cpu_baseline of BASELINE configs[2] ------------------
 def _martini_port(angle_kind=0, mass=None):
     from tests import martini_helpers as MH

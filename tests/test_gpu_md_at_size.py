@@ -1,4 +1,4 @@
-"""The MD step kernel (md_step_kernel, mythos_amd/csrc/langevin_core.inc) against a second implementation at the sizes it is
+"""The MD step kernel (md_step_kernel, mythos_amd/csrc/langevin_step.h) against a second implementation at the sizes it is
 benchmarked at, and for every instantiation that ships.
 
  * 1.1 kbp, fp64, device-built cell list + chunk order: five steps against oracle/langevin_oracle.py on the same

@@ -2,7 +2,7 @@
 scan emits ``state.position`` of EVERY step and nothing else; mythos/simulators/io.py:18-60 is what receives it).
 
 With ``e_trace == NULL`` the step launch that produces a saved state writes it to the caller's row as well
-(md_step_kernel, mythos_amd/csrc/langevin_core.inc): no energy-trace instantiation, no reduction launch, no closing launch.
+(md_step_kernel, mythos_amd/csrc/langevin_step.h): no energy-trace instantiation, no reduction launch, no closing launch.
 Held here to three independent routes to the same states, bit for bit:
 
  * the frames ``store`` hands out after single-step ``advance`` calls,
