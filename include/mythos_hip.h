@@ -341,7 +341,8 @@ int mythos_oxdna_write_trajectory(const char* path, int n, int n_frames, const d
  * restores the default.  Nothing in the library reads the environment. */
 enum mythos_debug_key {
   MYTHOS_DEBUG_CELL_BUCKET_CAP = 0, /* places per cell bucket, fixed (no growth): exercises the spill list */
-  MYTHOS_DEBUG_ENERGY_LIST_CAP = 1, /* entries per segment of the energy kernel's row walk (8 ... 192) */
+  MYTHOS_DEBUG_ENERGY_LIST_CAP = 1, /* entries per segment of the energy kernel's row walk (8 ... 192); used by
+                                       tests/test_gpu_energy_shapes.py: rows of 13 - 118 entries in two to fifteen segments */
   MYTHOS_DEBUG_MD_SEGMENT = 2,      /* step launches queued between two looks at the halt word (default 8192) */
   MYTHOS_DEBUG_MD_OVERFLOW_AT = 3,  /* k + 1: the scheduled list rebuild in front of step launch k reports a row
                                        overflow although its rows fit (one shot: cleared when it fires) */
