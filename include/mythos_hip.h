@@ -170,6 +170,31 @@ int mythos_oxdna_energy(mythos_system_t* sys, const void* center, const void* qu
 int mythos_oxdna_debye_sweep(mythos_system_t* sys, const void* center, const void* quat, int n_frames, int n_kt,
                              const double* dh_consts, double* e_dh, double* de_dconsts, mythos_stream_t stream);
 
+/* oxDNA's `bond` and `mindistance` order parameters of n_frames configurations: what an oxDNA umbrella-sampling run
+ * writes per configuration into the order-parameter columns of its energy file, which the reference reads back
+ * (mythos/simulators/oxdna/utils.py:348-384) as the bind_states of mythos/observables/melting_temp.py:109-140.
+ *   bond         number of listed pairs whose hydrogen-bonding energy is < hb_cutoff (oxDNA's HB_CUTOFF is -0.1)
+ *   mindistance  smallest minimum-image distance between the base (hydrogen-bonding) sites of the listed pairs
+ * The hydrogen-bonding energy of a pair is the one mythos_oxdna_energy sums: the system's current parameters, sequence
+ * and sequence-dependent weights, box and precision; the lower index takes the reference's role op_i, so (j, i) gives
+ * what (i, j) gives.  A pair listed twice counts twice.  Needs parameters, not neighbour rows.
+ *   center, quat  as mythos_oxdna_energy
+ *   op_kind       host int32[n_ops]: MYTHOS_OP_BOND or MYTHOS_OP_MINDISTANCE
+ *   op_first      host int32[n_ops + 1]: order parameter k owns pairs[op_first[k] .. op_first[k + 1]); no empty slice
+ *   pairs         host int32[n_pairs][2]: two different nucleotides each
+ *   op_out        dev double[n_frames][n_ops]: the count, or the distance (interfaces are the caller's)
+ *   hb_out        dev double[n_frames][n_pairs] or NULL: hydrogen-bonding energy of every listed pair
+ *   dist_out      dev double[n_frames][n_pairs] or NULL: base-base distance of every listed pair
+ * The lists are kept on the device between calls; a call with other lists first waits for `stream`.  Models 1, 2 and 3;
+ * model 4 (oxNA) and a system with a probabilistic sequence (an expected energy below the cutoff is not oxDNA's order
+ * parameter) are refused with MYTHOS_ERR_INVALID_ARGUMENT.  n_frames = 0 or n_ops = 0 returns MYTHOS_OK.  Reproducible
+ * bit for bit. */
+#define MYTHOS_OP_BOND 0
+#define MYTHOS_OP_MINDISTANCE 1
+int mythos_oxdna_order_params(mythos_system_t* sys, const void* center, const void* quat, int n_frames, int n_ops,
+                              const int32_t* op_kind, const int32_t* op_first, const int32_t* pairs, int n_pairs,
+                              double hb_cutoff, double* op_out, double* hb_out, double* dist_out, mythos_stream_t stream);
+
 /* ---- per-frame structural observables ------------------------------------------------------------
  * Replaces mythos/observables/propeller.py:19-71, pitch.py:33-102, rise.py:21-80 and the per-state part of
  * persistence_length.py:47-91, 168-185 (base.py:24-66 for the local helical axis and the quartets).

@@ -48,6 +48,7 @@ _SIGS = {
     "mythos_oxdna_energy_obs": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
     "mythos_oxdna_energy_dpseq": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
     "mythos_oxdna_debye_sweep": (C.c_int, [V, V, V, C.c_int, C.c_int, c_double_p, V, V, V]),
+    "mythos_oxdna_order_params": (C.c_int, [V, V, V, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, C.c_double, V, V, V, V]),
     "mythos_observables_create": (V, [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, C.c_int, C.c_int]),
     "mythos_observables_destroy": (None, [V]),
     "mythos_observables_width": (C.c_int, [V]),

@@ -124,6 +124,10 @@ struct mythos_system {
   // temperature-sweep scratch (debye_sweep.hip)
   mythos::DeviceBuf<double> d_sweep_consts;  // [n_kt][5] the caller's constant table
   mythos::DeviceBuf<double> d_sweep_part;    // [frames_chunk][tiles][n_kt_chunk][1 or 6]
+  // order-parameter lists of the last mythos_oxdna_order_params call (order_params.hip), kept between calls:
+  // [n_pairs][2] pairs, lower index first | [n_ops + 1] op_first | [n_ops] op_kind
+  std::vector<int> h_op_list;
+  mythos::DeviceBuf<int> d_op_list;
 
   // the members free themselves, on the system's device
   ~mythos_system() { (void)hipSetDevice(device); }

@@ -195,6 +195,16 @@ def pseq_tensors(energy_fns):
     return None
 
 
+def _set_flat(entry, flat):
+    """The entry's system with the flat parameter vector ``flat`` in place (uploaded when it differs from the last one)."""
+    flat_np = flat.detach().cpu().to(torch.float64)
+    tag = flat_np.numpy().tobytes()
+    if entry["flat"] != tag:
+        entry["sys"].set_params(flat_np)
+        entry["flat"] = tag
+    return entry["sys"]
+
+
 def _apply_pseq(entry, request) -> None:
     tag = None if request is None else (request[3], *(a.tobytes() for a in request[:3]))
     if entry["pseq"] != tag:
@@ -252,12 +262,7 @@ class _EnergyOp(torch.autograd.Function):
         """``marg`` (N, 4), ``bp`` (max(n_bp, 1), 4): the probabilistic sequence the system was given, as differentiable
         tensors - passed only when a gradient with respect to the distribution is wanted (the values the kernel reads
         are the ones ``_apply_pseq`` uploaded)."""
-        system = entry["sys"]
-        flat_np = flat.detach().cpu().to(torch.float64)
-        tag = flat_np.numpy().tobytes()
-        if entry["flat"] != tag:
-            system.set_params(flat_np)
-            entry["flat"] = tag
+        system = _set_flat(entry, flat)
         need_x = center.requires_grad or quat.requires_grad
         need_p = flat.requires_grad
         need_s = marg is not None and (marg.requires_grad or bp.requires_grad)
@@ -338,12 +343,7 @@ class _SweepOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat, eps_all, consts_all, center, quat, entry, weights, rho, table, model):
-        system = entry["sys"]
-        flat_np = flat.detach().cpu().to(torch.float64)
-        tag = flat_np.numpy().tobytes()
-        if entry["flat"] != tag:
-            system.set_params(flat_np)
-            entry["flat"] = tag
+        system = _set_flat(entry, flat)
         need_p = any(t is not None and t.requires_grad for t in (flat, eps_all, consts_all))
         w = torch.as_tensor(weights, dtype=torch.float64)
         sweep = model in (2, 3) and float(w[_K_DH]) != 0.0

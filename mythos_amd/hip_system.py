@@ -64,6 +64,7 @@ class OxdnaSystem(_lib.Handle):
         )
         self._pseq_n_bp = 0
         self._pseq_terms = 0
+        self._op_lists = None  # (ops, kind, first, pairs) of the last order_params call
         # oxNA (model 4): three vectors - oxDNA2, oxRNA2, hybrid - one after the other; dU/dparams rows likewise
         self.n_params = self._lib.mythos_oxdna_param_count() * (3 if self.model == 4 else 1)
         if self.model == 4:
@@ -223,6 +224,47 @@ class OxdnaSystem(_lib.Handle):
             "debye_sweep",
         )
         return e, de
+
+    def order_params(self, center, quat, ops, *, raw=False, hb_cutoff=-0.1):
+        """oxDNA's ``bond`` and ``mindistance`` order parameters of every frame (mythos_oxdna_order_params).  ``ops``: a
+        sequence of ``mythos_amd.input.order_parameters.OrderParameter``.  Returns the (F, n_ops) float64 values - for
+        ``bond`` the number of listed pairs whose hydrogen-bonding energy is below ``hb_cutoff``, for ``mindistance`` the
+        smallest base-base distance of the listed pairs (the interfaces are applied by
+        ``mythos_amd.observables.OrderParameters``) - and with ``raw`` also the (F, P) hydrogen-bonding energies and
+        base-base distances of the listed pairs, all order parameters' lists one after the other.  oxDNA1, oxDNA2 and
+        oxRNA2 systems with a discrete sequence; needs parameters, not neighbours."""
+        from mythos_amd.input.order_parameters import KINDS
+
+        c = self._check(center, (self.n, 3), "center")
+        q = self._check(quat, (self.n, 4), "quat")
+        if c.dim() == 2:
+            c, q = c[None], q[None]
+        nf = c.shape[0]
+        if q.shape[0] != nf:
+            raise ValueError("center and quat disagree on the number of frames")
+        cached = self._op_lists  # a trajectory is evaluated with one set of lists, call after call
+        if cached is not None and (cached[0] is ops or cached[0] == ops):
+            _, kind, first, pairs = cached
+        else:
+            ops = tuple(ops)
+            kind = np.ascontiguousarray([KINDS.index(o.kind) for o in ops], dtype=np.int32)
+            first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(o.pairs) for o in ops])]), dtype=np.int32)
+            pairs = np.ascontiguousarray([p for o in ops for p in o.pairs], dtype=np.int32).reshape(-1, 2)
+            if pairs.size and int(pairs.max()) >= self.n:
+                raise ValueError(f"an order parameter names nucleotide {int(pairs.max())}; the system has {self.n}")
+            self._op_lists = (ops, kind, first, pairs)
+        n_pairs = int(pairs.shape[0])
+        out = torch.empty((nf, len(ops)), dtype=torch.float64, device=self.device)
+        hb = torch.empty((nf, n_pairs), dtype=torch.float64, device=self.device) if raw else None
+        dist = torch.empty((nf, n_pairs), dtype=torch.float64, device=self.device) if raw else None
+        _lib.check(
+            self._lib.mythos_oxdna_order_params(
+                self._h, _lib.ptr(c), _lib.ptr(q), nf, len(ops), kind.ctypes.data_as(_lib.c_int_p), first.ctypes.data_as(_lib.c_int_p),
+                pairs.ctypes.data_as(_lib.c_int_p), n_pairs, float(hb_cutoff), _lib.ptr(out), _lib.ptr(hb), _lib.ptr(dist),
+                _lib.stream(self.device)),
+            "order_params",
+        )
+        return (out, hb, dist) if raw else out
 
 
 def _touched(*tensors) -> None:

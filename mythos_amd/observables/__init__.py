@@ -3,7 +3,8 @@ by the HIP library - stand-alone, or in the same call as the energy launch (``en
 MARTINI bond-length / triplet-angle distributions with their weighted Wasserstein distance to reference distributions, and
 the membrane observables of a bilayer: thickness, area per lipid and the melting temperature fitted to it, and the
 duplex-mechanics set: helical diameter, extension, twist, RMSE to a target, the stretch / torsion moduli and the
-worm-like-chain fit, and the duplex melting temperature by histogram reweighting of an umbrella-sampled trajectory."""
+worm-like-chain fit, and the duplex melting temperature by histogram reweighting of an umbrella-sampled trajectory, with
+oxDNA's ``bond`` / ``mindistance`` order parameters of stored frames and the umbrella histogram and weights built on them."""
 
 from mythos_amd.observables.base import ObservableSet, get_duplex_quartets
 from mythos_amd.observables.bond_distances import BondDistances, BondDistancesMapped
@@ -13,6 +14,8 @@ from mythos_amd.observables.melting_temp import (TARGETS, MeltingTemp, compute_c
 from mythos_amd.observables.membrane import AreaPerLipid, MembraneThickness
 from mythos_amd.observables.membrane_melting_temp import (MembraneMeltingTemp, apl_residual, calculate_apl, compute_membrane_tm,
                                                           fit_apl_sigmoid, get_initial_guess)
+from mythos_amd.observables.order_parameters import (OrderParameters, extrapolated_histogram, reweight_from_histogram,
+                                                     umbrella_histogram)
 from mythos_amd.observables.persistence_length import PersistenceLength, persistence_length_fit
 from mythos_amd.observables.pitch import PitchAngle, compute_pitch
 from mythos_amd.observables.propeller import PropellerTwist
@@ -24,8 +27,8 @@ from mythos_amd.observables.wasserstein import WassersteinDistance, WassersteinD
 from mythos_amd.observables.wlc import calculate_extension, coth, fit_wlc, loss
 
 __all__ = ["AreaPerLipid", "BondDistances", "BondDistancesMapped", "Diameter", "ExtensionZ", "MeltingTemp", "MembraneMeltingTemp", "MembraneThickness",
-           "ObservableSet", "PersistenceLength", "PitchAngle", "PropellerTwist", "RMSE", "Rise", "TripletAngles", "TripletAnglesMapped",
+           "ObservableSet", "OrderParameters", "PersistenceLength", "PitchAngle", "PropellerTwist", "RMSE", "Rise", "TripletAngles", "TripletAnglesMapped",
            "TwistXY", "WassersteinDistance", "WassersteinDistanceMapped", "apl_residual", "calculate_apl", "calculate_extension",
            "compute_membrane_tm", "compute_pitch", "coth", "fit_apl_sigmoid", "fit_wlc", "get_duplex_quartets", "get_initial_guess",
            "loss", "persistence_length_fit", "stretch", "stretch_torsion", "torsion", "wasserstein_1d", "TARGETS", "compute_curve_width",
-           "compute_finf", "extrapolated_ratios", "find_melting_temp", "interp1d"]
+           "compute_finf", "extrapolated_ratios", "find_melting_temp", "interp1d", "extrapolated_histogram", "reweight_from_histogram", "umbrella_histogram"]

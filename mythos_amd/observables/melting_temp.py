@@ -7,8 +7,11 @@ Debye-Hueckel sweep launch instead of T energy calls - and the finite-size-corre
 interpolated to 0.5.  Everything after the energies is a handful of torch operations on the (T, F) tensor, on its device,
 differentiable: autograd carries d(Tm)/d(E_t(f)) back into ``map_kt``.
 
-Not built: umbrella sampling or VMMC themselves (the frames, ``bind_states`` and ``umbrella_weights`` come from an oxDNA
-run: ``mythos_amd.input.oxdna_energy.read_energy``), and evaluating the ``bond`` order parameter from frames.
+``bind_states`` and ``umbrella_weights`` come from the energy file of an oxDNA run
+(``mythos_amd.input.oxdna_energy.read_energy``) or from the frames themselves: column 0 of
+``mythos_amd.observables.OrderParameters(op_file, energy_fn)(trajectory)`` and its ``weights``.
+
+Not built: umbrella sampling or VMMC themselves.
 """
 
 from __future__ import annotations
