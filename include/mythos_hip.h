@@ -200,7 +200,8 @@ int mythos_oxdna_order_params(mythos_system_t* sys, const void* center, const vo
  * persistence_length.py:47-91, 168-185 (base.py:24-66 for the local helical axis and the quartets).
  *   geometry    host double[3]: com_to_hb, backbone offset along a1, backbone offset along a2 (0 for oxDNA1; for
  *               oxRNA2, model 3, the offset along a3)
- *   box         host double[3] periodic box of the displacement function, or NULL (free space)
+ *   box         host double[3] periodic box of the displacement function, or NULL (free space); a box with an edge
+ *               that is not positive is refused (NULL, "box edges must be positive"), as mythos_duplex_obs_create does
  *   base_pairs  host int32[n_bp][2]       hydrogen-bonded pairs of the propeller twist
  *   quartets    host int32[n_q][2][2]     adjacent base pairs ((a1, b1), (a2, b2)) of rise / pitch / persistence length
  *   skip_ends   drop two quartets at either end in the persistence-length partials (persistence_length.py:84-87)

@@ -236,10 +236,11 @@ class Handle:
             pass
 
 
-def per_device(owner, device, make):
-    """``make()`` once per device for ``owner`` (an observable object, frozen dataclasses included), kept in its ``_sets``."""
+def per_device(owner, key, make):
+    """``make()`` once per ``key`` - the device alone, or (n, dtype, device) where an object serves trajectories of several
+    sizes - for ``owner`` (an observable object, frozen dataclasses included), kept in its ``_sets``."""
     sets = owner.__dict__.setdefault("_sets", {})
-    key = str(device)
+    key = str(key)
     if key not in sets:
         sets[key] = make()
     return sets[key]

@@ -197,8 +197,7 @@ static int sweep_typed(mythos_system* sys, const R* center, const R* quat, int n
     double r_max = 0.0;
     for (int t = t0; t < t0 + nt; ++t) r_max = std::max(r_max, dh_consts[(size_t)t * kSweepConsts + 3]);
     const double* consts = sys->d_sweep_consts.get() + (size_t)t0 * kSweepConsts;
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-      const int nf = std::min(chunk, n_frames - f0);
+    const int rc = for_frame_chunks(n_frames, chunk, [&](int f0, int nf) {
       const R* c = center + (size_t)f0 * n * 3;
       const R* q = quat + (size_t)f0 * n * 4;
       auto launch = [&](auto pgrad) {
@@ -213,7 +212,9 @@ static int sweep_typed(mythos_system* sys, const R* center, const R* quat, int n
                          nf, tiles, nt, width, (size_t)n_frames, f0, e_dh + (size_t)t0 * n_frames,
                          de_dconsts ? de_dconsts + (size_t)t0 * n_frames * kSweepConsts : nullptr);
       MYTHOS_HIP_TRY(hipGetLastError());
-    }
+      return 0;
+    });
+    if (rc) return rc;
   }
   return MYTHOS_OK;
 }
@@ -246,10 +247,9 @@ extern "C" int mythos_oxdna_debye_sweep(mythos_system_t* s, const void* center, 
     }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
-  const bool f32 = s->dtype == MYTHOS_F32;
-  if (s->model == 2)
-    return f32 ? sweep_typed<float, 2>(s, (const float*)center, (const float*)quat, n_frames, n_kt, dh_consts, e_dh, de_dconsts, st)
-               : sweep_typed<double, 2>(s, (const double*)center, (const double*)quat, n_frames, n_kt, dh_consts, e_dh, de_dconsts, st);
-  return f32 ? sweep_typed<float, 3>(s, (const float*)center, (const float*)quat, n_frames, n_kt, dh_consts, e_dh, de_dconsts, st)
-             : sweep_typed<double, 3>(s, (const double*)center, (const double*)quat, n_frames, n_kt, dh_consts, e_dh, de_dconsts, st);
+  return with_real(s->dtype, [&](auto r) {
+    using R = decltype(r);
+    if (s->model == 2) return sweep_typed<R, 2>(s, (const R*)center, (const R*)quat, n_frames, n_kt, dh_consts, e_dh, de_dconsts, st);
+    return sweep_typed<R, 3>(s, (const R*)center, (const R*)quat, n_frames, n_kt, dh_consts, e_dh, de_dconsts, st);
+  });
 }

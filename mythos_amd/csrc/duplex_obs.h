@@ -8,7 +8,7 @@
 //                                                                        base-base vectors of adjacent pairs, z dropped
 //   [3] RMSD               mythos/observables/rmse.py:19-67              to a centred target after optimal superposition
 // in oxDNA length units and radians.  Arithmetic in fp64 whatever the frames' precision; fixed-order reductions
-// (obs_block_sum of observables.h, whose D3, minimum image, clamp and site conventions are used as they are).
+// (block_sum of wave_ops.h; the sites, minimum image and clamp are those of observables.h).
 #pragma once
 #include "observables.h"
 
@@ -21,10 +21,7 @@ struct DuplexView {
   int n_bp = 0, n_q = 0;
   int has_ends = 0;
   int ends[4] = {0, 0, 0, 0};     // a1, b1, a2, b2 of the extension
-  int model = 2;
-  double g_hb = 0, g_k1 = 0, g_k2 = 0;
-  int box_on = 0;
-  double box[3] = {1, 1, 1};
+  SiteGeo geo;                    // site offsets and box (host_checks.h)
 };
 
 // The proper rotation that takes the centred frame x onto the target t in the least-squares sense, from

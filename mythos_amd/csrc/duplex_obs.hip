@@ -26,43 +26,35 @@ __global__ __launch_bounds__(256) void duplex_obs_kernel(const DuplexView v, int
   const R* __restrict__ center = center_all + f * n * 3;
   const R* __restrict__ quat = quat_all + f * n * 4;
   double* __restrict__ out = out_all + f * MYTHOS_DUPLEX_ROW;
-  ObsView mi;  // (the minimum image of observables.h reads its box from an ObsView)
-  mi.box_on = v.box_on, mi.box[0] = v.box[0], mi.box[1] = v.box[1], mi.box[2] = v.box[2];
-  auto centre = [&](int i) { return D3{(double)center[3 * i], (double)center[3 * i + 1], (double)center[3 * i + 2]}; };
-  auto axes = [&](int i, D3& a1, D3& a2, D3& a3) {
-    const double q0 = quat[4 * i], q1 = quat[4 * i + 1], q2 = quat[4 * i + 2], q3 = quat[4 * i + 3];
-    a1 = {q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3, 2 * (q1 * q2 + q0 * q3), 2 * (q1 * q3 - q0 * q2)};
-    a2 = {2 * (q1 * q2 - q0 * q3), q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3, 2 * (q2 * q3 + q0 * q1)};
-    a3 = {2 * (q1 * q3 + q0 * q2), 2 * (q2 * q3 - q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3};
-  };
-  // the model's backbone site, as frame_observables (observables.h): second coefficient on a2, for oxRNA2 on a3
-  auto back_site = [&](int i) {
+  const SiteGeo& geo = v.geo;
+  auto centre = [&](int i) { return obs_centre(center, i); };
+  auto back = [&](int i) {
     D3 a1, a2, a3;
-    axes(i, a1, a2, a3);
-    return centre(i) + v.g_k1 * a1 + v.g_k2 * (v.model == 3 ? a3 : a2);
+    obs_axes(quat, i, a1, a2, a3);
+    return back_site(geo, centre(i), a1, a2, a3);
   };
-  auto base_site = [&](int i) {
+  auto base = [&](int i) {
     D3 a1, a2, a3;
-    axes(i, a1, a2, a3);
-    return centre(i) + v.g_hb * a1;
+    obs_axes(quat, i, a1, a2, a3);
+    return base_site(geo, centre(i), a1);
   };
   // ---- [0] backbone distance (diameter.py:37-41)
   double bd = 0.0;
   for (int k = threadIdx.x; k < v.n_bp; k += blockDim.x) {
-    const D3 d = obs_min_image(back_site(v.bps[2 * k]) - back_site(v.bps[2 * k + 1]), mi);
-    bd += sqrt(ddot(d, d));
+    const D3 d = obs_min_image(back(v.bps[2 * k]) - back(v.bps[2 * k + 1]), geo);
+    bd += sqrt(dot(d, d));
   }
-  bd = obs_block_sum(bd, red);
+  bd = block_sum(bd, red);
   // ---- [2] twist in the x-y plane (stretch_torsion.py:19-35); 0 / 0 = NaN for a pair along z, as the reference
   double tw = 0.0;
   for (int k = threadIdx.x; k < v.n_q; k += blockDim.x) {
     const int a1 = v.quartets[4 * k], b1 = v.quartets[4 * k + 1], a2 = v.quartets[4 * k + 2], b2 = v.quartets[4 * k + 3];
-    const D3 d1 = obs_min_image(base_site(b1) - base_site(a1), mi);
-    const D3 d2 = obs_min_image(base_site(b2) - base_site(a2), mi);
+    const D3 d1 = obs_min_image(base(b1) - base(a1), geo);
+    const D3 d2 = obs_min_image(base(b2) - base(a2), geo);
     const double n1 = sqrt(d1.x * d1.x + d1.y * d1.y), n2 = sqrt(d2.x * d2.x + d2.y * d2.y);
     tw += acos(obs_clamp((d1.x / n1) * (d2.x / n2) + (d1.y / n1) * (d2.y / n2)));
   }
-  tw = obs_block_sum(tw, red);
+  tw = block_sum(tw, red);
   // ---- [3] RMSD to the centred target (rmse.py:19-67): raw coordinates, no minimum image
   double rmsd = 0.0;
   if (v.target) {
@@ -71,7 +63,7 @@ __global__ __launch_bounds__(256) void duplex_obs_kernel(const DuplexView v, int
       const D3 c = centre(i);
       sx += c.x, sy += c.y, sz += c.z;
     }
-    sx = obs_block_sum(sx, red), sy = obs_block_sum(sy, red), sz = obs_block_sum(sz, red);
+    sx = block_sum(sx, red), sy = block_sum(sy, red), sz = block_sum(sz, red);
     const D3 mean{sx / n, sy / n, sz / n};
     double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
@@ -82,7 +74,7 @@ __global__ __launch_bounds__(256) void duplex_obs_kernel(const DuplexView v, int
       S[6] += x.z * t0, S[7] += x.z * t1, S[8] += x.z * t2;
     }
 #pragma unroll
-    for (int k = 0; k < 9; ++k) S[k] = obs_block_sum(S[k], red);
+    for (int k = 0; k < 9; ++k) S[k] = block_sum(S[k], red);
     if (threadIdx.x == 0) horn_rotation(S, s_rot);
     __syncthreads();
     // second pass: the residual itself (the identity |x|^2 + |t|^2 - 2 sum sigma cancels to nothing near the target)
@@ -94,7 +86,7 @@ __global__ __launch_bounds__(256) void duplex_obs_kernel(const DuplexView v, int
       const double d2 = s_rot[6] * x.x + s_rot[7] * x.y + s_rot[8] * x.z - v.target[3 * (size_t)i + 2];
       r2 += d0 * d0 + d1 * d1 + d2 * d2;
     }
-    rmsd = sqrt(obs_block_sum(r2, red) / n);
+    rmsd = sqrt(block_sum(r2, red) / n);
   }
   if (threadIdx.x == 0) {
     out[0] = v.n_bp > 0 ? bd / v.n_bp : 0.0;
@@ -102,9 +94,9 @@ __global__ __launch_bounds__(256) void duplex_obs_kernel(const DuplexView v, int
     double ext = 0.0;
     if (v.has_ends) {
       const D3 ca1 = centre(v.ends[0]), ca2 = centre(v.ends[2]);
-      const D3 m1 = ca1 + 0.5 * obs_min_image(centre(v.ends[1]) - ca1, mi);
-      const D3 m2 = ca2 + 0.5 * obs_min_image(centre(v.ends[3]) - ca2, mi);
-      ext = fabs(obs_min_image(m2 - m1, mi).z);
+      const D3 m1 = ca1 + 0.5 * obs_min_image(centre(v.ends[1]) - ca1, geo);
+      const D3 m2 = ca2 + 0.5 * obs_min_image(centre(v.ends[3]) - ca2, geo);
+      ext = fabs(obs_min_image(m2 - m1, geo).z);
     }
     out[1] = ext;
     out[2] = v.n_q > 0 ? tw : 0.0;
@@ -126,35 +118,17 @@ mythos_duplex_obs_t* mythos_duplex_obs_create(int model, int n, const double* ge
     set_error("mythos_duplex_obs_create: invalid argument");
     return nullptr;
   }
-  for (int k = 0; k < 2 * n_bp; ++k)
-    if (base_pairs[k] < 0 || base_pairs[k] >= n) {
-      set_error("mythos_duplex_obs_create: base-pair index out of range");
-      return nullptr;
-    }
-  for (int k = 0; k < 4 * n_quartets; ++k)
-    if (quartets[k] < 0 || quartets[k] >= n) {
-      set_error("mythos_duplex_obs_create: quartet index out of range");
-      return nullptr;
-    }
-  for (int k = 0; end_pairs && k < 4; ++k)
-    if (end_pairs[k] < 0 || end_pairs[k] >= n) {
-      set_error("mythos_duplex_obs_create: end-pair index out of range");
-      return nullptr;
-    }
-  if (box && !(box[0] > 0 && box[1] > 0 && box[2] > 0)) {
-    set_error("mythos_duplex_obs_create: box edges must be positive");
+  SiteGeo geo;
+  if (!indices_in_range(base_pairs, 2 * (size_t)n_bp, n, "mythos_duplex_obs_create: base-pair index out of range") ||
+      !indices_in_range(quartets, 4 * (size_t)n_quartets, n, "mythos_duplex_obs_create: quartet index out of range") ||
+      !indices_in_range(end_pairs, end_pairs ? 4 : 0, n, "mythos_duplex_obs_create: end-pair index out of range") ||
+      !site_geo_from(model, geometry, box, "mythos_duplex_obs_create", &geo))
     return nullptr;
-  }
   if (select_device(device, "mythos_duplex_obs_create")) return nullptr;
   auto o = std::make_unique<mythos_duplex_obs>();
   o->n = n, o->device = device;
   DuplexView& v = o->view;
-  v.n_bp = n_bp, v.n_q = n_quartets, v.model = model;
-  v.g_hb = geometry[0], v.g_k1 = geometry[1], v.g_k2 = model >= 2 ? geometry[2] : 0.0;
-  if (box) {
-    v.box_on = 1;
-    for (int k = 0; k < 3; ++k) v.box[k] = box[k];
-  }
+  v.n_bp = n_bp, v.n_q = n_quartets, v.geo = geo;
   if (end_pairs) {
     v.has_ends = 1;
     for (int k = 0; k < 4; ++k) v.ends[k] = end_pairs[k];
@@ -183,18 +157,15 @@ int mythos_duplex_obs_eval(mythos_duplex_obs_t* o, const void* center, const voi
   // workgroup size as observables_launch chooses it: one wavefront when every list fits one (the centres are the
   // RMSD's list), four otherwise
   const int threads = (v.n_bp <= 64 && v.n_q <= 64 && (!v.target || o->n <= 64)) ? 64 : 256;
-  constexpr int kFramesPerLaunch = 1 << 20;  // far below the grid limit; the frame index is blockIdx.x + frame0
-  for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-    const int nf = std::min(n_frames - f0, kFramesPerLaunch);
-    if (dtype == MYTHOS_F32)
-      hipLaunchKernelGGL(duplex_obs_kernel<float>, dim3(nf), dim3(threads), 0, (hipStream_t)stream, v, o->n, (const float*)center,
-                         (const float*)quat, f0, out);
-    else
-      hipLaunchKernelGGL(duplex_obs_kernel<double>, dim3(nf), dim3(threads), 0, (hipStream_t)stream, v, o->n, (const double*)center,
-                         (const double*)quat, f0, out);
-  }
-  MYTHOS_HIP_TRY(hipGetLastError());
-  return MYTHOS_OK;
+  return with_real(dtype, [&](auto r) {
+    using R = decltype(r);
+    return for_frame_chunks(n_frames, kFramesPerLaunch, [&](int f0, int nf) {
+      hipLaunchKernelGGL(duplex_obs_kernel<R>, dim3(nf), dim3(threads), 0, (hipStream_t)stream, v, o->n, (const R*)center,
+                         (const R*)quat, f0, out);
+      MYTHOS_HIP_TRY(hipGetLastError());
+      return 0;
+    });
+  });
 }
 
 }  // extern "C"

@@ -507,11 +507,10 @@ int mythos_martini_energy(mythos_martini_t* m, const void* pos, const void* box,
   }
   if (n_frames == 0) return MYTHOS_OK;
   MYTHOS_HIP_TRY(hipSetDevice(m->device));
-  if (m->dtype == MYTHOS_F32)
-    return martini_energy_typed<float>(m, (const float*)pos, (const float*)box, n_frames, e_terms, (float*)dU_dpos,
-                                       (hipStream_t)stream);
-  return martini_energy_typed<double>(m, (const double*)pos, (const double*)box, n_frames, e_terms, (double*)dU_dpos,
-                                      (hipStream_t)stream);
+  return with_real(m->dtype, [&](auto r) {
+    using R = decltype(r);
+    return martini_energy_typed<R>(m, (const R*)pos, (const R*)box, n_frames, e_terms, (R*)dU_dpos, (hipStream_t)stream);
+  });
 }
 
 int mythos_martini_param_grads(mythos_martini_t* m, const void* pos, const void* box, int n_frames, double* d_sigma,
@@ -523,11 +522,11 @@ int mythos_martini_param_grads(mythos_martini_t* m, const void* pos, const void*
   }
   if (n_frames == 0) return MYTHOS_OK;
   MYTHOS_HIP_TRY(hipSetDevice(m->device));
-  if (m->dtype == MYTHOS_F32)
-    return martini_pgrad_typed<float>(m, (const float*)pos, (const float*)box, n_frames, d_sigma, d_eps, d_bond_k,
-                                      d_bond_r0, d_angle_k, d_angle_t0, (hipStream_t)stream);
-  return martini_pgrad_typed<double>(m, (const double*)pos, (const double*)box, n_frames, d_sigma, d_eps, d_bond_k,
-                                     d_bond_r0, d_angle_k, d_angle_t0, (hipStream_t)stream);
+  return with_real(m->dtype, [&](auto r) {
+    using R = decltype(r);
+    return martini_pgrad_typed<R>(m, (const R*)pos, (const R*)box, n_frames, d_sigma, d_eps, d_bond_k, d_bond_r0, d_angle_k,
+                                  d_angle_t0, (hipStream_t)stream);
+  });
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include <memory>
 #include <vector>
 
+#include "host_checks.h"
 #include "mythos_internal.h"
 
 struct mythos_martini_obs {
@@ -88,11 +89,7 @@ mythos_martini_obs_t* mythos_martini_obs_create(int n, int n_groups, const int32
       return nullptr;
     }
     for (int b = 0; b < members[g]; ++b, ix += w) {
-      for (int k = 0; k < w; ++k)
-        if (ix[k] < 0 || ix[k] >= n) {
-          set_error("mythos_martini_obs_create: bead index out of range");
-          return nullptr;
-        }
+      if (!indices_in_range(ix, (size_t)w, n, "mythos_martini_obs_create: bead index out of range")) return nullptr;
       beads.push_back(make_int4(ix[0], ix[1], w == 3 ? ix[2] : -1, 0));
       place.push_back(make_int4((int)before, members[g], b, 0));
     }
@@ -125,17 +122,15 @@ int mythos_martini_obs_eval(mythos_martini_obs_t* h, const void* pos, const void
   if (n_frames == 0) return MYTHOS_OK;
   MYTHOS_HIP_TRY(hipSetDevice(h->device));
   const unsigned nbx = (unsigned)((h->n_items + kObsBlock - 1) / kObsBlock);
-  for (int f0 = 0; f0 < n_frames; f0 += 32768) {  // grid.y <= 65535
-    const int nf = std::min(n_frames - f0, 32768);
-    if (dtype == MYTHOS_F32)
-      hipLaunchKernelGGL(martini_obs_kernel<float>, dim3(nbx, nf), dim3(kObsBlock), 0, (hipStream_t)stream, h->n, h->n_items,
-                         h->d_beads.get(), h->d_place.get(), (const float*)pos, (const float*)box, f0, n_frames, out);
-    else
-      hipLaunchKernelGGL(martini_obs_kernel<double>, dim3(nbx, nf), dim3(kObsBlock), 0, (hipStream_t)stream, h->n, h->n_items,
-                         h->d_beads.get(), h->d_place.get(), (const double*)pos, (const double*)box, f0, n_frames, out);
-  }
-  MYTHOS_HIP_TRY(hipGetLastError());
-  return MYTHOS_OK;
+  return with_real(dtype, [&](auto r) {
+    using R = decltype(r);
+    return for_frame_chunks(n_frames, 32768, [&](int f0, int nf) {  // the frame is blockIdx.y: grid.y <= 65535
+      hipLaunchKernelGGL(martini_obs_kernel<R>, dim3(nbx, nf), dim3(kObsBlock), 0, (hipStream_t)stream, h->n, h->n_items,
+                         h->d_beads.get(), h->d_place.get(), (const R*)pos, (const R*)box, f0, n_frames, out);
+      MYTHOS_HIP_TRY(hipGetLastError());
+      return 0;
+    });
+  });
 }
 
 }  // extern "C"

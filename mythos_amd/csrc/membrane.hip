@@ -13,12 +13,13 @@
 // One workgroup per frame, three passes of the workgroup over the index lists: the selection's beads for the midpoint,
 // the lipids for the leaflets, the thickness beads for the two means.  A thickness bead recomputes its lipid's z by the
 // same function the leaflet pass used (same operations in the same order: the same bits), so nothing is kept per
-// lipid and their number has no limit.  Sums are double and in a fixed order: thread-strided partials, the wavefront
-// butterfly of wave_ops.h, the wavefronts' totals in order through LDS.  No atomics: a frame's row depends on that
-// frame only.  The kernel is launch and gather bound (3 - 4 gathered z per lipid and frame).
+// lipid and their number has no limit.  Sums are double and in a fixed order: thread-strided partials, then block_sum
+// of wave_ops.h (the wavefront's tree, the wavefronts' totals in order through LDS).  No atomics: a frame's row depends
+// on that frame only.  The kernel is launch and gather bound (3 - 4 gathered z per lipid and frame).
 #include <memory>
 #include <vector>
 
+#include "host_checks.h"
 #include "mythos_internal.h"
 #include "wave_ops.h"
 
@@ -35,18 +36,6 @@ namespace mythos {
 
 constexpr int kMemBlock = 256;
 
-// every thread gets the workgroup's sum; s_w: kMemBlock / 64 doubles.  Every thread must call it.
-__device__ __forceinline__ double mem_block_sum(double v, double* s_w) {
-  v = group_sum<64>(v);
-  __syncthreads();  // s_w may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < kMemBlock / 64; ++w) s += s_w[w];
-  return s;
-}
-
 template <typename R>
 __device__ __forceinline__ double lipid_z(const R* __restrict__ p, const int* __restrict__ start, const int* __restrict__ sel, int l) {
   const int a = start[l], b = start[l + 1];
@@ -62,12 +51,14 @@ __global__ __launch_bounds__(kMemBlock) void membrane_kernel(int n, int n_lipids
                                                              const R* __restrict__ pos, const R* __restrict__ box, int frame0,
                                                              double* __restrict__ out, int8_t* __restrict__ leaflets) {
   __shared__ double s_w[kMemBlock / 64];
+  const unsigned int block = blockDim.x;
+  __builtin_assume(block == kMemBlock);  // (the one launch site; block_sum then adds its four totals unrolled)
   const int frame = frame0 + blockIdx.x;
   const R* __restrict__ p = pos + (size_t)frame * n * 3;
   // midpoint: over beads
   double zs = 0.0;
   for (int k = threadIdx.x; k < n_sel; k += kMemBlock) zs += double(p[3 * (size_t)sel[k] + 2]);
-  const double mid = mem_block_sum(zs, s_w) / double(n_sel);
+  const double mid = block_sum(zs, s_w) / double(n_sel);
   // leaflets
   double up = 0.0;
   for (int l = threadIdx.x; l < n_lipids; l += kMemBlock) {
@@ -75,7 +66,7 @@ __global__ __launch_bounds__(kMemBlock) void membrane_kernel(int n, int n_lipids
     up += upper ? 1.0 : 0.0;
     if (leaflets) leaflets[(size_t)frame * n_lipids + l] = upper ? 1 : -1;
   }
-  const double n_up = mem_block_sum(up, s_w), n_lo = double(n_lipids) - n_up;  // counts: exact in double
+  const double n_up = block_sum(up, s_w), n_lo = double(n_lipids) - n_up;  // counts: exact in double
   // thickness beads by the leaflet of their lipid
   double zu = 0.0, zl = 0.0, cu = 0.0;
   for (int t = threadIdx.x; t < n_thick; t += kMemBlock) {
@@ -85,7 +76,7 @@ __global__ __launch_bounds__(kMemBlock) void membrane_kernel(int n, int n_lipids
     else
       zl += z;
   }
-  zu = mem_block_sum(zu, s_w), zl = mem_block_sum(zl, s_w), cu = mem_block_sum(cu, s_w);
+  zu = block_sum(zu, s_w), zl = block_sum(zl, s_w), cu = block_sum(cu, s_w);
   if (threadIdx.x == 0) {
     const double cl = double(n_thick) - cu, nan = __builtin_nan("");
     const double mu = cu > 0.0 ? zu / cu : nan, ml = cl > 0.0 ? zl / cl : nan;
@@ -124,16 +115,10 @@ mythos_membrane_t* mythos_membrane_create(int n, int n_lipids, const int32_t* li
       return nullptr;
     }
   const int n_sel = lipid_start[n_lipids];
-  for (int k = 0; k < n_sel; ++k)
-    if (lipid_beads[k] < 0 || lipid_beads[k] >= n) {
-      set_error("mythos_membrane_create: bead index out of range");
-      return nullptr;
-    }
-  for (int t = 0; t < n_thick; ++t)
-    if (thick_beads[t] < 0 || thick_beads[t] >= n || thick_lipid[t] < 0 || thick_lipid[t] >= n_lipids) {
-      set_error("mythos_membrane_create: thickness bead or its lipid out of range");
-      return nullptr;
-    }
+  if (!indices_in_range(lipid_beads, (size_t)n_sel, n, "mythos_membrane_create: bead index out of range") ||
+      !indices_in_range(thick_beads, (size_t)n_thick, n, "mythos_membrane_create: thickness bead or its lipid out of range") ||
+      !indices_in_range(thick_lipid, (size_t)n_thick, n_lipids, "mythos_membrane_create: thickness bead or its lipid out of range"))
+    return nullptr;
   if (select_device(device, "mythos_membrane_create")) return nullptr;
   auto h = std::make_unique<mythos_membrane>();
   h->n = n, h->n_lipids = n_lipids, h->n_sel = n_sel, h->n_thick = n_thick, h->device = device;
@@ -157,20 +142,16 @@ int mythos_membrane_eval(mythos_membrane_t* h, const void* pos, const void* box,
   }
   if (n_frames == 0) return MYTHOS_OK;
   MYTHOS_HIP_TRY(hipSetDevice(h->device));
-  constexpr int kFramesPerLaunch = 1 << 20;  // far below the grid limit; the frame index is blockIdx.x + frame0
-  for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-    const int nf = std::min(n_frames - f0, kFramesPerLaunch);
-    if (dtype == MYTHOS_F32)
-      hipLaunchKernelGGL(membrane_kernel<float>, dim3(nf), dim3(kMemBlock), 0, (hipStream_t)stream, h->n, h->n_lipids, h->n_sel,
-                         h->n_thick, h->d_start.get(), h->d_sel.get(), h->d_thick.get(), h->d_thick_lipid.get(), (const float*)pos, (const float*)box, f0,
-                         out, leaflets);
-    else
-      hipLaunchKernelGGL(membrane_kernel<double>, dim3(nf), dim3(kMemBlock), 0, (hipStream_t)stream, h->n, h->n_lipids, h->n_sel,
-                         h->n_thick, h->d_start.get(), h->d_sel.get(), h->d_thick.get(), h->d_thick_lipid.get(), (const double*)pos, (const double*)box, f0,
-                         out, leaflets);
-  }
-  MYTHOS_HIP_TRY(hipGetLastError());
-  return MYTHOS_OK;
+  return with_real(dtype, [&](auto r) {
+    using R = decltype(r);
+    return for_frame_chunks(n_frames, kFramesPerLaunch, [&](int f0, int nf) {
+      hipLaunchKernelGGL(membrane_kernel<R>, dim3(nf), dim3(kMemBlock), 0, (hipStream_t)stream, h->n, h->n_lipids, h->n_sel,
+                         h->n_thick, h->d_start.get(), h->d_sel.get(), h->d_thick.get(), h->d_thick_lipid.get(), (const R*)pos,
+                         (const R*)box, f0, out, leaflets);
+      MYTHOS_HIP_TRY(hipGetLastError());
+      return 0;
+    });
+  });
 }
 
 }  // extern "C"

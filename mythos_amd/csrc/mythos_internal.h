@@ -175,6 +175,21 @@ template <class F>
 auto with_bool(bool on, F&& f) {
   return on ? f(std::true_type{}) : f(std::false_type{});
 }
+// A run-time precision (MYTHOS_F32 / MYTHOS_F64; the entry points checked it) as the type a kernel template takes: f is
+// called with float{} or double{}.
+template <class F>
+auto with_real(int dtype, F&& f) {
+  return dtype == MYTHOS_F32 ? f(float{}) : f(double{});
+}
+// The frames of a call in launches of at most `chunk`: f(f0, nf) -> 0 or an error code, which ends the loop.
+template <class F>
+int for_frame_chunks(int n_frames, int chunk, F&& f) {
+  for (int f0 = 0; f0 < n_frames; f0 += chunk)
+    if (int rc = f(f0, std::min(chunk, n_frames - f0))) return rc;
+  return 0;
+}
+// frames per launch of the kernels that give a frame one workgroup, blockIdx.x + frame0: far below the grid limit
+constexpr int kFramesPerLaunch = 1 << 20;
 
 // d_row_len holds three arrays back to back: row length [n] | bonded partners [n][ROW_BONDED_SLOTS] | end of the
 // "close" segment of the row [n]

@@ -20,7 +20,9 @@
 #include <hip/hip_runtime.h>
 
 #include "device_buf.h"
+#include "host_checks.h"
 #include "oxdna_math.h"
+#include "wave_ops.h"
 
 namespace mythos {
 
@@ -34,92 +36,78 @@ struct ObsView {
   int skip = 0;                   // quartets dropped at either end for the persistence-length partials (0 or 2)
   int n_corr = 0;                 // n_q - 2 * skip (>= 0)
   int width = 0;                  // 4 + n_corr; 0 = no observables
-  int model = 2;
-  double g_hb = 0, g_k1 = 0, g_k2 = 0;  // base site c + g_hb a1; backbone site c + g_k1 a1 + g_k2 a2 (model 3: g_k2 a3)
-  int box_on = 0;
-  double box[3] = {1, 1, 1};
+  SiteGeo geo;                    // site offsets and box (host_checks.h)
 };
 
-struct D3 {
-  double x, y, z;
-};
-__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 operator*(double s, D3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double ddot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+using D3 = V3<double>;
 
-__device__ __forceinline__ D3 obs_min_image(D3 d, const ObsView& v) {
-  if (v.box_on) {
-    d.x -= v.box[0] * rint(d.x / v.box[0]);
-    d.y -= v.box[1] * rint(d.y / v.box[1]);
-    d.z -= v.box[2] * rint(d.z / v.box[2]);
+// The sites of a nucleotide (SiteGeo) from its centre and axes, and the minimum image of a displacement between sites:
+// the one statement of them for every frame-observable kernel.
+__device__ __forceinline__ D3 base_site(const SiteGeo& g, D3 c, D3 a1) { return c + g.g_hb * a1; }
+__device__ __forceinline__ D3 back_site(const SiteGeo& g, D3 c, D3 a1, D3 a2, D3 a3) {
+  return c + g.g_k1 * a1 + g.g_k2 * (g.model == 3 ? a3 : a2);  // oxRNA2: second coefficient on a3 (rna2/nucleotide.py:56)
+}
+__device__ __forceinline__ D3 obs_min_image(D3 d, const SiteGeo& g) {
+  if (g.box_on) {
+    d.x -= g.box[0] * rint(d.x / g.box[0]);
+    d.y -= g.box[1] * rint(d.y / g.box[1]);
+    d.z -= g.box[2] * rint(d.z / g.box[2]);
   }
   return d;
 }
 
 __device__ __forceinline__ double obs_clamp(double c) { return c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c); }
 
-// sum over the workgroup in a fixed order: wavefront shuffles, then the wavefronts' partials in order.
-// red: shared scratch of blockDim.x / 64 doubles.  Every thread of the workgroup must call it.
-__device__ __forceinline__ double obs_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();  // red may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-  return s;
+// centre and axes of nucleotide i of one frame, in double whatever the frame's precision
+template <typename R>
+__device__ __forceinline__ D3 obs_centre(const R* __restrict__ center, int i) {
+  return D3{(double)center[3 * i], (double)center[3 * i + 1], (double)center[3 * i + 2]};
+}
+template <typename R>
+__device__ __forceinline__ void obs_axes(const R* __restrict__ quat, int i, D3& a1, D3& a2, D3& a3) {
+  quat_axes<double>(quat[4 * i], quat[4 * i + 1], quat[4 * i + 2], quat[4 * i + 3], a1, a2, a3);
 }
 
 // center [n][3], quat [n][4] of ONE frame; out [width]; axis scratch [n_q][3] of this frame.
 template <typename R>
 __device__ __forceinline__ void frame_observables(const ObsView& v, const R* __restrict__ center, const R* __restrict__ quat,
                                                   double* __restrict__ out, double* __restrict__ axis, double* red) {
-  auto centre = [&](int i) { return D3{(double)center[3 * i], (double)center[3 * i + 1], (double)center[3 * i + 2]}; };
-  auto axes = [&](int i, D3& a1, D3& a2, D3& a3) {
-    const double q0 = quat[4 * i], q1 = quat[4 * i + 1], q2 = quat[4 * i + 2], q3 = quat[4 * i + 3];
-    a1 = {q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3, 2 * (q1 * q2 + q0 * q3), 2 * (q1 * q3 - q0 * q2)};
-    a2 = {2 * (q1 * q2 - q0 * q3), q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3, 2 * (q2 * q3 + q0 * q1)};
-    a3 = {2 * (q1 * q3 + q0 * q2), 2 * (q2 * q3 - q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3};
-  };
+  const SiteGeo& g = v.geo;
   // ---- propeller twist
   double pt = 0.0;
   for (int k = threadIdx.x; k < v.n_bp; k += blockDim.x) {
     D3 a1, a2, n1, n2;
-    axes(v.bps[2 * k], a1, a2, n1);
-    axes(v.bps[2 * k + 1], a1, a2, n2);
-    pt += 180.0 - acos(obs_clamp(ddot(n1, n2))) * (180.0 / kPi);
+    obs_axes(quat, v.bps[2 * k], a1, a2, n1);
+    obs_axes(quat, v.bps[2 * k + 1], a1, a2, n2);
+    pt += 180.0 - acos(obs_clamp(dot(n1, n2))) * (180.0 / kPi);
   }
-  pt = obs_block_sum(pt, red);
+  pt = block_sum(pt, red);
   // ---- quartets: axis, rise, pitch angle, spacing
   double rise = 0.0, ang = 0.0, l0 = 0.0;
   for (int k = threadIdx.x; k < v.n_q; k += blockDim.x) {
     const int ia1 = v.quartets[4 * k], ib1 = v.quartets[4 * k + 1], ia2 = v.quartets[4 * k + 2], ib2 = v.quartets[4 * k + 3];
     D3 x1, y1, z1, x2, y2, z2, x3, y3, z3, x4, y4, z4;
-    axes(ia1, x1, y1, z1), axes(ib1, x2, y2, z2), axes(ia2, x3, y3, z3), axes(ib2, x4, y4, z4);
-    const D3 c1 = centre(ia1), c2 = centre(ib1), c3 = centre(ia2), c4 = centre(ib2);
-    const D3 m1 = 0.5 * ((c1 + v.g_hb * x1) + (c2 + v.g_hb * x2));
-    const D3 m2 = 0.5 * ((c3 + v.g_hb * x3) + (c4 + v.g_hb * x4));
-    const D3 dr = obs_min_image(m2 - m1, v);
-    const double norm = sqrt(ddot(dr, dr));
+    obs_axes(quat, ia1, x1, y1, z1), obs_axes(quat, ib1, x2, y2, z2), obs_axes(quat, ia2, x3, y3, z3), obs_axes(quat, ib2, x4, y4, z4);
+    const D3 c1 = obs_centre(center, ia1), c2 = obs_centre(center, ib1), c3 = obs_centre(center, ia2), c4 = obs_centre(center, ib2);
+    const D3 m1 = 0.5 * (base_site(g, c1, x1) + base_site(g, c2, x2));
+    const D3 m2 = 0.5 * (base_site(g, c3, x3) + base_site(g, c4, x4));
+    const D3 dr = obs_min_image(m2 - m1, g);
+    const double norm = sqrt(dot(dr, dr));
     const D3 ax = (1.0 / norm) * dr;
     axis[3 * k] = ax.x, axis[3 * k + 1] = ax.y, axis[3 * k + 2] = ax.z;
-    rise += ddot(dr, ax) * kAngstromPerOxdnaLength;
+    rise += dot(dr, ax) * kAngstromPerOxdnaLength;
     if (k >= v.skip && k < v.n_q - v.skip) l0 += norm;
     // backbone-backbone vectors of the two pairs, helical component removed
-    auto back = [&](D3 c, D3 a1, D3 ab) { return c + v.g_k1 * a1 + v.g_k2 * ab; };
-    const bool on_a3 = v.model == 3;  // oxRNA2 backbone site: second coefficient on a3 (rna2/nucleotide.py:56)
-    D3 bb1 = obs_min_image(back(c2, x2, on_a3 ? z2 : y2) - back(c1, x1, on_a3 ? z1 : y1), v);
-    D3 bb2 = obs_min_image(back(c4, x4, on_a3 ? z4 : y4) - back(c3, x3, on_a3 ? z3 : y3), v);
-    bb1 = obs_min_image(bb1 - ddot(ax, bb1) * ax, v);
-    bb2 = obs_min_image(bb2 - ddot(ax, bb2) * ax, v);
-    const double c = ddot(bb1, bb2) / sqrt(ddot(bb1, bb1) * ddot(bb2, bb2));
+    D3 bb1 = obs_min_image(back_site(g, c2, x2, y2, z2) - back_site(g, c1, x1, y1, z1), g);
+    D3 bb2 = obs_min_image(back_site(g, c4, x4, y4, z4) - back_site(g, c3, x3, y3, z3), g);
+    bb1 = obs_min_image(bb1 - dot(ax, bb1) * ax, g);
+    bb2 = obs_min_image(bb2 - dot(ax, bb2) * ax, g);
+    const double c = dot(bb1, bb2) / sqrt(dot(bb1, bb1) * dot(bb2, bb2));
     ang += acos(obs_clamp(c));
   }
-  rise = obs_block_sum(rise, red);
-  ang = obs_block_sum(ang, red);
-  l0 = obs_block_sum(l0, red);  // (its barriers also publish the axes of this frame to the whole workgroup)
+  rise = block_sum(rise, red);
+  ang = block_sum(ang, red);
+  l0 = block_sum(l0, red);  // (its barriers also publish the axes of this frame to the whole workgroup)
   __threadfence_block();
   if (threadIdx.x == 0) {
     out[0] = v.n_bp > 0 ? pt / v.n_bp : 0.0;
@@ -149,9 +137,10 @@ struct mythos_obs {
 };
 
 namespace mythos {
-// makes sure the axis scratch covers n_frames and returns the view to pass to a kernel
+// makes sure the axis scratch covers n_frames and returns the view to pass to observables_launch
 int obs_view_for(mythos_obs* o, int n_frames, ObsView* out);
-// the stand-alone kernel on n_frames frames (view: from obs_view_for, its axis pointer already at the first frame)
-int observables_launch(mythos_obs* o, const ObsView& view, const void* center, const void* quat, int n_frames, double* out,
+// the stand-alone kernel on frames f0 .. f0 + nf of the arrays obs_view_for sized the scratch for: center, quat, out and
+// the view's axis scratch are those of frame 0, the launch offsets all four
+int observables_launch(mythos_obs* o, ObsView view, const void* center, const void* quat, int f0, int nf, double* out,
                        hipStream_t stream);
 }  // namespace mythos

@@ -1,5 +1,6 @@
 // Observable sets behind the C ABI (mythos_observables_*): see observables.h for what is computed and where the
-// reference defines it.  One workgroup per frame; mythos_oxdna_energy_obs (oxdna_kernels.hip) queues the same kernel behind its energy launch.
+// reference defines it.  One workgroup per frame; mythos_oxdna_energy_obs (oxdna_kernels.hip) queues the same kernel behind
+// its energy launch, through the same observables_launch that mythos_observables_eval calls per chunk of frames.
 #include "observables.h"
 
 #include <memory>
@@ -24,18 +25,18 @@ int obs_view_for(mythos_obs* o, int n_frames, ObsView* out) {
   return 0;
 }
 
-int observables_launch(mythos_obs* o, const ObsView& v, const void* center, const void* quat, int n_frames, double* out,
+int observables_launch(mythos_obs* o, ObsView v, const void* center, const void* quat, int f0, int nf, double* out,
                        hipStream_t st) {
   // one workgroup per frame; a frame whose lists fit one wavefront (the DiffTRe systems: 30 base pairs, 31 quartets) gets
   // a workgroup of one - its sums are the first wavefront's sums of the wider workgroup bit for bit (the other partials
   // are zeros), its barriers cost nothing, and four times as many frames are in flight
   const int threads = (v.n_bp <= 64 && v.n_q <= 64) ? 64 : 256;
-  if (o->dtype == MYTHOS_F32)
-    hipLaunchKernelGGL(observables_kernel<float>, dim3(n_frames), dim3(threads), 0, st, v, o->n, (const float*)center,
-                       (const float*)quat, out);
-  else
-    hipLaunchKernelGGL(observables_kernel<double>, dim3(n_frames), dim3(threads), 0, st, v, o->n, (const double*)center,
-                       (const double*)quat, out);
+  v.axis += (size_t)f0 * v.n_q * 3;
+  with_real(o->dtype, [&](auto r) {
+    using R = decltype(r);
+    hipLaunchKernelGGL(observables_kernel<R>, dim3(nf), dim3(threads), 0, st, v, o->n, (const R*)center + (size_t)f0 * o->n * 3,
+                       (const R*)quat + (size_t)f0 * o->n * 4, out + (size_t)f0 * v.width);
+  });
   MYTHOS_HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -54,16 +55,11 @@ mythos_obs_t* mythos_observables_create(int model, int n, const double* geometry
     set_error("mythos_observables_create: invalid argument");
     return nullptr;
   }
-  for (int k = 0; k < 2 * n_bp; ++k)
-    if (base_pairs[k] < 0 || base_pairs[k] >= n) {
-      set_error("mythos_observables_create: base-pair index out of range");
-      return nullptr;
-    }
-  for (int k = 0; k < 4 * n_quartets; ++k)
-    if (quartets[k] < 0 || quartets[k] >= n) {
-      set_error("mythos_observables_create: quartet index out of range");
-      return nullptr;
-    }
+  SiteGeo geo;
+  if (!indices_in_range(base_pairs, 2 * (size_t)n_bp, n, "mythos_observables_create: base-pair index out of range") ||
+      !indices_in_range(quartets, 4 * (size_t)n_quartets, n, "mythos_observables_create: quartet index out of range") ||
+      !site_geo_from(model, geometry, box, "mythos_observables_create", &geo))
+    return nullptr;
   if (select_device(device, "mythos_observables_create")) return nullptr;
   auto o = std::make_unique<mythos_obs>();
   o->n = n, o->dtype = dtype, o->device = device;
@@ -72,12 +68,7 @@ mythos_obs_t* mythos_observables_create(int model, int n, const double* geometry
   v.skip = skip_ends ? 2 : 0;
   v.n_corr = std::max(0, n_quartets - 2 * v.skip);
   v.width = 4 + v.n_corr;
-  v.model = model;
-  v.g_hb = geometry[0], v.g_k1 = geometry[1], v.g_k2 = model >= 2 ? geometry[2] : 0.0;
-  if (box) {
-    v.box_on = 1;
-    for (int k = 0; k < 3; ++k) v.box[k] = box[k];
-  }
+  v.geo = geo;
   if ((n_bp > 0 && o->d_bps.upload(base_pairs, 2 * (size_t)n_bp)) ||
       (n_quartets > 0 && o->d_quartets.upload(quartets, 4 * (size_t)n_quartets))) {
     set_error("mythos_observables_create: device allocation failed");
@@ -101,7 +92,9 @@ int mythos_observables_eval(mythos_obs_t* o, const void* center, const void* qua
   MYTHOS_HIP_TRY(hipSetDevice(o->device));
   ObsView v;
   if (int rc = obs_view_for(o, n_frames, &v)) return rc;
-  return observables_launch(o, v, center, quat, n_frames, out, (hipStream_t)stream);
+  return for_frame_chunks(n_frames, kFramesPerLaunch, [&](int f0, int nf) {
+    return observables_launch(o, v, center, quat, f0, nf, out, (hipStream_t)stream);
+  });
 }
 
 }  // extern "C"

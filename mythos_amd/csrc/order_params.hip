@@ -110,16 +110,15 @@ static int order_params_typed(mythos_system* sys, const R* center, const R* quat
   const size_t groups_per_block = (size_t)kOpBlock >> g_log2;
   // frames per launch: the chunk of the energy entry points, fewer where that many would be more blocks than a grid takes
   const int chunk = (int)std::min<size_t>(kOpFramesPerLaunch, std::max<size_t>(1, (size_t(0x7fffffff) * groups_per_block) / (size_t)n_ops));
-  for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-    const int nf = std::min(chunk, n_frames - f0);
+  return for_frame_chunks(n_frames, chunk, [&](int f0, int nf) {
     const size_t blocks = ((size_t)nf * n_ops + groups_per_block - 1) / groups_per_block;
     hipLaunchKernelGGL((order_params_kernel<R, MODEL>), dim3((unsigned int)blocks), dim3(kOpBlock), 0, stream, device_params_of<R>(sys),
                        box, n, center + (size_t)f0 * n * 3, quat + (size_t)f0 * n * 4, sys->d_meta.get(), sys->d_op_list.get(), n_pairs,
                        n_ops, nf, g_log2, hb_cutoff, op_out + (size_t)f0 * n_ops, hb_out ? hb_out + (size_t)f0 * n_pairs : nullptr,
                        dist_out ? dist_out + (size_t)f0 * n_pairs : nullptr);
     MYTHOS_HIP_TRY(hipGetLastError());
-  }
-  return MYTHOS_OK;
+    return 0;
+  });
 }
 
 }  // namespace mythos
@@ -176,12 +175,12 @@ extern "C" int mythos_oxdna_order_params(mythos_system_t* s, const void* center,
     MYTHOS_HIP_TRY(hipMemcpy(s->d_op_list.get(), packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice));
     s->h_op_list.swap(packed);
   }
-  const bool f32 = s->dtype == MYTHOS_F32;
-  return with_model(s->model, [&](auto m) -> int {
+  return with_model(s->model, [&](auto m) {
     constexpr int M = decltype(m)::value == 4 ? 2 : decltype(m)::value;  // (model 4 was refused above)
-    return f32 ? order_params_typed<float, M>(s, (const float*)center, (const float*)quat, n_frames, n_ops, n_pairs, g_log2, hb_cutoff,
-                                              op_out, hb_out, dist_out, st)
-               : order_params_typed<double, M>(s, (const double*)center, (const double*)quat, n_frames, n_ops, n_pairs, g_log2, hb_cutoff,
-                                               op_out, hb_out, dist_out, st);
+    return with_real(s->dtype, [&](auto r) {
+      using R = decltype(r);
+      return order_params_typed<R, M>(s, (const R*)center, (const R*)quat, n_frames, n_ops, n_pairs, g_log2, hb_cutoff, op_out, hb_out,
+                                      dist_out, st);
+    });
   });
 }

@@ -394,7 +394,6 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
   for (int f0 = 0; f0 < n_frames; f0 += chunk) {
     const int nf = std::min(chunk, n_frames - f0);
     dim3 grid(blocks, nf);
-    if (obs.width > 0) obs.axis = oset->d_axis.get() + (size_t)f0 * obs.n_q * 3;
     const R* c = center + (size_t)f0 * n * 3;
     const R* q = quat + (size_t)f0 * n * 4;
     R* gc = dU_dcenter ? dU_dcenter + (size_t)f0 * n * 3 : nullptr;
@@ -424,7 +423,7 @@ static int launch_typed(mythos_system* sys, const R* center, const R* quat, int 
     // per call (its fp64 site algebra cost every workgroup of the launch registers and occupancy; DESIGN section 8).
     if (obs.width > 0) {
       MYTHOS_HIP_TRY(hipGetLastError());
-      if (int rc = observables_launch(oset, obs, c, q, nf, obs_out + (size_t)f0 * obs.width, stream)) return rc;
+      if (int rc = observables_launch(oset, obs, center, quat, f0, nf, obs_out, stream)) return rc;
     }
     MYTHOS_HIP_TRY(hipGetLastError());
     reduce_partials_launch(sys->d_epart.get(), nf, blocks, (int)T_COUNT, e_terms + (size_t)f0 * T_COUNT, (int)T_COUNT, stream);

@@ -102,6 +102,14 @@ __host__ __device__ __forceinline__ void axpy(V3<R>& y, R a, V3<R> x) {
   y.z += a * x.z;
 }
 
+// axes from an (un-normalised) quaternion, mythos/energy/utils.py:18-36
+template <typename R>
+__device__ __forceinline__ void quat_axes(R q0, R q1, R q2, R q3, V3<R>& a1, V3<R>& a2, V3<R>& a3) {
+  a1 = {q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3, R(2) * (q1 * q2 + q0 * q3), R(2) * (q1 * q3 - q0 * q2)};
+  a2 = {R(2) * (q1 * q2 - q0 * q3), q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3, R(2) * (q2 * q3 + q0 * q1)};
+  a3 = {R(2) * (q1 * q3 + q0 * q2), R(2) * (q2 * q3 - q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3};
+}
+
 __device__ __forceinline__ float m_sqrt(float x) { return sqrtf(x); }
 // fp64 square root (round 4): the compiler's expansion of sqrt(double) is v_rsq_f64 and two and a half coupled Newton steps
 // - the ten instructions below - wrapped in a scaling of inputs under 2^-767 (compare, select, two ldexp) and a class test that

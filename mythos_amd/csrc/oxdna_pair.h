@@ -45,14 +45,6 @@ struct Nuc {
   int rna;  // oxNA (MODEL 4): the nucleotide is RNA (topology nt_type); not read by the other instantiations
 };
 
-// axes from an (un-normalised) quaternion, mythos/energy/utils.py:18-36
-template <typename R>
-__device__ __forceinline__ void quat_axes(R q0, R q1, R q2, R q3, V3<R>& a1, V3<R>& a2, V3<R>& a3) {
-  a1 = {q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3, R(2) * (q1 * q2 + q0 * q3), R(2) * (q1 * q3 - q0 * q2)};
-  a2 = {R(2) * (q1 * q2 - q0 * q3), q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3, R(2) * (q2 * q3 + q0 * q1)};
-  a3 = {R(2) * (q1 * q3 + q0 * q2), R(2) * (q2 * q3 - q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3};
-}
-
 // 4x4 sequence-weight lookup: an indexed read of an LDS-staged vector, or a select chain over scalar
 // registers for the kernel-argument copy (a lane-varying index into kernel arguments would force the
 // whole block into scratch memory)

@@ -42,6 +42,19 @@ __device__ __forceinline__ R group_sum(R v) {
   return v;
 }
 
+// Sum over the workgroup in a fixed order, to every thread: wavefront shuffles, then the wavefronts' totals in order.
+// red: shared scratch of blockDim.x / 64 doubles.  Every thread of the workgroup must call it.
+__device__ __forceinline__ double block_sum(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  __syncthreads();  // red may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
+  return s;
+}
+
 // The value a given lane holds, as a wave-uniform (v_readlane: no LDS trip); `lane` must be uniform.
 __device__ __forceinline__ double read_lane(double v, int lane) {
   const long long b = __builtin_bit_cast(long long, v);

@@ -135,6 +135,17 @@ class OxdnaSystem(_lib.Handle):
             raise ValueError(f"{name} must have trailing shape {tail}, got {tuple(t.shape)}")
         return t.contiguous()
 
+    def _frames(self, center, quat):
+        """center (F, N, 3) or (N, 3), quat likewise with 4 -> (contiguous (F, N, 3), (F, N, 4), F, whether it was one frame)."""
+        single = center.dim() == 2
+        c = self._check(center, (self.n, 3), "center")
+        q = self._check(quat, (self.n, 4), "quat")
+        if single:
+            c, q = c[None], q[None]
+        if q.shape[0] != c.shape[0]:
+            raise ValueError("center and quat disagree on the number of frames")
+        return c, q, int(c.shape[0]), single
+
     def energy(self, center, quat, *, grads=False, param_grads=False, observables=None, pseq_grads=False):
         """Term energies (F, 8) [float64] and optionally dU/dcenter, dU/dquat, dU/dflat.
 
@@ -143,14 +154,7 @@ class OxdnaSystem(_lib.Handle):
         then returned as a fifth value.  ``pseq_grads`` (with ``param_grads``, after ``set_pseq``): also
         dU/d(marginals) (F, N, 4) and dU/d(base-pair type probabilities) (F, max(n_bp, 1), 4), as a fifth and sixth value.
         """
-        single = center.dim() == 2
-        c = self._check(center, (self.n, 3), "center")
-        q = self._check(quat, (self.n, 4), "quat")
-        if single:
-            c, q = c[None], q[None]
-        nf = c.shape[0]
-        if q.shape[0] != nf:
-            raise ValueError("center and quat disagree on the number of frames")
+        c, q, nf, single = self._frames(center, quat)
         e = torch.empty((nf, N_TERMS), dtype=torch.float64, device=self.device)
         gc = torch.empty_like(c) if grads else None
         gq = torch.empty_like(q) if grads else None
@@ -204,13 +208,7 @@ class OxdnaSystem(_lib.Handle):
     def debye_sweep(self, center, quat, table, *, const_grads=False):
         """Debye-Hueckel energy of every frame at every row of ``table`` (T, 5) [kappa, prefactor, bsmooth, rcut, rhigh]
         (mythos_oxdna_debye_sweep): (e_dh (T, F) float64, de/dconstants (T, F, 5) or None).  oxDNA2 and oxRNA2 systems."""
-        c = self._check(center, (self.n, 3), "center")
-        q = self._check(quat, (self.n, 4), "quat")
-        if c.dim() == 2:
-            c, q = c[None], q[None]
-        nf = c.shape[0]
-        if q.shape[0] != nf:
-            raise ValueError("center and quat disagree on the number of frames")
+        c, q, nf, _ = self._frames(center, quat)
         table = np.ascontiguousarray(table, dtype=np.float64)
         if table.ndim != 2 or table.shape[1] != 5:
             raise ValueError("table must have shape (T, 5)")
@@ -235,13 +233,7 @@ class OxdnaSystem(_lib.Handle):
         oxRNA2 systems with a discrete sequence; needs parameters, not neighbours."""
         from mythos_amd.input.order_parameters import KINDS
 
-        c = self._check(center, (self.n, 3), "center")
-        q = self._check(quat, (self.n, 4), "quat")
-        if c.dim() == 2:
-            c, q = c[None], q[None]
-        nf = c.shape[0]
-        if q.shape[0] != nf:
-            raise ValueError("center and quat disagree on the number of frames")
+        c, q, nf, _ = self._frames(center, quat)
         cached = self._op_lists  # a trajectory is evaluated with one set of lists, call after call
         if cached is not None and (cached[0] is ops or cached[0] == ops):
             _, kind, first, pairs = cached
@@ -432,6 +424,26 @@ class LangevinIntegrator(_MdIntegrator):
         _lib.check(self._lib.mythos_langevin_set_seed(self._h, C.c_uint64(int(seed) & (2**64 - 1))), "set_seed")
 
 
+def martini_frames(pos, box):
+    """pos (F, N, 3) or (N, 3), box (F, 3), (1, 3) or (3,) -> contiguous (F, N, 3) and (F, 3) of pos's dtype on its device:
+    what every MARTINI entry point of the library reads (a box row per frame).  For the energy calls and the observables."""
+    if box is None:
+        raise ValueError("MARTINI observables need trajectory.box_size (per-frame periodic box)")
+    if not isinstance(pos, torch.Tensor) or pos.device.type != "cuda":
+        raise _lib.MythosHipError("observables are evaluated by the HIP library: the trajectory must live on a GPU "
+                                  "(mythos_amd has no CPU fallback)")
+    if pos.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"unsupported dtype {pos.dtype}")
+    if pos.dim() == 2:
+        pos = pos[None]
+    box = torch.as_tensor(box, dtype=pos.dtype, device=pos.device).reshape(-1, 3)
+    if box.shape[0] == 1 and pos.shape[0] > 1:
+        box = box.expand(pos.shape[0], 3)
+    if box.shape[0] != pos.shape[0]:
+        raise ValueError(f"box_size has {box.shape[0]} rows for {pos.shape[0]} frames")
+    return pos.contiguous(), box.contiguous()
+
+
 class MartiniSystem(_lib.Handle):
     """One MARTINI system on one GPU (mythos_martini_t): LJ type tables, bonds, angles."""
 
@@ -463,15 +475,10 @@ class MartiniSystem(_lib.Handle):
         )
 
     def _frames(self, pos, box):
-        """pos (F, N, 3) or (N, 3), box (F, 3), (1, 3) or (3,) -> contiguous (F, N, 3) and (F, 3) on the device."""
-        if pos.dim() == 2:
-            pos, box = pos[None], torch.as_tensor(box).reshape(1, 3)
-        if pos.device != self.device or pos.dtype != self.dtype or tuple(pos.shape[1:]) != (self.n, 3):
+        """``martini_frames`` of positions that are this system's: its dtype, device and number of beads."""
+        if pos.device != self.device or pos.dtype != self.dtype or tuple(pos.shape[-2:]) != (self.n, 3):
             raise ValueError(f"pos must be a {self.dtype} tensor of shape (F, {self.n}, 3) on {self.device}")
-        box = torch.as_tensor(box, dtype=self.dtype, device=self.device).reshape(-1, 3)
-        if box.shape[0] == 1 and pos.shape[0] > 1:
-            box = box.expand(pos.shape[0], 3)
-        return pos.contiguous(), box.contiguous()
+        return martini_frames(pos, box)
 
     def energy(self, pos: torch.Tensor, box: torch.Tensor, grads: bool = False):
         """pos (F, N, 3) or (N, 3); box (F, 3) or (3,) -> (e_terms (F, 3) float64, dU/dpos or None)."""

@@ -38,34 +38,55 @@ def _geometry3(geometry: dict, model: int) -> np.ndarray:
     return np.array([float(geometry["com_to_hb"]), float(geometry["com_to_backbone"]), 0.0])
 
 
-class ObservableSet(_lib.Handle):
-    """mythos_obs_t: the index lists of up to one propeller-twist list and one quartet list on the device."""
+class _FrameSet(_lib.Handle):
+    """What the two observable sets of oxDNA frames share: base pairs, quartets, site geometry and box handed to the create
+    function the subclass names (its further arguments in between, the device last), and the launch over stored frames."""
 
-    _destroy = "mythos_observables_destroy"
-    fusable = True  # the handle mythos_oxdna_energy_obs takes
+    _create = ""
+    _eval = ""
+    _needs_geometry = ""  # the ValueError of lists that need site offsets when no [geometry] section was given
+    width = 0
+    fusable = False  # True: the handle mythos_oxdna_energy_obs takes (OxdnaSystem.energy(observables=...) refuses the others)
 
-    def __init__(self, n: int, model: int, geometry: dict | None, box, base_pairs, quartets, skip_ends: bool, dtype, device):
-        self.n, self.model, self.dtype, self.device = int(n), int(model), dtype, torch.device(device)
+    def __init__(self, n: int, model: int, geometry: dict | None, box, base_pairs, quartets, device, *more, geometry_for_pairs: bool):
+        self.n, self.model, self.device = int(n), int(model), torch.device(device)
         bps = np.ascontiguousarray(np.asarray(base_pairs if base_pairs is not None else np.zeros((0, 2)), dtype=np.int32).reshape(-1, 2))
         qs = np.ascontiguousarray(np.asarray(quartets if quartets is not None else np.zeros((0, 2, 2)), dtype=np.int32).reshape(-1, 2, 2))
-        if qs.shape[0] > 0 and geometry is None:
-            raise ValueError("rise, pitch and persistence length need the [geometry] section (site offsets)")
+        if (qs.shape[0] > 0 or (geometry_for_pairs and bps.shape[0] > 0)) and geometry is None:
+            raise ValueError(self._needs_geometry)
         g3 = _geometry3(geometry, model) if geometry is not None else np.zeros(3)
         box_arr = None if box is None else np.ascontiguousarray(np.broadcast_to(np.asarray(box, np.float64), (3,)))
         super().__init__(
-            "mythos_observables_create", self.model, self.n, g3.ctypes.data_as(_lib.c_double_p), None if box_arr is None else box_arr.ctypes.data_as(_lib.c_double_p),
-            int(bps.shape[0]), bps.ctypes.data_as(_lib.c_int_p), int(qs.shape[0]), qs.ctypes.data_as(_lib.c_int_p), int(bool(skip_ends)),
-            _lib.dtype_code(dtype), self.device.index or 0)
+            self._create, self.model, self.n, g3.ctypes.data_as(_lib.c_double_p), None if box_arr is None else box_arr.ctypes.data_as(_lib.c_double_p),
+            int(bps.shape[0]), bps.ctypes.data_as(_lib.c_int_p), int(qs.shape[0]), qs.ctypes.data_as(_lib.c_int_p), *more, self.device.index or 0)
+
+    def _rows(self, center: torch.Tensor, quat: torch.Tensor, *dtype_code) -> torch.Tensor:
+        c, q = center.contiguous(), quat.contiguous()
+        if int(c.shape[1]) != self.n:
+            raise ValueError(f"the trajectory has {int(c.shape[1])} nucleotides, the observable set {self.n}")
+        out = torch.empty((c.shape[0], self.width), dtype=torch.float64, device=self.device)
+        _lib.check(getattr(self._lib, self._eval)(self._h, _lib.ptr(c), _lib.ptr(q), *dtype_code, int(c.shape[0]), _lib.ptr(out),
+                                                  _lib.stream(self.device)), self._eval.removeprefix("mythos_"))
+        return out
+
+
+class ObservableSet(_FrameSet):
+    """mythos_obs_t: the index lists of up to one propeller-twist list and one quartet list on the device."""
+
+    _create, _eval, _destroy = "mythos_observables_create", "mythos_observables_eval", "mythos_observables_destroy"
+    _needs_geometry = "rise, pitch and persistence length need the [geometry] section (site offsets)"
+    fusable = True
+
+    def __init__(self, n: int, model: int, geometry: dict | None, box, base_pairs, quartets, skip_ends: bool, dtype, device):
+        self.dtype = dtype
+        super().__init__(n, model, geometry, box, base_pairs, quartets, device, int(bool(skip_ends)), _lib.dtype_code(dtype),
+                         geometry_for_pairs=False)
         self.width = int(self._lib.mythos_observables_width(self._h))
         self.n_corr = self.width - COL_CORR
 
     def eval(self, center: torch.Tensor, quat: torch.Tensor) -> torch.Tensor:
         """(S, width) float64 rows for (S, n, 3) / (S, n, 4) frames - the stand-alone launch."""
-        c, q = center.contiguous(), quat.contiguous()
-        out = torch.empty((c.shape[0], self.width), dtype=torch.float64, device=self.device)
-        _lib.check(self._lib.mythos_observables_eval(self._h, _lib.ptr(c), _lib.ptr(q), int(c.shape[0]), _lib.ptr(out),
-                                                     _lib.stream(self.device)), "observables_eval")
-        return out
+        return self._rows(center, quat)
 
 
 def _frames(trajectory):
@@ -146,11 +167,8 @@ class HipObservable:
         hit = lookup_fused(c, q, self.signature())
         if hit is not None:
             return hit
-        cache = self.__dict__.setdefault("_sets", {})
-        key = (int(c.shape[1]), c.dtype, str(c.device))
-        if key not in cache:
-            cache[key] = self.make_set(int(c.shape[1]), c.dtype, c.device)
-        return cache[key].eval(c, q)
+        n = int(c.shape[1])
+        return _lib.per_device(self, (n, c.dtype, c.device), lambda: self.make_set(n, c.dtype, c.device)).eval(c, q)
 
 
 # output row of mythos_duplex_obs_eval (MYTHOS_DUPLEX_ROW of include/mythos_hip.h)
@@ -158,43 +176,27 @@ DUPLEX_ROW = 4
 COL_BACKBONE_DISTANCE, COL_EXTENSION, COL_TWIST, COL_RMSD = 0, 1, 2, 3
 
 
-class DuplexSet(ObservableSet):
+class DuplexSet(_FrameSet):
     """mythos_duplex_obs_t: the lists of the duplex-mechanics observables on one device (any of them may be absent: its
-    column is then 0).  An observable set like its base - index lists on the device, ``eval(center, quat)`` -> rows, owned and
-    given back the same way - over its own handle type, row layout and entry points."""
+    column is then 0).  An observable set like ``ObservableSet`` - index lists on the device, ``eval(center, quat)`` ->
+    rows, owned and given back the same way - over its own handle type, row layout and entry points."""
 
+    _create, _eval, _destroy = "mythos_duplex_obs_create", "mythos_duplex_obs_eval", "mythos_duplex_obs_destroy"
+    _needs_geometry = "backbone distance and twist need the [geometry] section (site offsets)"
     width = DUPLEX_ROW
-    fusable = False  # its rows do not come out of mythos_oxdna_energy_obs: OxdnaSystem.energy(observables=...) refuses it
-
-    _destroy = "mythos_duplex_obs_destroy"
 
     def __init__(self, n: int, model: int, geometry: dict | None, box, base_pairs=None, quartets=None, end_pairs=None, target=None, device=None):
-        self.n, self.model, self.device = int(n), int(model), torch.device(device)
-        bps = np.ascontiguousarray(np.asarray(base_pairs if base_pairs is not None else np.zeros((0, 2)), dtype=np.int32).reshape(-1, 2))
-        qs = np.ascontiguousarray(np.asarray(quartets if quartets is not None else np.zeros((0, 2, 2)), dtype=np.int32).reshape(-1, 2, 2))
         ends = None if end_pairs is None else np.ascontiguousarray(np.asarray(end_pairs, dtype=np.int32).reshape(4))
         tgt = None if target is None else np.ascontiguousarray(np.asarray(target, dtype=np.float64).reshape(-1, 3))
-        if tgt is not None and tgt.shape[0] != self.n:
-            raise ValueError(f"the target has {tgt.shape[0]} nucleotides, the trajectory {self.n}")
-        if (bps.shape[0] > 0 or qs.shape[0] > 0) and geometry is None:
-            raise ValueError("backbone distance and twist need the [geometry] section (site offsets)")
-        g3 = _geometry3(geometry, model) if geometry is not None else np.zeros(3)
-        box_arr = None if box is None else np.ascontiguousarray(np.broadcast_to(np.asarray(box, np.float64), (3,)))
-        _lib.Handle.__init__(
-            self, "mythos_duplex_obs_create", self.model, self.n, g3.ctypes.data_as(_lib.c_double_p), None if box_arr is None else box_arr.ctypes.data_as(_lib.c_double_p),
-            int(bps.shape[0]), bps.ctypes.data_as(_lib.c_int_p), int(qs.shape[0]), qs.ctypes.data_as(_lib.c_int_p),
-            None if ends is None else ends.ctypes.data_as(_lib.c_int_p), None if tgt is None else tgt.ctypes.data_as(_lib.c_double_p),
-            self.device.index or 0)
+        if tgt is not None and tgt.shape[0] != int(n):
+            raise ValueError(f"the target has {tgt.shape[0]} nucleotides, the trajectory {int(n)}")
+        super().__init__(n, model, geometry, box, base_pairs, quartets, device,
+                         None if ends is None else ends.ctypes.data_as(_lib.c_int_p), None if tgt is None else tgt.ctypes.data_as(_lib.c_double_p),
+                         geometry_for_pairs=True)
 
     def eval(self, center: torch.Tensor, quat: torch.Tensor) -> torch.Tensor:
         """(S, 4) float64 rows for (S, n, 3) / (S, n, 4) frames."""
-        c, q = center.contiguous(), quat.contiguous()
-        if int(c.shape[1]) != self.n:
-            raise ValueError(f"the trajectory has {int(c.shape[1])} nucleotides, the observable set {self.n}")
-        out = torch.empty((c.shape[0], DUPLEX_ROW), dtype=torch.float64, device=self.device)
-        _lib.check(self._lib.mythos_duplex_obs_eval(self._h, _lib.ptr(c), _lib.ptr(q), _lib.dtype_code(c.dtype), int(c.shape[0]), _lib.ptr(out),
-                                                    _lib.stream(self.device)), "duplex_obs_eval")
-        return out
+        return self._rows(center, quat, _lib.dtype_code(center.dtype))
 
 
 class DuplexObservable:
@@ -211,9 +213,6 @@ class DuplexObservable:
 
     def rows(self, trajectory) -> torch.Tensor:
         c, q = _frames(trajectory)
-        cache = self.__dict__.setdefault("_sets", {})
-        key = (int(c.shape[1]), str(c.device))
-        if key not in cache:
-            box = getattr(self.displacement_fn, "box", None)
-            cache[key] = DuplexSet(int(c.shape[1]), self.model, self.geometry, box, self.base_pairs, self.quartets, self.end_pairs, self.target, c.device)
-        return cache[key].eval(c, q)
+        n, box = int(c.shape[1]), getattr(self.displacement_fn, "box", None)
+        return _lib.per_device(self, (n, c.device), lambda: DuplexSet(
+            n, self.model, self.geometry, box, self.base_pairs, self.quartets, self.end_pairs, self.target, c.device)).eval(c, q)

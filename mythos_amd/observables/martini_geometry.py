@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from mythos_amd import _lib
+from mythos_amd.hip_system import martini_frames
 
 
 def matching(all_names, name: str, kind: str) -> list[int]:
@@ -47,25 +48,6 @@ class GeometrySet(_lib.Handle):
         return out
 
 
-def _frames(trajectory):
-    pos = trajectory.center
-    if getattr(trajectory, "box_size", None) is None:
-        raise ValueError("MARTINI observables need trajectory.box_size (per-frame periodic box)")
-    if not isinstance(pos, torch.Tensor) or pos.device.type != "cuda":
-        raise _lib.MythosHipError("observables are evaluated by the HIP library: the trajectory must live on a GPU "
-                                  "(mythos_amd has no CPU fallback)")
-    if pos.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"unsupported dtype {pos.dtype}")
-    if pos.dim() == 2:
-        pos = pos[None]
-    box = torch.as_tensor(trajectory.box_size, dtype=pos.dtype, device=pos.device).reshape(-1, 3)
-    if box.shape[0] == 1 and pos.shape[0] > 1:
-        box = box.expand(pos.shape[0], 3)
-    if box.shape[0] != pos.shape[0]:
-        raise ValueError(f"box_size has {box.shape[0]} rows for {pos.shape[0]} frames")
-    return pos.contiguous(), box.contiguous()
-
-
 class MappedGeometry:
     """Base of the ``*Mapped`` observables: ``names`` -> dict of (S, n_matching) float64 device tensors, one launch.
 
@@ -97,7 +79,7 @@ class MappedGeometry:
     def packed(self, trajectory):
         """(block, S, members): the packed block of the launch and its layout."""
         lists = self.index_lists()
-        pos, box = _frames(trajectory)
+        pos, box = martini_frames(trajectory.center, getattr(trajectory, "box_size", None))
         if pos.shape[1] != len(self.topology.atom_names):
             raise ValueError(f"trajectory has {pos.shape[1]} beads, the topology {len(self.topology.atom_names)}")
         gs = _lib.per_device(self, pos.device, lambda: GeometrySet(int(pos.shape[1]), [self.width] * len(lists), lists, pos.device))

@@ -37,8 +37,8 @@ import numpy as np
 import torch
 
 from mythos_amd import _lib
+from mythos_amd.hip_system import martini_frames
 from mythos_amd.input.gromacs import MartiniTopology
-from mythos_amd.observables.martini_geometry import _frames
 
 ANGSTROM_PER_NM = 10.0
 _FIELDS = {"name": "atom_names", "resname": "residue_names"}
@@ -142,7 +142,7 @@ class _Membrane:
 
     def _rows(self, trajectory, want_leaflets=False):
         lists = self.index_lists()
-        pos, box = _frames(trajectory)
+        pos, box = martini_frames(trajectory.center, getattr(trajectory, "box_size", None))
         if pos.shape[1] != len(self.topology.atom_names):
             raise ValueError(f"trajectory has {pos.shape[1]} beads, the topology {len(self.topology.atom_names)}")
         return _lib.per_device(self, pos.device, lambda: MembraneSet(int(pos.shape[1]), *lists[1:], pos.device)).eval(pos, box, want_leaflets)

@@ -12,6 +12,10 @@
 // malloc-backed runtime; prints what was read back and, after every scope, the live allocations (the test wants 0).
 // `--md-plan`: the launch plan of the oxDNA step kernel (mythos_amd/csrc/md_plan.h) for a fixed table of systems, one line
 // each: lanes per nucleotide, then nucleotides per workgroup, workgroups, grid, the DENSE choice and the priority switch.
+// `--index-lists`: the argument checks the *_create functions of the frame observables share (mythos_amd/csrc/host_checks.h):
+// empty lists, the last valid and the first invalid index on either side, boxes with an edge that is not positive; one
+// line per case with the verdict and the error message it left.
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +25,7 @@
 #include <vector>
 
 #include "device_buf.h"
+#include "host_checks.h"
 #include "md_plan.h"
 
 namespace mythos {
@@ -208,8 +213,47 @@ static int md_plan_case() {
   return 0;
 }
 
+// host_checks.h on lists of exactly the length they are said to have (the sanitizer build sees a read past either end)
+static int index_lists_case() {
+  using mythos::indices_in_range;
+  auto list_case = [](const char* name, const std::vector<int32_t>& v, int n) {
+    const std::vector<int32_t> exact(v);  // capacity == size
+    mythos::g_error = "-";
+    const bool ok = indices_in_range(exact.data(), exact.size(), n, name);
+    printf("LISTS %s count %zu n %d -> %d: %s\n", name, exact.size(), n, ok ? 1 : 0, mythos::g_error.c_str());
+    return ok;
+  };
+  mythos::g_error = "-";
+  const bool null_ok = indices_in_range(nullptr, 0, 5, "null");
+  printf("LISTS null count 0 n 5 -> %d: %s\n", null_ok ? 1 : 0, mythos::g_error.c_str());
+  if (!null_ok || !list_case("empty", {}, 5)) return 70;
+  if (!list_case("first-and-last-valid", {0, 4, 2, 4}, 5) || !list_case("one-nucleotide", {0}, 1)) return 71;
+  if (list_case("n-itself", {0, 4, 5}, 5) || list_case("minus-one", {0, -1, 4}, 5) || list_case("n-at-the-front", {5, 0}, 5) ||
+      list_case("minus-one-at-the-end", {3, 2, 1, 0, -1}, 5) || list_case("int-min", {INT32_MIN}, 5) || list_case("int-max", {INT32_MAX}, INT32_MAX))
+    return 72;
+  const double geometry[3] = {0.4, -0.4, 0.25};
+  struct Box {
+    const char* name;
+    bool on;
+    double l[3];
+  };
+  const Box boxes[] = {{"free", false, {0, 0, 0}}, {"cube", true, {20, 20, 20}}, {"zero-edge", true, {20, 0, 20}},
+                       {"negative-edge", true, {20, 20, -1}}, {"nan-edge", true, {std::nan(""), 20, 20}}};
+  for (int model = 1; model <= 3; ++model)
+    for (const Box& b : boxes) {
+      mythos::SiteGeo g;
+      mythos::g_error = "-";
+      const bool ok = mythos::site_geo_from(model, geometry, b.on ? b.l : nullptr, "selftest", &g);
+      printf("GEO model %d %s -> %d model %d g %.3f %.3f %.3f box_on %d %.1f %.1f %.1f: %s\n", model, b.name, ok ? 1 : 0, g.model, g.g_hb,
+             g.g_k1, g.g_k2, g.box_on, g.box[0], g.box[1], g.box[2], mythos::g_error.c_str());
+      if (ok != (!b.on || (b.l[0] > 0 && b.l[1] > 0 && b.l[2] > 0)) || (ok && (g.box_on != (b.on ? 1 : 0) || g.g_k2 != (model >= 2 ? geometry[2] : 0.0)))) return 73;
+    }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
+  if (std::string(argv[1]) == "--index-lists") return index_lists_case();
   if (std::string(argv[1]) == "--device-buf") return device_buf_case();
   if (std::string(argv[1]) == "--md-plan") return md_plan_case();
   FILE* f = fopen(argv[1], "rb");

@@ -99,6 +99,68 @@ def test_the_kernels_with_scratch_are_the_known_ones():
     assert "-amdgpu-remove-redundant-endcf=0" in flags.split("CXXFLAGS ?=")[1].split("\n\n")[0]
 
 
+def _i32(values):
+    a = np.ascontiguousarray(values, dtype=np.int32).reshape(-1)
+    return a, a.ctypes.data_as(_lib.c_int_p)
+
+
+def _create_with(fn: str, bad: int, which: str, box=None):
+    """The named create function on a system of n = 6 whose list `which` holds index `bad` at its end: (handle, message)."""
+    lib = _lib.load()
+    n, ok = 6, 5  # (5: the last valid index)
+    pick = lambda name: bad if which == name else ok  # noqa: E731
+    g = np.array([0.4, -0.4, 0.25])
+    gp = g.ctypes.data_as(_lib.c_double_p)
+    b = None if box is None else np.ascontiguousarray(box, dtype=np.float64)
+    bp = None if b is None else b.ctypes.data_as(_lib.c_double_p)
+    keep = []  # the arrays the pointers below look into
+
+    def lst(values):
+        keep.append(_i32(values))
+        return keep[-1][1]
+
+    if fn in ("mythos_observables_create", "mythos_duplex_obs_create"):
+        pairs, quartets = lst([0, 5, 1, pick("base-pair")]), lst([0, 5, 1, pick("quartet")])
+        if fn == "mythos_observables_create":
+            h = lib.mythos_observables_create(2, n, gp, bp, 2, pairs, 1, quartets, 0, 0, 0)
+        else:
+            h = lib.mythos_duplex_obs_create(2, n, gp, bp, 2, pairs, 1, quartets, lst([0, 5, 2, pick("end-pair")]), None, 0)
+    elif fn == "mythos_membrane_create":
+        # two lipids of two and one bead, two thickness beads; thick_lipid indexes the 2 lipids
+        tl = {-1: -1, n: 2}.get(bad, 1) if which == "thickness-lipid" else 1
+        h = lib.mythos_membrane_create(n, 2, lst([0, 2, 3]), lst([0, 1, pick("bead")]), 2, lst([0, pick("thickness-bead")]), lst([0, tl]), 0)
+    else:
+        h = lib.mythos_martini_obs_create(n, 2, lst([2, 3]), lst([1, 1]), lst([0, 5, 1, 2, pick("bead")]), 0)
+    return h, _lib.last_error()
+
+
+@pytest.mark.parametrize("fn,which,message", [
+    ("mythos_observables_create", "base-pair", "mythos_observables_create: base-pair index out of range"),
+    ("mythos_observables_create", "quartet", "mythos_observables_create: quartet index out of range"),
+    ("mythos_duplex_obs_create", "base-pair", "mythos_duplex_obs_create: base-pair index out of range"),
+    ("mythos_duplex_obs_create", "quartet", "mythos_duplex_obs_create: quartet index out of range"),
+    ("mythos_duplex_obs_create", "end-pair", "mythos_duplex_obs_create: end-pair index out of range"),
+    ("mythos_membrane_create", "bead", "mythos_membrane_create: bead index out of range"),
+    ("mythos_membrane_create", "thickness-bead", "mythos_membrane_create: thickness bead or its lipid out of range"),
+    ("mythos_membrane_create", "thickness-lipid", "mythos_membrane_create: thickness bead or its lipid out of range"),
+    ("mythos_martini_obs_create", "bead", "mythos_martini_obs_create: bead index out of range"),
+])
+def test_create_functions_of_the_frame_observables_refuse_an_index_outside_the_system(fn, which, message):
+    """Index -1 and index n, in every list of the four create functions: NULL and the function's message, from the host
+    checks in front of the device selection - so also where there is no GPU (with one, a list of valid indices passes
+    them: that is every GPU test of these units)."""
+    for bad in (-1, 6):
+        h, msg = _create_with(fn, bad, which)
+        assert not h and msg == message, (bad, msg)
+
+
+@pytest.mark.parametrize("fn", ["mythos_observables_create", "mythos_duplex_obs_create"])
+@pytest.mark.parametrize("box", [(20.0, 0.0, 20.0), (0.0, 20.0, 20.0), (20.0, 20.0, -1.0), (20.0, float("nan"), 20.0)])
+def test_observable_sets_refuse_a_box_with_an_edge_that_is_not_positive(fn, box):
+    h, msg = _create_with(fn, 5, "none", box=box)
+    assert not h and msg == f"{fn}: box edges must be positive"
+
+
 def test_no_gpu_means_loud_failure():
     if torch.cuda.is_available():
         pytest.skip("a GPU is present")

@@ -347,6 +347,40 @@ def test_md_launch_plan_boundaries():
         assert r.stdout.splitlines() == lines
 
 
+def test_index_list_and_site_geometry_checks_agree_between_the_plain_and_the_sanitizer_build():
+    """mythos_amd/csrc/host_checks.h, what the *_create functions of the frame observables refuse a list or a box with, run
+    by the stand-alone programs over lists of exactly their stated length: a null pointer with a count of 0 and an empty
+    list pass, the last valid index passes, the first invalid one on either side is refused wherever it stands, and a box
+    with a zero, negative or NaN edge is refused for every model.  The same lines from both builds, a clean sanitizer log."""
+    plain, san = cpu_port.BUILD / "md_cpu_selftest", cpu_port.BUILD / "md_cpu_selftest_san"
+    if not san.exists():
+        subprocess.run(["make", "-C", str(cpu_port.BUILD.parent)], check=True, capture_output=True)
+    env = {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}
+    a = subprocess.run([str(plain), "--index-lists"], capture_output=True, text=True, env=env, timeout=60)
+    b = subprocess.run([str(san), "--index-lists"], capture_output=True, text=True, env=env, timeout=60)
+    assert a.returncode == 0, (a.stdout, a.stderr)
+    assert b.returncode == 0, (b.stdout, b.stderr[-3000:])
+    assert a.stdout == b.stdout
+    assert b.stderr.strip() == "", b.stderr[-3000:]
+    lines = a.stdout.splitlines()
+    verdict = {ln.split()[1]: (ln.split(" -> ")[1][0], ln.rsplit(": ", 1)[1]) for ln in lines if ln.startswith("LISTS ")}
+    assert verdict == {
+        "null": ("1", "-"), "empty": ("1", "-"), "first-and-last-valid": ("1", "-"), "one-nucleotide": ("1", "-"),
+        "n-itself": ("0", "n-itself"), "minus-one": ("0", "minus-one"), "n-at-the-front": ("0", "n-at-the-front"),
+        "minus-one-at-the-end": ("0", "minus-one-at-the-end"), "int-min": ("0", "int-min"), "int-max": ("0", "int-max"),
+    }
+    geo = [ln for ln in lines if ln.startswith("GEO ")]
+    assert len(geo) == 15
+    for ln in geo:
+        model, box = int(ln.split()[2]), ln.split()[3]
+        if box in ("free", "cube"):
+            k2 = "0.250" if model >= 2 else "0.000"  # oxDNA1 has no second backbone coefficient
+            on = "box_on 1 20.0 20.0 20.0" if box == "cube" else "box_on 0 1.0 1.0 1.0"
+            assert ln.endswith(f"-> 1 model {model} g 0.400 -0.400 {k2} {on}: -"), ln
+        else:
+            assert " -> 0 " in ln and ln.endswith(": selftest: box edges must be positive"), ln
+
+
 # ---- MARTINI (oracle/cpu_port/martini_cpu.cpp): bench.py's cpu_baseline of BASELINE configs[2] ------------------
 def _martini_port(angle_kind=0, mass=None):
     from tests import martini_helpers as MH

@@ -441,7 +441,7 @@ def test_integrator_and_system_close_in_either_order(make):
 def test_close_is_idempotent_for_every_handle_class():
     """Each class of mythos_amd that owns a handle of the C ABI: the second close() does not reach the library."""
     from mythos_amd import _lib
-    from mythos_amd.observables.base import ObservableSet
+    from mythos_amd.observables.base import DuplexSet, ObservableSet
     from mythos_amd.observables.martini_geometry import GeometrySet
     from mythos_amd.observables.membrane import MembraneSet
     from mythos_amd.observables.wasserstein import W1Plan
@@ -461,11 +461,15 @@ def test_close_is_idempotent_for_every_handle_class():
     samples = torch.tensor([0.3, 0.1, 0.2], dtype=torch.float64, device=DEV)
     handles = [ix, sx, im, sm,
                ObservableSet(16, 2, None, None, [[0, 15], [1, 14]], None, True, torch.float32, DEV),
+               DuplexSet(16, 2, None, None, end_pairs=[0, 15, 7, 8], device=DEV),
                GeometrySet(8, [2, 3], [np.array([[0, 1], [2, 3]]), np.array([[0, 1, 2]])], DEV),
                MembraneSet(8, [0, 1, 2], [0, 4], [1, 5], [0, 1], DEV),
                W1Plan(samples, [3], [1], [torch.tensor([0.15, 0.25], dtype=torch.float64, device=DEV)], [None])]
-    owners = {c for c in _lib.Handle.__subclasses__() if c.__module__.startswith("mythos_amd.") and not c.__name__.startswith("_")}
-    assert {type(h) for h in handles} >= owners and len(owners) == 6
+    def below(c):  # every class under c, at any depth (the two observable sets and the two integrators share a private base)
+        return {s for d in c.__subclasses__() for s in {d} | below(d)}
+
+    owners = {c for c in below(_lib.Handle) if c.__module__.startswith("mythos_amd.") and not c.__name__.startswith("_")}
+    assert {type(h) for h in handles} == owners and len(owners) == 9
     for h in handles:
         assert isinstance(h, _lib.Handle) and h._h
         spy = h._lib = Counting(h._lib)

@@ -201,8 +201,8 @@ def test_argument_errors():
 
 
 def test_a_duplex_set_gives_its_handle_back_once():
-    """close() any number of times, then the finaliser: one mythos_duplex_obs_destroy (the check test_gpu_api.py makes of
-    the handle classes that derive from Handle directly; this one derives from ObservableSet)."""
+    """close() any number of times, then the finaliser: one mythos_duplex_obs_destroy, by name (test_gpu_api.py makes
+    the check of every handle class; this one reaches Handle through the base it shares with ObservableSet)."""
     s = PB.DuplexSet(16, 2, None, None, end_pairs=[0, 15, 7, 8], device=DEV)
     assert isinstance(s, _lib.Handle) and s._h and s._destroy == "mythos_duplex_obs_destroy"
 
