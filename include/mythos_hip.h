@@ -464,6 +464,34 @@ int mythos_martini_langevin_neighbor_stats(const mythos_martini_sim_t* sim, int*
  * *stride is set.  Synchronises the device. */
 int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* sim, int which, int32_t* rows, int32_t* row_len, int* stride);
 
+/* ---- MARTINI NPT: pressure and cell-rescaling pressure coupling ------------------------------------------------
+ * Stands in for the pressure coupling of the GROMACS runs the reference drives (data/templates/martini/m2/DMPC/273K/
+ * md.mdp): kind <- pcoupl, coupling <- pcoupltype, tau_p <- tau-p, compressibility <- compressibility, ref_p <- ref-p,
+ * every <- nstpcouple.  First-order cell rescaling only: kind 1 is Berendsen, kind 2 stochastic cell rescaling (C-rescale,
+ * Bernetti & Bussi 2020: Berendsen's drift plus its fluctuation-dissipation noise, velocities scaled by 1 / mu); kind 0
+ * switches coupling off (the default: every call then runs exactly as without this entry point).  The reference's own
+ * choice, Parrinello-Rahman, is not built; neither are anisotropic / off-diagonal coupling or a barostat for oxDNA.
+ *   coupling         0 isotropic (ref_p[0], compressibility[0]), 1 semi-isotropic ([0]: xy, [1]: z; compressibility[1] = 0
+ *                    fixes the box height, the reference's setting)
+ *   ref_p bar, compressibility 1/bar, tau_p ps; compressibility all 0 is "off" as well
+ * An event happens at the closed state of every absolute step s > 0 with s % every == 0 (mythos_martini_langevin_get_step
+ * counts them), so advance(a); advance(b) stays advance(a + b) bit for bit.  mu = exp(-f (P0 - P) / 3 ...) with
+ * f = compressibility every dt / tau_p; GROMACS' Berendsen uses the linear 1 - f (P0 - P) / 3, equal up to O(f^2).
+ * The noise is normals6(seed, particle 0, step s, stream 2) of the thermostat's generator.  An event that would make an edge
+ * shorter than 2 (r_cut + skin) ends the call with INVALID_ARGUMENT; the state of that step stays resident, unscaled.
+ * Each event costs a closing launch, a pressure launch, a list rebuild and one stream synchronisation. */
+int mythos_martini_langevin_set_barostat(mythos_martini_sim_t* sim, int kind, int coupling, const double ref_p[2],
+                                         const double compressibility[2], double tau_p, int every);
+/* Pressure of the resident state (what `gmx energy` reports as Pres-XX / -YY / -ZZ): out = K[3], W[3] (kJ/mol: sum m v_d^2
+ * and the virial -dU/dln s_d of LJ + bonds + angles), P[3] = (K + W) / V x 16.6053907 (bar), V (nm^3).  Closes an open
+ * frame first, as store does; a closed frame is left bitwise as it was.  Synchronises the stream. */
+int mythos_martini_langevin_pressure(mythos_martini_sim_t* sim, double out[10], mythos_stream_t stream);
+/* the box of the resident state (host double[3]): the one loaded, rescaled by the coupling events since */
+int mythos_martini_langevin_get_box(const mythos_martini_sim_t* sim, double box[3]);
+/* The box of every row the last run / advance saved, host double[*n_rows][3] (the .gro / .trr box line of a GROMACS
+ * trajectory).  A row saved at an event step holds the state before the event and its box.  boxes == NULL: only *n_rows. */
+int mythos_martini_langevin_last_boxes(const mythos_martini_sim_t* sim, double* boxes, int* n_rows);
+
 /* ---- MARTINI observables: named bond lengths and triplet angles ------------------------------
  * Replaces mythos/observables/bond_distances.py:15-17, 51-69 (BondDistances / BondDistancesMapped) and
  * triplet_angles.py:15-31, 73-92 (TripletAngles / TripletAnglesMapped) with the angle of

@@ -96,6 +96,10 @@ _SIGS = {
     "mythos_martini_langevin_last_recoveries": (C.c_int, [V, C.POINTER(C.c_int)]),
     "mythos_martini_langevin_neighbor_stats": (C.c_int, [V, C.POINTER(C.c_int), c_double_p]),
     "mythos_martini_langevin_get_rows": (C.c_int, [V, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "mythos_martini_langevin_set_barostat": (C.c_int, [V, C.c_int, C.c_int, c_double_p, c_double_p, C.c_double, C.c_int]),
+    "mythos_martini_langevin_pressure": (C.c_int, [V, c_double_p, V]),
+    "mythos_martini_langevin_get_box": (C.c_int, [V, c_double_p]),
+    "mythos_martini_langevin_last_boxes": (C.c_int, [V, c_double_p, C.POINTER(C.c_int)]),
     "mythos_martini_obs_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int]),
     "mythos_martini_obs_destroy": (None, [V]),
     "mythos_martini_obs_count": (C.c_int64, [V]),

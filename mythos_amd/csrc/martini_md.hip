@@ -538,6 +538,25 @@ __global__ __launch_bounds__(256) void mm_build_rows_allpairs_kernel(
 
 using namespace mythos;
 
+// Pressure coupling of the resident state (martini_npt.inc): what mythos_martini_langevin_set_barostat set, the device and
+// pinned records of the last pressure evaluation / coupling event, and the box of every row the last call saved.
+struct MmBarostat {
+  int kind = 0;      // 0 off, 1 Berendsen, 2 stochastic cell rescaling
+  int coupling = 0;  // 0 isotropic, 1 semi-isotropic (xy, z)
+  double ref_p[2] = {1.0, 1.0}, beta[2] = {0.0, 0.0}, tau_p = 1.0;  // bar, 1/bar, ps
+  int every = 10;
+  mythos::DeviceBuf<double> d_part, d_rec;  // per-workgroup partials [blocks][6]; the record the scale kernel reads
+  double* h_rec = nullptr;                  // the same record in pinned host memory, written by the device
+  double* d_hrec = nullptr;                 // device address of h_rec
+  std::vector<double> last_boxes;           // [rows][3] of the last run / advance
+  MmBarostat() = default;
+  MmBarostat(const MmBarostat&) = delete;
+  MmBarostat& operator=(const MmBarostat&) = delete;
+  ~MmBarostat() {  // (the owner's destructor has selected the device)
+    if (h_rec) (void)hipHostFree(h_rec);
+  }
+};
+
 struct mythos_martini_sim : mythos::MdRun {
   mythos_martini* sys = nullptr;
   double dt = 0.02, kT = 2.27, gamma = 1.0;
@@ -563,6 +582,7 @@ struct mythos_martini_sim : mythos::MdRun {
   int inner_every = 4;
   DeviceBuf<double> d_epart;
   double box[3] = {0, 0, 0};  // of the resident state (mythos_martini_langevin_load / advance / store)
+  MmBarostat baro;            // off until mythos_martini_langevin_set_barostat: box is then constant between two loads
   ~mythos_martini_sim() { (void)hipSetDevice(device); }  // the members, MdRun's too, free themselves on that device
 };
 
@@ -732,6 +752,8 @@ static int mm_store_typed(mythos_martini_sim* sim, R* pos, R* v, hipStream_t st)
 
 }  // namespace mythos
 
+#include "martini_npt.inc"
+
 extern "C" {
 
 void mythos_martini_langevin_destroy(mythos_martini_sim_t* s) { delete s; }
@@ -868,8 +890,13 @@ int mm_load(mythos_martini_sim_t* s, const void* pos, const void* vel, const dou
                                      : mm_load_typed<double>(s, (const double*)pos, (const double*)vel, box, st);
 }
 int mm_advance(mythos_martini_sim_t* s, int n_steps, int save_every, bool close, void* traj, double* e_trace, hipStream_t st) {
-  return s->sys->dtype == MYTHOS_F32 ? mm_advance_typed<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
-                                     : mm_advance_typed<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+  if (mm_barostat_on(s))  // chunks that end at coupling events (martini_npt.inc); off: the call below, as ever
+    return s->sys->dtype == MYTHOS_F32 ? mm_advance_npt<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
+                                       : mm_advance_npt<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+  const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_typed<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
+                                             : mm_advance_typed<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+  mm_constant_boxes(s, rc == MYTHOS_OK && save_every > 0 ? n_steps / save_every : 0);
+  return rc;
 }
 int mm_store(mythos_martini_sim_t* s, void* pos, void* vel, hipStream_t st) {
   return s->sys->dtype == MYTHOS_F32 ? mm_store_typed<float>(s, (float*)pos, (float*)vel, st) : mm_store_typed<double>(s, (double*)pos, (double*)vel, st);

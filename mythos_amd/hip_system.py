@@ -539,6 +539,50 @@ class MartiniLangevinIntegrator(_MdIntegrator):
         margin <= 0 switches them off again) - include/mythos_hip.h."""
         _lib.check(self._lib.mythos_martini_langevin_set_inner_list(self._h, float(margin), int(every)), "set_inner_list")
 
+    BAROSTATS = {None: 0, "berendsen": 1, "c-rescale": 2}  # the reference's mdp key ``pcoupl``
+    COUPLINGS = {"isotropic": 0, "semiisotropic": 1}         # ``pcoupltype``
+
+    def set_barostat(self, kind=None, coupling="isotropic", ref_p=1.0, compressibility=4.5e-5, tau_p=1.0, every=10) -> None:
+        """Pressure coupling by cell rescaling (mythos_martini_langevin_set_barostat): ``kind`` None (off), "berendsen" or
+        "c-rescale" (stochastic cell rescaling); ``coupling`` "isotropic" or "semiisotropic", for which ``ref_p`` (bar) and
+        ``compressibility`` (1/bar) are (xy, z) pairs - a scalar serves both; ``tau_p`` in ps; an event every ``every``
+        steps of the integrator's step counter.  GROMACS' ``ref-p``, ``compressibility``, ``tau-p``, ``nstpcouple``."""
+        if kind not in self.BAROSTATS or coupling not in self.COUPLINGS:
+            raise ValueError(f"kind must be one of {list(self.BAROSTATS)}, coupling one of {list(self.COUPLINGS)}")
+        pair = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (2,)))  # noqa: E731
+        p0, beta = pair(ref_p), pair(compressibility)
+        _lib.check(self._lib.mythos_martini_langevin_set_barostat(
+            self._h, self.BAROSTATS[kind], self.COUPLINGS[coupling], p0.ctypes.data_as(_lib.c_double_p),
+            beta.ctypes.data_as(_lib.c_double_p), float(tau_p), int(every)), "set_barostat")
+
+    def pressure(self) -> dict:
+        """Pressure of the resident state (mythos_martini_langevin_pressure; synchronises): ``kinetic`` and ``virial``
+        (3,) float64 in kJ/mol - sum m v_d^2 and -dU/dln s_d -, ``pressure`` (3,) in bar, ``volume`` in nm^3 and the
+        scalar ``p`` = mean of the three.  An open frame is closed first, as ``store`` does."""
+        out = np.zeros(10, dtype=np.float64)
+        _lib.check(self._lib.mythos_martini_langevin_pressure(self._h, out.ctypes.data_as(_lib.c_double_p), _lib.stream(self.system.device)),
+                   "martini_langevin_pressure")
+        return {"kinetic": out[0:3].copy(), "virial": out[3:6].copy(), "pressure": out[6:9].copy(), "volume": float(out[9]),
+                "p": float(out[6:9].mean())}
+
+    @property
+    def box(self) -> np.ndarray:
+        """(3,) float64: the box of the resident state - the one loaded, rescaled by the coupling events since."""
+        b = np.zeros(3, dtype=np.float64)
+        _lib.check(self._lib.mythos_martini_langevin_get_box(self._h, b.ctypes.data_as(_lib.c_double_p)), "get_box")
+        return b
+
+    @property
+    def last_boxes(self) -> torch.Tensor:
+        """(S, 3) float64 on the system's device: the box of every row the last ``run`` / ``advance`` saved - what
+        ``SimulatorTrajectory.box_size`` takes.  A row saved at a coupling step is the state before the event, with its box."""
+        n = C.c_int(0)
+        _lib.check(self._lib.mythos_martini_langevin_last_boxes(self._h, None, C.byref(n)), "last_boxes")
+        b = np.zeros((n.value, 3), dtype=np.float64)
+        if n.value:
+            _lib.check(self._lib.mythos_martini_langevin_last_boxes(self._h, b.ctypes.data_as(_lib.c_double_p), C.byref(n)), "last_boxes")
+        return torch.as_tensor(b, device=self.system.device)
+
     def init_velocities(self) -> torch.Tensor:
         v = torch.empty((self.system.n, 3), dtype=self.system.dtype, device=self.system.device)
         _lib.check(self._lib.mythos_martini_langevin_init_velocities(self._h, _lib.ptr(v), _lib.stream(self.system.device)), "init_velocities")
