@@ -315,6 +315,52 @@ int mythos_langevin_set_seed(mythos_sim_t* sim, uint64_t seed);
  * kick of that launch, i.e. with the external part of the NEXT step's opening half kick already in the momenta. */
 int mythos_langevin_set_external_forces(mythos_sim_t* sim, int count, const int32_t* index, const double* force);
 
+/* Position-dependent external forces on centres of mass - the three fixes of the reference's stretch-torsion protocol
+ * (data/templates/lammps-stretch-tors/: LAMMPS' spring/self, addforce with a variable of summed coordinates, addtorque).
+ * None is a body torque.  Coordinates are the integrator's own, unfolded and without a minimum image.
+ *   tethers  F_i = -k_i A_i (x_i - a_i),  U = sum k_i / 2 |A_i (x_i - a_i)|^2
+ *     t_index  host int32[n_tethers]      nucleotides, each in [0, n) and listed once
+ *     t_k      host double[n_tethers]     k_i >= 0
+ *     t_anchor host double[n_tethers][3]  a_i
+ *     t_mask   host int32[n_tethers]      A_i: bit 0 / 1 / 2 set = x / y / z restrained
+ *   groups, a CSR list: group g has the members g_member[g_first[g] .. g_first[g + 1]), distinct within the group; a
+ *   nucleotide may be in several groups and have a tether as well
+ *     g_kind   host int32[n_groups]       MYTHOS_RESTRAINT_SUM or MYTHOS_RESTRAINT_TORQUE
+ *     g_first  host int32[n_groups + 1]   g_first[0] = 0
+ *     g_member host int32[g_first[n_groups]]
+ *     g_vec    host double[n_groups][3]   sum: (k, unused, unused), k >= 0;  torque: T, |T| > 0
+ *     g_target host double[n_groups][3]   sum: s0 (torque: unused)
+ *     g_mask   host int32[n_groups]       sum: A as above (torque: unused)
+ *   sum restraint:  s = sum_{j in G} x_j,  F_i = -k A (s - s0) on every member,  U = k / 2 |A (s - s0)|^2  (at least 1 member)
+ *   torque:         d_i = x_i - centroid(G),  t = T / |T|,  S = sum_j |d_j - (d_j.t) t|^2,  F_i = (T x d_i) / S: the forces
+ *                   add up to zero and their torque about the centroid along t is |T| (at least 2 members).  A group
+ *                   whose members all lie on the axis (S = 0; in floating point S <= 1e-24 sum |x_j|^2) gets no force.
+ *                   The torque has no potential.
+ * Everything is held and summed in double in both precisions, in a fixed order: a run is reproducible to the bit.
+ * n_tethers = n_groups = 0 clears the restraints; a run without restraints issues no launch for them, and constant
+ * forces (mythos_langevin_set_external_forces) keep exactly their own launch.  With restraints set every step launch is
+ * preceded by two more small launches - the groups' sums, then the kick of every restrained momentum by the multiple of
+ * dt F(x) that step launch applies of dt F, F taken at the positions that launch reads, which the kick does not write:
+ * the pair is BAOAB with the total force.  The kick follows the halt / abort / resume protocol as the constant one does.
+ * MYTHOS_ERR_INVALID_ARGUMENT: while the resident frame is open (as mythos_langevin_set_external_forces); an index out of
+ * range; a nucleotide listed twice among the tethers or within one group; a value that is not finite; k < 0; T = 0; too
+ * few members.  mythos_langevin_run / _advance refuse to step with restraints on the unfused oxNA path.
+ * The energy-trace rows stay what they are: neither the tether nor the sum-restraint energy is part of them (nor the
+ * work of the torque, which has no potential), and the kinetic energies of a row are taken after the external kicks of
+ * that launch - see mythos_langevin_set_external_forces.  mythos_langevin_eval_external returns the energies. */
+enum mythos_restraint_kind { MYTHOS_RESTRAINT_SUM = 0, MYTHOS_RESTRAINT_TORQUE = 1 };
+int mythos_langevin_set_restraints(mythos_sim_t* sim, int n_tethers, const int32_t* t_index, const double* t_k, const double* t_anchor,
+                                   const int32_t* t_mask, int n_groups, const int32_t* g_kind, const int32_t* g_first,
+                                   const int32_t* g_member, const double* g_vec, const double* g_target, const int32_t* g_mask);
+
+/* The external field of the integrator - constant forces, tethers, sum restraints and torques - at the caller's centres,
+ * through the kernels the integrator kicks with (c dt = 1 on zeroed momenta).  Needs no resident state and changes none.
+ *   center     device (N,3), the system's precision
+ *   force_out  device (N,3), the system's precision
+ *   energy_out device double[3]: -sum F.x of the constant forces, the tether energy, the sum-restraint energy
+ * Asynchronous on `stream`; the scratch arrays belong to the integrator, so one call at a time per integrator. */
+int mythos_langevin_eval_external(mythos_sim_t* sim, const void* center, void* force_out, double* energy_out, mythos_stream_t stream);
+
 /* Integrator options.  MYTHOS_LANGEVIN_UNFUSED (oxNA systems only, value 0 / 1): step through the two-launch path -
  * the energy kernel's forces launch + a one-thread-per-nucleotide integrator - instead of the fused step kernel.  A
  * second implementation of the same map (same Philox stream), kept as the cross-check of the fused oxNA instantiation;

@@ -117,6 +117,11 @@ int md_advance(mythos_sim_t* s, int n_steps, int save_every, bool close, void* t
               "(MYTHOS_LANGEVIN_UNFUSED); clear them or step through the fused kernel");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
+  if (s->rst.n_entries > 0 && s->unfused.active) {
+    set_error("mythos_langevin_run / advance: restraints are not applied on the unfused oxNA path "
+              "(MYTHOS_LANGEVIN_UNFUSED); clear them or step through the fused kernel");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
   // quaternion rows are written as one 4-vector per nucleotide
   const size_t q_align = s->sys->dtype == MYTHOS_F32 ? sizeof(float4) : sizeof(double4);
   if (save_every > 0 && tq && (reinterpret_cast<uintptr_t>(tq) % q_align) != 0) {
@@ -198,7 +203,7 @@ int mythos_langevin_set_step(mythos_sim_t* s, int64_t step) {
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   s->step = step;
-  s->ext_stamp_stale = true;  // (the stamp of the last external kick names a step index)
+  s->ext_stamp_stale = s->rst_stamp_stale = true;  // (the stamp of the last external kick names a step index)
   return MYTHOS_OK;
 }
 
@@ -249,6 +254,108 @@ int mythos_langevin_set_external_forces(mythos_sim_t* s, int count, const int32_
     if (int rc = s->d_ext_stamp.alloc(1)) return rc;
   s->ext_count = count;
   return MYTHOS_OK;
+}
+
+int mythos_langevin_set_restraints(mythos_sim_t* s, int n_tethers, const int32_t* t_index, const double* t_k, const double* t_anchor,
+                                   const int32_t* t_mask, int n_groups, const int32_t* g_kind, const int32_t* g_first,
+                                   const int32_t* g_member, const double* g_vec, const double* g_target, const int32_t* g_mask) {
+  const std::string who = "mythos_langevin_set_restraints";
+  auto refuse = [&](const std::string& why) {
+    set_error(who + ": " + why);
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  };
+  if (!s || n_tethers < 0 || n_groups < 0 || (n_tethers > 0 && (!t_index || !t_k || !t_anchor || !t_mask)) ||
+      (n_groups > 0 && (!g_kind || !g_first || !g_member || !g_vec || !g_target || !g_mask)))
+    return refuse("invalid argument");
+  if (s->resident && s->open)
+    return refuse("the resident frame is open (its pending closing half kick would mix two forces); call mythos_langevin_store first");
+  const int n = s->sys->n;
+  auto in_range = [&](int i) { return i >= 0 && i < n; };
+  auto finite3 = [](const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
+  const std::string range = " out of range [0, " + std::to_string(n) + ")";
+  // terms[i]: the terms that name nucleotide i, the tether first, then the groups ascending (the order the kick adds in)
+  std::vector<std::vector<int>> terms((size_t)n);
+  for (int t = 0; t < n_tethers; ++t) {
+    const int i = t_index[t];
+    if (!in_range(i)) return refuse("nucleotide index " + std::to_string(i) + range);
+    if (!terms[i].empty()) return refuse("nucleotide " + std::to_string(i) + " is listed twice among the tethers");
+    if (!std::isfinite(t_k[t]) || !finite3(t_anchor + 3 * (size_t)t)) return refuse("a tether's stiffness or anchor is not finite");
+    if (t_k[t] < 0) return refuse("a tether's stiffness is negative (k >= 0)");
+    if (t_mask[t] < 0 || t_mask[t] > 7) return refuse("an axis mask is not a combination of the bits 1, 2, 4");
+    terms[i].push_back(t);
+  }
+  if (n_groups > 0 && g_first[0] != 0) return refuse("the member ranges start at 0");
+  std::vector<int> last_group((size_t)n, -1);
+  for (int g = 0; g < n_groups; ++g) {
+    const int b = g_first[g], e = g_first[g + 1];
+    const bool torque = g_kind[g] == EXT_GROUP_TORQUE;
+    if (g_kind[g] != EXT_GROUP_SUM && !torque) return refuse("group kind " + std::to_string(g_kind[g]) + " (0: sum restraint, 1: torque)");
+    if (e < b) return refuse("the member ranges must not decrease");
+    if (e - b < (torque ? 2 : 1))
+      return refuse("group " + std::to_string(g) + " has " + std::to_string(e - b) + " members (a sum restraint needs at least one, a torque group two)");
+    const double* vec = g_vec + 3 * (size_t)g;
+    if (torque) {
+      if (!finite3(vec)) return refuse("a torque is not finite");
+      if (!(vec[0] * vec[0] + vec[1] * vec[1] + vec[2] * vec[2] > 0)) return refuse("a torque is zero (|T| > 0)");
+    } else {
+      if (!std::isfinite(vec[0]) || !finite3(g_target + 3 * (size_t)g)) return refuse("a sum restraint's stiffness or target is not finite");
+      if (vec[0] < 0) return refuse("a sum restraint's stiffness is negative (k >= 0)");
+      if (g_mask[g] < 0 || g_mask[g] > 7) return refuse("an axis mask is not a combination of the bits 1, 2, 4");
+    }
+    for (int m = b; m < e; ++m) {
+      const int i = g_member[m];
+      if (!in_range(i)) return refuse("nucleotide index " + std::to_string(i) + range);
+      if (last_group[i] == g) return refuse("nucleotide " + std::to_string(i) + " is listed twice in group " + std::to_string(g));
+      last_group[i] = g;
+      terms[i].push_back(~g);
+    }
+  }
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
+  s->rst_stamp_stale = true;
+  if (n_tethers == 0 && n_groups == 0) {
+    s->rst = ExtFieldView{};
+    return MYTHOS_OK;
+  }
+  // an earlier advance may still be reading the old arrays on its stream: wait before replacing them
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());
+  std::vector<int> e_index, e_first{0}, e_term;
+  for (int i = 0; i < n; ++i) {
+    if (terms[i].empty()) continue;
+    e_index.push_back(i);
+    e_term.insert(e_term.end(), terms[i].begin(), terms[i].end());
+    e_first.push_back((int)e_term.size());
+  }
+  s->rst = ExtFieldView{};  // (nothing half replaced counts)
+  const size_t nt = (size_t)n_tethers, ng = (size_t)n_groups, nm = n_groups > 0 ? (size_t)g_first[n_groups] : 0;
+  int rc = 0;
+  auto up = [&](auto& buf, const auto* host, size_t count) {
+    if (!rc) rc = buf.upload(host, count);
+  };
+  up(s->d_rst_t_index, t_index, nt), up(s->d_rst_t_k, t_k, nt), up(s->d_rst_t_anchor, t_anchor, 3 * nt), up(s->d_rst_t_mask, t_mask, nt);
+  up(s->d_rst_g_kind, g_kind, ng), up(s->d_rst_g_first, g_first, n_groups > 0 ? ng + 1 : 0), up(s->d_rst_g_member, g_member, nm);
+  up(s->d_rst_g_vec, g_vec, 3 * ng), up(s->d_rst_g_target, g_target, 3 * ng), up(s->d_rst_g_mask, g_mask, ng);
+  up(s->d_rst_e_index, e_index.data(), e_index.size()), up(s->d_rst_e_first, e_first.data(), e_first.size());
+  up(s->d_rst_e_term, e_term.data(), e_term.size());
+  if (!rc) rc = s->d_rst_g_row.alloc(ng * kExtRow);
+  if (!rc) rc = s->d_rst_stamp.alloc((e_index.size() + 255) / 256);
+  if (rc) return rc;
+  ExtFieldView v;
+  v.n_tethers = n_tethers, v.n_groups = n_groups, v.n_entries = (int)e_index.size();
+  v.t_index = s->d_rst_t_index.get(), v.t_k = s->d_rst_t_k.get(), v.t_anchor = s->d_rst_t_anchor.get(), v.t_mask = s->d_rst_t_mask.get();
+  v.g_kind = s->d_rst_g_kind.get(), v.g_first = s->d_rst_g_first.get(), v.g_member = s->d_rst_g_member.get();
+  v.g_vec = s->d_rst_g_vec.get(), v.g_target = s->d_rst_g_target.get(), v.g_mask = s->d_rst_g_mask.get(), v.g_row = s->d_rst_g_row.get();
+  v.e_index = s->d_rst_e_index.get(), v.e_first = s->d_rst_e_first.get(), v.e_term = s->d_rst_e_term.get();
+  s->rst = v;
+  return MYTHOS_OK;
+}
+
+int mythos_langevin_eval_external(mythos_sim_t* s, const void* center, void* force_out, double* energy_out, mythos_stream_t stream) {
+  if (!s || !center || !force_out || !energy_out) {
+    set_error("mythos_langevin_eval_external: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
+  return md_entries_of(s).eval_external(s, center, force_out, energy_out, (hipStream_t)stream);
 }
 
 int mythos_langevin_set_seed(mythos_sim_t* s, uint64_t seed) {

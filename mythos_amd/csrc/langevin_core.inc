@@ -5,6 +5,7 @@
 // The parts, by concern:
 //   langevin_step.h      the fused step kernel md_step_kernel and its device helpers (device code only)
 //   langevin_frame.h     pack / unpack / rederive / init-momenta / external-kick kernels
+//   ext_field.h          the position-dependent external kick: tethers, sum restraints, group torques
 //   langevin_sim.h       struct mythos_sim and the host helpers that only read it
 //   langevin_unfused.inc the oxNA cross-check path, a second integrator with its own state and step loop
 //   md_plan.h            which instantiation a launch takes (pure host arithmetic, checked by the CPU suite)
@@ -34,6 +35,7 @@
 
 #include "langevin_step.h"
 #include "langevin_frame.h"
+#include "ext_field.h"
 #include "langevin_unfused.inc"  // (UnfusedState, then langevin_sim.h, then the path's host side)
 
 using namespace mythos;
@@ -65,6 +67,19 @@ static int update_chunk_order(mythos_sim* sim, const typename Vec4T<R>::type* p0
   return 0;
 }
 
+// The position-dependent external kick (ext_field.h) of view v on the momenta `mom`, forces taken at (p0, pl): the group
+// rows, then the gather-and-kick with one stamp word per workgroup.  The one place these two kernels are launched - in
+// front of a step launch, and by mythos_langevin_eval_external with c_dt = 1 on zeroed momenta.
+inline int ext_field_blocks(const ExtFieldView& v) { return (v.n_entries + 255) / 256; }
+template <typename R>
+static void launch_ext_field_kick(const ExtFieldView& v, const typename Vec4T<R>::type* p0, const typename Vec4T<R>::type* pl, double c_dt,
+                                  typename Vec4T<R>::type* mom, const int* flags, const int* halt_words, int k, unsigned long long stamp,
+                                  unsigned long long* stamps, hipStream_t st) {
+  if (v.n_groups > 0) hipLaunchKernelGGL(ext_group_kernel<R>, dim3(v.n_groups), dim3(256), 0, st, v, p0, pl);
+  hipLaunchKernelGGL(ext_field_kick_kernel<R>, dim3(ext_field_blocks(v)), dim3(256), 0, st, v, p0, pl, c_dt, mom, flags, halt_words, k,
+                     stamp, stamps);
+}
+
 // Caller's (N,3)/(N,4) arrays -> the resident frames.  The list of a previous state does not carry over.
 template <typename R, int MODEL>
 static int load_typed(mythos_sim* sim, const R* center, const R* quat, const R* p_lin, const R* p_ang, hipStream_t st) {
@@ -88,6 +103,7 @@ static int load_typed(mythos_sim* sim, const R* center, const R* quat, const R* 
   sim->items_big = false;
   sim->open = false;
   sim->ext_stamp_stale = true;
+  sim->rst_stamp_stale = true;
   sim->param_epoch = sys->param_epoch;
   const int cus = device_cus(sys);
   sim->lanes = md_lanes_for(n, cus, debug_value(MYTHOS_DEBUG_MD_LANES));  // (the debug value is read here, at load)
@@ -162,6 +178,16 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
       hipLaunchKernelGGL(ext_kick_kernel<R>, dim3(1), dim3(256), 0, st, sim->ext_count, (const int*)sim->d_ext_index.get(),
                          (const V4*)sim->d_ext_force.get(), R(c * sim->dt), fr[cur].mom, (const int*)sim->d_flags.get(),
                          (const int*)halt_words, k, stamp, sim->d_ext_stamp.get());
+    }
+    if (sim->rst.n_entries > 0) {  // the position-dependent kick of this launch (ext_field.h), same slot, same stamp value
+      if (sim->rst_stamp_stale) {
+        (void)hipMemsetAsync(sim->d_rst_stamp.get(), 0, sizeof(unsigned long long) * (size_t)ext_field_blocks(sim->rst), st);
+        sim->rst_stamp_stale = false;
+      }
+      const double c = double(row.kick_close) + 0.5 * row.do_step;
+      const unsigned long long stamp = 2ull * (unsigned long long)(sim->step + k) + (row.kick_close != 0.0f ? 1ull : 0ull) + 1ull;
+      launch_ext_field_kick<R>(sim->rst, fr[cur].p0, kHiLo<R> ? fr[cur].pl : nullptr, c * sim->dt, fr[cur].mom,
+                               (const int*)sim->d_flags.get(), (const int*)halt_words, k, stamp, sim->d_rst_stamp.get(), st);
     }
     // The one launch of md_step_kernel, its arguments written once.  With events: the pair receives the begin / end time
     // stamps of THIS dispatch (the same stamps a profiler's kernel trace reports), not the time between two markers in
@@ -269,16 +295,49 @@ static int entry_init_momenta(mythos_sim* s, void* p_lin, void* p_ang, hipStream
   return MYTHOS_OK;
 }
 
+// mythos_langevin_eval_external: the caller's packed centres become the p0 words of a scratch frame with zero momenta, the
+// kick kernels of the integrator run on it with c dt = 1, and the momenta go out as the forces.
+template <typename R>
+static int entry_eval_external(mythos_sim* s, const void* center, void* force_out, double* energy_out, hipStream_t st) {
+  using V4 = typename Vec4T<R>::type;
+  const int n = s->sys->n;
+  const int blocks = std::max(1, ext_field_blocks(s->rst));
+  const size_t ctl_bytes = MdRun::kCtlWords * sizeof(int) + sizeof(unsigned long long) * (size_t)(1 + blocks);
+  if (int rc = s->d_eval_p0.grow(sizeof(V4) * (size_t)n)) return rc;
+  if (int rc = s->d_eval_mom.grow(sizeof(V4) * (size_t)n)) return rc;
+  if (int rc = s->d_eval_ctl.grow(ctl_bytes)) return rc;
+  if (int rc = s->d_eval_group_row.grow((size_t)std::max(1, s->rst.n_groups) * kExtRow)) return rc;
+  MYTHOS_HIP_TRY(hipMemsetAsync(s->d_eval_ctl.get(), 0, ctl_bytes, st));
+  V4* p0 = (V4*)s->d_eval_p0.get();
+  V4* mom = (V4*)s->d_eval_mom.get();
+  const int* flags = (const int*)s->d_eval_ctl.get();
+  unsigned long long* stamps = (unsigned long long*)((char*)s->d_eval_ctl.get() + MdRun::kCtlWords * sizeof(int));
+  static_assert(MdRun::kCtlWords * sizeof(int) % sizeof(unsigned long long) == 0, "the stamps follow the control words aligned");
+  hipLaunchKernelGGL(ext_eval_pack_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const R*)center, p0, mom);
+  if (s->ext_count > 0)
+    hipLaunchKernelGGL(ext_kick_kernel<R>, dim3(1), dim3(256), 0, st, s->ext_count, (const int*)s->d_ext_index.get(),
+                       (const V4*)s->d_ext_force.get(), R(1), mom, flags, (const int*)nullptr, 0, 1ull, stamps);
+  ExtFieldView v = s->rst;
+  v.g_row = s->d_eval_group_row.get();  // (the rows of a resident run are not disturbed)
+  if (v.n_entries > 0) launch_ext_field_kick<R>(v, p0, nullptr, 1.0, mom, flags, nullptr, 0, 1ull, stamps + 1, st);
+  hipLaunchKernelGGL(ext_eval_unpack_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const V4*)mom, (R*)force_out);
+  hipLaunchKernelGGL(ext_energy_kernel<R>, dim3(1), dim3(256), 0, st, s->ext_count, (const int*)s->d_ext_index.get(),
+                     (const V4*)s->d_ext_force.get(), v, (const V4*)p0, energy_out);
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return MYTHOS_OK;
+}
+
 // One precision's entry points as a table; langevin.hip chooses between its own and langevin_f64.hip's by the system's dtype.
 struct MdEntries {
   int (*load)(mythos_sim*, void*, void*, void*, void*, hipStream_t);
   int (*advance)(mythos_sim*, int, int, bool, void*, void*, double*, hipStream_t);
   int (*store)(mythos_sim*, void*, void*, void*, void*, hipStream_t);
   int (*init_momenta)(mythos_sim*, void*, void*, hipStream_t);
+  int (*eval_external)(mythos_sim*, const void*, void*, double*, hipStream_t);
 };
 template <typename R>
 constexpr MdEntries md_entries() {
-  return {entry_load<R>, entry_advance<R>, entry_store<R>, entry_init_momenta<R>};
+  return {entry_load<R>, entry_advance<R>, entry_store<R>, entry_init_momenta<R>, entry_eval_external<R>};
 }
 MdEntries md_entries_f64();  // langevin_f64.hip
 

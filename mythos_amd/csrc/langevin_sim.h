@@ -7,6 +7,7 @@
 #endif
 #include <cmath>
 
+#include "ext_field.h"
 #include "langevin_step.h"
 #include "md_driver.h"
 
@@ -37,6 +38,16 @@ struct mythos_sim : mythos::MdRun {
   mythos::DeviceBytes d_ext_force;                     // [ext_count] Vec4T<R>: (F, 0)
   mythos::DeviceBuf<unsigned long long> d_ext_stamp;   // [1] the last kick applied (ext_kick_kernel)
   bool ext_stamp_stale = true;                 // load / set_step / set_external_forces: cleared in front of the next kick
+  // position-dependent external forces (mythos_langevin_set_restraints; ext_field.h), held in double in both precisions
+  mythos::ExtFieldView rst;                            // the counts and the device arrays below (all zero / null: none set)
+  mythos::DeviceBuf<int> d_rst_t_index, d_rst_t_mask, d_rst_g_kind, d_rst_g_first, d_rst_g_member, d_rst_g_mask;
+  mythos::DeviceBuf<int> d_rst_e_index, d_rst_e_first, d_rst_e_term;
+  mythos::DeviceBuf<double> d_rst_t_k, d_rst_t_anchor, d_rst_g_vec, d_rst_g_target, d_rst_g_row;
+  mythos::DeviceBuf<unsigned long long> d_rst_stamp;   // [workgroups of ext_field_kick_kernel] each one's last kick applied
+  bool rst_stamp_stale = true;                         // as ext_stamp_stale, for d_rst_stamp
+  // scratch of mythos_langevin_eval_external: p0 and momentum words, zeroed control words and stamps
+  mythos::DeviceBytes d_eval_p0, d_eval_mom, d_eval_ctl;
+  mythos::DeviceBuf<double> d_eval_group_row;
   ~mythos_sim() { (void)hipSetDevice(device); }  // the members, MdRun's too, free themselves on that device
 };
 

@@ -321,6 +321,7 @@ class LangevinIntegrator(_MdIntegrator):
                          inertia.ctypes.data_as(_lib.c_double_p), C.c_uint64(int(seed) & (2**64 - 1)))
         self.dt, self.kT = float(dt), float(kT)
         self.external_forces = (np.zeros(0, np.int32), np.zeros((0, 3), np.float64))
+        self.restraints = None  # the set last handed to set_restraints (None: never called)
 
     def set_neighbor_policy(self, r_cut: float, skin: float, every: int) -> None:
         _lib.check(
@@ -348,6 +349,38 @@ class LangevinIntegrator(_MdIntegrator):
         _lib.check(self._lib.mythos_langevin_set_external_forces(self._h, int(idx.shape[0]), idx.ctypes.data_as(_lib.c_int_p),
                                                                  f.ctypes.data_as(_lib.c_double_p)), "set_external_forces")
         self.external_forces = (idx, f)
+
+    def set_restraints(self, restraints=None, reference_center=None, *, n_one=None, n_rep=1, offsets=None) -> None:
+        """Position-dependent forces on centres of mass (mythos_amd.simulators.restraints; mythos_langevin_set_restraints):
+        harmonic tethers, restraints of a sum of positions, torques on groups.  ``reference_center`` (n, 3): the state that
+        ``anchor=None`` / ``target=None`` take their positions from.  None, or an empty set, clears them.  Refused between
+        ``advance`` and ``store`` (an open frame).  ``restraints`` keeps the set; the keyword arguments repeat it per
+        replica (Restraints.lower; HipMDSimulator passes them)."""
+        from mythos_amd.simulators.restraints import Restraints
+
+        rs = Restraints() if restraints is None else restraints
+        if isinstance(reference_center, torch.Tensor):
+            reference_center = reference_center.detach().double().cpu().numpy()
+        a = rs.lower(reference_center, n_one=self.system.n if n_one is None else n_one, n_rep=n_rep, offsets=offsets)
+        ip, dp = (lambda x: x.ctypes.data_as(_lib.c_int_p)), (lambda x: x.ctypes.data_as(_lib.c_double_p))
+        _lib.check(self._lib.mythos_langevin_set_restraints(
+            self._h, int(a["t_index"].shape[0]), ip(a["t_index"]), dp(a["t_k"]), dp(a["t_anchor"]), ip(a["t_mask"]),
+            int(a["g_kind"].shape[0]), ip(a["g_kind"]), ip(a["g_first"]), ip(a["g_member"]), dp(a["g_vec"]), dp(a["g_target"]),
+            ip(a["g_mask"])), "set_restraints")
+        self.restraints = rs
+
+    def external_field(self, center):
+        """The external field at ``center`` (n, 3) - constant forces, tethers, sum restraints, torques - evaluated by the
+        kernels the integrator kicks with (mythos_langevin_eval_external): -> (force (n, 3) in the system's precision,
+        energies (3,) float64: -sum F.x of the constant forces, the tether energy, the sum-restraint energy; the torque
+        has no potential).  Needs no resident state and changes none."""
+        s = self.system
+        c = s._check(center, (s.n, 3), "center")
+        force = torch.empty((s.n, 3), dtype=s.dtype, device=s.device)
+        energies = torch.empty(3, dtype=torch.float64, device=s.device)
+        _lib.check(self._lib.mythos_langevin_eval_external(self._h, _lib.ptr(c), _lib.ptr(force), _lib.ptr(energies), _lib.stream(s.device)),
+                   "eval_external")
+        return force, energies
 
     def init_momenta(self):
         s = self.system

@@ -197,6 +197,11 @@ class HipMDSimulator(Simulator):
     # oxDNA external-force file (mythos_amd.input.external_forces).  With replicas the list is repeated per replica at
     # ``index + r * n``.  None: no forces, and exactly the launches of a simulator that never had any.
     external_forces: Any = None
+    # Position-dependent forces on centres of mass (mythos_amd.simulators.restraints.Restraints: tethers, sum restraints,
+    # group torques - the stretch-torsion protocol), repeated per replica like the constant forces, anchors and targets
+    # moved with each replica to its place on the grid; ``anchor=None`` / ``target=None`` resolve from ``init_state``.
+    # Combines with ``external_forces``.  None: no restraints, and no launch for them.
+    restraints: Any = None
     # device-side objects kept between calls: {key: (OxdnaSystem, LangevinIntegrator, ReplicaLayout)}
     _resident: dict = dc.field(default_factory=dict, init=False, repr=False, compare=False)
 
@@ -267,6 +272,14 @@ class HipMDSimulator(Simulator):
             raise ValueError(f"external_forces: nucleotide index out of range [0, {layout.n_one})")
         integ.set_external_forces(*layout.forces(index, force))
 
+    def _apply_restraints(self, integ, layout, c_init, offsets) -> None:
+        if not self.restraints:
+            if integ.restraints:
+                integ.set_restraints()
+            return
+        ref, off = layout.restraint_frames(c_init, offsets)
+        integ.set_restraints(self.restraints, ref, n_one=layout.n_one, n_rep=layout.n_rep, offsets=off)
+
     def _prepare(self, opt_params, key, state_device):
         """The device-side objects of this simulator at ``opt_params``: (system, integrator, device, replicas, nucleotides
         per replica) - built on first use, afterwards the kept ones with the new parameter vector, key and step 0."""
@@ -313,7 +326,9 @@ class HipMDSimulator(Simulator):
         q = init_state.orientation.vec.to(device=dev, dtype=self.dtype).contiguous().clone()
         r_list = (nb.r_cutoff + nb.dr_threshold) if isinstance(nb, VerletNeighborList) else 4.0
         layout = ReplicaLayout(n_rep, n_one)
+        c_init = c
         c, q, offsets = layout.place(c, q, r_list)
+        self._apply_restraints(integ, layout, c_init, offsets)
         p, ang = integ.init_momenta()
         tc, tq, et = integ.run(c, q, p, ang, int(n_steps), save_every=self.save_every, want_energy=self.trace_energy)
         tc, tq, et = layout.unplace_rows(tc, tq, et, offsets)

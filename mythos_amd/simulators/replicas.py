@@ -40,6 +40,15 @@ class ReplicaLayout:
             return index, force
         return self._shifted(index, 1).reshape(-1), np.tile(force, (self.n_rep, 1))
 
+    def restraint_frames(self, c_init: torch.Tensor, offsets):
+        """What restraints need of the layout (Restraints.lower): the initial centres of every replica in its own frame
+        (n_rep, n_one, 3) and the translation ``place`` gave each replica (n_rep, 3), both float64 on the host - an anchor
+        moves with its replica, the target of a sum by the translation times its number of members."""
+        ref = c_init.detach().double().cpu().numpy().reshape(-1, self.n_one, 3)
+        ref = np.broadcast_to(ref, (self.n_rep, self.n_one, 3))
+        off = np.zeros((self.n_rep, 3)) if offsets is None else offsets.detach().double().cpu().numpy().reshape(self.n_rep, 3)
+        return ref, off
+
     def pseq(self, marg, unit, bp, terms):
         """Sequence tables (pseq_request) with every replica its own copy of the base pairs: base pair ``k`` of replica
         ``r`` is row ``k + n_bp * r``, its two members the units ``2 k + 2 n_bp r`` and ``+ 1``."""
