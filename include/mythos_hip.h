@@ -361,6 +361,62 @@ int mythos_langevin_set_restraints(mythos_sim_t* sim, int n_tethers, const int32
  * Asynchronous on `stream`; the scratch arrays belong to the integrator, so one call at a time per integrator. */
 int mythos_langevin_eval_external(mythos_sim_t* sim, const void* center, void* force_out, double* energy_out, mythos_stream_t stream);
 
+/* Point forces: oxDNA's external forces that act on ONE nucleotide's centre of mass each - the moving `string`, `trap`,
+ * `mutual_trap`, `repulsion_plane`, `repulsion_sphere` of an external_forces_file, by oxDNA's definitions.  A set of
+ * its own beside the restraints: either is set or cleared without the other, and both add up with the constant forces.
+ *   kind         host int32[n_terms]     enum mythos_point_force_kind
+ *   particle     host int32[n_terms]     the nucleotide the term acts on; any number of terms may name one nucleotide
+ *   ref_particle host int32[n_terms]     mutual trap: the partner (!= particle), which gets no force from this term and
+ *                                        needs none of its own; other kinds: ignored
+ *   flags        host int32[n_terms]     mutual trap: MYTHOS_POINT_PBC = the minimum image of the system's box; others: 0
+ *   param        host double[n_terms][8] by kind, unused words finite (0); dir is normalised here, d = dir / |dir|
+ *     STRING       F0, rate, dir.xyz, origin.xyz   F = (F0 + rate s) d                  U = -(F0 + rate s) d.(x - origin)
+ *     TRAP         stiff, rate, dir.xyz, pos0.xyz  F = -stiff (x - pos0 - rate s d)     U = stiff / 2 |x - pos0 - rate s d|^2
+ *     MUTUAL_TRAP  stiff, r0, rate                 D = x_ref - x, r = |D|: F = stiff (r - r0 - rate s) D / r (r = 0: none)
+ *                                                                                       U = stiff / 2 (r - r0 - rate s)^2
+ *     PLANE        stiff, position, dir.xyz        h = d.x + position < 0: F = -stiff h d,  U = stiff / 2 h^2;  else 0
+ *     SPHERE       stiff, r0, rate, center.xyz     rho = x - center, R = r0 + rate s, |rho| > R:
+ *                                                  F = -stiff (1 - R / |rho|) rho,     U = stiff / 2 (|rho| - R)^2;  else 0
+ * Time.  s is the step count of the frame whose positions the force is taken at: mythos_langevin_get_step when the
+ * integrator stood at that frame.  The kick in front of launch k of a call uses (step at the call's start) + k, a double
+ * computed on the host per launch - the same number when a launch is halted, the list rebuilt and the run resumed, and
+ * when one advance(a + b) is advance(a) then advance(b); both half kicks around a frame use the force of that frame's
+ * s.  mythos_langevin_set_step moves the clock.  Agreement with oxDNA's own trajectories is statistical, as for the
+ * rest of the integrator: the laws are oxDNA's, the noise and the splitting are not.
+ * The terms join the restraint kick (mythos_langevin_set_restraints): per nucleotide its tether, its groups ascending,
+ * then its point terms in the order given, added in double and kicked once - reproducible to the bit, no launch added to
+ * the group launch and the kick launch of a step.  A set without point terms launches what it launched before there
+ * were any; with neither restraints nor point terms nothing is launched for them.  A STRING with rate = 0 is better
+ * given to mythos_langevin_set_external_forces, which keeps its own launch.
+ * n_terms = 0 clears the set.  MYTHOS_ERR_INVALID_ARGUMENT, the message naming the term: while the resident frame is
+ * open; an index out of range; ref_particle == particle; a value that is not finite; stiff < 0; r0 < 0; dir = 0 on a
+ * string, a plane or a moving trap; MYTHOS_POINT_PBC on a system without a box, or on another kind.
+ * mythos_langevin_run / _advance refuse to step with point forces on the unfused oxNA path.  The energy-trace rows do
+ * not hold these energies; mythos_langevin_eval_external_at returns them. */
+enum mythos_point_force_kind {
+  MYTHOS_POINT_STRING = 0,
+  MYTHOS_POINT_TRAP = 1,
+  MYTHOS_POINT_MUTUAL_TRAP = 2,
+  MYTHOS_POINT_PLANE = 3,
+  MYTHOS_POINT_SPHERE = 4,
+  MYTHOS_POINT_KINDS = 5
+};
+enum mythos_point_force_flag { MYTHOS_POINT_PBC = 1 };
+int mythos_langevin_set_point_forces(mythos_sim_t* sim, int n_terms, const int32_t* kind, const int32_t* particle,
+                                     const int32_t* ref_particle, const int32_t* flags, const double* param);
+
+/* The checks of mythos_langevin_set_point_forces on their own, for a system of n nucleotides with (has_box != 0) or
+ * without a box: MYTHOS_OK, or MYTHOS_ERR_INVALID_ARGUMENT and the message.  Touches no device. */
+int mythos_point_forces_check(int n, int has_box, int n_terms, const int32_t* kind, const int32_t* particle, const int32_t* ref_particle,
+                              const int32_t* flags, const double* param);
+
+/* mythos_langevin_eval_external at step count `step`, with the point forces' energies:
+ *   energy_out device double[8]: the three words of mythos_langevin_eval_external, then the energy of the point terms
+ *                                of each kind in the enum's order (string, trap, mutual trap, plane, sphere)
+ * mythos_langevin_eval_external is this function at step = 0 with the first three words. */
+int mythos_langevin_eval_external_at(mythos_sim_t* sim, const void* center, double step, void* force_out, double* energy_out,
+                                     mythos_stream_t stream);
+
 /* Integrator options.  MYTHOS_LANGEVIN_UNFUSED (oxNA systems only, value 0 / 1): step through the two-launch path -
  * the energy kernel's forces launch + a one-thread-per-nucleotide integrator - instead of the fused step kernel.  A
  * second implementation of the same map (same Philox stream), kept as the cross-check of the fused oxNA instantiation;

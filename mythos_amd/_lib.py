@@ -68,6 +68,9 @@ _SIGS = {
     "mythos_langevin_set_restraints": (C.c_int, [V, C.c_int, c_int_p, c_double_p, c_double_p, c_int_p, C.c_int, c_int_p, c_int_p, c_int_p,
                                                  c_double_p, c_double_p, c_int_p]),
     "mythos_langevin_eval_external": (C.c_int, [V, V, V, V, V]),
+    "mythos_langevin_set_point_forces": (C.c_int, [V, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]),
+    "mythos_point_forces_check": (C.c_int, [C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]),
+    "mythos_langevin_eval_external_at": (C.c_int, [V, V, C.c_double, V, V, V]),
     "mythos_langevin_last_kernel_ms": (C.c_int, [V, c_double_p, c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mythos_langevin_set_option": (C.c_int, [V, C.c_int, C.c_int64]),
     "mythos_langevin_set_timing": (C.c_int, [V, C.c_int]),

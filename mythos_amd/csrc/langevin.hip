@@ -1,13 +1,60 @@
 // Langevin integrator, translation unit 1 of 2: the fp32 instantiations of langevin_core.inc and the C entry points
 // (mythos_langevin_*).  The fp64 instantiations are in langevin_f64.hip.
+#include <algorithm>
 #include <memory>
 #include <vector>
 
 #include "langevin_core.inc"
+#include "point_force_checks.h"
 
 namespace {
 // the entry points of the system's precision: this unit's own, or langevin_f64.hip's
 MdEntries md_entries_of(const mythos_sim* s) { return s->sys->dtype == MYTHOS_F32 ? md_entries<float>() : md_entries_f64(); }
+
+// the point terms' half of a view (mythos_langevin_set_point_forces), everything of the restraints' half unset
+ExtFieldView ext_point_part(const ExtFieldView& v) {
+  ExtFieldView o;
+  o.n_points = v.n_points;
+  o.pt_kind = v.pt_kind, o.pt_particle = v.pt_particle, o.pt_ref = v.pt_ref, o.pt_flags = v.pt_flags, o.pt_param = v.pt_param;
+  for (int a = 0; a < 3; ++a) o.box[a] = v.box[a];
+  return o;
+}
+
+// The entries of s->rst - the nucleotides a restraint or a point term names, ascending - from what the two sets
+// contribute (the host copies in mythos_sim), with each entry's range of restraint terms and of point terms; one stamp
+// word per workgroup of the kick.  Both setters end here, after the device has gone idle.  With no point terms the
+// entries are the restraints' own, as they were uploaded before there were any.
+int ext_entries_merge(mythos_sim* s) {
+  const std::vector<int>&ri = s->h_rst_index, &rf = s->h_rst_first, &rt = s->h_rst_term, &pp = s->h_pt_particle;
+  ExtFieldView& v = s->rst;
+  v.n_entries = v.n_points = 0;  // (nothing half replaced counts)
+  v.e_index = v.e_first = v.e_term = v.pt_first = nullptr;
+  std::vector<int> e_index, e_first{0}, e_term, pt_first{0};
+  size_t a = 0, b = 0;
+  while (a < ri.size() || b < pp.size()) {
+    const int i = (b >= pp.size() || (a < ri.size() && ri[a] <= pp[b])) ? ri[a] : pp[b];
+    e_index.push_back(i);
+    if (a < ri.size() && ri[a] == i) {
+      e_term.insert(e_term.end(), rt.begin() + rf[a], rt.begin() + rf[a + 1]);
+      ++a;
+    }
+    e_first.push_back((int)e_term.size());
+    while (b < pp.size() && pp[b] == i) ++b;
+    pt_first.push_back((int)b);
+  }
+  if (e_index.empty()) return MYTHOS_OK;
+  int rc = s->d_rst_e_index.upload(e_index);
+  if (!rc) rc = s->d_rst_e_first.upload(e_first);
+  if (!rc) rc = s->d_rst_e_term.upload(e_term);
+  if (!rc && !pp.empty()) rc = s->d_pt_first.upload(pt_first);
+  if (!rc) rc = s->d_rst_stamp.alloc((e_index.size() + 255) / 256);
+  if (rc) return rc;
+  v.e_index = s->d_rst_e_index.get(), v.e_first = s->d_rst_e_first.get(), v.e_term = s->d_rst_e_term.get();
+  if (!pp.empty()) v.pt_first = s->d_pt_first.get();
+  v.n_points = (int)pp.size();
+  v.n_entries = (int)e_index.size();
+  return MYTHOS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -118,7 +165,7 @@ int md_advance(mythos_sim_t* s, int n_steps, int save_every, bool close, void* t
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   if (s->rst.n_entries > 0 && s->unfused.active) {
-    set_error("mythos_langevin_run / advance: restraints are not applied on the unfused oxNA path "
+    set_error("mythos_langevin_run / advance: restraints and point forces are not applied on the unfused oxNA path "
               "(MYTHOS_LANGEVIN_UNFUSED); clear them or step through the fused kernel");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
@@ -312,12 +359,11 @@ int mythos_langevin_set_restraints(mythos_sim_t* s, int n_tethers, const int32_t
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
   s->rst_stamp_stale = true;
-  if (n_tethers == 0 && n_groups == 0) {
-    s->rst = ExtFieldView{};
-    return MYTHOS_OK;
-  }
   // an earlier advance may still be reading the old arrays on its stream: wait before replacing them
-  MYTHOS_HIP_TRY(hipDeviceSynchronize());
+  if (s->rst.n_entries > 0 || n_tethers > 0 || n_groups > 0) MYTHOS_HIP_TRY(hipDeviceSynchronize());
+  s->rst = ext_point_part(s->rst);  // (nothing half replaced counts; the point terms are not this call's)
+  s->h_rst_index.clear(), s->h_rst_term.clear(), s->h_rst_first.assign(1, 0);
+  if (n_tethers == 0 && n_groups == 0) return ext_entries_merge(s);
   std::vector<int> e_index, e_first{0}, e_term;
   for (int i = 0; i < n; ++i) {
     if (terms[i].empty()) continue;
@@ -325,7 +371,6 @@ int mythos_langevin_set_restraints(mythos_sim_t* s, int n_tethers, const int32_t
     e_term.insert(e_term.end(), terms[i].begin(), terms[i].end());
     e_first.push_back((int)e_term.size());
   }
-  s->rst = ExtFieldView{};  // (nothing half replaced counts)
   const size_t nt = (size_t)n_tethers, ng = (size_t)n_groups, nm = n_groups > 0 ? (size_t)g_first[n_groups] : 0;
   int rc = 0;
   auto up = [&](auto& buf, const auto* host, size_t count) {
@@ -334,19 +379,92 @@ int mythos_langevin_set_restraints(mythos_sim_t* s, int n_tethers, const int32_t
   up(s->d_rst_t_index, t_index, nt), up(s->d_rst_t_k, t_k, nt), up(s->d_rst_t_anchor, t_anchor, 3 * nt), up(s->d_rst_t_mask, t_mask, nt);
   up(s->d_rst_g_kind, g_kind, ng), up(s->d_rst_g_first, g_first, n_groups > 0 ? ng + 1 : 0), up(s->d_rst_g_member, g_member, nm);
   up(s->d_rst_g_vec, g_vec, 3 * ng), up(s->d_rst_g_target, g_target, 3 * ng), up(s->d_rst_g_mask, g_mask, ng);
-  up(s->d_rst_e_index, e_index.data(), e_index.size()), up(s->d_rst_e_first, e_first.data(), e_first.size());
-  up(s->d_rst_e_term, e_term.data(), e_term.size());
   if (!rc) rc = s->d_rst_g_row.alloc(ng * kExtRow);
-  if (!rc) rc = s->d_rst_stamp.alloc((e_index.size() + 255) / 256);
-  if (rc) return rc;
-  ExtFieldView v;
-  v.n_tethers = n_tethers, v.n_groups = n_groups, v.n_entries = (int)e_index.size();
+  if (rc) return ext_entries_merge(s), rc;
+  ExtFieldView& v = s->rst;
+  v.n_tethers = n_tethers, v.n_groups = n_groups;
   v.t_index = s->d_rst_t_index.get(), v.t_k = s->d_rst_t_k.get(), v.t_anchor = s->d_rst_t_anchor.get(), v.t_mask = s->d_rst_t_mask.get();
   v.g_kind = s->d_rst_g_kind.get(), v.g_first = s->d_rst_g_first.get(), v.g_member = s->d_rst_g_member.get();
   v.g_vec = s->d_rst_g_vec.get(), v.g_target = s->d_rst_g_target.get(), v.g_mask = s->d_rst_g_mask.get(), v.g_row = s->d_rst_g_row.get();
-  v.e_index = s->d_rst_e_index.get(), v.e_first = s->d_rst_e_first.get(), v.e_term = s->d_rst_e_term.get();
-  s->rst = v;
-  return MYTHOS_OK;
+  s->h_rst_index = std::move(e_index), s->h_rst_first = std::move(e_first), s->h_rst_term = std::move(e_term);
+  return ext_entries_merge(s);
+}
+
+int mythos_point_forces_check(int n, int has_box, int n_terms, const int32_t* kind, const int32_t* particle, const int32_t* ref_particle,
+                              const int32_t* flags, const double* param) {
+  const char* who = "mythos_point_forces_check";
+  if (n < 0 || n_terms < 0 || (n_terms > 0 && (!kind || !particle || !ref_particle || !flags || !param))) {
+    set_error(std::string(who) + ": invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  return point_forces_valid(who, n, has_box != 0, n_terms, kind, particle, ref_particle, flags, param) ? MYTHOS_OK : MYTHOS_ERR_INVALID_ARGUMENT;
+}
+
+int mythos_langevin_set_point_forces(mythos_sim_t* s, int n_terms, const int32_t* kind, const int32_t* particle, const int32_t* ref_particle,
+                                     const int32_t* flags, const double* param) {
+  const char* who = "mythos_langevin_set_point_forces";
+  if (!s || n_terms < 0 || (n_terms > 0 && (!kind || !particle || !ref_particle || !flags || !param))) {
+    set_error(std::string(who) + ": invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (s->resident && s->open) {
+    set_error(std::string(who) + ": the resident frame is open (its pending closing half kick would mix two forces); call "
+              "mythos_langevin_store first");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  const mythos_system* sys = s->sys;
+  if (!point_forces_valid(who, sys->n, sys->has_box, n_terms, kind, particle, ref_particle, flags, param)) return MYTHOS_ERR_INVALID_ARGUMENT;
+  static_assert(kPointForceParams == kExtPointParams && (int)MYTHOS_POINT_KINDS == (int)EXT_POINT_KINDS && (int)MYTHOS_POINT_PBC == (int)EXT_POINT_PBC &&
+                    (int)MYTHOS_POINT_SPHERE == (int)EXT_POINT_SPHERE,
+                "the public enum is the kernel's");
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
+  s->rst_stamp_stale = true;
+  // an earlier advance may still be reading the old arrays on its stream: wait before replacing them
+  if (s->rst.n_entries > 0 || n_terms > 0) MYTHOS_HIP_TRY(hipDeviceSynchronize());
+  ExtFieldView& v = s->rst;
+  v.n_entries = v.n_points = 0;  // (nothing half replaced counts)
+  v.pt_first = v.pt_kind = v.pt_particle = v.pt_ref = v.pt_flags = nullptr, v.pt_param = nullptr;
+  s->h_pt_particle.clear();
+  if (n_terms == 0) return ext_entries_merge(s);
+  // by nucleotide, and within one in the order given: the order the kick adds in
+  std::vector<int> order((size_t)n_terms);
+  for (int t = 0; t < n_terms; ++t) order[t] = t;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return particle[a] < particle[b]; });
+  std::vector<int> k_s, p_s, r_s, f_s;
+  std::vector<double> q_s;
+  for (int t : order) {
+    k_s.push_back(kind[t]), p_s.push_back(particle[t]), f_s.push_back(flags[t]);
+    r_s.push_back(kind[t] == MYTHOS_POINT_MUTUAL_TRAP ? ref_particle[t] : particle[t]);  // (read by a mutual trap alone)
+    double q[kPointForceParams];
+    for (int a = 0; a < kPointForceParams; ++a) q[a] = param[(size_t)t * kPointForceParams + a];
+    const int d = point_force_dir_at(kind[t]);
+    if (d >= 0) {  // dir -> dir / |dir| (a resting trap may have none: zeros stay)
+      const double len = std::sqrt(q[d] * q[d] + q[d + 1] * q[d + 1] + q[d + 2] * q[d + 2]);
+      if (len > 0) q[d] /= len, q[d + 1] /= len, q[d + 2] /= len;
+    }
+    q_s.insert(q_s.end(), q, q + kPointForceParams);
+  }
+  int rc = s->d_pt_kind.upload(k_s);
+  if (!rc) rc = s->d_pt_particle.upload(p_s);
+  if (!rc) rc = s->d_pt_ref.upload(r_s);
+  if (!rc) rc = s->d_pt_flags.upload(f_s);
+  if (!rc) rc = s->d_pt_param.upload(q_s);
+  if (rc) return ext_entries_merge(s), rc;
+  v.pt_kind = s->d_pt_kind.get(), v.pt_particle = s->d_pt_particle.get(), v.pt_ref = s->d_pt_ref.get(), v.pt_flags = s->d_pt_flags.get();
+  v.pt_param = s->d_pt_param.get();
+  for (int a = 0; a < 3; ++a) v.box[a] = sys->has_box ? sys->box[a] : 1.0;
+  s->h_pt_particle = std::move(p_s);
+  return ext_entries_merge(s);
+}
+
+int mythos_langevin_eval_external_at(mythos_sim_t* s, const void* center, double step, void* force_out, double* energy_out,
+                                     mythos_stream_t stream) {
+  if (!s || !center || !force_out || !energy_out || !std::isfinite(step)) {
+    set_error("mythos_langevin_eval_external_at: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
+  return md_entries_of(s).eval_external(s, center, step, force_out, energy_out, kExtEnergies, (hipStream_t)stream);
 }
 
 int mythos_langevin_eval_external(mythos_sim_t* s, const void* center, void* force_out, double* energy_out, mythos_stream_t stream) {
@@ -355,7 +473,7 @@ int mythos_langevin_eval_external(mythos_sim_t* s, const void* center, void* for
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
-  return md_entries_of(s).eval_external(s, center, force_out, energy_out, (hipStream_t)stream);
+  return md_entries_of(s).eval_external(s, center, 0.0, force_out, energy_out, 3, (hipStream_t)stream);
 }
 
 int mythos_langevin_set_seed(mythos_sim_t* s, uint64_t seed) {

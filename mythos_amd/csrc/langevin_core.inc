@@ -5,7 +5,7 @@
 // The parts, by concern:
 //   langevin_step.h      the fused step kernel md_step_kernel and its device helpers (device code only)
 //   langevin_frame.h     pack / unpack / rederive / init-momenta / external-kick kernels
-//   ext_field.h          the position-dependent external kick: tethers, sum restraints, group torques
+//   ext_field.h          the position-dependent external kick: tethers, sum restraints, group torques, point terms
 //   langevin_sim.h       struct mythos_sim and the host helpers that only read it
 //   langevin_unfused.inc the oxNA cross-check path, a second integrator with its own state and step loop
 //   md_plan.h            which instantiation a launch takes (pure host arithmetic, checked by the CPU suite)
@@ -69,15 +69,17 @@ static int update_chunk_order(mythos_sim* sim, const typename Vec4T<R>::type* p0
 
 // The position-dependent external kick (ext_field.h) of view v on the momenta `mom`, forces taken at (p0, pl): the group
 // rows, then the gather-and-kick with one stamp word per workgroup.  The one place these two kernels are launched - in
-// front of a step launch, and by mythos_langevin_eval_external with c_dt = 1 on zeroed momenta.
+// front of a step launch, and by mythos_langevin_eval_external(_at) with c_dt = 1 on zeroed momenta.  The point terms
+// (mythos_langevin_set_point_forces) are terms of the same entries: they add no launch.  step: the step count of the
+// frame (p0, pl), which the moving laws take as their time (ext_field.h).
 inline int ext_field_blocks(const ExtFieldView& v) { return (v.n_entries + 255) / 256; }
 template <typename R>
 static void launch_ext_field_kick(const ExtFieldView& v, const typename Vec4T<R>::type* p0, const typename Vec4T<R>::type* pl, double c_dt,
-                                  typename Vec4T<R>::type* mom, const int* flags, const int* halt_words, int k, unsigned long long stamp,
-                                  unsigned long long* stamps, hipStream_t st) {
+                                  double step, typename Vec4T<R>::type* mom, const int* flags, const int* halt_words, int k,
+                                  unsigned long long stamp, unsigned long long* stamps, hipStream_t st) {
   if (v.n_groups > 0) hipLaunchKernelGGL(ext_group_kernel<R>, dim3(v.n_groups), dim3(256), 0, st, v, p0, pl);
-  hipLaunchKernelGGL(ext_field_kick_kernel<R>, dim3(ext_field_blocks(v)), dim3(256), 0, st, v, p0, pl, c_dt, mom, flags, halt_words, k,
-                     stamp, stamps);
+  hipLaunchKernelGGL(ext_field_kick_kernel<R>, dim3(ext_field_blocks(v)), dim3(256), 0, st, v, p0, pl, c_dt, step, mom, flags, halt_words,
+                     k, stamp, stamps);
 }
 
 // Caller's (N,3)/(N,4) arrays -> the resident frames.  The list of a previous state does not carry over.
@@ -186,7 +188,7 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
       }
       const double c = double(row.kick_close) + 0.5 * row.do_step;
       const unsigned long long stamp = 2ull * (unsigned long long)(sim->step + k) + (row.kick_close != 0.0f ? 1ull : 0ull) + 1ull;
-      launch_ext_field_kick<R>(sim->rst, fr[cur].p0, kHiLo<R> ? fr[cur].pl : nullptr, c * sim->dt, fr[cur].mom,
+      launch_ext_field_kick<R>(sim->rst, fr[cur].p0, kHiLo<R> ? fr[cur].pl : nullptr, c * sim->dt, double(sim->step + k), fr[cur].mom,
                                (const int*)sim->d_flags.get(), (const int*)halt_words, k, stamp, sim->d_rst_stamp.get(), st);
     }
     // The one launch of md_step_kernel, its arguments written once.  With events: the pair receives the begin / end time
@@ -295,10 +297,12 @@ static int entry_init_momenta(mythos_sim* s, void* p_lin, void* p_ang, hipStream
   return MYTHOS_OK;
 }
 
-// mythos_langevin_eval_external: the caller's packed centres become the p0 words of a scratch frame with zero momenta, the
-// kick kernels of the integrator run on it with c dt = 1, and the momenta go out as the forces.
+// mythos_langevin_eval_external_at: the caller's packed centres become the p0 words of a scratch frame with zero momenta,
+// the kick kernels of the integrator run on it with c dt = 1 at step count `step`, and the momenta go out as the forces.
+// n_energies: kExtEnergies, or 3 for the first three words alone (mythos_langevin_eval_external).
 template <typename R>
-static int entry_eval_external(mythos_sim* s, const void* center, void* force_out, double* energy_out, hipStream_t st) {
+static int entry_eval_external(mythos_sim* s, const void* center, double step, void* force_out, double* energy_out, int n_energies,
+                               hipStream_t st) {
   using V4 = typename Vec4T<R>::type;
   const int n = s->sys->n;
   const int blocks = std::max(1, ext_field_blocks(s->rst));
@@ -319,10 +323,10 @@ static int entry_eval_external(mythos_sim* s, const void* center, void* force_ou
                        (const V4*)s->d_ext_force.get(), R(1), mom, flags, (const int*)nullptr, 0, 1ull, stamps);
   ExtFieldView v = s->rst;
   v.g_row = s->d_eval_group_row.get();  // (the rows of a resident run are not disturbed)
-  if (v.n_entries > 0) launch_ext_field_kick<R>(v, p0, nullptr, 1.0, mom, flags, nullptr, 0, 1ull, stamps + 1, st);
+  if (v.n_entries > 0) launch_ext_field_kick<R>(v, p0, nullptr, 1.0, step, mom, flags, nullptr, 0, 1ull, stamps + 1, st);
   hipLaunchKernelGGL(ext_eval_unpack_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const V4*)mom, (R*)force_out);
   hipLaunchKernelGGL(ext_energy_kernel<R>, dim3(1), dim3(256), 0, st, s->ext_count, (const int*)s->d_ext_index.get(),
-                     (const V4*)s->d_ext_force.get(), v, (const V4*)p0, energy_out);
+                     (const V4*)s->d_ext_force.get(), v, (const V4*)p0, step, n_energies, energy_out);
   MYTHOS_HIP_TRY(hipGetLastError());
   return MYTHOS_OK;
 }
@@ -333,7 +337,7 @@ struct MdEntries {
   int (*advance)(mythos_sim*, int, int, bool, void*, void*, double*, hipStream_t);
   int (*store)(mythos_sim*, void*, void*, void*, void*, hipStream_t);
   int (*init_momenta)(mythos_sim*, void*, void*, hipStream_t);
-  int (*eval_external)(mythos_sim*, const void*, void*, double*, hipStream_t);
+  int (*eval_external)(mythos_sim*, const void*, double, void*, double*, int, hipStream_t);
 };
 template <typename R>
 constexpr MdEntries md_entries() {

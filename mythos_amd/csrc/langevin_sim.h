@@ -6,6 +6,7 @@
 #error "langevin_sim.h needs UnfusedState: include langevin_unfused.inc (or langevin_core.inc), which defines it and then includes this file"
 #endif
 #include <cmath>
+#include <vector>
 
 #include "ext_field.h"
 #include "langevin_step.h"
@@ -45,6 +46,13 @@ struct mythos_sim : mythos::MdRun {
   mythos::DeviceBuf<double> d_rst_t_k, d_rst_t_anchor, d_rst_g_vec, d_rst_g_target, d_rst_g_row;
   mythos::DeviceBuf<unsigned long long> d_rst_stamp;   // [workgroups of ext_field_kick_kernel] each one's last kick applied
   bool rst_stamp_stale = true;                         // as ext_stamp_stale, for d_rst_stamp
+  // point terms (mythos_langevin_set_point_forces), the other half of `rst`: sorted by nucleotide, in the order given
+  mythos::DeviceBuf<int> d_pt_first, d_pt_kind, d_pt_particle, d_pt_ref, d_pt_flags;
+  mythos::DeviceBuf<double> d_pt_param;
+  // The two sets are set and cleared independently and share the entries of `rst`: the host keeps what each contributes
+  // - the restraints' entries (index, term range, terms) and the point terms' nucleotides - and merges them when either
+  // changes (ext_entries_merge, langevin.hip).
+  std::vector<int> h_rst_index, h_rst_first{0}, h_rst_term, h_pt_particle;
   // scratch of mythos_langevin_eval_external: p0 and momentum words, zeroed control words and stamps
   mythos::DeviceBytes d_eval_p0, d_eval_mom, d_eval_ctl;
   mythos::DeviceBuf<double> d_eval_group_row;

@@ -322,6 +322,7 @@ class LangevinIntegrator(_MdIntegrator):
         self.dt, self.kT = float(dt), float(kT)
         self.external_forces = (np.zeros(0, np.int32), np.zeros((0, 3), np.float64))
         self.restraints = None  # the set last handed to set_restraints (None: never called)
+        self.point_forces = None  # the set last handed to set_point_forces (None: never called)
 
     def set_neighbor_policy(self, r_cut: float, skin: float, every: int) -> None:
         _lib.check(
@@ -380,6 +381,34 @@ class LangevinIntegrator(_MdIntegrator):
         energies = torch.empty(3, dtype=torch.float64, device=s.device)
         _lib.check(self._lib.mythos_langevin_eval_external(self._h, _lib.ptr(c), _lib.ptr(force), _lib.ptr(energies), _lib.stream(s.device)),
                    "eval_external")
+        return force, energies
+
+    def set_point_forces(self, point_forces=None, *, n_one=None, n_rep=1, offsets=None) -> None:
+        """oxDNA's point forces on single nucleotides (mythos_amd.simulators.restraints.PointForces: moving strings, traps,
+        mutual traps, repulsion planes and spheres; mythos_langevin_set_point_forces).  The moving ones take the
+        integrator's step count (``step``) as their time.  A set of its own beside ``set_restraints`` and
+        ``set_external_forces``: all three add up.  None, or an empty set, clears it.  Refused between ``advance`` and
+        ``store`` (an open frame).  The keyword arguments repeat the set per replica (PointForces.lower)."""
+        from mythos_amd.simulators.restraints import PointForces
+
+        pf = PointForces() if point_forces is None else point_forces
+        a = pf.lower(n_one=self.system.n if n_one is None else n_one, n_rep=n_rep, offsets=offsets)
+        ip = lambda x: x.ctypes.data_as(_lib.c_int_p)  # noqa: E731
+        _lib.check(self._lib.mythos_langevin_set_point_forces(
+            self._h, int(a["kind"].shape[0]), ip(a["kind"]), ip(a["particle"]), ip(a["ref_particle"]), ip(a["flags"]),
+            a["param"].ctypes.data_as(_lib.c_double_p)), "set_point_forces")
+        self.point_forces = pf
+
+    def external_field_at(self, center, step):
+        """``external_field`` at step count ``step``, with the point forces: -> (force (n, 3), energies (8,) float64: the
+        three of ``external_field``, then the energy of the point terms of each kind - string, trap, mutual trap,
+        repulsion plane, repulsion sphere (mythos_langevin_eval_external_at)."""
+        s = self.system
+        c = s._check(center, (s.n, 3), "center")
+        force = torch.empty((s.n, 3), dtype=s.dtype, device=s.device)
+        energies = torch.empty(8, dtype=torch.float64, device=s.device)
+        _lib.check(self._lib.mythos_langevin_eval_external_at(self._h, _lib.ptr(c), float(step), _lib.ptr(force), _lib.ptr(energies),
+                                                              _lib.stream(s.device)), "eval_external_at")
         return force, energies
 
     def init_momenta(self):

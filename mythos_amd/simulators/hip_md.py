@@ -30,7 +30,7 @@ import torch
 from mythos_amd.energy.base import ComposedEnergyFunction, EnergyFunction, Quaternion, RigidBody, _pairs_2xP, pair_tag, topology_key
 from mythos_amd.energy.lowering import lower
 from mythos_amd.hip_system import LangevinIntegrator, OxdnaSystem
-from mythos_amd.input.external_forces import read_external_forces
+from mythos_amd.input.external_forces import read_external_field, read_external_forces
 from mythos_amd.simulators.base import Simulator, SimulatorOutput
 from mythos_amd.simulators.io import SimulatorTrajectory
 from mythos_amd.simulators.replicas import ReplicaLayout
@@ -202,6 +202,12 @@ class HipMDSimulator(Simulator):
     # moved with each replica to its place on the grid; ``anchor=None`` / ``target=None`` resolve from ``init_state``.
     # Combines with ``external_forces``.  None: no restraints, and no launch for them.
     restraints: Any = None
+    # oxDNA's point forces (mythos_amd.simulators.restraints.PointForces: moving strings, traps, mutual traps, repulsion
+    # planes and spheres) or the path of an oxDNA external-force file (read_external_field), repeated per replica with
+    # positions moved to each replica's place.  The moving ones take the integrator's step count, 0 at the start of every
+    # run.  A file's constant strings go where ``external_forces`` go, which then has to be None.  Combines with
+    # ``external_forces`` and ``restraints``.  None: no point forces, and exactly the launches of a simulator without.
+    point_forces: Any = None
     # device-side objects kept between calls: {key: (OxdnaSystem, LangevinIntegrator, ReplicaLayout)}
     _resident: dict = dc.field(default_factory=dict, init=False, repr=False, compare=False)
 
@@ -258,8 +264,29 @@ class HipMDSimulator(Simulator):
         self._resident[key_res] = (system, integ, layout)
         return system, integ, True
 
-    def _apply_external_forces(self, integ, layout) -> None:
-        ext = self.external_forces
+    def _external_field(self, n_one):
+        """-> (the point forces of this run, its constant forces): the two fields, with a file given as ``point_forces``
+        read and its constant strings (``rate = 0``) taken as the constant forces."""
+        pf, ext = self.point_forces, self.external_forces
+        if isinstance(pf, (str, bytes)) or hasattr(pf, "__fspath__"):
+            pf, const = read_external_field(pf, n_one)
+            if const[0].size:
+                if ext is not None:
+                    raise ValueError("point_forces: the file holds constant strings (rate = 0) and external_forces is given as "
+                                     "well; put them in one place")
+                ext = const
+        return pf, ext
+
+    def _apply_point_forces(self, integ, layout, offsets) -> None:
+        pf, _ = self._external_field(layout.n_one)
+        if not pf:
+            if integ.point_forces:
+                integ.set_point_forces()
+            return
+        _, off = layout.restraint_frames(torch.zeros((layout.n_one, 3)), offsets)
+        integ.set_point_forces(pf, n_one=layout.n_one, n_rep=layout.n_rep, offsets=off)
+
+    def _apply_external_forces(self, integ, layout, ext) -> None:
         if ext is None:
             if integ.external_forces[0].size:
                 integ.set_external_forces()
@@ -301,7 +328,7 @@ class HipMDSimulator(Simulator):
         if not new:
             integ.set_seed(int(key))
             integ.step = 0  # a run starts its noise stream at (key, step 0), as a new integrator would
-        self._apply_external_forces(integ, layout)
+        self._apply_external_forces(integ, layout, self._external_field(layout.n_one)[1])
         # a probabilistic sequence rides along into the dynamics, as it does in the reference - there the stacking /
         # hydrogen-bonding configurations carry pseq into whatever energy function a simulator steps with
         # (dna1/stacking.py:284-285, hydrogen_bonding.py:330-331)
@@ -329,6 +356,7 @@ class HipMDSimulator(Simulator):
         c_init = c
         c, q, offsets = layout.place(c, q, r_list)
         self._apply_restraints(integ, layout, c_init, offsets)
+        self._apply_point_forces(integ, layout, offsets)
         p, ang = integ.init_momenta()
         tc, tq, et = integ.run(c, q, p, ang, int(n_steps), save_every=self.save_every, want_energy=self.trace_energy)
         tc, tq, et = layout.unplace_rows(tc, tq, et, offsets)
