@@ -139,6 +139,11 @@ int mythos_oxdna_build_neighbors(mythos_system_t* sys, const void* center, doubl
                                  mythos_stream_t stream);
 /* max and mean row length of the current list (directed neighbours per nucleotide) */
 int mythos_oxdna_neighbor_stats(mythos_system_t* sys, int* max_row, double* mean_row);
+/* The rows the device holds (diagnostics / tests; synchronises): host int32 rows[n][*stride] - the bonded slots, then the
+ * close segment, then the far segment, an entry = neighbour index | role bit - row_len[n] (bonded slots included) and
+ * row_close[n] (end of the close segment).  Call with all three null to learn *stride, then with buffers of that size;
+ * any of the three may be null. */
+int mythos_oxdna_get_rows(mythos_system_t* sys, int32_t* rows, int32_t* row_len, int32_t* row_close, int* stride);
 
 /* Energy of n_frames configurations; replaces ComposedEnergyFunction.compute_terms / map
  * (mythos/energy/base.py:312-319, 90-93) and the jax.grad of them.

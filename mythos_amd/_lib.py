@@ -44,6 +44,7 @@ _SIGS = {
     "mythos_oxdna_set_neighbors": (C.c_int, [V, c_int_p, C.c_int]),
     "mythos_oxdna_build_neighbors": (C.c_int, [V, V, C.c_double, C.c_double, V]),
     "mythos_oxdna_neighbor_stats": (C.c_int, [V, C.POINTER(C.c_int), c_double_p]),
+    "mythos_oxdna_get_rows": (C.c_int, [V, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "mythos_oxdna_energy": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V]),
     "mythos_oxdna_energy_obs": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
     "mythos_oxdna_energy_dpseq": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),

@@ -290,6 +290,26 @@ int mythos_oxdna_neighbor_stats(mythos_system_t* s, int* max_row, double* mean_r
   return row_stats(s->d_row_len.get(), s->n, ROW_BONDED_SLOTS, max_row, mean_row);
 }
 
+int mythos_oxdna_get_rows(mythos_system_t* s, int32_t* rows, int32_t* row_len, int32_t* row_close, int* stride) {
+  if (!s) {
+    set_error("mythos_oxdna_get_rows: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (!s->nbrs_set) {
+    set_error("mythos_oxdna_get_rows: no neighbour list");
+    return MYTHOS_ERR_NOT_READY;
+  }
+  if (stride) *stride = s->list.stride;
+  if (!rows && !row_len && !row_close) return MYTHOS_OK;
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());
+  const size_t n = (size_t)s->n;
+  if (rows) MYTHOS_HIP_TRY(hipMemcpy(rows, s->list.d_rows.get(), n * s->list.stride * sizeof(int), hipMemcpyDeviceToHost));
+  if (row_len) MYTHOS_HIP_TRY(hipMemcpy(row_len, s->d_row_len.get(), n * sizeof(int), hipMemcpyDeviceToHost));
+  if (row_close) MYTHOS_HIP_TRY(hipMemcpy(row_close, row_close_of(s), n * sizeof(int), hipMemcpyDeviceToHost));
+  return MYTHOS_OK;
+}
+
 int mythos_oxdna_energy(mythos_system_t* s, const void* center, const void* quat, int n_frames, double* e_terms,
                         void* dU_dcenter, void* dU_dquat, double* dU_dparams, mythos_stream_t stream) {
   if (!s || n_frames < 0 || (n_frames > 0 && (!center || !quat || !e_terms))) {

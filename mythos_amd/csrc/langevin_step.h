@@ -505,67 +505,202 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   const int row_room = ITEMS - (extra_bonds ? ROW_BONDED_SLOTS - 2 : 0);  // result rows left for flagged neighbours
   const int lane64 = threadIdx.x & 63;
   const int gshift = lane64 & ~(G - 1);
-  // Software pipeline: the lane's row entries are fetched kEnt at a time, and the neighbour
-  // state (centre, backbone offset) of entry k+1 is requested before entry k is evaluated, so the
+  // Software pipeline: ONE sweep over the unbonded slots [ROW_BONDED_SLOTS, len) in strides of G - lane l of a group takes
+  // slots ROW_BONDED_SLOTS + l + G t, so the close entries sit on the lanes and in the iterations of their own (the flagged
+  // lists keep their order) and the far segment follows on without a second prologue: its first entries and their state
+  // are in flight while the last close stride is evaluated.  Row entries are fetched two strides ahead, and the neighbour
+  // state (centre, backbone offset, a1) of stride t + 1 is requested before stride t is evaluated, so the
   // L2 / Infinity-Cache round trips overlap the arithmetic instead of serialising with it.
   // (rolled: keeping the body once in the instruction stream matters more than unrolling - the whole
   // kernel has to stay inside the instruction cache that two CUs share)
-  // (the prefetches are unconditional: an entry past the end of the segment is read from the segment's last slot and
-  // replaced by -1, a missing neighbour's state is read from the lane's OWN nucleotide and never used - lines that are
-  // in the cache anyway; a load behind a lane-dependent branch made the compiler wait for ALL outstanding loads at
-  // the join, the one just issued included)
+  // (within a stride the prefetches are unconditional per lane: an entry past the end of the row is read from the row's
+  // last slot and replaced by -1, a missing neighbour's state is read from the lane's OWN nucleotide and never used -
+  // lines that are in the cache anyway; a load behind a lane-dependent branch made the compiler wait for ALL outstanding
+  // loads at the join, the one just issued included.  WHETHER a stride is fetched at all is a question to the whole
+  // wavefront - a scalar compare, a scalar branch: no load is issued for a stride in which no lane has an entry, and a1
+  // only if one of those entries is in a close segment, so the last iteration of the sweep issues no load.  Until the two
+  // segments were one sweep each of them ended on a full set of prefetches nobody read: 7 of a wavefront's 54.5 read
+  // instructions per launch at 12 kbp, on the L1 port the three workgroups of a CU contend for in this pass.)
+  // The body of an iteration is chosen per wavefront as well: the close body while any lane has a slot below its
+  // close_end - a far entry that shares such a stride goes through it with `close` forced false and gets exactly the
+  // backbone terms of the far body - and the far body (backbone - backbone only) from the first all-far stride on.
   auto row_at = [&](int s, int end) -> int {
     const int v = row[max(min(s, end - 1), 0)];
     return s < end ? v : -1;
   };
+  auto row_word = [&](int s) -> int { return row[max(min(s, len - 1), 0)]; };
   auto slot_of_entry = [&](int e) -> int { return e >= 0 ? (e & ROW_INDEX_MASK) : ii; };
-  {
-    int e_cur = -1, e_nxt = -1;
-    V4 n0{}, n3{}, n1{}, nl{};
+  // oxNA (MODEL 4) keeps the two separate pipelines - close segment, then far segment - it had before the single sweep:
+  // with the sweep, hipcc's register allocation of md_step_kernel<double, 4, true, *, false, false, 8> parks the
+  // kernel-argument tuple {flags, traj_c, traj_q, e_part} in spill lanes AFTER two later scalar loads have overwritten
+  // three quarters of it, and the launch writes its trajectory rows through the wrong pointers (seen on the GPU: dynamics
+  // exact, saved rows never written; read in the -S output: s_load_dwordx8 s[12:19] at 0x1d0, s_load s[14:15] / s[16:23],
+  // then v_writelane of s12 .. s19).  Its instantiations compile to what they were; DESIGN section 8.
+  // So do the 16-lane instantiations (GL == 16, small systems): a row of ~25 entries is two strides either way, and the
+  // 1 kbp run measured the sweep 1.4 % SLOWER there (86.2 k against 87.5 k steps/s, three alternations).
+  if constexpr (MODEL == 4 || GL != kMdG) {
     {
-      const int s = ROW_BONDED_SLOTS + lane;
-      e_cur = row_at(s, close_end);
-      e_nxt = row_at(s + G, close_end);
-      const int j = slot_of_entry(e_cur);
-      n0 = in.p0[j];
-      n3 = in.p3[j];
-      n1 = in.p1[j];
-      if constexpr (kHiLo<R>) nl = in.pl[j];
-    }
-#pragma unroll 1
-    for (int s0 = ROW_BONDED_SLOTS; s0 < close_end; s0 += G) {
-      const int s = s0 + lane;
-      const int entry = e_cur;
-      const V4 o0 = n0, o3 = n3, o1 = n1, ol = nl;
-      e_cur = e_nxt;
-      e_nxt = row_at(s + 2 * G, close_end);
-      {  // the close segment reads a1 as well: nearly all of its entries need it
-        const int jn = slot_of_entry(e_cur);
-        n0 = in.p0[jn];
-        n3 = in.p3[jn];
-        n1 = in.p1[jn];
-        if constexpr (kHiLo<R>) nl = in.pl[jn];
+      int e_cur = -1, e_nxt = -1;
+      V4 n0{}, n3{}, n1{}, nl{};
+      {
+        const int s = ROW_BONDED_SLOTS + lane;
+        e_cur = row_at(s, close_end);
+        e_nxt = row_at(s + G, close_end);
+        const int j = slot_of_entry(e_cur);
+        n0 = in.p0[j];
+        n3 = in.p3[j];
+        n1 = in.p1[j];
+        if constexpr (kHiLo<R>) nl = in.pl[j];
       }
-      bool flag[2] = {false, false};
-      if (entry >= 0) {
-        const bool role_p = (entry & ROW_ROLE_Q) == 0;
-        MD_RADSET_OF_ENTRY
-        const bool o_rna = (MODEL == 4) && ((((int)o0.w) >> 3) & 1);
-        const R gba_s = (MODEL == 4 && self.rna) ? Prna[GEO_BASE] : g_ba, gba_o = o_rna ? Prna[GEO_BASE] : g_ba;
-        const R gst_s = (MODEL == 4 && self.rna) ? Prna[GEO_STACK] : g_st, gst_o = o_rna ? Prna[GEO_STACK] : g_st;
-        (void)gst_s, (void)gst_o;
-        const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
-        const V3<R> offb_o = xyz<R>(o3);
-        const bool close = dot(dco, dco) < cut.rcom2;
-        // backbone - backbone: excluded volume + Debye-Hueckel
+#pragma unroll 1
+      for (int s0 = ROW_BONDED_SLOTS; s0 < close_end; s0 += G) {
+        const int s = s0 + lane;
+        const int entry = e_cur;
+        const V4 o0 = n0, o3 = n3, o1 = n1, ol = nl;
+        e_cur = e_nxt;
+        e_nxt = row_at(s + 2 * G, close_end);
+        {  // the close segment reads a1 as well: nearly all of its entries need it
+          const int jn = slot_of_entry(e_cur);
+          n0 = in.p0[jn];
+          n3 = in.p3[jn];
+          n1 = in.p1[jn];
+          if constexpr (kHiLo<R>) nl = in.pl[jn];
+        }
+        bool flag[2] = {false, false};
+        if (entry >= 0) {
+          const bool role_p = (entry & ROW_ROLE_Q) == 0;
+          MD_RADSET_OF_ENTRY
+          const bool o_rna = (MODEL == 4) && ((((int)o0.w) >> 3) & 1);
+          const R gba_s = (MODEL == 4 && self.rna) ? Prna[GEO_BASE] : g_ba, gba_o = o_rna ? Prna[GEO_BASE] : g_ba;
+          const R gst_s = (MODEL == 4 && self.rna) ? Prna[GEO_STACK] : g_st, gst_o = o_rna ? Prna[GEO_STACK] : g_st;
+          (void)gst_s, (void)gst_o;
+          const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
+          const V3<R> offb_o = xyz<R>(o3);
+          const bool close = dot(dco, dco) < cut.rcom2;
+          // backbone - backbone: excluded volume + Debye-Hueckel
+          {
+            const V3<R> d = dco + offb_o - offb_s;
+            const R r2 = dot(d, d);
+            if (r2 < rs.rbb2) {
+              const R r = m_sqrt(r2);
+              const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
+              R dVdr = rs.tw_n * v.d;
+              R en = v.f;
+              if constexpr (MODEL >= 2) {
+                const FD<R> dh = debye_eval(r, rs.dhp);
+                R mult = R(1);
+                if (rs.half_ends) {
+                  const int mo = (int)o0.w;
+                  mult = (self.is_end ? R(0.5) : R(1)) * (((mo >> 2) & 1) ? R(0.5) : R(1));
+                }
+                dVdr += rs.tw_dh * mult * dh.d;
+                if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
+              }
+              if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
+              axpy(gbk, dVdr / r, d);
+            }
+          }
+          if (close) {
+            const V3<R> a1o = xyz<R>(o1);
+            R en = R(0);
+            // self backbone - other base and self base - other backbone: which of the two is the reference's
+            // "back_p - base_q" / "base_p - back_q" depends on the role; the squared distances are routed by
+            // role so both parameter blocks stay scalar operands
+            {
+              V3<R> dA = dco - offb_s;
+              axpy(dA, gba_o, a1o);
+              V3<R> dB = dco + offb_o;
+              axpy(dB, -gba_s, self.a1);
+              const R ra2 = dot(dA, dA), rb2 = dot(dB, dB);
+              R c1, c2;
+              en += f3_coef(rs.eps_n, rs.tw_n, rs.f_bkba, role_p ? ra2 : rb2, c1);
+              en += f3_coef(rs.eps_n, rs.tw_n, rs.f_babk, role_p ? rb2 : ra2, c2);
+              axpy(gbk, role_p ? c1 : c2, dA);
+              axpy(gba, role_p ? c2 : c1, dB);
+            }
+            const V3<R> da = a1o - self.a1;
+            {
+              V3<R> d = dco;
+              if constexpr (MODEL == 4) {  // each nucleotide's base site at the offset of its own type
+                axpy(d, gba_o, a1o);
+                axpy(d, -gba_s, self.a1);
+              } else {
+                axpy(d, g_ba, da);
+              }
+              const R r2 = dot(d, d);
+              en += f3_radial(rs.eps_n, rs.tw_n, rs.f_base, d, r2, gba);
+              flag[0] = rs.cr_lo2 < r2 && r2 < rs.cr_hi2;
+              if (!flag[0] && rs.hb_lo2 < r2 && r2 < rs.hb_hi2) {  // H-bond only for pairs with a non-zero weight
+                const int so = (int)o0.w & 3;
+                if (PSEQ && (pseq.terms & 2) != 0)
+                  flag[0] = rs.hb_mask != 0u;  // the weight is an expectation over both bases: any non-zero table entry may count
+                else
+                  flag[0] = (rs.hb_mask >> (role_p ? (self.seq * 4 + so) : (so * 4 + self.seq))) & 1u;
+              }
+            }
+            {
+              V3<R> d = dco;
+              if constexpr (MODEL == 4) {
+                axpy(d, gst_o, a1o);
+                axpy(d, -gst_s, self.a1);
+              } else {
+                axpy(d, g_st, da);
+              }
+              const R r2 = dot(d, d);
+              flag[1] = rs.cx_lo2 < r2 && r2 < rs.cx_hi2;
+            }
+            if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
+          }
+        }
+        // append the flagged slots of this group to its two LDS lists, in slot order
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const unsigned long long bal = __ballot(flag[t]);
+          const unsigned int gm = (unsigned int)(bal >> gshift) & ((1u << G) - 1u);
+          if (flag[t]) {
+            const int pos = n_items[t] + __popc(gm & ((1u << lane) - 1u));
+            if (pos < ITEMS) items[t][grp][pos] = entry;  // (row_room <= ITEMS; an over-full nucleotide aborts the launch below)
+          }
+          n_items[t] += __popc(gm);
+        }
+      }
+    }
+    // far segment: only the backbone-backbone terms (excluded volume + Debye-Hueckel) can act
+    MD_PRIO(1);
+    {
+      int e_cur = -1, e_nxt = -1;
+      V4 n0{}, n3{}, nl{};
+      {
+        const int s = close_end + lane;
+        e_cur = row_at(s, len);
+        e_nxt = row_at(s + G, len);
+        const int j = slot_of_entry(e_cur);
+        n0 = in.p0[j];
+        n3 = in.p3[j];
+        if constexpr (kHiLo<R>) nl = in.pl[j];
+      }
+#pragma unroll 1
+      for (int s0 = close_end; s0 < len; s0 += G) {
+        const int s = s0 + lane;
+        const int entry = e_cur;
+        const V4 o0 = n0, o3 = n3, ol = nl;
+        e_cur = e_nxt;
+        e_nxt = row_at(s + 2 * G, len);
         {
-          const V3<R> d = dco + offb_o - offb_s;
+          const int jn = slot_of_entry(e_cur);
+          n0 = in.p0[jn];
+          n3 = in.p3[jn];
+          if constexpr (kHiLo<R>) nl = in.pl[jn];
+        }
+        if (entry >= 0) {
+          MD_RADSET_OF_ENTRY
+          const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
+          const V3<R> d = dco + xyz<R>(o3) - offb_s;
           const R r2 = dot(d, d);
           if (r2 < rs.rbb2) {
             const R r = m_sqrt(r2);
             const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
             R dVdr = rs.tw_n * v.d;
-            R en = v.f;
             if constexpr (MODEL >= 2) {
               const FD<R> dh = debye_eval(r, rs.dhp);
               R mult = R(1);
@@ -576,123 +711,178 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
               dVdr += rs.tw_dh * mult * dh.d;
               if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
             }
-            if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
+            if constexpr (SAVE) e[T_NEXC] += R(0.5) * v.f;
             axpy(gbk, dVdr / r, d);
           }
         }
-        if (close) {
-          const V3<R> a1o = xyz<R>(o1);
-          R en = R(0);
-          // self backbone - other base and self base - other backbone: which of the two is the reference's
-          // "back_p - base_q" / "base_p - back_q" depends on the role; the squared distances are routed by
-          // role so both parameter blocks stay scalar operands
-          {
-            V3<R> dA = dco - offb_s;
-            axpy(dA, gba_o, a1o);
-            V3<R> dB = dco + offb_o;
-            axpy(dB, -gba_s, self.a1);
-            const R ra2 = dot(dA, dA), rb2 = dot(dB, dB);
-            R c1, c2;
-            en += f3_coef(rs.eps_n, rs.tw_n, rs.f_bkba, role_p ? ra2 : rb2, c1);
-            en += f3_coef(rs.eps_n, rs.tw_n, rs.f_babk, role_p ? rb2 : ra2, c2);
-            axpy(gbk, role_p ? c1 : c2, dA);
-            axpy(gba, role_p ? c2 : c1, dB);
-          }
-          const V3<R> da = a1o - self.a1;
-          {
-            V3<R> d = dco;
-            if constexpr (MODEL == 4) {  // each nucleotide's base site at the offset of its own type
-              axpy(d, gba_o, a1o);
-              axpy(d, -gba_s, self.a1);
-            } else {
-              axpy(d, g_ba, da);
-            }
-            const R r2 = dot(d, d);
-            en += f3_radial(rs.eps_n, rs.tw_n, rs.f_base, d, r2, gba);
-            flag[0] = rs.cr_lo2 < r2 && r2 < rs.cr_hi2;
-            if (!flag[0] && rs.hb_lo2 < r2 && r2 < rs.hb_hi2) {  // H-bond only for pairs with a non-zero weight
-              const int so = (int)o0.w & 3;
-              if (PSEQ && (pseq.terms & 2) != 0)
-                flag[0] = rs.hb_mask != 0u;  // the weight is an expectation over both bases: any non-zero table entry may count
-              else
-                flag[0] = (rs.hb_mask >> (role_p ? (self.seq * 4 + so) : (so * 4 + self.seq))) & 1u;
-            }
-          }
-          {
-            V3<R> d = dco;
-            if constexpr (MODEL == 4) {
-              axpy(d, gst_o, a1o);
-              axpy(d, -gst_s, self.a1);
-            } else {
-              axpy(d, g_st, da);
-            }
-            const R r2 = dot(d, d);
-            flag[1] = rs.cx_lo2 < r2 && r2 < rs.cx_hi2;
-          }
-          if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
-        }
-      }
-      // append the flagged slots of this group to its two LDS lists, in slot order
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const unsigned long long bal = __ballot(flag[t]);
-        const unsigned int gm = (unsigned int)(bal >> gshift) & ((1u << G) - 1u);
-        if (flag[t]) {
-          const int pos = n_items[t] + __popc(gm & ((1u << lane) - 1u));
-          if (pos < ITEMS) items[t][grp][pos] = entry;  // (row_room <= ITEMS; an over-full nucleotide aborts the launch below)
-        }
-        n_items[t] += __popc(gm);
       }
     }
-  }
-  // far segment: only the backbone-backbone terms (excluded volume + Debye-Hueckel) can act
-  MD_PRIO(1);
-  {
-    int e_cur = -1, e_nxt = -1;
-    V4 n0{}, n3{}, nl{};
+  } else {
     {
-      const int s = close_end + lane;
-      e_cur = row_at(s, len);
-      e_nxt = row_at(s + G, len);
-      const int j = slot_of_entry(e_cur);
-      n0 = in.p0[j];
-      n3 = in.p3[j];
-      if constexpr (kHiLo<R>) nl = in.pl[j];
-    }
-#pragma unroll 1
-    for (int s0 = close_end; s0 < len; s0 += G) {
-      const int s = s0 + lane;
-      const int entry = e_cur;
-      const V4 o0 = n0, o3 = n3, ol = nl;
-      e_cur = e_nxt;
-      e_nxt = row_at(s + 2 * G, len);
-      {
-        const int jn = slot_of_entry(e_cur);
-        n0 = in.p0[jn];
-        n3 = in.p3[jn];
-        if constexpr (kHiLo<R>) nl = in.pl[jn];
+      // (e_nxt is the word as it was read: whether the lane has an entry there is decided from the slot when the word moves
+      // up to e_cur, an iteration later - a select right behind the conditional load would wait for it on the spot)
+      int e_cur = -1, e_nxt = -1;
+      V4 n0{}, n3{}, n1{}, nl{};
+      // the longest row and the longest close segment of the wavefront, as scalars: the lanes of a group hold the same two
+      // numbers, so one lane per group is read.  "Some lane has an entry in the stride at s0" is then s0 < wlen and "some
+      // lane's slot there is in its close segment" s0 < wclose - scalar loop control and no mask to carry.  (The same
+      // questions as ballots over s < len, carried from iteration to iteration or asked again at each use, cost scratch:
+      // 36 B in md_step_kernel<double, 2> under a probabilistic sequence, 20 - 36 B in the DENSE instantiation.)
+      int wlen = 0, wclose = 0;
+#pragma unroll
+      for (int k = 0; k < 64 / G; ++k) {
+        wlen = max(wlen, __builtin_amdgcn_readlane(len, k * G));
+        wclose = max(wclose, __builtin_amdgcn_readlane(close_end, k * G));
       }
-      if (entry >= 0) {
-        MD_RADSET_OF_ENTRY
-        const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
-        const V3<R> d = dco + xyz<R>(o3) - offb_s;
-        const R r2 = dot(d, d);
-        if (r2 < rs.rbb2) {
-          const R r = m_sqrt(r2);
-          const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
-          R dVdr = rs.tw_n * v.d;
-          if constexpr (MODEL >= 2) {
-            const FD<R> dh = debye_eval(r, rs.dhp);
-            R mult = R(1);
-            if (rs.half_ends) {
-              const int mo = (int)o0.w;
-              mult = (self.is_end ? R(0.5) : R(1)) * (((mo >> 2) & 1) ? R(0.5) : R(1));
+      int s0 = ROW_BONDED_SLOTS;
+      if (s0 < wlen) {
+        const int s = s0 + lane;
+        e_cur = row_at(s, len);
+        if (s0 + G < wlen) e_nxt = row_word(s + G);
+        const int j = slot_of_entry(e_cur);
+        n0 = in.p0[j];
+        n3 = in.p3[j];
+        if (s0 < wclose) n1 = in.p1[j];
+        if constexpr (kHiLo<R>) nl = in.pl[j];
+      }
+#pragma unroll 1
+      for (; s0 < wlen; s0 += G) {
+        const int s = s0 + lane;
+        const int entry = e_cur;
+        const V4 o0 = n0, o3 = n3, o1 = n1, ol = nl;
+        e_cur = s + G < len ? e_nxt : -1;
+        if (s0 + G < wlen) {
+          if (s0 + 2 * G < wlen) e_nxt = row_word(s + 2 * G);
+          const int jn = slot_of_entry(e_cur);
+          n0 = in.p0[jn];
+          n3 = in.p3[jn];
+          if (s0 + G < wclose) n1 = in.p1[jn];  // the close segment reads a1 as well: nearly all of its entries need it
+          if constexpr (kHiLo<R>) nl = in.pl[jn];
+        }
+        if (s0 < wclose) {
+          bool flag[2] = {false, false};
+          if (entry >= 0) {
+            const bool role_p = (entry & ROW_ROLE_Q) == 0;
+            MD_RADSET_OF_ENTRY
+            const bool o_rna = (MODEL == 4) && ((((int)o0.w) >> 3) & 1);
+            const R gba_s = (MODEL == 4 && self.rna) ? Prna[GEO_BASE] : g_ba, gba_o = o_rna ? Prna[GEO_BASE] : g_ba;
+            const R gst_s = (MODEL == 4 && self.rna) ? Prna[GEO_STACK] : g_st, gst_o = o_rna ? Prna[GEO_STACK] : g_st;
+            (void)gst_s, (void)gst_o;
+            const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
+            const V3<R> offb_o = xyz<R>(o3);
+            const bool close = s < close_end && dot(dco, dco) < cut.rcom2;  // (a far entry in a mixed stride: backbone terms only)
+            // backbone - backbone: excluded volume + Debye-Hueckel
+            {
+              const V3<R> d = dco + offb_o - offb_s;
+              const R r2 = dot(d, d);
+              if (r2 < rs.rbb2) {
+                const R r = m_sqrt(r2);
+                const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
+                R dVdr = rs.tw_n * v.d;
+                R en = v.f;
+                if constexpr (MODEL >= 2) {
+                  const FD<R> dh = debye_eval(r, rs.dhp);
+                  R mult = R(1);
+                  if (rs.half_ends) {
+                    const int mo = (int)o0.w;
+                    mult = (self.is_end ? R(0.5) : R(1)) * (((mo >> 2) & 1) ? R(0.5) : R(1));
+                  }
+                  dVdr += rs.tw_dh * mult * dh.d;
+                  if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
+                }
+                if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
+                axpy(gbk, dVdr / r, d);
+              }
             }
-            dVdr += rs.tw_dh * mult * dh.d;
-            if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
+            if (close) {
+              const V3<R> a1o = xyz<R>(o1);
+              R en = R(0);
+              // self backbone - other base and self base - other backbone: which of the two is the reference's
+              // "back_p - base_q" / "base_p - back_q" depends on the role; the squared distances are routed by
+              // role so both parameter blocks stay scalar operands
+              {
+                V3<R> dA = dco - offb_s;
+                axpy(dA, gba_o, a1o);
+                V3<R> dB = dco + offb_o;
+                axpy(dB, -gba_s, self.a1);
+                const R ra2 = dot(dA, dA), rb2 = dot(dB, dB);
+                R c1, c2;
+                en += f3_coef(rs.eps_n, rs.tw_n, rs.f_bkba, role_p ? ra2 : rb2, c1);
+                en += f3_coef(rs.eps_n, rs.tw_n, rs.f_babk, role_p ? rb2 : ra2, c2);
+                axpy(gbk, role_p ? c1 : c2, dA);
+                axpy(gba, role_p ? c2 : c1, dB);
+              }
+              const V3<R> da = a1o - self.a1;
+              {
+                V3<R> d = dco;
+                if constexpr (MODEL == 4) {  // each nucleotide's base site at the offset of its own type
+                  axpy(d, gba_o, a1o);
+                  axpy(d, -gba_s, self.a1);
+                } else {
+                  axpy(d, g_ba, da);
+                }
+                const R r2 = dot(d, d);
+                en += f3_radial(rs.eps_n, rs.tw_n, rs.f_base, d, r2, gba);
+                flag[0] = rs.cr_lo2 < r2 && r2 < rs.cr_hi2;
+                if (!flag[0] && rs.hb_lo2 < r2 && r2 < rs.hb_hi2) {  // H-bond only for pairs with a non-zero weight
+                  const int so = (int)o0.w & 3;
+                  if (PSEQ && (pseq.terms & 2) != 0)
+                    flag[0] = rs.hb_mask != 0u;  // the weight is an expectation over both bases: any non-zero table entry may count
+                  else
+                    flag[0] = (rs.hb_mask >> (role_p ? (self.seq * 4 + so) : (so * 4 + self.seq))) & 1u;
+                }
+              }
+              {
+                V3<R> d = dco;
+                if constexpr (MODEL == 4) {
+                  axpy(d, gst_o, a1o);
+                  axpy(d, -gst_s, self.a1);
+                } else {
+                  axpy(d, g_st, da);
+                }
+                const R r2 = dot(d, d);
+                flag[1] = rs.cx_lo2 < r2 && r2 < rs.cx_hi2;
+              }
+              if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
+            }
           }
-          if constexpr (SAVE) e[T_NEXC] += R(0.5) * v.f;
-          axpy(gbk, dVdr / r, d);
+          // append the flagged slots of this group to its two LDS lists, in slot order
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const unsigned long long bal = __ballot(flag[t]);
+            const unsigned int gm = (unsigned int)(bal >> gshift) & ((1u << G) - 1u);
+            if (flag[t]) {
+              const int pos = n_items[t] + __popc(gm & ((1u << lane) - 1u));
+              if (pos < ITEMS) items[t][grp][pos] = entry;  // (row_room <= ITEMS; an over-full nucleotide aborts the launch below)
+            }
+            n_items[t] += __popc(gm);
+          }
+        } else {
+          // all-far stride: only the backbone-backbone terms (excluded volume + Debye-Hueckel) can act
+          MD_PRIO(1);
+          if (entry >= 0) {
+            MD_RADSET_OF_ENTRY
+            const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
+            const V3<R> d = dco + xyz<R>(o3) - offb_s;
+            const R r2 = dot(d, d);
+            if (r2 < rs.rbb2) {
+              const R r = m_sqrt(r2);
+              const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
+              R dVdr = rs.tw_n * v.d;
+              if constexpr (MODEL >= 2) {
+                const FD<R> dh = debye_eval(r, rs.dhp);
+                R mult = R(1);
+                if (rs.half_ends) {
+                  const int mo = (int)o0.w;
+                  mult = (self.is_end ? R(0.5) : R(1)) * (((mo >> 2) & 1) ? R(0.5) : R(1));
+                }
+                dVdr += rs.tw_dh * mult * dh.d;
+                if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
+              }
+              if constexpr (SAVE) e[T_NEXC] += R(0.5) * v.f;
+              axpy(gbk, dVdr / r, d);
+            }
+          }
         }
       }
     }

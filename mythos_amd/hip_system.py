@@ -125,6 +125,20 @@ class OxdnaSystem(_lib.Handle):
         _lib.check(self._lib.mythos_oxdna_neighbor_stats(self._h, C.byref(mx), C.byref(mean)), "neighbor_stats")
         return mx.value, mean.value
 
+    def rows(self):
+        """(rows (n, stride) int32, len (n,) int32, close (n,) int32) of the neighbour rows the device holds, as numpy
+        arrays: row i is its bonded slots, then the close segment [bonded slots, close[i]), then the far segment
+        [close[i], len[i]); an entry is neighbour index | role bit (diagnostics / tests; synchronises)."""
+        stride = C.c_int(0)
+        _lib.check(self._lib.mythos_oxdna_get_rows(self._h, None, None, None, C.byref(stride)), "get_rows")
+        rows = np.empty((self.n, stride.value), dtype=np.int32)
+        lens = np.empty(self.n, dtype=np.int32)
+        close = np.empty(self.n, dtype=np.int32)
+        p32 = C.POINTER(C.c_int32)
+        _lib.check(self._lib.mythos_oxdna_get_rows(self._h, rows.ctypes.data_as(p32), lens.ctypes.data_as(p32),
+                                                   close.ctypes.data_as(p32), C.byref(stride)), "get_rows")
+        return rows, lens, close
+
     # ---- energy --------------------------------------------------------------------------------
     def _check(self, t: torch.Tensor, tail: tuple, name: str) -> torch.Tensor:
         if not isinstance(t, torch.Tensor) or t.device != self.device:
