@@ -262,11 +262,14 @@ constexpr int md_prio_digit(int phase) {
 // (0 for the first kernel of a run, 1/2 otherwise); do_step = 0 for the closing-only kernel.
 //
 // Work decomposition: 8 lanes per nucleotide, 32 nucleotides per 256-thread workgroup.
-//   phase 1 (radial): the lanes stride over the nucleotide's unbonded row, close segment then far segment;
-//           per neighbour they read the centre (hi, lo), the backbone offset and - in the close segment -
-//           a1, evaluate Debye-Hueckel and the excluded-volume site pairs with early-outs on squared
-//           distances, and flag the few neighbours whose base-base / stack-stack distance lies in the
-//           support of an angular term (two LDS lists per nucleotide: base-pair terms, coaxial stacking);
+//   phase 1 (radial): the lanes stride over the nucleotide's unbonded row - in ONE pipelined sweep over [4, len) whose
+//           strides run the close body while any lane of the wavefront has a slot in its close segment and the far body
+//           after that; oxNA and the 16-lane instantiations walk the close segment, then the far segment, as two
+//           pipelines.  Either way one set of helpers evaluates an entry (close_entry, far_entry, backbone_term) and one
+//           fetches the next neighbour's state (NbrState): per neighbour the centre (hi, lo), the backbone offset and -
+//           in a close stride - a1; Debye-Hueckel and the excluded-volume site pairs with early-outs on squared
+//           distances; the few neighbours whose base-base / stack-stack distance lies in the support of an angular
+//           term are flagged (two LDS lists per nucleotide: base-pair terms, coaxial stacking);
 //   phase 2 (angular): work items of the whole workgroup, one code path per wavefront: the bonded
 //           neighbours (FENE, bonded excluded volume, stacking), the two halves of the base-pair list
 //           (H-bond + cross-stacking evaluated together), the coaxial list; results go to LDS rows;
@@ -357,10 +360,50 @@ __device__ __forceinline__ RadSet<R> pick3(const RadSet<R>& a, const RadSet<R>& 
 // the parameter set of the row entry being evaluated: the one set of the model, or (oxNA) the set of the pair's kind -
 // 0 DNA-DNA, 1 RNA-RNA, 2 hybrid - from the type bits of the two meta words
 #define MD_RADSET_OF_ENTRY                                                                                         \
-  const int md_kind = (MODEL == 4) ? na1_kind(self.rna, ((int)o0.w >> 3) & 1) : 0;                                 \
+  const int md_kind = (MODEL == 4) ? na1_kind(self.rna, meta_of(o0.w).rna) : 0;                                    \
   const RadSet<R> rs_picked = (MODEL == 4) ? pick3(rs0, rs1, rs2, md_kind) : rs0;                                  \
   const RadSet<R>& rs = (MODEL == 4) ? rs_picked : rs0;
 __device__ __forceinline__ int na1_kind(int self_rna, int other_rna) { return (self_rna && other_rna) ? 1 : ((self_rna || other_rna) ? 2 : 0); }
+
+// The meta word of a nucleotide as a frame carries it (p0.w): bits 0 - 1 the base, bit 2 strand end, bit 3 RNA (oxNA)
+struct Meta {
+  int seq, is_end, rna;
+};
+template <typename R>
+__device__ __forceinline__ Meta meta_of(R w) {
+  const int m = (int)w;
+  return Meta{m & 3, (m >> 2) & 1, (m >> 3) & 1};
+}
+template <typename R>
+__device__ __forceinline__ void set_meta(Nuc<R>& nuc, R w) {
+  const Meta m = meta_of(w);
+  nuc.seq = m.seq, nuc.is_end = m.is_end, nuc.rna = m.rna;
+}
+// centre and axes of a workgroup's own nucleotide from its self_lds row (words 0 - 8).  The meta word (9) and the low
+// part of the centre (10 - 12) stay with the caller: read here, the meta word was kept in a register from the head of the
+// integrator to the frame store at its end, which reads it again.  (seq, is_end, rna and idx are the caller's to set.)
+template <typename R>
+__device__ __forceinline__ Nuc<R> nuc_from_lds(const R* ms) {
+  Nuc<R> nuc;
+  nuc.c = V3<R>{ms[0], ms[1], ms[2]};
+  nuc.a1 = V3<R>{ms[3], ms[4], ms[5]};
+  nuc.a3 = V3<R>{ms[6], ms[7], ms[8]};
+  nuc.a2 = cross(nuc.a3, nuc.a1);
+  return nuc;
+}
+
+// Neighbour state in flight for the radial pass: centre and meta word, backbone offset, a1 (close strides only) and, in
+// fp32, the low part of the centre.  with_a1 is a constant or wave-uniform.
+template <typename R>
+struct NbrState {
+  typename Vec4T<R>::type n0{}, n3{}, n1{}, nl{};
+  __device__ __forceinline__ void fetch(const Frame<R>& in, int j, bool with_a1) {
+    n0 = in.p0[j];
+    n3 = in.p3[j];
+    if (with_a1) n1 = in.p1[j];
+    if constexpr (kHiLo<R>) nl = in.pl[j];
+  }
+};
 
 // ITEMS: result rows per nucleotide for the angular work lists.  16 is enough for any duplex, junction or origami
 // at physical density (a base has 3 - 5 partners inside the range of an angular term); a nucleotide with more makes
@@ -475,10 +518,7 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     self.a3 = xyz<R>(s2);
     self.a2 = cross(self.a3, self.a1);
     offb_s = xyz<R>(s3);
-    const int m = (int)s0.w;
-    self.seq = m & 3;
-    self.is_end = (m >> 2) & 1;
-    self.rna = (m >> 3) & 1;
+    set_meta(self, s0.w);
     if (lane == 0) {
       R* sl = self_lds[grp];
       sl[0] = s0.x, sl[1] = s0.y, sl[2] = s0.z, sl[3] = s1.x, sl[4] = s1.y, sl[5] = s1.z;
@@ -530,6 +570,121 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   };
   auto row_word = [&](int s) -> int { return row[max(min(s, len - 1), 0)]; };
   auto slot_of_entry = [&](int e) -> int { return e >= 0 ? (e & ROW_INDEX_MASK) : ii; };
+  // The radial terms of ONE row entry, written once for the two loop structures below.  o: the neighbour's state as the
+  // pipeline delivered it - the loops take the four vectors out of the prefetch struct first and hand the helpers a
+  // temporary built from them: with `const NbrState<R> o = nb;` as the loop's copy md_step_kernel<double, 2, false, 16,
+  // false, false, 16> took 36 B of scratch where it had none (profiles/r06_radial_entry.md has the shapes that were tried:
+  // the compiler inlines these helpers only after its first scalar-replacement pass, so what crosses a helper's boundary
+  // is allocated differently, and no shape reproduces the hand-written copies' code instruction for instruction).
+  // backbone - backbone: excluded volume + Debye-Hueckel
+  auto backbone_term = [&](const RadSet<R>& rs, const V3<R>& dco, const V3<R>& offb_o, const V4& o0) __attribute__((always_inline)) {
+    const V3<R> d = dco + offb_o - offb_s;
+    const R r2 = dot(d, d);
+    if (r2 < rs.rbb2) {
+      const R r = m_sqrt(r2);
+      const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
+      R dVdr = rs.tw_n * v.d;
+      R en = v.f;
+      if constexpr (MODEL >= 2) {
+        const FD<R> dh = debye_eval(r, rs.dhp);
+        R mult = R(1);
+        if (rs.half_ends) mult = (self.is_end ? R(0.5) : R(1)) * (meta_of(o0.w).is_end ? R(0.5) : R(1));
+        dVdr += rs.tw_dh * mult * dh.d;
+        if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
+      }
+      if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
+      axpy(gbk, dVdr / r, d);
+    }
+  };
+  // an entry of the far segment: only the backbone - backbone terms can act
+  auto far_entry = [&](const NbrState<R>& o) __attribute__((always_inline)) {
+    const V4& o0 = o.n0;
+    MD_RADSET_OF_ENTRY
+    const V3<R> dco = min_image(centre_diff<R>(o0, o.nl, self.c, self_lo), box);
+    backbone_term(rs, dco, xyz<R>(o.n3), o0);
+  };
+  // an entry of a stride that holds close entries.  in_close: the slot lies in the close segment, so any term may act and
+  // the entry may be flagged for the angular lists (flag[0] base-pair terms, flag[1] coaxial stacking); an entry of the
+  // far segment that shares the stride gets exactly the backbone terms of far_entry
+  auto close_entry = [&](int entry, const NbrState<R>& o, bool in_close, bool (&flag)[2]) __attribute__((always_inline)) {
+    const V4 &o0 = o.n0, &o1 = o.n1;
+    const bool role_p = (entry & ROW_ROLE_Q) == 0;
+    MD_RADSET_OF_ENTRY
+    const bool o_rna = (MODEL == 4) && meta_of(o0.w).rna;
+    const R gba_s = (MODEL == 4 && self.rna) ? Prna[GEO_BASE] : g_ba, gba_o = o_rna ? Prna[GEO_BASE] : g_ba;
+    const R gst_s = (MODEL == 4 && self.rna) ? Prna[GEO_STACK] : g_st, gst_o = o_rna ? Prna[GEO_STACK] : g_st;
+    (void)gst_s, (void)gst_o;
+    const V3<R> dco = min_image(centre_diff<R>(o0, o.nl, self.c, self_lo), box);
+    const V3<R> offb_o = xyz<R>(o.n3);
+    const bool close = in_close && dot(dco, dco) < cut.rcom2;
+    backbone_term(rs, dco, offb_o, o0);
+    if (close) {
+      const V3<R> a1o = xyz<R>(o1);
+      R en = R(0);
+      // self backbone - other base and self base - other backbone: which of the two is the reference's
+      // "back_p - base_q" / "base_p - back_q" depends on the role; the squared distances are routed by
+      // role so both parameter blocks stay scalar operands
+      {
+        V3<R> dA = dco - offb_s;
+        axpy(dA, gba_o, a1o);
+        V3<R> dB = dco + offb_o;
+        axpy(dB, -gba_s, self.a1);
+        const R ra2 = dot(dA, dA), rb2 = dot(dB, dB);
+        R c1, c2;
+        en += f3_coef(rs.eps_n, rs.tw_n, rs.f_bkba, role_p ? ra2 : rb2, c1);
+        en += f3_coef(rs.eps_n, rs.tw_n, rs.f_babk, role_p ? rb2 : ra2, c2);
+        axpy(gbk, role_p ? c1 : c2, dA);
+        axpy(gba, role_p ? c2 : c1, dB);
+      }
+      const V3<R> da = a1o - self.a1;
+      {
+        V3<R> d = dco;
+        if constexpr (MODEL == 4) {  // each nucleotide's base site at the offset of its own type
+          axpy(d, gba_o, a1o);
+          axpy(d, -gba_s, self.a1);
+        } else {
+          axpy(d, g_ba, da);
+        }
+        const R r2 = dot(d, d);
+        en += f3_radial(rs.eps_n, rs.tw_n, rs.f_base, d, r2, gba);
+        // (& and not &&, here and for flag[1]: written to a flag the caller owns, the short-circuit forms stayed branches -
+        // twelve instructions and a saved EXEC per entry in place of the parent's five; 12 kbp fp32 0.2 - 0.4 % slower)
+        flag[0] = (rs.cr_lo2 < r2) & (r2 < rs.cr_hi2);
+        if (!flag[0] & (rs.hb_lo2 < r2) & (r2 < rs.hb_hi2)) {  // H-bond only for pairs with a non-zero weight
+          const int so = meta_of(o0.w).seq;
+          if (PSEQ && (pseq.terms & 2) != 0)
+            flag[0] = rs.hb_mask != 0u;  // the weight is an expectation over both bases: any non-zero table entry may count
+          else
+            flag[0] = (rs.hb_mask >> (role_p ? (self.seq * 4 + so) : (so * 4 + self.seq))) & 1u;
+        }
+      }
+      {
+        V3<R> d = dco;
+        if constexpr (MODEL == 4) {
+          axpy(d, gst_o, a1o);
+          axpy(d, -gst_s, self.a1);
+        } else {
+          axpy(d, g_st, da);
+        }
+        const R r2 = dot(d, d);
+        flag[1] = (rs.cx_lo2 < r2) & (r2 < rs.cx_hi2);
+      }
+      if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
+    }
+  };
+  // append the flagged slots of this group to its two LDS lists, in slot order
+  auto append_flagged = [&](const bool (&flag)[2], int entry) __attribute__((always_inline)) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const unsigned long long bal = __ballot(flag[t]);
+      const unsigned int gm = (unsigned int)(bal >> gshift) & ((1u << G) - 1u);
+      if (flag[t]) {
+        const int pos = n_items[t] + __popc(gm & ((1u << lane) - 1u));
+        if (pos < ITEMS) items[t][grp][pos] = entry;  // (row_room <= ITEMS; an over-full nucleotide aborts the launch below)
+      }
+      n_items[t] += __popc(gm);
+    }
+  };
   // oxNA (MODEL 4) keeps the two separate pipelines - close segment, then far segment - it had before the single sweep:
   // with the sweep, hipcc's register allocation of md_step_kernel<double, 4, true, *, false, false, 8> parks the
   // kernel-argument tuple {flags, traj_c, traj_q, e_part} in spill lanes AFTER two later scalar loads have overwritten
@@ -541,180 +696,46 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   if constexpr (MODEL == 4 || GL != kMdG) {
     {
       int e_cur = -1, e_nxt = -1;
-      V4 n0{}, n3{}, n1{}, nl{};
+      NbrState<R> nb;
       {
         const int s = ROW_BONDED_SLOTS + lane;
         e_cur = row_at(s, close_end);
         e_nxt = row_at(s + G, close_end);
-        const int j = slot_of_entry(e_cur);
-        n0 = in.p0[j];
-        n3 = in.p3[j];
-        n1 = in.p1[j];
-        if constexpr (kHiLo<R>) nl = in.pl[j];
+        nb.fetch(in, slot_of_entry(e_cur), true);
       }
 #pragma unroll 1
       for (int s0 = ROW_BONDED_SLOTS; s0 < close_end; s0 += G) {
         const int s = s0 + lane;
         const int entry = e_cur;
-        const V4 o0 = n0, o3 = n3, o1 = n1, ol = nl;
+        const V4 o0 = nb.n0, o3 = nb.n3, o1 = nb.n1, ol = nb.nl;
         e_cur = e_nxt;
         e_nxt = row_at(s + 2 * G, close_end);
-        {  // the close segment reads a1 as well: nearly all of its entries need it
-          const int jn = slot_of_entry(e_cur);
-          n0 = in.p0[jn];
-          n3 = in.p3[jn];
-          n1 = in.p1[jn];
-          if constexpr (kHiLo<R>) nl = in.pl[jn];
-        }
+        nb.fetch(in, slot_of_entry(e_cur), true);  // the close segment reads a1 as well: nearly all of its entries need it
         bool flag[2] = {false, false};
-        if (entry >= 0) {
-          const bool role_p = (entry & ROW_ROLE_Q) == 0;
-          MD_RADSET_OF_ENTRY
-          const bool o_rna = (MODEL == 4) && ((((int)o0.w) >> 3) & 1);
-          const R gba_s = (MODEL == 4 && self.rna) ? Prna[GEO_BASE] : g_ba, gba_o = o_rna ? Prna[GEO_BASE] : g_ba;
-          const R gst_s = (MODEL == 4 && self.rna) ? Prna[GEO_STACK] : g_st, gst_o = o_rna ? Prna[GEO_STACK] : g_st;
-          (void)gst_s, (void)gst_o;
-          const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
-          const V3<R> offb_o = xyz<R>(o3);
-          const bool close = dot(dco, dco) < cut.rcom2;
-          // backbone - backbone: excluded volume + Debye-Hueckel
-          {
-            const V3<R> d = dco + offb_o - offb_s;
-            const R r2 = dot(d, d);
-            if (r2 < rs.rbb2) {
-              const R r = m_sqrt(r2);
-              const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
-              R dVdr = rs.tw_n * v.d;
-              R en = v.f;
-              if constexpr (MODEL >= 2) {
-                const FD<R> dh = debye_eval(r, rs.dhp);
-                R mult = R(1);
-                if (rs.half_ends) {
-                  const int mo = (int)o0.w;
-                  mult = (self.is_end ? R(0.5) : R(1)) * (((mo >> 2) & 1) ? R(0.5) : R(1));
-                }
-                dVdr += rs.tw_dh * mult * dh.d;
-                if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
-              }
-              if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
-              axpy(gbk, dVdr / r, d);
-            }
-          }
-          if (close) {
-            const V3<R> a1o = xyz<R>(o1);
-            R en = R(0);
-            // self backbone - other base and self base - other backbone: which of the two is the reference's
-            // "back_p - base_q" / "base_p - back_q" depends on the role; the squared distances are routed by
-            // role so both parameter blocks stay scalar operands
-            {
-              V3<R> dA = dco - offb_s;
-              axpy(dA, gba_o, a1o);
-              V3<R> dB = dco + offb_o;
-              axpy(dB, -gba_s, self.a1);
-              const R ra2 = dot(dA, dA), rb2 = dot(dB, dB);
-              R c1, c2;
-              en += f3_coef(rs.eps_n, rs.tw_n, rs.f_bkba, role_p ? ra2 : rb2, c1);
-              en += f3_coef(rs.eps_n, rs.tw_n, rs.f_babk, role_p ? rb2 : ra2, c2);
-              axpy(gbk, role_p ? c1 : c2, dA);
-              axpy(gba, role_p ? c2 : c1, dB);
-            }
-            const V3<R> da = a1o - self.a1;
-            {
-              V3<R> d = dco;
-              if constexpr (MODEL == 4) {  // each nucleotide's base site at the offset of its own type
-                axpy(d, gba_o, a1o);
-                axpy(d, -gba_s, self.a1);
-              } else {
-                axpy(d, g_ba, da);
-              }
-              const R r2 = dot(d, d);
-              en += f3_radial(rs.eps_n, rs.tw_n, rs.f_base, d, r2, gba);
-              flag[0] = rs.cr_lo2 < r2 && r2 < rs.cr_hi2;
-              if (!flag[0] && rs.hb_lo2 < r2 && r2 < rs.hb_hi2) {  // H-bond only for pairs with a non-zero weight
-                const int so = (int)o0.w & 3;
-                if (PSEQ && (pseq.terms & 2) != 0)
-                  flag[0] = rs.hb_mask != 0u;  // the weight is an expectation over both bases: any non-zero table entry may count
-                else
-                  flag[0] = (rs.hb_mask >> (role_p ? (self.seq * 4 + so) : (so * 4 + self.seq))) & 1u;
-              }
-            }
-            {
-              V3<R> d = dco;
-              if constexpr (MODEL == 4) {
-                axpy(d, gst_o, a1o);
-                axpy(d, -gst_s, self.a1);
-              } else {
-                axpy(d, g_st, da);
-              }
-              const R r2 = dot(d, d);
-              flag[1] = rs.cx_lo2 < r2 && r2 < rs.cx_hi2;
-            }
-            if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
-          }
-        }
-        // append the flagged slots of this group to its two LDS lists, in slot order
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const unsigned long long bal = __ballot(flag[t]);
-          const unsigned int gm = (unsigned int)(bal >> gshift) & ((1u << G) - 1u);
-          if (flag[t]) {
-            const int pos = n_items[t] + __popc(gm & ((1u << lane) - 1u));
-            if (pos < ITEMS) items[t][grp][pos] = entry;  // (row_room <= ITEMS; an over-full nucleotide aborts the launch below)
-          }
-          n_items[t] += __popc(gm);
-        }
+        if (entry >= 0) close_entry(entry, NbrState<R>{o0, o3, o1, ol}, true, flag);
+        append_flagged(flag, entry);
       }
     }
     // far segment: only the backbone-backbone terms (excluded volume + Debye-Hueckel) can act
     MD_PRIO(1);
     {
       int e_cur = -1, e_nxt = -1;
-      V4 n0{}, n3{}, nl{};
+      NbrState<R> nb;
       {
         const int s = close_end + lane;
         e_cur = row_at(s, len);
         e_nxt = row_at(s + G, len);
-        const int j = slot_of_entry(e_cur);
-        n0 = in.p0[j];
-        n3 = in.p3[j];
-        if constexpr (kHiLo<R>) nl = in.pl[j];
+        nb.fetch(in, slot_of_entry(e_cur), false);
       }
 #pragma unroll 1
       for (int s0 = close_end; s0 < len; s0 += G) {
         const int s = s0 + lane;
         const int entry = e_cur;
-        const V4 o0 = n0, o3 = n3, ol = nl;
+        const V4 o0 = nb.n0, o3 = nb.n3, o1 = nb.n1, ol = nb.nl;
         e_cur = e_nxt;
         e_nxt = row_at(s + 2 * G, len);
-        {
-          const int jn = slot_of_entry(e_cur);
-          n0 = in.p0[jn];
-          n3 = in.p3[jn];
-          if constexpr (kHiLo<R>) nl = in.pl[jn];
-        }
-        if (entry >= 0) {
-          MD_RADSET_OF_ENTRY
-          const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
-          const V3<R> d = dco + xyz<R>(o3) - offb_s;
-          const R r2 = dot(d, d);
-          if (r2 < rs.rbb2) {
-            const R r = m_sqrt(r2);
-            const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
-            R dVdr = rs.tw_n * v.d;
-            if constexpr (MODEL >= 2) {
-              const FD<R> dh = debye_eval(r, rs.dhp);
-              R mult = R(1);
-              if (rs.half_ends) {
-                const int mo = (int)o0.w;
-                mult = (self.is_end ? R(0.5) : R(1)) * (((mo >> 2) & 1) ? R(0.5) : R(1));
-              }
-              dVdr += rs.tw_dh * mult * dh.d;
-              if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
-            }
-            if constexpr (SAVE) e[T_NEXC] += R(0.5) * v.f;
-            axpy(gbk, dVdr / r, d);
-          }
-        }
+        nb.fetch(in, slot_of_entry(e_cur), false);
+        if (entry >= 0) far_entry(NbrState<R>{o0, o3, o1, ol});
       }
     }
   } else {
@@ -722,7 +743,7 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
       // (e_nxt is the word as it was read: whether the lane has an entry there is decided from the slot when the word moves
       // up to e_cur, an iteration later - a select right behind the conditional load would wait for it on the spot)
       int e_cur = -1, e_nxt = -1;
-      V4 n0{}, n3{}, n1{}, nl{};
+      NbrState<R> nb;
       // the longest row and the longest close segment of the wavefront, as scalars: the lanes of a group hold the same two
       // numbers, so one lane per group is read.  "Some lane has an entry in the stride at s0" is then s0 < wlen and "some
       // lane's slot there is in its close segment" s0 < wclose - scalar loop control and no mask to carry.  (The same
@@ -739,150 +760,26 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
         const int s = s0 + lane;
         e_cur = row_at(s, len);
         if (s0 + G < wlen) e_nxt = row_word(s + G);
-        const int j = slot_of_entry(e_cur);
-        n0 = in.p0[j];
-        n3 = in.p3[j];
-        if (s0 < wclose) n1 = in.p1[j];
-        if constexpr (kHiLo<R>) nl = in.pl[j];
+        nb.fetch(in, slot_of_entry(e_cur), s0 < wclose);
       }
 #pragma unroll 1
       for (; s0 < wlen; s0 += G) {
         const int s = s0 + lane;
         const int entry = e_cur;
-        const V4 o0 = n0, o3 = n3, o1 = n1, ol = nl;
+        const V4 o0 = nb.n0, o3 = nb.n3, o1 = nb.n1, ol = nb.nl;
         e_cur = s + G < len ? e_nxt : -1;
         if (s0 + G < wlen) {
           if (s0 + 2 * G < wlen) e_nxt = row_word(s + 2 * G);
-          const int jn = slot_of_entry(e_cur);
-          n0 = in.p0[jn];
-          n3 = in.p3[jn];
-          if (s0 + G < wclose) n1 = in.p1[jn];  // the close segment reads a1 as well: nearly all of its entries need it
-          if constexpr (kHiLo<R>) nl = in.pl[jn];
+          nb.fetch(in, slot_of_entry(e_cur), s0 + G < wclose);  // the close segment reads a1 as well: nearly all of its entries need it
         }
         if (s0 < wclose) {
           bool flag[2] = {false, false};
-          if (entry >= 0) {
-            const bool role_p = (entry & ROW_ROLE_Q) == 0;
-            MD_RADSET_OF_ENTRY
-            const bool o_rna = (MODEL == 4) && ((((int)o0.w) >> 3) & 1);
-            const R gba_s = (MODEL == 4 && self.rna) ? Prna[GEO_BASE] : g_ba, gba_o = o_rna ? Prna[GEO_BASE] : g_ba;
-            const R gst_s = (MODEL == 4 && self.rna) ? Prna[GEO_STACK] : g_st, gst_o = o_rna ? Prna[GEO_STACK] : g_st;
-            (void)gst_s, (void)gst_o;
-            const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
-            const V3<R> offb_o = xyz<R>(o3);
-            const bool close = s < close_end && dot(dco, dco) < cut.rcom2;  // (a far entry in a mixed stride: backbone terms only)
-            // backbone - backbone: excluded volume + Debye-Hueckel
-            {
-              const V3<R> d = dco + offb_o - offb_s;
-              const R r2 = dot(d, d);
-              if (r2 < rs.rbb2) {
-                const R r = m_sqrt(r2);
-                const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
-                R dVdr = rs.tw_n * v.d;
-                R en = v.f;
-                if constexpr (MODEL >= 2) {
-                  const FD<R> dh = debye_eval(r, rs.dhp);
-                  R mult = R(1);
-                  if (rs.half_ends) {
-                    const int mo = (int)o0.w;
-                    mult = (self.is_end ? R(0.5) : R(1)) * (((mo >> 2) & 1) ? R(0.5) : R(1));
-                  }
-                  dVdr += rs.tw_dh * mult * dh.d;
-                  if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
-                }
-                if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
-                axpy(gbk, dVdr / r, d);
-              }
-            }
-            if (close) {
-              const V3<R> a1o = xyz<R>(o1);
-              R en = R(0);
-              // self backbone - other base and self base - other backbone: which of the two is the reference's
-              // "back_p - base_q" / "base_p - back_q" depends on the role; the squared distances are routed by
-              // role so both parameter blocks stay scalar operands
-              {
-                V3<R> dA = dco - offb_s;
-                axpy(dA, gba_o, a1o);
-                V3<R> dB = dco + offb_o;
-                axpy(dB, -gba_s, self.a1);
-                const R ra2 = dot(dA, dA), rb2 = dot(dB, dB);
-                R c1, c2;
-                en += f3_coef(rs.eps_n, rs.tw_n, rs.f_bkba, role_p ? ra2 : rb2, c1);
-                en += f3_coef(rs.eps_n, rs.tw_n, rs.f_babk, role_p ? rb2 : ra2, c2);
-                axpy(gbk, role_p ? c1 : c2, dA);
-                axpy(gba, role_p ? c2 : c1, dB);
-              }
-              const V3<R> da = a1o - self.a1;
-              {
-                V3<R> d = dco;
-                if constexpr (MODEL == 4) {  // each nucleotide's base site at the offset of its own type
-                  axpy(d, gba_o, a1o);
-                  axpy(d, -gba_s, self.a1);
-                } else {
-                  axpy(d, g_ba, da);
-                }
-                const R r2 = dot(d, d);
-                en += f3_radial(rs.eps_n, rs.tw_n, rs.f_base, d, r2, gba);
-                flag[0] = rs.cr_lo2 < r2 && r2 < rs.cr_hi2;
-                if (!flag[0] && rs.hb_lo2 < r2 && r2 < rs.hb_hi2) {  // H-bond only for pairs with a non-zero weight
-                  const int so = (int)o0.w & 3;
-                  if (PSEQ && (pseq.terms & 2) != 0)
-                    flag[0] = rs.hb_mask != 0u;  // the weight is an expectation over both bases: any non-zero table entry may count
-                  else
-                    flag[0] = (rs.hb_mask >> (role_p ? (self.seq * 4 + so) : (so * 4 + self.seq))) & 1u;
-                }
-              }
-              {
-                V3<R> d = dco;
-                if constexpr (MODEL == 4) {
-                  axpy(d, gst_o, a1o);
-                  axpy(d, -gst_s, self.a1);
-                } else {
-                  axpy(d, g_st, da);
-                }
-                const R r2 = dot(d, d);
-                flag[1] = rs.cx_lo2 < r2 && r2 < rs.cx_hi2;
-              }
-              if constexpr (SAVE) e[T_NEXC] += R(0.5) * en;
-            }
-          }
-          // append the flagged slots of this group to its two LDS lists, in slot order
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            const unsigned long long bal = __ballot(flag[t]);
-            const unsigned int gm = (unsigned int)(bal >> gshift) & ((1u << G) - 1u);
-            if (flag[t]) {
-              const int pos = n_items[t] + __popc(gm & ((1u << lane) - 1u));
-              if (pos < ITEMS) items[t][grp][pos] = entry;  // (row_room <= ITEMS; an over-full nucleotide aborts the launch below)
-            }
-            n_items[t] += __popc(gm);
-          }
+          if (entry >= 0) close_entry(entry, NbrState<R>{o0, o3, o1, ol}, s < close_end, flag);  // (a far entry in a mixed stride: backbone terms only)
+          append_flagged(flag, entry);
         } else {
           // all-far stride: only the backbone-backbone terms (excluded volume + Debye-Hueckel) can act
           MD_PRIO(1);
-          if (entry >= 0) {
-            MD_RADSET_OF_ENTRY
-            const V3<R> dco = min_image(centre_diff<R>(o0, ol, self.c, self_lo), box);
-            const V3<R> d = dco + xyz<R>(o3) - offb_s;
-            const R r2 = dot(d, d);
-            if (r2 < rs.rbb2) {
-              const R r = m_sqrt(r2);
-              const FD<R> v = f3_eval(r, rs.eps_n, rs.f_bb);
-              R dVdr = rs.tw_n * v.d;
-              if constexpr (MODEL >= 2) {
-                const FD<R> dh = debye_eval(r, rs.dhp);
-                R mult = R(1);
-                if (rs.half_ends) {
-                  const int mo = (int)o0.w;
-                  mult = (self.is_end ? R(0.5) : R(1)) * (((mo >> 2) & 1) ? R(0.5) : R(1));
-                }
-                dVdr += rs.tw_dh * mult * dh.d;
-                if constexpr (SAVE) e[T_DH] += R(0.5) * mult * dh.f;
-              }
-              if constexpr (SAVE) e[T_NEXC] += R(0.5) * v.f;
-              axpy(gbk, dVdr / r, d);
-            }
-          }
+          if (entry >= 0) far_entry(NbrState<R>{o0, o3, o1, ol});
         }
       }
     }
@@ -992,16 +889,9 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
       if (entry >= 0) {
         const int j = entry & ROW_INDEX_MASK;
         const bool role_p = bonded_wave ? ((sl & 1) == 1) : ((entry & ROW_ROLE_Q) == 0);
-        Nuc<R> me, o;
         const R* ms = self_lds[p];
-        me.c = V3<R>{ms[0], ms[1], ms[2]};
-        me.a1 = V3<R>{ms[3], ms[4], ms[5]};
-        me.a3 = V3<R>{ms[6], ms[7], ms[8]};
-        me.a2 = cross(me.a3, me.a1);
-        const int mm = (int)ms[9];
-        me.seq = mm & 3;
-        me.is_end = (mm >> 2) & 1;
-        me.rna = (mm >> 3) & 1;
+        Nuc<R> me = nuc_from_lds(ms), o;
+        set_meta(me, ms[9]);
         me.idx = ip, o.idx = j;  // (read only by the expectation of a probabilistic sequence)
         const V4 o0 = in.p0[j], o1 = in.p1[j], o2 = in.p2[j];
         V4 ol{};
@@ -1010,10 +900,7 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
         o.a1 = xyz<R>(o1);
         o.a3 = xyz<R>(o2);
         o.a2 = cross(o.a3, o.a1);
-        const int mo = (int)o0.w;
-        o.seq = mo & 3;
-        o.is_end = (mo >> 2) & 1;
-        o.rna = (mo >> 3) & 1;
+        set_meta(o, o0.w);
         const V3<R> dco = min_image(centre_diff<R>(o0, ol, me.c, V3<R>{ms[10], ms[11], ms[12]}), box);
         // (oxNA: the pair templates pick vector, form and sites by the kind of the pair from the three vectors)
         const auto& PP = [&]() -> const auto& {
@@ -1116,11 +1003,7 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   // four gradients: the conversion (three cross products, three projections) is done here, by 32 lanes of four
   // wavefronts at once, instead of at the head of the integrating wavefront's stream behind the last barrier.
   if (lane == 0) {
-    Nuc<R> own;
-    const R* ms = self_lds[grp];
-    own.a1 = V3<R>{ms[3], ms[4], ms[5]};
-    own.a3 = V3<R>{ms[6], ms[7], ms[8]};
-    own.a2 = cross(own.a3, own.a1);
+    const Nuc<R> own = nuc_from_lds(self_lds[grp]);  // (the axes are read; the loads of the centre and the meta word are dropped)
     const V3<R> tl = axes_grad_to_torque(own, sg);
     R* fr = kPooled ? pool_row(pool_ok ? rb : grp * 2) : fixed_row(grp, 0);  // (pool exhausted: the launch does not count; any free row will do)
     fr[0] = -sg.dc.x, fr[1] = -sg.dc.y, fr[2] = -sg.dc.z;
@@ -1131,19 +1014,12 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   double ke_t = 0.0, ke_r = 0.0;
   if (integrates) {
     const int i = i_int;
-    Nuc<R> self;
-    {
-      const R* ms = self_lds[il];
-      self.c = V3<R>{ms[0], ms[1], ms[2]};
-      self.a1 = V3<R>{ms[3], ms[4], ms[5]};
-      self.a3 = V3<R>{ms[6], ms[7], ms[8]};
-      self.a2 = cross(self.a3, self.a1);
-    }
+    const Nuc<R> self = nuc_from_lds(self_lds[il]);
     // force and body torque of this nucleotide, as the fold left them
     const R* fr = kPooled ? pool_row(row_base[fw][PPB] <= kPool ? row_base[fw][il] : il * 2) : fixed_row(il, 0);
     const V3<R> F{fr[0], fr[1], fr[2]};
     const R tb[3] = {fr[3], fr[4], fr[5]};
-    const bool int_rna = (MODEL == 4) && ((((int)self_lds[il][9]) >> 3) & 1);  // oxNA: this nucleotide's own geometry
+    const bool int_rna = (MODEL == 4) && meta_of(self_lds[il][9]).rna;  // oxNA: this nucleotide's own geometry
     const R g_k1 = int_rna ? Prna[GEO_BACK_A1] : P[GEO_BACK_A1];
     const R g_k2 = (MODEL >= 2) ? (int_rna ? Prna[GEO_BACK_A2] : P[GEO_BACK_A2]) : R(0);
     R p[3] = {pm.x, pm.y, pm.z}, L[3] = {lm.x, lm.y, lm.z};

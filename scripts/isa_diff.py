@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """dev: is the device code of two builds of libmythos_hip.so the same?  The gate of a refactor that moves device text.
 
-usage: isa_diff.py parent.so branch.so      exit code 0: identical, 1: something differs (listed)
+usage: isa_diff.py [--table] parent.so branch.so      exit code 0: identical, 1: something differs (listed)
+       --table: first a markdown table of the kernels that differ - registers, scratch, instruction counts of both
 
 Compared PER CODE OBJECT (one per translation unit, in link order), not per library: an fp64 kernel that leaked into the
 fp32 unit would hide behind an identical name in a per-library comparison.  For every function symbol of a code object:
@@ -83,11 +84,38 @@ def describe(lib):
     return objs
 
 
+def table(a, b):
+    """The kernels whose text or metadata differ, one markdown row each (first library -> second), and how many of them
+    break what a refactor may not: LDS bytes and kernarg size equal, scratch bytes not above the first library's."""
+    names = [n for (fa, _), (fb, _) in zip(a, b) for n in sorted(set(fa) & set(fb))]
+    short = dict(zip(names, subprocess.run(["c++filt"], input="\n".join(names), check=True, capture_output=True, text=True).stdout.split("\n")))
+    print("| kernel | VGPR | SGPR | scratch B | instructions | LDS, kernarg |\n|---|---|---|---|---|---|")
+    broken = 0
+    for k, ((fa, ma), (fb, mb)) in enumerate(zip(a, b)):
+        for name in sorted(set(fa) & set(fb)):
+            if fa[name] == fb[name] and ma.get(name) == mb.get(name):
+                continue
+            pa, pb = ma.get(name, {}), mb.get(name, {})
+            ok = pa.get("lds") == pb.get("lds") and pa.get("kernarg") == pb.get("kernarg") and pb.get("scratch", 0) <= pa.get("scratch", 0)
+            broken += not ok
+            cell = lambda key: f"{pa.get(key)} -> {pb.get(key)}" if pa.get(key) != pb.get(key) else f"{pa.get(key)}"
+            label = short[name].split("(")[0].replace("void mythos::", "")
+            print(f"| `{label}` | {cell('vgpr')} | {cell('sgpr')} | {cell('scratch')} | {fa[name][1]} -> {fb[name][1]} | "
+                  f"{cell('lds')}, {cell('kernarg')}{'' if ok else ' **not allowed**'} |")
+    return broken
+
+
 def main():
+    want_table = "--table" in sys.argv
+    if want_table:
+        sys.argv.remove("--table")
     if len(sys.argv) != 3:
         print(__doc__)
         return 2
     a, b = describe(sys.argv[1]), describe(sys.argv[2])
+    if want_table and len(a) == len(b):
+        broken = table(a, b)
+        print(f"\n{broken} kernel(s) with more scratch, other LDS bytes or another kernarg size")
     bad = 0
     if len(a) != len(b):
         print(f"code objects: {len(a)} against {len(b)}")
