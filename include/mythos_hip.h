@@ -453,6 +453,59 @@ int mythos_langevin_last_recoveries(const mythos_sim_t* sim, int* recoveries);
  * list and the out-of-turn ones above are not counted.  bench.py reports it next to the timed region. */
 int mythos_langevin_last_rebuilds(const mythos_sim_t* sim, int* scheduled);
 
+/* ---- umbrella sampling on the resident Langevin state ---------------------------------------------
+ * Replaces the external oxDNA run behind the reference's oxDNAUmbrellaSampler (mythos/simulators/oxdna/oxdna.py:225-275)
+ * and the order-parameter and weight columns it reads back (mythos/simulators/oxdna/utils.py:348-429) for the `bond` and
+ * `mindistance` order parameters of mythos_oxdna_order_params, per replica of a batched free-space system (replica r
+ * owns the nucleotides [r n / n_rep, (r + 1) n / n_rep)) or for one periodic system (n_rep = 1).
+ * Method: segment-Metropolis on the integrator.  A segment is segment_steps ordinary steps from a closed frame (x, p),
+ * closed again by the launch mythos_langevin_store uses; the replica's proposal (x', p') has order-parameter state s' and
+ * is accepted iff W(s') > 0 and u W(s) < W(s'), s the state it holds; a rejected replica goes back to (x, -p) - linear and
+ * body-frame angular momenta negated.  The Langevin map is reversible with respect to the Boltzmann density under
+ * momentum reversal up to the integrator's O(dt^2) error, so the chain leaves pi(x, p) W(Q(x)) invariant.  Weights and the
+ * decision are double in both precisions; u = (c[0] + 0.5) 2^-32 from Philox4x32-10 with the integrator's seed as key and
+ * the counter {replica, step lo, step hi, 4}, step the absolute step count at the boundary.  The neighbour rows are
+ * rebuilt at the start of every segment exactly as after mythos_langevin_load (the closed frame passes through the
+ * kernels of store and load), so a run does not depend on which replicas were rejected, and with a flat table it is bit
+ * for bit the loop load; advance(segment_steps); store.
+ *   op_kind, op_first, pairs  as mythos_oxdna_order_params; pairs name nucleotides of ONE replica, [0, n / n_rep)
+ *   iface_first   host int32[n_ops + 1]: a mindistance parameter k owns interfaces[iface_first[k] .. iface_first[k + 1]), its
+ *                 state is the number of them the distance exceeds (strictly); a bond parameter owns none, its state is
+ *                 the count
+ *   table_shape   host int32[n_ops]; table host double[prod(table_shape)], dense and row-major, one axis per order
+ *                 parameter, every weight finite and >= 0 (a missing row is weight 0).  An axis holds every reachable
+ *                 state: slice length + 1 for bond, interfaces + 1 for mindistance; a shorter one is refused
+ * mythos_umbrella_check: the checks alone, for a system of n nucleotides of `model` whose backbone neighbours inside one
+ * replica are bonded[n_bonded][2] (a listed pair must not be one).  Touches no device.
+ * mythos_langevin_set_umbrella: n_ops = 0 clears the bias; with none set every other call issues exactly the launches it
+ * issued before.  Refused (MYTHOS_ERR_INVALID_ARGUMENT, by name) while the resident frame is open, for moving point forces
+ * (rate != 0: the force depends on the step count, which breaks reversibility), the unfused oxNA path, model 4 and a
+ * probabilistic sequence - advance_umbrella refuses the same should they appear later.
+ * mythos_langevin_advance_umbrella: n_segments segments on the resident state (an open frame is closed first).  The first
+ * call after a load or a set_umbrella primes: the resident state becomes every replica's snapshot, and a replica whose
+ * state has weight 0 is an error naming it.  So does the first call after anything else that moved the state or its
+ * weights away from the snapshot: unbiased steps (mythos_langevin_advance with n_steps > 0, mythos_langevin_run, which
+ * loads) and new parameters (mythos_oxdna_set_params) - the chain starts again from the state as it stands, and no
+ * rejection reaches back across them.  One stream synchronisation per segment.  All outputs are device arrays,
+ * any may be NULL:
+ *   traj_center, traj_quat  real[n_segments / sample_every][n][3 | 4]: the state after the decision of boundaries
+ *                           sample_every, 2 sample_every, ... (sample_every = 0: none); quaternion rows aligned to 4 elements
+ *   prop_center, prop_quat  the same rows of the proposals, before the decision
+ *   record        double[n_segments][n_rep][3 n_ops + 4]: the proposal's values (as mythos_oxdna_order_params returns
+ *                 them for the proposal row, bit for bit), its states, W_old, W_new, u, accept (0 / 1), then the states
+ *                 the replica holds after the decision (the sample row's)
+ * advance_umbrella(a) then (b) continues bit for bit like one call of a + b segments.
+ * mythos_langevin_umbrella_counts: decisions accepted and taken since set_umbrella (the priming boundary is not one). */
+int mythos_umbrella_check(int n, int n_rep, int model, int n_bonded, const int32_t* bonded, int n_ops, const int32_t* op_kind,
+                          const int32_t* op_first, const int32_t* pairs, int n_pairs, const int32_t* iface_first,
+                          const double* interfaces, const int32_t* table_shape, const double* table, int segment_steps);
+int mythos_langevin_set_umbrella(mythos_sim_t* sim, int n_rep, int n_ops, const int32_t* op_kind, const int32_t* op_first,
+                                 const int32_t* pairs, int n_pairs, const int32_t* iface_first, const double* interfaces,
+                                 const int32_t* table_shape, const double* table, double hb_cutoff, int segment_steps);
+int mythos_langevin_advance_umbrella(mythos_sim_t* sim, int n_segments, int sample_every, void* traj_center, void* traj_quat,
+                                     void* prop_center, void* prop_quat, double* record, mythos_stream_t stream);
+int mythos_langevin_umbrella_counts(mythos_sim_t* sim, int64_t* accepted, int64_t* decided);
+
 /* ---- oxDNA text trajectories (host only) -----------------------------------------------------
  * Replaces the Python parse of mythos/input/trajectory.py:192-320 (frames of `t = / b = / E =` header lines and
  * n rows of 15 numbers: com, a1, a3, v, L).  Call once with frames == NULL to count (n_frames out), then with

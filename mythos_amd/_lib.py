@@ -78,6 +78,12 @@ _SIGS = {
     "mythos_martini_langevin_set_timing": (C.c_int, [V, C.c_int]),
     "mythos_langevin_last_recoveries": (C.c_int, [V, C.POINTER(C.c_int)]),
     "mythos_langevin_last_rebuilds": (C.c_int, [V, C.POINTER(C.c_int)]),
+    "mythos_umbrella_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, c_int_p,
+                                        c_double_p, c_int_p, c_double_p, C.c_int]),
+    "mythos_langevin_set_umbrella": (C.c_int, [V, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, c_int_p, c_double_p, c_int_p,
+                                               c_double_p, C.c_double, C.c_int]),
+    "mythos_langevin_advance_umbrella": (C.c_int, [V, C.c_int, C.c_int, V, V, V, V, V, V]),
+    "mythos_langevin_umbrella_counts": (C.c_int, [V, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mythos_oxdna_read_trajectory": (C.c_int, [C.c_char_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]),
     "mythos_oxdna_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int]),
     "mythos_martini_create": (

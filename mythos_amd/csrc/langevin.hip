@@ -155,6 +155,8 @@ int md_ready(mythos_sim_t* s, const char* who) {
 
 int md_load(mythos_sim_t* s, void* c, void* q, void* p, void* l, hipStream_t st) {
   s->unfused.active = s->unfused.want && s->sys->model == 4;
+  s->umb.primed = false;  // (another state: the snapshot and the weights held are not its)
+  s->umb.frame_loaded = true;
   return md_entries_of(s).load(s, c, q, p, l, st);
 }
 
@@ -175,6 +177,7 @@ int md_advance(mythos_sim_t* s, int n_steps, int save_every, bool close, void* t
     set_error("mythos_langevin_run / advance: traj_quat must be aligned to 4 elements (" + std::to_string(q_align) + " bytes)");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
+  s->umb.frame_loaded = false;
   return md_entries_of(s).advance(s, n_steps, save_every, close, tc, tq, e_trace, st);
 }
 
@@ -222,6 +225,7 @@ int mythos_langevin_advance(mythos_sim_t* s, int n_steps, int save_every, void* 
     return MYTHOS_ERR_NOT_READY;
   }
   if (int rc = md_ready(s, "mythos_langevin_advance")) return rc;
+  if (n_steps > 0) s->umb.primed = false;  // (unbiased steps: the snapshot and the weights held are no longer this state's)
   return md_advance(s, n_steps, save_every, false, traj_center, traj_quat, e_trace, (hipStream_t)stream);
 }
 
@@ -425,6 +429,11 @@ int mythos_langevin_set_point_forces(mythos_sim_t* s, int n_terms, const int32_t
   v.n_entries = v.n_points = 0;  // (nothing half replaced counts)
   v.pt_first = v.pt_kind = v.pt_particle = v.pt_ref = v.pt_flags = nullptr, v.pt_param = nullptr;
   s->h_pt_particle.clear();
+  s->pt_moving = false;
+  for (int t = 0; t < n_terms; ++t) {
+    const int at = point_force_rate_at(kind[t]);
+    if (at >= 0 && param[(size_t)t * kPointForceParams + at] != 0.0) s->pt_moving = true;
+  }
   if (n_terms == 0) return ext_entries_merge(s);
   // by nucleotide, and within one in the order given: the order the kick adds in
   std::vector<int> order((size_t)n_terms);
@@ -512,5 +521,191 @@ int mythos_langevin_set_option(mythos_sim_t* s, int option, int64_t value) {
 }
 
 int mythos_langevin_set_timing(mythos_sim_t* s, int samples) { return md_set_timing(s, samples, "mythos_langevin_set_timing"); }
+
+// ---- umbrella sampling (umbrella.h; mythos/simulators/oxdna/oxdna.py:225-275, utils.py:348-429)
+namespace {
+// what neither set_umbrella nor advance_umbrella steps with, by name
+int umbrella_refusals(const mythos_sim* s, const std::string& who) {
+  auto refuse = [&](const std::string& why) {
+    set_error(who + ": " + why);
+    return (int)MYTHOS_ERR_INVALID_ARGUMENT;
+  };
+  if (s->sys->model == 4)
+    return refuse("an oxNA system (model 4) has three hydrogen-bonding parameter sets and two site geometries; the order "
+                  "parameters are built for oxDNA1, oxDNA2 and oxRNA2");
+  if (s->unfused.want || s->unfused.active) return refuse("the unfused oxNA path (MYTHOS_LANGEVIN_UNFUSED) is not sampled under a bias");
+  if (s->sys->pseq_terms != 0)
+    return refuse("the system carries a probabilistic sequence (mythos_oxdna_set_pseq): an expected hydrogen-bonding energy "
+                  "below the cutoff is not oxDNA's order parameter");
+  if (s->pt_moving)
+    return refuse("a point force moves (rate != 0): its force depends on the step count, which breaks the reversibility the "
+                  "acceptance rule rests on; clear it (mythos_langevin_set_point_forces) or give it rate = 0");
+  return MYTHOS_OK;
+}
+}  // namespace
+
+int mythos_langevin_set_umbrella(mythos_sim_t* s, int n_rep, int n_ops, const int32_t* op_kind, const int32_t* op_first, const int32_t* pairs,
+                                 int n_pairs, const int32_t* iface_first, const double* interfaces, const int32_t* table_shape,
+                                 const double* table, double hb_cutoff, int segment_steps) {
+  const std::string who = "mythos_langevin_set_umbrella";
+  auto refuse = [&](const std::string& why) {
+    set_error(who + ": " + why);
+    return (int)MYTHOS_ERR_INVALID_ARGUMENT;
+  };
+  if (!s || n_ops < 0) return refuse("invalid argument");
+  if (s->resident && s->open)
+    return refuse("the resident frame is open (a segment starts from a closed frame); call mythos_langevin_store first");
+  UmbrellaState& u = s->umb;
+  if (n_ops == 0) {  // no bias: every other call issues the launches it issued before one was set
+    u.n_ops = 0;
+    u.primed = false;
+    return MYTHOS_OK;
+  }
+  if (int rc = umbrella_refusals(s, who)) return rc;
+  if (!std::isfinite(hb_cutoff)) return refuse("hb_cutoff is not finite");
+  if (n_rep < 1) return refuse("invalid argument");
+  const mythos_system* sys = s->sys;
+  const int n = sys->n, n_one = n / n_rep;
+  std::vector<int32_t> bonded;  // the backbone neighbours inside the first replica
+  for (int i = 0; i < n_one; ++i)
+    for (int k = 0; k < ROW_BONDED_SLOTS; ++k) {
+      const int j = sys->h_partners[(size_t)ROW_BONDED_SLOTS * i + k];
+      if (j > i && j < n_one) bonded.push_back(i), bonded.push_back(j);
+    }
+  if (!umbrella_valid(who, n, n_rep, sys->model, (int)(bonded.size() / 2), bonded.data(), n_ops, op_kind, op_first, pairs, n_pairs,
+                      iface_first, interfaces, table_shape, table, segment_steps))
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  std::vector<int> list;
+  for (int k = 0; k < n_pairs; ++k) list.push_back(std::min(pairs[2 * k], pairs[2 * k + 1])), list.push_back(std::max(pairs[2 * k], pairs[2 * k + 1]));
+  list.insert(list.end(), op_first, op_first + n_ops + 1);
+  list.insert(list.end(), op_kind, op_kind + n_ops);
+  list.insert(list.end(), iface_first, iface_first + n_ops + 1);
+  list.insert(list.end(), table_shape, table_shape + n_ops);
+  size_t cells = 1;
+  for (int k = 0; k < n_ops; ++k) cells *= (size_t)table_shape[k];
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());  // an earlier advance may still be reading the old arrays on its stream
+  u.n_ops = 0;  // (nothing half replaced counts)
+  u.primed = false;
+  const size_t real = sys->dtype == MYTHOS_F32 ? sizeof(float) : sizeof(double);
+  int rc = u.d_list.upload(list);
+  if (!rc) rc = u.d_iface.upload(interfaces, (size_t)iface_first[n_ops]);
+  if (!rc) rc = u.d_table.upload(table, cells);
+  if (!rc) rc = u.d_w_cur.alloc((size_t)n_rep);
+  if (!rc) rc = u.d_accept.alloc((size_t)n_rep);
+  if (!rc) rc = u.d_state.alloc(2 * (size_t)n_rep * n_ops);
+  if (!rc) rc = u.d_counts.alloc(2);
+  if (!rc) rc = u.d_err.alloc(1);
+  if (!rc) rc = u.d_prime_rec.alloc((size_t)n_rep * umbrella_record_width(n_ops));
+  for (int w = 0; w < 8 && !rc; ++w) rc = u.snap[w].grow(4 * real * (size_t)n);
+  if (!rc) rc = u.stage_c.grow(3 * real * (size_t)n);
+  if (!rc) rc = u.stage_q.grow(4 * real * (size_t)n);
+  if (!rc) rc = u.stage_p.grow(3 * real * (size_t)n);
+  if (!rc) rc = u.stage_l.grow(3 * real * (size_t)n);
+  if (rc) return rc;
+  MYTHOS_HIP_TRY(hipMemset(u.d_counts.get(), 0, 2 * sizeof(unsigned long long)));
+  u.n_pairs = n_pairs, u.n_rep = n_rep, u.n_one = n_one, u.segment_steps = segment_steps, u.hb_cutoff = hb_cutoff;
+  u.n_ops = n_ops;
+  return MYTHOS_OK;
+}
+
+int mythos_langevin_advance_umbrella(mythos_sim_t* s, int n_segments, int sample_every, void* traj_center, void* traj_quat, void* prop_center,
+                                     void* prop_quat, double* record, mythos_stream_t stream) {
+  const std::string who = "mythos_langevin_advance_umbrella";
+  if (!s || n_segments < 0 || sample_every < 0) {
+    set_error(who + ": invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  UmbrellaState& u = s->umb;
+  if (u.n_ops == 0) {
+    set_error(who + ": no bias is set (call mythos_langevin_set_umbrella first)");
+    return MYTHOS_ERR_NOT_READY;
+  }
+  if (!s->resident) {
+    set_error(who + ": no resident state (call mythos_langevin_load first; a run that ended in a numeric error drops its state)");
+    return MYTHOS_ERR_NOT_READY;
+  }
+  if (int rc = md_ready(s, who.c_str())) return rc;
+  if (int rc = umbrella_refusals(s, who)) return rc;
+  mythos_system* sys = s->sys;
+  if (sys->n != u.n_rep * u.n_one) {
+    set_error(who + ": the bias was set for another system size");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  const size_t q_align = sys->dtype == MYTHOS_F32 ? sizeof(float4) : sizeof(double4);
+  for (const void* tq : {traj_quat, prop_quat})
+    if (tq && (reinterpret_cast<uintptr_t>(tq) % q_align) != 0) {
+      set_error(who + ": traj_quat and prop_quat must be aligned to 4 elements (" + std::to_string(q_align) + " bytes)");
+      return MYTHOS_ERR_INVALID_ARGUMENT;
+    }
+  hipStream_t st = (hipStream_t)stream;
+  const MdEntries entries = md_entries_of(s);
+  if (s->open)  // a segment starts from a closed frame
+    if (int rc = md_advance(s, 0, 0, true, nullptr, nullptr, nullptr, st)) return rc;
+  const UmbrellaView v{u.n_ops,         u.n_pairs,       u.n_rep,          u.n_one,          u.hb_cutoff,     u.d_list.get(),   u.d_iface.get(),
+                       u.d_table.get(), u.d_w_cur.get(), u.d_accept.get(), u.d_state.get(), u.d_counts.get(), u.d_err.get()};
+  const int width = umbrella_record_width(u.n_ops);
+  void* snap[8];
+  for (int w = 0; w < 8; ++w) snap[w] = u.snap[w].get();
+  // the boundary at the resident (closed) frame: decide, then commit with the rows of sample `row` (negative: none)
+  auto boundary = [&](bool prime, double* rec, long long row) -> int {
+    void* frame[8];
+    for (int w = 0; w < 8; ++w) frame[w] = s->frame[s->cur][w].get();
+    if (int rc = umbrella_decide_launch(sys, v, frame[0], frame[4], s->seed, (uint64_t)s->step, prime, rec, st)) return rc;
+    const size_t real = sys->dtype == MYTHOS_F32 ? sizeof(float) : sizeof(double);
+    auto at = [&](void* base, int w) -> void* { return (base && row >= 0) ? (char*)base + (size_t)row * sys->n * w * real : nullptr; };
+    return umbrella_commit_launch(sys->dtype, sys->n, u.n_one, frame, snap, u.d_accept.get(), at(traj_center, 3), at(traj_quat, 4),
+                                  at(prop_center, 3), at(prop_quat, 4), st);
+  };
+  // parameters replaced since the weights held were looked up (mythos_oxdna_set_params): the states are evaluated again
+  if (u.param_epoch != sys->param_epoch) u.primed = false;
+  if (!u.primed) {
+    // the first boundary: the resident state becomes the snapshot whatever its weight, and a weight of 0 is an error
+    MYTHOS_HIP_TRY(hipMemsetAsync(u.d_err.get(), 0x7f, sizeof(int), st));
+    if (int rc = boundary(true, u.d_prime_rec.get(), -1)) return rc;
+    int bad = 0;
+    MYTHOS_HIP_TRY(hipMemcpyAsync(&bad, u.d_err.get(), sizeof(int), hipMemcpyDeviceToHost, st));
+    MYTHOS_HIP_TRY(hipStreamSynchronize(st));
+    if (bad >= 0 && bad < u.n_rep) {
+      std::vector<double> row((size_t)width);
+      MYTHOS_HIP_TRY(hipMemcpy(row.data(), u.d_prime_rec.get() + (size_t)bad * width, width * sizeof(double), hipMemcpyDeviceToHost));
+      std::string state;
+      for (int k = 0; k < u.n_ops; ++k) state += (k ? ", " : "") + std::to_string((long long)row[u.n_ops + k]);
+      set_error(who + ": replica " + std::to_string(bad) + " starts in state (" + state + "), which has weight 0 in the table");
+      return MYTHOS_ERR_INVALID_ARGUMENT;
+    }
+    u.primed = true;
+    u.param_epoch = sys->param_epoch;
+  }
+  for (int b = 0; b < n_segments; ++b) {
+    // The neighbour rows are rebuilt at the start of every segment exactly as after mythos_langevin_load - by loading: the
+    // closed frame goes out and comes back through the kernels of store and load (a frame that load has just left is
+    // theirs already).  One build per segment, whichever replicas were rejected, and a run that is bit for bit the loop
+    // load; advance(L); store of the plain integrator where every proposal is accepted.
+    if (!u.frame_loaded) {
+      if (int rc = entries.store(s, u.stage_c.get(), u.stage_q.get(), u.stage_p.get(), u.stage_l.get(), st)) return rc;
+      if (int rc = entries.load(s, u.stage_c.get(), u.stage_q.get(), u.stage_p.get(), u.stage_l.get(), st)) return rc;
+    }
+    if (int rc = md_advance(s, u.segment_steps, 0, true, nullptr, nullptr, nullptr, st)) return rc;
+    const bool sample = sample_every > 0 && (b + 1) % sample_every == 0;
+    if (int rc = boundary(false, record ? record + (size_t)b * u.n_rep * width : nullptr, sample ? (b + 1) / sample_every - 1 : -1)) return rc;
+  }
+  return MYTHOS_OK;
+}
+
+int mythos_langevin_umbrella_counts(mythos_sim_t* s, int64_t* accepted, int64_t* decided) {
+  if (!s || !accepted || !decided) {
+    set_error("mythos_langevin_umbrella_counts: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  *accepted = *decided = 0;
+  if (!s->umb.d_counts) return MYTHOS_OK;
+  unsigned long long c[2] = {0, 0};
+  MYTHOS_HIP_TRY(hipSetDevice(s->device));
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());
+  MYTHOS_HIP_TRY(hipMemcpy(c, s->umb.d_counts.get(), sizeof(c), hipMemcpyDeviceToHost));
+  *accepted = (int64_t)c[0], *decided = (int64_t)c[1];
+  return MYTHOS_OK;
+}
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 #include "ext_field.h"
 #include "langevin_step.h"
 #include "md_driver.h"
+#include "umbrella.h"
 
 struct mythos_sim : mythos::MdRun {
   mythos_system* sys = nullptr;
@@ -53,6 +54,9 @@ struct mythos_sim : mythos::MdRun {
   // - the restraints' entries (index, term range, terms) and the point terms' nucleotides - and merges them when either
   // changes (ext_entries_merge, langevin.hip).
   std::vector<int> h_rst_index, h_rst_first{0}, h_rst_term, h_pt_particle;
+  bool pt_moving = false;  // a point term has rate != 0: its force depends on the step count
+  // umbrella sampling (mythos_langevin_set_umbrella; umbrella.h): the bias, the snapshot and the decisions' words
+  mythos::UmbrellaState umb;
   // scratch of mythos_langevin_eval_external: p0 and momentum words, zeroed control words and stamps
   mythos::DeviceBytes d_eval_p0, d_eval_mom, d_eval_ctl;
   mythos::DeviceBuf<double> d_eval_group_row;

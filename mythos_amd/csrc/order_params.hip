@@ -17,27 +17,13 @@
 // integer adds and minima: the result does not depend on the order and is reproducible bit for bit.  No atomics, no
 // LDS, no second launch; where a slice of op_first begins or ends never matters, since no group sees another's pairs.
 #include "mythos_internal.h"
+#include "order_param_pair.h"
 #include "oxdna_gather.h"
 
 namespace mythos {
 
 constexpr int kOpBlock = 256;
 constexpr int kOpFramesPerLaunch = 65535;  // frames per launch, as the energy entry points split theirs
-
-template <typename R>
-struct OrderedBits;
-template <>
-struct OrderedBits<float> {
-  using type = unsigned int;
-  static __device__ __forceinline__ type of(float v) { return __float_as_uint(v); }
-  static __device__ __forceinline__ float back(type b) { return __uint_as_float(b); }
-};
-template <>
-struct OrderedBits<double> {
-  using type = unsigned long long;
-  static __device__ __forceinline__ type of(double v) { return (type)__double_as_longlong(v); }
-  static __device__ __forceinline__ double back(type b) { return __longlong_as_double((long long)b); }
-};
 
 // list: [n_pairs][2] pairs, lower index first | [n_ops + 1] op_first | [n_ops] op_kind
 template <typename R, int MODEL>
@@ -68,30 +54,11 @@ __global__ __launch_bounds__(kOpBlock) void order_params_kernel(
   int count = 0;
   typename Bits::type nearest = ~(typename Bits::type)0;
   for (int k = k0 + lane; k < k1; k += G) {
-    Nuc<R> p, q;
-    R q4[4];
-    ld.load(pairs[2 * k], p, q4);
-    ld.load(pairs[2 * k + 1], q, q4);
-    // The energy takes the minimum image of the CENTRE displacement, as the energy kernel does; the distance that of the
-    // displacement between the SITES, as the reference's displacement function does - the same vector for any pair close
-    // enough to bind, and the shorter one where a component of the displacement is near half a box edge.
-    const V3<R> raw = q.c - p.c;
-    const V3<R> dco = min_image(raw, box);
-    const V3<R> d = min_image(geo.base_base(raw, p, q), box);
-    const R r = m_sqrt(dot(d, d));
-    R e[T_COUNT];
-#pragma unroll
-    for (int t = 0; t < T_COUNT; ++t) e[t] = R(0);
-    if (want_hb) {
-      SelfGrad<R> sg;
-      NoPG pg;
-      unbonded_angular_geo<R, MODEL, false, NoPG, 1>(P, p, q, dco, true, R(1), e, sg, pg, geo);
-    }
-    count += (double(e[T_HB]) < hb_cutoff) ? 1 : 0;
-    const typename Bits::type b = Bits::of(r);
-    nearest = b < nearest ? b : nearest;
+    R e_hb, r;
+    order_param_pair<R, MODEL>(P, geo, ld, box, pairs[2 * k], pairs[2 * k + 1], want_hb, e_hb, r);
+    order_param_accumulate<R>(e_hb, r, hb_cutoff, count, nearest);
     const size_t at = (size_t)frame * n_pairs + k;
-    if (hb_out) hb_out[at] = double(e[T_HB]);
+    if (hb_out) hb_out[at] = double(e_hb);
     if (dist_out) dist_out[at] = double(r);
   }
   for (int o = G >> 1; o > 0; o >>= 1) {

@@ -24,6 +24,19 @@ inline int point_force_dir_at(int kind) {
   return (kind == MYTHOS_POINT_STRING || kind == MYTHOS_POINT_TRAP || kind == MYTHOS_POINT_PLANE) ? 2 : -1;
 }
 
+// where a kind's rate is in its row (-1: the kind cannot move): word 1 of a string and a trap, word 2 of a mutual trap and
+// a sphere.  A kind this does not know is an error of whoever added it, not a resting term.
+inline int point_force_rate_at(int kind) {
+  static_assert(MYTHOS_POINT_KINDS == 5, "a new point-force kind: say where its rate is");
+  switch (kind) {
+    case MYTHOS_POINT_STRING:
+    case MYTHOS_POINT_TRAP: return 1;
+    case MYTHOS_POINT_MUTUAL_TRAP:
+    case MYTHOS_POINT_SPHERE: return 2;
+    default: return -1;  // (a plane)
+  }
+}
+
 // true: every term is one the kernel evaluates.  false, with "<who>: term <t> (<kind>): ..." as the error message.
 // n: nucleotides of the system; has_box: whether a minimum image exists.  n_terms = 0 reads nothing.
 inline bool point_forces_valid(const char* who, int n, bool has_box, int n_terms, const int32_t* kind, const int32_t* particle,

@@ -491,6 +491,54 @@ class LangevinIntegrator(_MdIntegrator):
         _touched(center, quat, p_lin, p_ang)  # (the arrays are written even when closing an open frame failed)
         _lib.check(rc, "langevin_store")
 
+    # ---- umbrella sampling on the resident state (mythos_amd.simulators.umbrella) -----------------------
+    def set_umbrella(self, ops=None, table=None, segment_steps: int = 50, n_rep: int = 1, hb_cutoff: float = -0.1) -> None:
+        """Bias the resident dynamics by a weights table over the states of ``ops`` (``bond`` / ``mindistance``
+        ``OrderParameter``s or the path of their file, naming nucleotides of ONE of the ``n_rep`` replicas;
+        mythos_langevin_set_umbrella).  ``table``: {state tuple: weight} or an array with one axis per order parameter
+        (``lower_table``).  ``segment_steps``: steps per proposal.  No arguments clear the bias.  Refused between ``advance``
+        and ``store`` (an open frame), for moving point forces, oxNA systems and a probabilistic sequence."""
+        from mythos_amd.simulators import umbrella as U
+
+        if ops is None:
+            _lib.check(self._lib.mythos_langevin_set_umbrella(self._h, 1, 0, None, None, None, 0, None, None, None, None, float(hb_cutoff), 1),
+                       "set_umbrella")
+            self._umbrella_ops = ()
+            return
+        ops = U.as_order_parameters(ops)
+        dense = U.lower_table(ops, table)
+        keep, args = U._bias_args(ops, dense)
+        _lib.check(self._lib.mythos_langevin_set_umbrella(self._h, int(n_rep), *args, float(hb_cutoff), int(segment_steps)), "set_umbrella")
+        del keep
+        self._umbrella_ops, self._umbrella_rep = ops, int(n_rep)
+
+    def advance_umbrella(self, n_segments: int, sample_every: int = 1, proposals: bool = False):
+        """``n_segments`` segments of the biased chain on the resident state (mythos_langevin_advance_umbrella) ->
+        (traj_center (S, n, 3), traj_quat (S, n, 4), ``UmbrellaRecord``), S = n_segments // sample_every rows holding the
+        state after the decision of every ``sample_every``-th boundary (``sample_every = 0``: no rows, Nones).  The record's
+        tensors have the leading shape (n_segments, n_rep); ``proposals``: it also carries the proposals' rows."""
+        from mythos_amd.simulators import umbrella as U
+
+        ops = getattr(self, "_umbrella_ops", ())
+        if not ops:
+            raise ValueError("advance_umbrella: no bias is set (set_umbrella)")
+        s = self.system
+        n_seg, n_rep = int(n_segments), self._umbrella_rep
+        n_save = n_seg // sample_every if sample_every > 0 else 0
+        rows = lambda w: torch.empty((n_save, s.n, w), dtype=s.dtype, device=s.device) if n_save else None  # noqa: E731
+        tc, tq = rows(3), rows(4)
+        pc, pq = (rows(3), rows(4)) if proposals else (None, None)
+        raw = torch.zeros((n_seg, n_rep, 3 * len(ops) + 4), dtype=torch.float64, device=s.device)
+        _lib.check(self._lib.mythos_langevin_advance_umbrella(self._h, n_seg, int(sample_every), _lib.ptr(tc), _lib.ptr(tq), _lib.ptr(pc),
+                                                              _lib.ptr(pq), _lib.ptr(raw), _lib.stream(s.device)), "advance_umbrella")
+        return tc, tq, U.record_of(raw, len(ops), pc, pq)
+
+    def umbrella_counts(self) -> tuple[int, int]:
+        """(accepted, decided) decisions since ``set_umbrella`` (mythos_langevin_umbrella_counts)."""
+        a, d = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.mythos_langevin_umbrella_counts(self._h, C.byref(a), C.byref(d)), "umbrella_counts")
+        return int(a.value), int(d.value)
+
     @_MdIntegrator.step.setter
     def step(self, value: int) -> None:
         _lib.check(self._lib.mythos_langevin_set_step(self._h, int(value)), "set_step")

@@ -9,9 +9,9 @@ The definitions (checked against oxDNA's own columns of tests/golden/melting_tem
 sequence weights.  ``mindistance``: the smallest minimum-image distance between the base (hydrogen-bonding) sites of
 the listed pairs; its state is the number of ``interfaces`` the distance exceeds (strictly).
 
-Evaluated by one launch of mythos_oxdna_order_params per call, one lane per (frame, pair).  Not built: umbrella
-sampling or VMMC themselves, order parameters inside the energy or MD launches, oxNA, gradients, and an all-pairs
-hydrogen-bond count over the neighbour rows.
+Evaluated by one launch of mythos_oxdna_order_params per call, one lane per (frame, pair).  The sampling run that
+produces such frames is mythos_amd.simulators.umbrella.HipUmbrellaSampler.  Not built: VMMC, order parameters inside the
+energy or MD step launches, oxNA, gradients, and an all-pairs hydrogen-bond count over the neighbour rows.
 """
 
 from __future__ import annotations
