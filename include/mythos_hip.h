@@ -575,6 +575,26 @@ int mythos_martini_param_grads(mythos_martini_t* m, const void* pos, const void*
                                double* d_eps, double* d_bond_k, double* d_bond_r0, double* d_angle_k,
                                double* d_angle_t0, mythos_stream_t stream);
 
+/* Reaction-field Coulomb (GROMACS' coulombtype = reaction-field with the Verlet scheme's potential shift, the setting of
+ * every MARTINI run the reference drives: data/templates/martini/m2/DMPC/<T>/md.mdp, epsilon_r = 15, epsilon_rf = 0).  The reference
+ * itself evaluates no Coulomb term and ships no Coulomb energies: the formula below is the pin.  Units nm, kJ/mol, e.
+ *   f = 138.935458, k_rf = (eps_rf - eps_r) / ((2 eps_rf + eps_r) r_c^3) (eps_rf = 0 means infinity: 1 / (2 r_c^3)),
+ *   c_rf = 1 / r_c + k_rf r_c^2, r_c = the system's r_cut (one list, one cut-off)
+ *   pair inside r_c, not excluded   V = (f / eps_r) q_i q_j (1 / r + k_rf r^2 - c_rf)
+ *   excluded (bonded) pair inside r_c   V = (f / eps_r) q_i q_j (k_rf r^2 - c_rf), with its force
+ *   self term                       -1/2 (f / eps_r) c_rf sum q_i^2
+ * mythos_martini_set_charges: q host double[n] or NULL.  NULL or all zeros clears the charges - the system then behaves
+ * exactly as one that never had any.  Refused: epsilon_r <= 0, epsilon_rf < 0, non-finite input, and more than 8 distinct
+ * charge values (0 included): the step kernel keeps them in a table of that size.  mythos_martini_energy,
+ * mythos_martini_param_grads and MYTHOS_MARTINI_N_TERMS do not see the charges.  An integrator bound to the system
+ * takes the charges in force when a call of it begins (load, run, advance, store, pressure).
+ * mythos_martini_coulomb: e_coul dev double[n_frames] (pairs + excluded pairs + self term), dU_dpos dev real[n_frames][n][3]
+ * or NULL, written (not accumulated); all-pairs sweep and fixed-order reduction of mythos_martini_energy.  Without charges
+ * both are zero. */
+int mythos_martini_set_charges(mythos_martini_t* m, const double* q, double epsilon_r, double epsilon_rf);
+int mythos_martini_coulomb(mythos_martini_t* m, const void* pos, const void* box, int n_frames, double* e_coul,
+                           void* dU_dpos, mythos_stream_t stream);
+
 /* ---- MARTINI Langevin MD ----------------------------------------------------------------------
  * BASELINE configs[2].  The reference runs MARTINI dynamics in GROMACS as an external process
  * (mythos/simulators/gromacs/) and has no integrator of its own for it; this is the device-resident
@@ -583,6 +603,8 @@ int mythos_martini_param_grads(mythos_martini_t* m, const void* pos, const void*
  *   gamma    friction rate 1/ps (GROMACS sd integrator: 1 / tau_t);  mass host double[n] or NULL (72 amu)
  *   pos, vel dev real[n][3], updated in place;  box host double[3] (orthorhombic, fixed during the run)
  *   traj_pos dev real[n_steps/save_every][n][3] or NULL;  e_trace dev double[.][4] = lj, bond, angle, kinetic
+ *   While the system holds charges (mythos_martini_set_charges) the forces include reaction-field Coulomb and a row of
+ *   e_trace has FIVE columns: lj, bond, angle, kinetic, coulomb (self term included); the caller allocates for that.
  * Errors and the halt-and-resume protocol as mythos_langevin_run (NUMERIC: NaN). */
 mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, double dt, double kT, double gamma,
                                                      const double* mass, uint64_t seed);
@@ -643,7 +665,7 @@ int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* sim, int which,
 int mythos_martini_langevin_set_barostat(mythos_martini_sim_t* sim, int kind, int coupling, const double ref_p[2],
                                          const double compressibility[2], double tau_p, int every);
 /* Pressure of the resident state (what `gmx energy` reports as Pres-XX / -YY / -ZZ): out = K[3], W[3] (kJ/mol: sum m v_d^2
- * and the virial -dU/dln s_d of LJ + bonds + angles), P[3] = (K + W) / V x 16.6053907 (bar), V (nm^3).  Closes an open
+ * and the virial -dU/dln s_d of LJ + bonds + angles, plus reaction-field Coulomb while the system holds charges), P[3] = (K + W) / V x 16.6053907 (bar), V (nm^3).  Closes an open
  * frame first, as store does; a closed frame is left bitwise as it was.  Synchronises the stream. */
 int mythos_martini_langevin_pressure(mythos_martini_sim_t* sim, double out[10], mythos_stream_t stream);
 /* the box of the resident state (host double[3]): the one loaded, rescaled by the coupling events since */

@@ -94,6 +94,8 @@ _SIGS = {
     "mythos_martini_destroy": (None, [V]),
     "mythos_martini_energy": (C.c_int, [V, V, V, C.c_int, V, V, V]),
     "mythos_martini_param_grads": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
+    "mythos_martini_set_charges": (C.c_int, [V, c_double_p, C.c_double, C.c_double]),
+    "mythos_martini_coulomb": (C.c_int, [V, V, V, C.c_int, V, V, V]),
     "mythos_martini_langevin_create": (V, [V, C.c_double, C.c_double, C.c_double, c_double_p, C.c_uint64]),
     "mythos_martini_langevin_destroy": (None, [V]),
     "mythos_martini_langevin_set_neighbor_policy": (C.c_int, [V, C.c_double, C.c_int]),

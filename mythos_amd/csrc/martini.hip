@@ -11,11 +11,14 @@
 // per-bead list that is consulted only inside the cut-off.  Every pair is visited from both ends
 // (energy weight 1/2).  Bonds and angles are gathered per bead from incidence lists.  The terms are martini_terms.h's;
 // the energy and the LJ parameter-gradient kernel run the same sweep (lj_tile_sweep) with their own per-pair work.
+// Reaction-field Coulomb of stored frames (mythos_martini_set_charges / mythos_martini_coulomb; the reference evaluates no
+// Coulomb term, its GROMACS runs do) is a third kernel on the same sweep, with its own term for the excluded pairs.
 // Roofline: the sweep is ALU/LDS bound, not HBM bound: 16 B per bead per tile pass from L2/HBM versus
 // ~20 flops per pair per lane.
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <string>
 
 #include "martini_internal.h"
 
@@ -23,8 +26,9 @@ namespace mythos {
 
 // The sweep of one thread over its share of the partner tiles (tile js, js + n_js, ...): stages each tile in LDS
 // (s_x: 3 kLjBlock reals and kLjBlock ints behind the caller's tables; the first barrier also publishes those), wraps,
-// tests cut-off and exclusions, and calls pair(tp, dx, dy, dz, r2) for every accepted partner - tp indexes the type-pair
-// tables - and tile_done() behind each tile.
+// tests the cut-off, and calls pair(tp, j, excluded, dx, dy, dz, r2) for every partner j != i inside it - tp indexes the
+// type-pair tables, excluded: j is on the bead's exclusion list (LJ drops those, reaction-field Coulomb has a term for
+// them) - and tile_done() behind each tile.
 template <typename R, typename Pair, typename TileDone>
 __device__ __forceinline__ void lj_tile_sweep(int n, const R* __restrict__ p, const R* __restrict__ box,
                                               const int* __restrict__ types, const int* __restrict__ excl, R rc2,
@@ -61,10 +65,10 @@ __device__ __forceinline__ void lj_tile_sweep(int n, const R* __restrict__ p, co
         const R r2 = dx * dx + dy * dy + dz * dz;
         if (r2 < rc2) {
           const int j = j0 + k;
-          bool skip = (j == i);
+          bool excluded = false;
 #pragma unroll
-          for (int q = 0; q < kMaxExcl; ++q) skip = skip || (ex[q] == j);
-          if (!skip) pair(ti + s_t[k], dx, dy, dz, r2);
+          for (int q = 0; q < kMaxExcl; ++q) excluded = excluded || (ex[q] == j);
+          if (j != i) pair(ti + s_t[k], j, excluded, dx, dy, dz, r2);
         }
       }
       tile_done();
@@ -101,7 +105,8 @@ __global__ __launch_bounds__(kLjBlock) void martini_lj_kernel(
   double e = 0.0;
   lj_tile_sweep<R>(
       n, pos + (size_t)frame * n * 3, box + frame * 3, types, excl, K.rc2, K.n_types, n_tiles, s_x,
-      [&](int tp, R dx, R dy, R dz, R r2) {
+      [&](int tp, int, bool excluded, R dx, R dy, R dz, R r2) {
+        if (excluded) return;
         const R ep = s_eps[tp];
         const LjPair<R> t = lj_pair(s_sig[tp], ep, r2);
         et += R(4) * ep * (t.s12 - t.s6) - s_shift[tp];
@@ -120,6 +125,48 @@ __global__ __launch_bounds__(kLjBlock) void martini_lj_kernel(
     double s = 0;
     for (int w = 0; w < kLjBlock / 64; ++w) s += s_e[w];
     e_part[((size_t)frame * n_js + js) * gridDim.x + blockIdx.x] = 0.5 * s;
+  }
+}
+
+// Reaction-field Coulomb of stored frames on the same sweep (mythos_martini_coulomb): a pair inside r_c gives rf_pair, an
+// excluded pair inside r_c rf_excluded (martini_terms.h); partials laid out as martini_lj_kernel's, n_js slots of f_part.
+// The partner's charge is one address for the whole wavefront; a bead without charge does no arithmetic.
+template <typename R>
+__global__ __launch_bounds__(kLjBlock) void martini_coulomb_kernel(
+    int n, const R* __restrict__ pos, const R* __restrict__ box, const int* __restrict__ types,
+    const R* __restrict__ charge, const int* __restrict__ excl, MartiniConst<R> K, RfConst<R> C, int n_tiles,
+    R* __restrict__ f_part, double* __restrict__ e_part) {
+  extern __shared__ unsigned char smem_raw[];
+  R* s_x = reinterpret_cast<R*>(smem_raw);
+  __shared__ double s_e[kLjBlock / 64];
+  const int frame = blockIdx.z;
+  const int js = blockIdx.y, n_js = gridDim.y;
+  const int i = blockIdx.x * kLjBlock + threadIdx.x;
+  const R qi = i < n ? C.pref * charge[i] : R(0);
+  R fx = 0, fy = 0, fz = 0, et = 0;
+  double e = 0.0;
+  lj_tile_sweep<R>(
+      n, pos + (size_t)frame * n * 3, box + frame * 3, types, excl, K.rc2, K.n_types, n_tiles, s_x,
+      [&](int, int j, bool excluded, R dx, R dy, R dz, R r2) {
+        const R qq = qi * charge[j];
+        if (qq == R(0)) return;
+        const RfPair<R> t = excluded ? rf_excluded(r2, C.k_rf, C.c_rf) : rf_pair(r2, C.k_rf, C.c_rf);
+        et += qq * t.v;
+        const R g = qq * t.g;
+        fx += g * dx, fy += g * dy, fz += g * dz;
+      },
+      [&] { e += double(et), et = 0; });
+  if (i < n) {
+    R* o = f_part + (((size_t)frame * n_js + js) * n + i) * 3;
+    o[0] = fx, o[1] = fy, o[2] = fz;
+  }
+  for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
+  if ((threadIdx.x & 63) == 0) s_e[threadIdx.x >> 6] = e;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0;
+    for (int w = 0; w < kLjBlock / 64; ++w) s += s_e[w];
+    e_part[((size_t)frame * n_js + js) * gridDim.x + blockIdx.x] = 0.5 * s;  // (every pair is visited from both ends)
   }
 }
 
@@ -233,7 +280,8 @@ __global__ __launch_bounds__(kLjBlock) void martini_lj_pgrad_kernel(
   for (int k = threadIdx.x; k < kLjWaves * 2 * tt; k += kLjBlock) s_tab[k] = 0.0;
   lj_tile_sweep<R>(
       n, pos + (size_t)frame * n * 3, box + frame * 3, types, excl, K.rc2, K.n_types, n_tiles, s_x,
-      [&](int tp, R, R, R, R r2) {
+      [&](int tp, int, bool excluded, R, R, R, R r2) {
+        if (excluded) return;
         const R sg = s_sig[tp], ep = s_eps[tp];
         const LjPair<R> t = lj_pair(sg * sg, ep, r2);
         const R c6 = lj_pow6(sg * sg, irc2), c12 = c6 * c6;
@@ -320,7 +368,7 @@ __global__ void martini_bonded_pgrad_kernel(int n, const R* __restrict__ pos, co
 template <typename R>
 __global__ void martini_reduce_kernel(int n, int n_slots, const R* __restrict__ f_part, R* __restrict__ dU,
                                       const double* __restrict__ e_part, int n_e, const double* __restrict__ eb_part,
-                                      int n_eb, double* __restrict__ e_terms) {
+                                      int n_eb, double* __restrict__ e_terms, int n_cols, double e_const) {
   const int frame = blockIdx.y;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (dU && t < n * 3) {
@@ -328,14 +376,16 @@ __global__ void martini_reduce_kernel(int n, int n_slots, const R* __restrict__ 
     for (int k = 0; k < n_slots; ++k) s += f_part[((size_t)frame * n_slots + k) * n * 3 + t];
     dU[(size_t)frame * n * 3 + t] = s;
   }
-  if (blockIdx.x == 0 && threadIdx.x < 3) {
+  // n_cols = 3: lj, bond, angle; n_cols = 1 (mythos_martini_coulomb): the e_part sum plus e_const, the self term
+  if (blockIdx.x == 0 && (int)threadIdx.x < n_cols) {
     double s = 0;
     if (threadIdx.x == 0) {
       for (int k = 0; k < n_e; ++k) s += e_part[(size_t)frame * n_e + k];
     } else {
       for (int k = 0; k < n_eb; ++k) s += eb_part[((size_t)frame * n_eb + k) * 2 + (threadIdx.x - 1)];
     }
-    e_terms[(size_t)frame * 3 + threadIdx.x] = s;
+    if (n_cols == 1) s += e_const;
+    e_terms[(size_t)frame * n_cols + threadIdx.x] = s;
   }
 }
 
@@ -375,7 +425,35 @@ static int martini_energy_typed(mythos_martini* m, const R* pos, const R* box, i
                        m->d_ebpart.get());
     hipLaunchKernelGGL(martini_reduce_kernel<R>, dim3((n * 3 + 255) / 256, nf), dim3(256), 0, st, n, n_js + 1,
                        (const R*)m->d_fpart.get(), dU ? dU + (size_t)f0 * n * 3 : nullptr, m->d_epart.get(), n_js * nbx,
-                       m->d_ebpart.get(), nbb, e_terms + (size_t)f0 * 3);
+                       m->d_ebpart.get(), nbb, e_terms + (size_t)f0 * 3, 3, 0.0);
+    MYTHOS_HIP_TRY(hipGetLastError());
+    f0 += nf;
+  }
+  return 0;
+}
+
+// e_coul[frame] and dU/dpos of the reaction-field term: the sweep and the fixed-order reduction of martini_energy_typed
+template <typename R>
+static int martini_coulomb_typed(mythos_martini* m, const R* pos, const R* box, int n_frames, double* e_coul, R* dU, hipStream_t st) {
+  const int n = m->n;
+  const int nbx = (n + kLjBlock - 1) / kLjBlock;
+  double self = 0.0;
+  for (double q : m->h_charge) self += q * q;
+  self *= -0.5 * (kCoulombF / m->eps_r) * double(m->rf<double>().c_rf);
+  for (int f0 = 0; f0 < n_frames;) {
+    int n_js = std::min(nbx, std::max(1, 768 / std::max(1, nbx)));
+    const size_t per_frame = (size_t)n_js * n * 3 * sizeof(R);
+    int nf = (int)std::min<size_t>(std::min(n_frames - f0, 4096), std::max<size_t>(1, (size_t(512) << 20) / per_frame));
+    if (nf > 16) n_js = std::max(1, n_js / 4);
+    if (int rc = m->d_fpart.grow((size_t)nf * n_js * n * 3 * sizeof(R))) return rc;
+    if (int rc = m->d_epart.grow((size_t)nf * n_js * nbx)) return rc;
+    MartiniConst<R> K{R(m->r_cut * m->r_cut), m->n_types, m->angle_kind};
+    const size_t lds = 3 * kLjBlock * sizeof(R) + kLjBlock * sizeof(int);
+    hipLaunchKernelGGL(martini_coulomb_kernel<R>, dim3(nbx, n_js, nf), dim3(kLjBlock), lds, st, n, pos + (size_t)f0 * n * 3,
+                       box + (size_t)f0 * 3, m->d_types.get(), (const R*)m->d_charge.get(), m->d_excl.get(), K, m->rf<R>(), nbx,
+                       (R*)m->d_fpart.get(), m->d_epart.get());
+    hipLaunchKernelGGL(martini_reduce_kernel<R>, dim3((n * 3 + 255) / 256, nf), dim3(256), 0, st, n, n_js, (const R*)m->d_fpart.get(),
+                       dU ? dU + (size_t)f0 * n * 3 : nullptr, m->d_epart.get(), n_js * nbx, (const double*)nullptr, 0, e_coul + f0, 1, self);
     MYTHOS_HIP_TRY(hipGetLastError());
     f0 += nf;
   }
@@ -510,6 +588,60 @@ int mythos_martini_energy(mythos_martini_t* m, const void* pos, const void* box,
   return with_real(m->dtype, [&](auto r) {
     using R = decltype(r);
     return martini_energy_typed<R>(m, (const R*)pos, (const R*)box, n_frames, e_terms, (R*)dU_dpos, (hipStream_t)stream);
+  });
+}
+
+int mythos_martini_set_charges(mythos_martini_t* m, const double* q, double epsilon_r, double epsilon_rf) {
+  if (!m || !(epsilon_r > 0) || !(epsilon_rf >= 0) || !std::isfinite(epsilon_r) || !std::isfinite(epsilon_rf)) {
+    set_error("mythos_martini_set_charges: epsilon_r > 0 and epsilon_rf >= 0 (0: infinity), both finite, required");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  bool any = false;
+  std::vector<double> classes{0.0};
+  for (int i = 0; q && i < m->n; ++i) {
+    if (!std::isfinite(q[i])) {
+      set_error("mythos_martini_set_charges: charge of bead " + std::to_string(i) + " is not finite");
+      return MYTHOS_ERR_INVALID_ARGUMENT;
+    }
+    any = any || q[i] != 0.0;
+    if (std::find(classes.begin(), classes.end(), q[i]) == classes.end()) classes.push_back(q[i]);
+    if ((int)classes.size() > kMaxChargeClasses) {
+      set_error("mythos_martini_set_charges: more than " + std::to_string(kMaxChargeClasses) +
+                " distinct charge values, 0 included: the step kernel's charge table does not hold them");
+      return MYTHOS_ERR_INVALID_ARGUMENT;
+    }
+  }
+  if (!any && !m->has_charge) return MYTHOS_OK;  // nothing to clear: the system stays exactly as it was
+  MYTHOS_HIP_TRY(hipSetDevice(m->device));
+  if (any) {
+    if (int rc = m->d_charge.upload_real(m->dtype, q, (size_t)m->n)) return rc;
+    m->h_charge.assign(q, q + m->n);
+  } else {
+    m->h_charge.clear();
+  }
+  m->has_charge = any, m->eps_r = epsilon_r, m->eps_rf = epsilon_rf;
+  ++m->charge_gen;
+  return MYTHOS_OK;
+}
+
+int mythos_martini_coulomb(mythos_martini_t* m, const void* pos, const void* box, int n_frames, double* e_coul, void* dU_dpos,
+                           mythos_stream_t stream) {
+  if (!m || !pos || !box || !e_coul || n_frames < 0) {
+    set_error("mythos_martini_coulomb: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (n_frames == 0) return MYTHOS_OK;
+  MYTHOS_HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (!m->has_charge) {  // no charges: zero energy, zero forces
+    const size_t w = m->dtype == MYTHOS_F32 ? sizeof(float) : sizeof(double);
+    MYTHOS_HIP_TRY(hipMemsetAsync(e_coul, 0, (size_t)n_frames * sizeof(double), st));
+    if (dU_dpos) MYTHOS_HIP_TRY(hipMemsetAsync(dU_dpos, 0, (size_t)n_frames * m->n * 3 * w, st));
+    return MYTHOS_OK;
+  }
+  return with_real(m->dtype, [&](auto r) {
+    using R = decltype(r);
+    return martini_coulomb_typed<R>(m, (const R*)pos, (const R*)box, n_frames, e_coul, (R*)dU_dpos, st);
   });
 }
 

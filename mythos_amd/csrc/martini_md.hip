@@ -6,6 +6,7 @@
 // list, harmonic bonds, G96 / harmonic angles (the terms of martini_terms.h, as in martini.hip), and the BAOAB
 // Langevin splitting used for oxDNA (langevin_step.h) specialised to point particles:
 //   B  v += h F / m      A  x += h v      O  v = c1 v + sqrt(kT (1 - c1^2) / m) xi,  c1 = exp(-gamma dt)
+// While the system holds charges (mythos_martini_set_charges) the COUL instantiations add reaction-field Coulomb.
 // Units are GROMACS': nm, ps, amu, kJ/mol (1 kJ/mol = 1 amu nm^2 / ps^2), kT = 0.0083144626 T.
 //
 // Work decomposition (as md_step_kernel): 16 lanes per bead (kMmG), 16 beads per 256-thread workgroup; the lanes stride
@@ -48,7 +49,8 @@ constexpr int kMmBlock = MYTHOS_MM_BLOCK;
 #endif
 constexpr int kMmG = MYTHOS_MM_G;
 constexpr int kMmPPB = kMmBlock / kMmG;
-constexpr int kMmTrace = 4;  // lj, bond, angle, kinetic
+constexpr int kMmTrace = 4;      // lj, bond, angle, kinetic
+constexpr int kMmTraceCoul = 5;  // and the reaction-field Coulomb energy, while the system holds charges
 
 template <typename R>
 struct Real4;
@@ -71,6 +73,14 @@ struct MmConst {
   R step_max_sq;   // a bead may move (margin / 2) / (inner_every - 1) per step while pruned rows are in use; <= 0: no check
   int n_types, angle_kind;
 };
+
+// Reaction-field Coulomb in the step and pressure kernels (COUL instantiations; mythos_martini_set_charges).  A frame's .w
+// carries type + kMaxTypes x charge class while charges are set (class 0: no charge, so .w is the plain type otherwise).
+// The kernels' arguments are those of the instantiations without charges: the Coulomb record travels behind the
+// epsilon table, eps[n_types^2 + ...] = f / eps_r, k_rf, c_rf, the self term -1/2 (f / eps_r) c_rf sum q^2, then the
+// charge of every class - staged in LDS with the type tables, so a neighbour's charge costs no second gather.
+constexpr int kCoulPref = 0, kCoulKrf = 1, kCoulCrf = 2, kCoulSelf = 3, kCoulQ = 4;
+constexpr int kCoulRec = kCoulQ + kMaxChargeClasses;
 
 // Wave priority by phase (see md_step_kernel, langevin_step.h): MYTHOS_MM_PRIO_MAP = three decimal digits, the s_setprio
 // level of the row loop, the bonded lists, and everything behind the barrier (0 = no s_setprio)
@@ -95,7 +105,10 @@ constexpr int mm_prio_digit(int phase) {
 // than margin / 2 in total (checked per step, conservatively; a violation halts like a bead that leaves its skin, and
 // the recovery rebuilds both lists).  GROMACS prunes its pair list the same way between searches ("dynamic pruning").
 // Which list a launch walks is a function of the steps since the Verlet rows were built, so split calls stay bitwise equal.
-template <typename R, bool SAVE, bool EMIT = false>
+// COUL: reaction-field Coulomb on top (the record behind eps, above): the pair term inside the row walk's cut-off test,
+// the excluded-pair term on the bond slots.  The instantiations without it are, instruction for instruction, those from
+// before the flag existed (scripts/isa_diff.py --alias).
+template <typename R, bool SAVE, bool EMIT = false, bool COUL = false>
 __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_kernel(
     int n, const MmConst<R> K, const typename Real4<R>::type* __restrict__ in, typename Real4<R>::type* __restrict__ out,
     typename Real4<R>::type* __restrict__ vel, const int* __restrict__ rows, const int* __restrict__ row_len,
@@ -108,11 +121,14 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
     int* __restrict__ emit_len, const int* __restrict__ bb_partner, const int2* __restrict__ ba_partner) {
   using V4 = typename Real4<R>::type;
   constexpr int G = kMmG, PPB = kMmPPB;
+  constexpr int NT = COUL ? kMmTraceCoul : kMmTrace;
   extern __shared__ unsigned char smem_raw[];
   R* s_sig2 = reinterpret_cast<R*>(smem_raw);
   R* s_eps = s_sig2 + K.n_types * K.n_types;
+  R* s_c = s_eps + K.n_types * K.n_types;  // (COUL) the Coulomb record
+  (void)s_c;
   __shared__ R s_f[PPB][4];
-  __shared__ double s_e[SAVE ? PPB : 1][kMmTrace];
+  __shared__ double s_e[SAVE ? PPB : 1][NT];
 
   const int n_blocks = (n + PPB - 1) / PPB;
   const int bid = (int)(blockIdx.x & 7) * ((n_blocks + 7) >> 3) + (int)(blockIdx.x >> 3);  // XCD-aware order
@@ -137,8 +153,11 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
     s_sig2[k] = sigma[k];
     s_eps[k] = eps[k];
   }
+  if constexpr (COUL)
+    if (threadIdx.x < kCoulRec) s_c[threadIdx.x] = eps[tt + threadIdx.x];
   const V4 me = in[ii];
-  const int type_i = (int)me.w * K.n_types;  // the bead type travels as an integer-valued real in .w
+  // the bead type travels as an integer-valued real in .w (COUL: with the charge class above it, see kCoulRec)
+  const int type_i = (COUL ? ((int)me.w & (kMaxTypes - 1)) : (int)me.w) * K.n_types;
   const int* __restrict__ row = rows + (size_t)ii * row_stride;
   const int len = valid ? row_len[ii] : 0;
   // bonds and angles: the lane's incidence entry and the partner beads it names are requested here, in front of the row
@@ -150,12 +169,34 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
     if (lane < kMaxBeadBonds) ent_b0 = bead_bonds[(size_t)i * kMaxBeadBonds + lane], par_b0 = bb_partner[(size_t)i * kMaxBeadBonds + lane];
     if (lane < kMaxBeadAngles) ent_a0 = bead_angles[(size_t)i * kMaxBeadAngles + lane], par_a0 = ba_partner[(size_t)i * kMaxBeadAngles + lane];
   }
+  // (COUL) The excluded-pair term counts a partner once, as the exclusion table does, however many bonds join the pair:
+  // a slot that repeats the partner of a lower slot of this bead does not carry it.
+  bool coul_dup = false;
+  (void)coul_dup;
+  if constexpr (COUL) {
+    static_assert(kMaxBeadBonds <= G, "one bond slot per lane");
+#pragma unroll
+    for (int t = 0; t < kMaxBeadBonds - 1; ++t) {
+      const int pt = __shfl(par_b0, t, G);
+      coul_dup = coul_dup || (t < lane && pt == par_b0);
+    }
+  }
   __syncthreads();
 
   MM_PRIO(0);
   R gx = 0, gy = 0, gz = 0;  // dU/dx_i
-  R e_lj = 0, e_b = 0, e_a = 0;
+  R e_lj = 0, e_b = 0, e_a = 0, e_c = 0;
+  (void)e_c;
   const R irc2 = R(1) / K.rc2;
+  // (COUL) f / eps_r times this bead's charge; 0 for most beads, whose groups skip the Coulomb arithmetic
+  R qi = 0, k_rf = 0, c_rf = 0;
+  const R* s_q = s_c + kCoulQ;
+  (void)qi, (void)k_rf, (void)c_rf, (void)s_q;
+  if constexpr (COUL) {
+    qi = valid ? s_c[kCoulPref] * s_q[(int)me.w >> 6] : R(0);
+    k_rf = s_c[kCoulKrf], c_rf = s_c[kCoulCrf];
+  }
+  static_assert(kMaxTypes == 64, "the charge class sits above six bits of type");
   // ---- Lennard-Jones over the row, kLjBatch entries per lane at a time: their neighbour positions are requested
   //      together and the next batch's row entries before this batch is evaluated.  20 480 beads x 8 lanes are 2.5
   //      wavefronts per SIMD, too few to hide a gather per iteration (one-ahead prefetch: 14 exposed round trips per
@@ -196,11 +237,20 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
           n_in += __popc(gm);
         }
         if (have && r2 < K.rc2) {
-          const int tp = type_i + (int)o[u].w;
+          const int tp = type_i + (COUL ? ((int)o[u].w & (kMaxTypes - 1)) : (int)o[u].w);
           const R ep = s_eps[tp];
           const LjPair<R> t = lj_pair(s_sig2[tp], ep, r2);
           gx += t.g * dx, gy += t.g * dy, gz += t.g * dz;
           if constexpr (SAVE) e_lj += R(0.5) * R(4) * ep * lj_shifted(t, lj_pow6(s_sig2[tp], irc2));
+          if constexpr (COUL) {
+            if (qi != R(0)) {
+              const R qq = qi * s_q[(int)o[u].w >> 6];
+              const RfPair<R> c = rf_pair(r2, k_rf, c_rf);
+              const R cg = qq * c.g;
+              gx += cg * dx, gy += cg * dy, gz += cg * dz;
+              if constexpr (SAVE) e_c += R(0.5) * qq * c.v;
+            }
+          }
         }
       }
     }
@@ -221,6 +271,16 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
       gx += t.c * dx, gy += t.c * dy, gz += t.c * dz;
       if constexpr (SAVE)
         if (side == 0) e_b += R(0.5) * bond_k[b] * t.x * t.x;
+      if constexpr (COUL) {  // the excluded pair's reaction-field term, once per pair and owner
+        const R r2 = dx * dx + dy * dy + dz * dz;
+        if (qi != R(0) && !coul_dup && r2 < K.rc2) {
+          const R qq = qi * s_q[(int)o.w >> 6];
+          const RfPair<R> c = rf_excluded(r2, k_rf, c_rf);
+          const R cg = qq * c.g;
+          gx += cg * dx, gy += cg * dy, gz += cg * dz;
+          if constexpr (SAVE) e_c += R(0.5) * qq * c.v;
+        }
+      }
     }
     for (int s = lane; s < kMaxBeadAngles; s += G) {
       const int ent = (s == lane) ? ent_a0 : bead_angles[(size_t)i * kMaxBeadAngles + s];
@@ -250,6 +310,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
     e_lj = group_sum<G>(e_lj);
     e_b = group_sum<G>(e_b);
     e_a = group_sum<G>(e_a);
+    if constexpr (COUL) e_c = group_sum<G>(e_c);
   }
   if (lane == 0) {
     s_f[grp][0] = gx, s_f[grp][1] = gy, s_f[grp][2] = gz;
@@ -258,6 +319,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
       s_e[grp][1] = valid ? double(e_b) : 0.0;
       s_e[grp][2] = valid ? double(e_a) : 0.0;
       s_e[grp][3] = 0.0;
+      if constexpr (COUL) s_e[grp][4] = valid ? double(e_c) : 0.0;
     }
   }
   // ---- integrator prologue, before the barrier: the integrating wavefront draws its thermostat noise and fetches
@@ -324,10 +386,12 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
   }
   if constexpr (SAVE) {
     __syncthreads();
-    if (threadIdx.x < kMmTrace) {
+    if (threadIdx.x < NT) {
       double s = 0.0;
       for (int g = 0; g < PPB; ++g) s += s_e[g][threadIdx.x];
-      e_part[(size_t)bid * kMmTrace + threadIdx.x] = s;
+      if constexpr (COUL)
+        if (bid == 0 && threadIdx.x == 4) s += double(s_c[kCoulSelf]);
+      e_part[(size_t)bid * NT + threadIdx.x] = s;
     }
   }
 }
@@ -339,8 +403,15 @@ __global__ void mm_pack_kernel(int n, const R* __restrict__ pos, const R* __rest
   using V4 = typename Real4<R>::type;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  frame[i] = V4{pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], R(types[i])};
+  frame[i] = V4{pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], R(types[i])};  // (types: with the charge class, see kCoulRec)
   vel[i] = V4{v[3 * i], v[3 * i + 1], v[3 * i + 2], inv_mass[i]};
+}
+
+// the charges changed under a resident frame (mm_sync_charges): its .w takes the new packed types
+template <typename R>
+__global__ void mm_retype_kernel(int n, const int* __restrict__ types, typename Real4<R>::type* __restrict__ frame) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) frame[i].w = R(types[i]);
 }
 
 template <typename R>
@@ -568,6 +639,13 @@ struct mythos_martini_sim : mythos::MdRun {
   // already squared.  d_ctypes: the compact type of every bead (what the frames carry in .w).
   int n_ctypes = 0;
   DeviceBuf<int> d_ctypes;
+  // Reaction-field Coulomb: derived from the system's charges whenever its charge_gen moved (mm_sync_charges).  d_ctypes
+  // then holds h_ctypes + kMaxTypes x charge class, d_ceps the Coulomb record behind h_ceps (kCoulRec reals, always there).
+  std::vector<int> h_ctypes;
+  std::vector<double> h_ceps;
+  int charge_gen = 0;
+  bool coul = false;
+  int trace_width() const { return coul ? kMmTraceCoul : kMmTrace; }
   DeviceBytes d_csig2, d_ceps;
   // per incidence slot of a bead: the partner of the bond, the two other beads of the angle (see the step kernel)
   DeviceBuf<int> d_bb_partner;
@@ -638,6 +716,57 @@ static MmConst<R> mm_const(const mythos_martini_sim* sim) {
   return K;
 }
 
+// The integrator's view of the system's charges, brought up to date at the head of every call (load, advance, store,
+// pressure) when mythos_martini_set_charges has changed them since: the charge classes, the packed types and the Coulomb
+// record behind the epsilon table.  A resident frame is retyped in place.  Rare: synchronises.
+static int mm_sync_charges(mythos_martini_sim* sim, hipStream_t st) {
+  const mythos_martini* m = sim->sys;
+  if (sim->charge_gen == m->charge_gen) return MYTHOS_OK;
+  MYTHOS_HIP_TRY(hipStreamSynchronize(st));  // (launches that read the tables replaced below)
+  const int n = m->n;
+  std::vector<int> packed = sim->h_ctypes;
+  std::vector<double> tab(kMaxChargeClasses, 0.0), ce = sim->h_ceps;
+  double self = 0.0;  // sum q^2
+  if (m->has_charge) {
+    const std::vector<double>& q = m->h_charge;
+    int n_cls = 1;  // class 0: no charge
+    for (int i = 0; i < n; ++i) {
+      int c = 0;
+      while (c < n_cls && tab[c] != q[i]) ++c;
+      if (c == n_cls) {
+        if (n_cls == kMaxChargeClasses) {  // (mythos_martini_set_charges refuses such a system)
+          set_error("mythos_martini_langevin: more distinct charge values than the charge table holds");
+          return MYTHOS_ERR_INVALID_ARGUMENT;
+        }
+        tab[n_cls++] = q[i];
+      }
+      packed[i] += kMaxTypes * c;
+      self += q[i] * q[i];
+    }
+    const RfConst<double> c = m->rf<double>();
+    const double rec[4] = {c.pref, c.k_rf, c.c_rf, -0.5 * c.pref * c.c_rf * self};
+    ce.insert(ce.end(), rec, rec + 4);
+    ce.insert(ce.end(), tab.begin(), tab.end());
+  }
+  ce.resize(sim->h_ceps.size() + kCoulRec, 0.0);
+  if (sim->d_ctypes.upload(packed) || sim->d_ceps.upload_real(m->dtype, ce.data(), ce.size())) {
+    set_error("mythos_martini_langevin: device allocation failed");
+    return MYTHOS_ERR_HIP;
+  }
+  sim->coul = m->has_charge;
+  if (sim->resident) {
+    const int tb = (n + 255) / 256;
+    if (m->dtype == MYTHOS_F32)
+      hipLaunchKernelGGL(mm_retype_kernel<float>, dim3(tb), dim3(256), 0, st, n, sim->d_ctypes.get(), (float4*)sim->frame[sim->cur].get());
+    else
+      hipLaunchKernelGGL(mm_retype_kernel<double>, dim3(tb), dim3(256), 0, st, n, sim->d_ctypes.get(), (double4*)sim->frame[sim->cur].get());
+    MYTHOS_HIP_TRY(hipGetLastError());
+  }
+  if (int rc = sim->d_epart.grow((size_t)((n + kMmPPB - 1) / kMmPPB) * kMmTraceCoul)) return rc;
+  sim->charge_gen = m->charge_gen;
+  return MYTHOS_OK;
+}
+
 // caller's (n, 3) arrays -> the resident frame; the list of a previous state does not carry over
 template <typename R>
 static int mm_load_typed(mythos_martini_sim* sim, const R* pos, const R* v, const double box[3], hipStream_t st) {
@@ -679,7 +808,8 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
     return sim->d_rows_in.grow((size_t)n * sim->list.stride);  // (a stride only grows)
   };
   if (int rc = ensure_inner()) return rc;
-  const size_t lds = (size_t)2 * sim->n_ctypes * sim->n_ctypes * sizeof(R);
+  const bool coul = sim->coul;
+  const size_t lds = ((size_t)2 * sim->n_ctypes * sim->n_ctypes + (coul ? kCoulRec : 0)) * sizeof(R);
   auto launch_step = [&](int k, const LaunchRow& row) {
     const int cur = row.cur;
     const R kick_close = R(row.kick_close);
@@ -699,19 +829,27 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
       (const R*)sim->d_angle_ref.get(), kick_close, do_step, sim->seed, (uint64_t)(sim->step + k),                        \
       (const V4*)sim->ref_pos.get(), sim->d_flags.get(), tp, sim->d_epart.get(), sim->list.d_overflow.get(), k,           \
       emit_rows, emit_len, sim->d_bb_partner.get(), sim->d_ba_partner.get()
-    auto go = [&](auto save_tag, auto emit_tag) {
-      constexpr bool SV = decltype(save_tag)::value, EM = decltype(emit_tag)::value;
+    auto go_coul = [&](auto save_tag, auto emit_tag, auto coul_tag) {
+      constexpr bool SV = decltype(save_tag)::value, EM = decltype(emit_tag)::value, CL = decltype(coul_tag)::value;
       if (row.ea) {
-        hipExtLaunchKernelGGL((martini_md_step_kernel<R, SV, EM>), dim3(grid), dim3(kMmBlock), lds, st, row.ea, row.eb, 0, MM_ARGS);
+        hipExtLaunchKernelGGL((martini_md_step_kernel<R, SV, EM, CL>), dim3(grid), dim3(kMmBlock), lds, st, row.ea, row.eb, 0, MM_ARGS);
       } else {
-        hipLaunchKernelGGL((martini_md_step_kernel<R, SV, EM>), dim3(grid), dim3(kMmBlock), lds, st, MM_ARGS);
+        hipLaunchKernelGGL((martini_md_step_kernel<R, SV, EM, CL>), dim3(grid), dim3(kMmBlock), lds, st, MM_ARGS);
       }
     };
 #undef MM_ARGS
+    // the system holds charges: the instantiations with reaction-field Coulomb
+    auto go = [&](auto save_tag, auto emit_tag) {
+      if (coul) go_coul(save_tag, emit_tag, std::true_type{}); else go_coul(save_tag, emit_tag, std::false_type{});
+    };
     if (row.save) {
       if (emit) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{});
-      hipLaunchKernelGGL(reduce_trace_kernel<kMmTrace>, dim3(1), dim3(256), 0, st, sim->d_epart.get(), blocks,
-                         e_trace + (size_t)row.sidx * kMmTrace);
+      if (coul)
+        hipLaunchKernelGGL(reduce_trace_kernel<kMmTraceCoul>, dim3(1), dim3(256), 0, st, sim->d_epart.get(), blocks,
+                           e_trace + (size_t)row.sidx * kMmTraceCoul);
+      else
+        hipLaunchKernelGGL(reduce_trace_kernel<kMmTrace>, dim3(1), dim3(256), 0, st, sim->d_epart.get(), blocks,
+                           e_trace + (size_t)row.sidx * kMmTrace);
     } else {
       if (emit) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{});
     }
@@ -812,6 +950,9 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
     }
   for (int& t : types) t = (t >= 0 && t < T) ? cmap[t] : 0;
   s->n_ctypes = C;
+  s->h_ctypes = types;
+  for (double e : ce) s->h_ceps.push_back(rounded(e));
+  ce.resize(ce.size() + kCoulRec, 0.0);  // the Coulomb record, all zero until the system holds charges (mm_sync_charges)
   std::vector<double> ref(sys->h_angle_t0.size());
   for (size_t a = 0; a < ref.size(); ++a) {
     const double t0 = rounded(sys->h_angle_t0[a]);
@@ -886,10 +1027,12 @@ int mm_check_box(const mythos_martini_sim_t* s, const double* box, const char* w
 }
 
 int mm_load(mythos_martini_sim_t* s, const void* pos, const void* vel, const double* box, hipStream_t st) {
+  if (int rc = mm_sync_charges(s, st)) return rc;
   return s->sys->dtype == MYTHOS_F32 ? mm_load_typed<float>(s, (const float*)pos, (const float*)vel, box, st)
                                      : mm_load_typed<double>(s, (const double*)pos, (const double*)vel, box, st);
 }
 int mm_advance(mythos_martini_sim_t* s, int n_steps, int save_every, bool close, void* traj, double* e_trace, hipStream_t st) {
+  if (int rc = mm_sync_charges(s, st)) return rc;
   if (mm_barostat_on(s))  // chunks that end at coupling events (martini_npt.inc); off: the call below, as ever
     return s->sys->dtype == MYTHOS_F32 ? mm_advance_npt<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
                                        : mm_advance_npt<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
@@ -899,6 +1042,7 @@ int mm_advance(mythos_martini_sim_t* s, int n_steps, int save_every, bool close,
   return rc;
 }
 int mm_store(mythos_martini_sim_t* s, void* pos, void* vel, hipStream_t st) {
+  if (int rc = mm_sync_charges(s, st)) return rc;
   return s->sys->dtype == MYTHOS_F32 ? mm_store_typed<float>(s, (float*)pos, (float*)vel, st) : mm_store_typed<double>(s, (double*)pos, (double*)vel, st);
 }
 

@@ -29,7 +29,9 @@ enum { kRecBox = 0, kRecMu = 3, kRecP = 6, kRecK = 9, kRecW = 12, kRecV = 15, kR
 // The step kernel's decomposition (16 lanes per bead over its Verlet row, then its bond and angle incidence slots, DPP
 // fold) with the strain derivative in place of the force: an LJ pair or a bond gives -1/2 g dx_d^2 to either bead, an
 // angle -u_d dU/dx_id at its first and -v_d dU/dx_kd at its last bead.  Sums in R inside a lane, in double across groups.
-template <typename R>
+// COUL (the system holds charges; the record behind eps, martini_md.hip): the reaction-field pair term on the row walk and the excluded-pair term on the bond
+// slots that carry it, both central: -1/2 (dV/dr) / r dx_d^2 to either bead, as LJ and bonds.
+template <typename R, bool COUL>
 __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_pressure_kernel(
     int n, const MmConst<R> K, const typename Real4<R>::type* __restrict__ in, const typename Real4<R>::type* __restrict__ vel,
     const int* __restrict__ rows, const int* __restrict__ row_len, int row_stride, const R* __restrict__ sigma,
@@ -41,6 +43,8 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_pressure_ke
   extern __shared__ unsigned char smem_raw[];
   R* s_sig2 = reinterpret_cast<R*>(smem_raw);
   R* s_eps = s_sig2 + K.n_types * K.n_types;
+  R* s_c = s_eps + K.n_types * K.n_types;  // (COUL) the Coulomb record
+  (void)s_c;
   __shared__ double s_p[PPB][kMmVir];
 
   const int bid = (int)blockIdx.x;  // (the grid is exactly the workgroups that hold beads)
@@ -53,13 +57,22 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_pressure_ke
     s_sig2[k] = sigma[k];
     s_eps[k] = eps[k];
   }
+  if constexpr (COUL)
+    if (threadIdx.x < kCoulRec) s_c[threadIdx.x] = eps[tt + threadIdx.x];
   const V4 me = in[ii];
-  const int type_i = (int)me.w * K.n_types;
+  const int type_i = (COUL ? ((int)me.w & (kMaxTypes - 1)) : (int)me.w) * K.n_types;
   const int* __restrict__ row = rows + (size_t)ii * row_stride;
   const int len = valid ? row_len[ii] : 0;
   __syncthreads();
 
   R wx = 0, wy = 0, wz = 0;
+  R qi = 0, k_rf = 0, c_rf = 0;
+  const R* s_q = s_c + kCoulQ;
+  (void)qi, (void)k_rf, (void)c_rf, (void)s_q;
+  if constexpr (COUL) {
+    qi = valid ? s_c[kCoulPref] * s_q[(int)me.w >> 6] : R(0);
+    k_rf = s_c[kCoulKrf], c_rf = s_c[kCoulCrf];
+  }
   {
     constexpr int kB = MYTHOS_MM_BATCH;
 #pragma unroll 1
@@ -78,11 +91,28 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_pressure_ke
         const R dx = wrap_fma(me.x - o[u].x, K.lx, K.ilx), dy = wrap_fma(me.y - o[u].y, K.ly, K.ily), dz = wrap_fma(me.z - o[u].z, K.lz, K.ilz);
         const R r2 = m_fma(dz, dz, m_fma(dy, dy, dx * dx));
         if (j[u] >= 0 && r2 < K.rc2) {
-          const int tp = type_i + (int)o[u].w;
+          const int tp = type_i + (COUL ? ((int)o[u].w & (kMaxTypes - 1)) : (int)o[u].w);
           const R h = R(-0.5) * lj_pair(s_sig2[tp], s_eps[tp], r2).g;
           wx += h * dx * dx, wy += h * dy * dy, wz += h * dz * dz;
+          if constexpr (COUL) {
+            if (qi != R(0)) {
+              const R hc = R(-0.5) * qi * s_q[(int)o[u].w >> 6] * rf_pair(r2, k_rf, c_rf).g;
+              wx += hc * dx * dx, wy += hc * dy * dy, wz += hc * dz * dz;
+            }
+          }
         }
       }
+    }
+  }
+  // (COUL) a bond slot that repeats the partner of a lower slot carries no excluded-pair term (see the step kernel)
+  bool coul_dup = false;
+  (void)coul_dup;
+  if constexpr (COUL) {
+    const int par = (valid && lane < kMaxBeadBonds) ? bb_partner[(size_t)i * kMaxBeadBonds + lane] : -1;
+#pragma unroll
+    for (int t = 0; t < kMaxBeadBonds - 1; ++t) {
+      const int pt = __shfl(par, t, G);
+      coul_dup = coul_dup || (t < lane && pt == par);
     }
   }
   if (valid) {
@@ -94,6 +124,13 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_pressure_ke
       const R dx = wrap(me.x - o.x, K.lx, K.ilx), dy = wrap(me.y - o.y, K.ly, K.ily), dz = wrap(me.z - o.z, K.lz, K.ilz);
       const R h = R(-0.5) * bond_term(dx * dx + dy * dy + dz * dz, bond_k[b], bond_r0[b]).c;
       wx += h * dx * dx, wy += h * dy * dy, wz += h * dz * dz;
+      if constexpr (COUL) {
+        const R r2 = dx * dx + dy * dy + dz * dz;
+        if (qi != R(0) && !coul_dup && r2 < K.rc2) {
+          const R hc = R(-0.5) * qi * s_q[(int)o.w >> 6] * rf_excluded(r2, k_rf, c_rf).g;
+          wx += hc * dx * dx, wy += hc * dy * dy, wz += hc * dz * dz;
+        }
+      }
     }
     for (int s = lane; s < kMaxBeadAngles; s += G) {
       const int ent = bead_angles[(size_t)i * kMaxBeadAngles + s];
@@ -244,13 +281,18 @@ static int mm_pressure_typed(mythos_martini_sim* sim, bool event, hipStream_t st
   if (int rc = mm_npt_buffers(sim)) return rc;
   const int n = m->n, blocks = (n + kMmPPB - 1) / kMmPPB;
   const MmConst<R> K = mm_const<R>(sim);
-  const size_t lds = (size_t)2 * sim->n_ctypes * sim->n_ctypes * sizeof(R);
+  const size_t lds = ((size_t)2 * sim->n_ctypes * sim->n_ctypes + (sim->coul ? kCoulRec : 0)) * sizeof(R);
   V4* frame = (V4*)sim->frame[sim->cur].get();
-  hipLaunchKernelGGL(martini_pressure_kernel<R>, dim3(blocks), dim3(kMmBlock), lds, st, n, K, (const V4*)frame, (const V4*)sim->vel.get(),
-                     sim->list.d_rows.get(), sim->d_row_len.get(), sim->list.stride, (const R*)sim->d_csig2.get(),
-                     (const R*)sim->d_ceps.get(), m->d_bead_bonds.get(), m->d_bead_angles.get(), (const R*)m->d_bond_k.get(),
-                     (const R*)m->d_bond_r0.get(), (const R*)m->d_angle_k.get(), (const R*)sim->d_angle_ref.get(),
-                     sim->d_bb_partner.get(), sim->d_ba_partner.get(), b.d_part.get());
+#define MM_P_ARGS                                                                                                          \
+  n, K, (const V4*)frame, (const V4*)sim->vel.get(), sim->list.d_rows.get(), sim->d_row_len.get(), sim->list.stride,        \
+      (const R*)sim->d_csig2.get(), (const R*)sim->d_ceps.get(), m->d_bead_bonds.get(), m->d_bead_angles.get(),             \
+      (const R*)m->d_bond_k.get(), (const R*)m->d_bond_r0.get(), (const R*)m->d_angle_k.get(),                              \
+      (const R*)sim->d_angle_ref.get(), sim->d_bb_partner.get(), sim->d_ba_partner.get(), b.d_part.get()
+  if (sim->coul)
+    hipLaunchKernelGGL((martini_pressure_kernel<R, true>), dim3(blocks), dim3(kMmBlock), lds, st, MM_P_ARGS);
+  else
+    hipLaunchKernelGGL((martini_pressure_kernel<R, false>), dim3(blocks), dim3(kMmBlock), lds, st, MM_P_ARGS);
+#undef MM_P_ARGS
   MmBaroArgs a;
   for (int d = 0; d < 3; ++d) a.box[d] = sim->box[d];
   for (int d = 0; d < 2; ++d) a.ref_p[d] = b.ref_p[d], a.f[d] = b.beta[d] * b.every * sim->dt / b.tau_p;
@@ -297,7 +339,7 @@ static int mm_advance_npt(mythos_martini_sim* sim, int n_steps, int save_every, 
     const bool event = len == to_event, save = len == to_save;
     const bool last = done + len == n_steps;
     const int rc = mm_advance_typed<R>(sim, len, save ? len : 0, event || (last && close), traj_pos ? traj_pos + rows * row_reals : nullptr,
-                                       e_trace ? e_trace + (size_t)rows * kMmTrace : nullptr, st);
+                                       e_trace ? e_trace + (size_t)rows * sim->trace_width() : nullptr, st);
     rebuilds += sim->last_rebuilds, recoveries += sim->last_recoveries, launches += sim->last_launches;
     sim->last_rebuilds = rebuilds, sim->last_recoveries = recoveries, sim->last_launches = launches;
     if (rc) return rc;
@@ -347,6 +389,7 @@ int mythos_martini_langevin_pressure(mythos_martini_sim_t* s, double out[10], my
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
   const bool f32 = s->sys->dtype == MYTHOS_F32;
+  if (int rc = mm_sync_charges(s, st)) return rc;
   // an open frame gets its closing half kick, a state without rows its rows: the zero-step closing call of store
   if (s->open || !s->list_valid || !s->list_fitted)
     if (int rc = f32 ? mm_advance_typed<float>(s, 0, 0, true, nullptr, nullptr, st) : mm_advance_typed<double>(s, 0, 0, true, nullptr, nullptr, st))

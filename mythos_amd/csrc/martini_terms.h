@@ -54,6 +54,23 @@ __device__ __forceinline__ R lj_shifted(const LjPair<R>& t, R c6) {
   return (t.s12 - t.s6) - (c6 * c6 - c6);
 }
 
+// ---- reaction-field Coulomb with the potential shifted to 0 at r_c (GROMACS, coulombtype = reaction-field under the
+// Verlet scheme): V = qq (1/r + k_rf r^2 - c_rf) for a pair inside r_c, V = qq (k_rf r^2 - c_rf) for an excluded (bonded)
+// pair inside r_c, qq = (f / eps_r) q_i q_j.  The factors are per unit qq; 1/r^3 from one reciprocal square root.
+template <typename R>
+struct RfPair {
+  R v, g;  // V / qq and (dV/dr) / (r qq)
+};
+template <typename R>
+__device__ __forceinline__ RfPair<R> rf_pair(R r2, R k_rf, R c_rf) {
+  const R ir = m_rsqrt(r2);
+  return {ir + k_rf * r2 - c_rf, R(2) * k_rf - ir * ir * ir};
+}
+template <typename R>
+__device__ __forceinline__ RfPair<R> rf_excluded(R r2, R k_rf, R c_rf) {
+  return {k_rf * r2 - c_rf, R(2) * k_rf};
+}
+
 // ---- harmonic bond, E = 1/2 k x^2, from the squared length of the wrapped displacement d; dE/dd = c d
 template <typename R>
 struct BondTerm {

@@ -1,6 +1,7 @@
 """MARTINI 2/3 energy functions with the reference's surface (mythos/energy/martini/base.py:46-208,
 m2/lj.py:14-157, m2/bond.py:15-71, m2/angle.py:16-129, m3/angle.py:8-11), evaluated by the HIP kernels
-of mythos_amd/csrc/martini.hip.
+of mythos_amd/csrc/martini.hip, and ``Coulomb`` - reaction-field electrostatics as the GROMACS runs of the reference's
+MARTINI workflows use them, which the reference itself never evaluates.
 
     top = MartiniTopology.from_top("topol.top")
     lj = LJ.from_topology(topology=top, params=LJConfiguration(**lj_params))
@@ -28,6 +29,8 @@ BOND_K_PREFIX = "bond_k_"
 BOND_R0_PREFIX = "bond_r0_"
 ANGLE_K_PREFIX = "angle_k_"
 ANGLE_THETA0_PREFIX = "angle_theta0_"
+EPSILON_R = "epsilon_r"
+EPSILON_RF = "epsilon_rf"
 
 
 class MartiniEnergyConfiguration:
@@ -122,6 +125,35 @@ class AngleConfiguration(MartiniEnergyConfiguration):
                 raise ValueError(f"Unexpected parameter {p} for AngleConfiguration")
         if len(self.params) == 0 or len(self.params) % 2 != 0:
             raise ValueError("AngleConfiguration requires pairs of k and theta0 parameters")
+
+
+class CoulombConfiguration(MartiniEnergyConfiguration):
+    """``epsilon_r`` (relative permittivity inside the cut-off) and ``epsilon_rf`` (beyond it; 0 means infinity) of
+    reaction-field Coulomb - the mdp keys of the same names; the defaults are those of the reference's MARTINI runs
+    (data/templates/martini/m2/DMPC/*/md.mdp).  ``epsilon_r`` may be optimised while ``epsilon_rf`` is 0; charges are
+    not parameters."""
+
+    def __init__(self, couplings: dict[str, list[str]] | None = None, **kwargs):
+        kwargs.setdefault(EPSILON_R, 15.0)
+        kwargs.setdefault(EPSILON_RF, 0.0)
+        super().__init__(couplings, **kwargs)
+
+    def __post_init__(self) -> None:
+        for p in self.params:
+            if p not in (EPSILON_R, EPSILON_RF):
+                raise ValueError(f"Unexpected parameter {p} for CoulombConfiguration")
+        if isinstance(self.params[EPSILON_RF], torch.Tensor) and self.params[EPSILON_RF].requires_grad:
+            raise ValueError("epsilon_rf is not optimisable")
+        if not _num(self.params[EPSILON_R]) > 0 or _num(self.params[EPSILON_RF]) < 0:
+            raise ValueError("CoulombConfiguration needs epsilon_r > 0 and epsilon_rf >= 0 (0: infinity)")
+        er = self.params[EPSILON_R]
+        if isinstance(er, torch.Tensor) and er.requires_grad and _num(self.params[EPSILON_RF]) != 0.0:
+            # with a finite epsilon_rf the energy is no longer proportional to 1 / epsilon_r: k_rf depends on it too
+            raise ValueError("epsilon_r can only be optimised with epsilon_rf = 0 (infinity)")
+
+    @property
+    def opt_params(self) -> dict:
+        return {k: v for k, v in super().opt_params.items() if k != EPSILON_RF}
 
 
 def _as_scalar(v) -> torch.Tensor:
@@ -336,6 +368,72 @@ class Angle3(Angle):
     angle_kind = 1
 
 
+class _CoulombOp(torch.autograd.Function):
+    """Reaction-field Coulomb energy per frame (mythos_martini_coulomb).  With epsilon_rf = 0 the energy is
+    proportional to 1 / epsilon_r: dE/d(epsilon_r) = -E / epsilon_r, exact, on the host."""
+
+    @staticmethod
+    def forward(ctx, pos, box, system, eps_r):
+        want_pos = pos.requires_grad
+        e, g = system.coulomb(pos.detach(), box, grads=want_pos)
+        ctx.single = pos.dim() == 2
+        ctx.want_pos = want_pos
+        ctx.save_for_backward(e, eps_r, *([g] if want_pos else []))
+        return e
+
+    @staticmethod
+    def backward(ctx, g_out):
+        e, eps_r, *rest = ctx.saved_tensors
+        gpos = None
+        if ctx.want_pos:
+            scale = g_out.to(rest[0].dtype)
+            gpos = rest[0] * (scale if ctx.single else scale[:, None, None])
+        g_eps = None
+        if ctx.needs_input_grad[3]:
+            g_eps = (-(g_out.to(torch.float64) * e).sum() / eps_r.to(e.device)).to(eps_r.device).reshape(eps_r.shape)
+        return gpos, None, None, g_eps
+
+
+class Coulomb(MartiniEnergyFunction):
+    """Reaction-field Coulomb between the charged beads, one cut-off with LJ (the system's ``r_cut``), potential shifted
+    to zero there; bonded pairs carry the reaction-field part only, plus the constant self term (include/mythos_hip.h).
+    The reference evaluates no Coulomb term - it leaves it to the GROMACS runs it drives - so this term has no
+    counterpart in mythos/energy/martini; it makes `MartiniLangevinIntegrator` frames those of the GROMACS system."""
+
+    def __init__(self, *, charges, **kwargs):
+        super().__init__(**kwargs)
+        if charges is None:
+            raise ValueError("Coulomb needs per-bead charges (a topology read from a .top or .tpr carries them)")
+        self.charges = np.ascontiguousarray(charges, dtype=np.float64)
+        if self.charges.shape != (len(self.atom_types),):
+            raise ValueError(f"charges must have shape ({len(self.atom_types)},)")
+
+    @classmethod
+    def from_topology(cls, topology: MartiniTopology, **kwargs) -> "Coulomb":
+        kwargs.setdefault("params", CoulombConfiguration())
+        return super().from_topology(topology, charges=topology.charges, **kwargs)
+
+    def _get_system(self, device):
+        fresh = self._system is None or self._system.device != device
+        system = super()._get_system(device)
+        if fresh:
+            system.set_charges(self.charges, _num(self.params[EPSILON_R]), _num(self.params[EPSILON_RF]))
+        return system
+
+    def compute_energy(self, trajectory) -> torch.Tensor:
+        if self.transform_fn is not None:
+            trajectory = self.transform_fn(trajectory)
+        pos = trajectory.center
+        if not isinstance(pos, torch.Tensor) or pos.device.type != "cuda":
+            raise ValueError("trajectory.center must be a CUDA/HIP tensor (no CPU fallback)")
+        if trajectory.box_size is None:
+            raise ValueError("MARTINI energy functions need trajectory.box_size")
+        system = self._get_system(pos.device)
+        return _CoulombOp.apply(pos.to(self.dtype), trajectory.box_size, system, _as_scalar(self.params[EPSILON_R]))
+
+    __call__ = compute_energy
+
+
 class MartiniComposedEnergyFunction:
     """Sum of MARTINI terms: the counterpart of ``ComposedEnergyFunction(energy_fns=..., strict_params=...)`` as the
     reference's MARTINI workflow builds it (examples/scripts/martini_full_reparameterization.py:147-154).
@@ -382,6 +480,6 @@ class MartiniComposedEnergyFunction:
 
 
 __all__ = [
-    "Angle", "Angle3", "AngleConfiguration", "Bond", "BondConfiguration", "LJ", "LJConfiguration",
+    "Angle", "Angle3", "AngleConfiguration", "Bond", "BondConfiguration", "Coulomb", "CoulombConfiguration", "LJ", "LJConfiguration",
     "MartiniComposedEnergyFunction", "MartiniEnergyConfiguration", "MartiniEnergyFunction", "MartiniTopology",
 ]

@@ -597,6 +597,35 @@ class MartiniSystem(_lib.Handle):
             angles.ctypes.data_as(_lib.c_int_p), dp(angle_k), dp(angle_t0), int(angle_kind), float(r_cut),
             _lib.dtype_code(dtype), self.device.index or 0,
         )
+        self.charged = False
+
+    def set_charges(self, charges=None, epsilon_r: float = 15.0, epsilon_rf: float = 0.0) -> None:
+        """Bead charges (e) for reaction-field Coulomb with the system's cut-off (mythos_martini_set_charges): relative
+        permittivity ``epsilon_r`` inside it, ``epsilon_rf`` beyond (0: infinity) - GROMACS' ``epsilon_r`` / ``epsilon_rf``.
+        ``None`` or all zeros clears them: the system then behaves as one that never had any.  An integrator of this
+        system takes the charges with its next call."""
+        q = None
+        if charges is not None:
+            q = np.ascontiguousarray(charges, dtype=np.float64)
+            if q.shape != (self.n,):
+                raise ValueError(f"charges must have shape ({self.n},)")
+        _lib.check(self._lib.mythos_martini_set_charges(self._h, None if q is None else q.ctypes.data_as(_lib.c_double_p),
+                                                        float(epsilon_r), float(epsilon_rf)), "martini_set_charges")
+        self.charged = q is not None and bool(np.any(q != 0.0))
+
+    def coulomb(self, pos: torch.Tensor, box: torch.Tensor, grads: bool = False):
+        """pos (F, N, 3) or (N, 3); box (F, 3) or (3,) -> (reaction-field Coulomb energy (F,) float64 - pairs, excluded
+        pairs and the self term -, dU/dpos or None).  Zero for a system without charges."""
+        single = pos.dim() == 2
+        pos, box = self._frames(pos, box)
+        nf = pos.shape[0]
+        e = torch.empty((nf,), dtype=torch.float64, device=self.device)
+        g = torch.empty_like(pos) if grads else None
+        _lib.check(
+            self._lib.mythos_martini_coulomb(self._h, _lib.ptr(pos), _lib.ptr(box), nf, _lib.ptr(e), _lib.ptr(g), _lib.stream(self.device)),
+            "martini_coulomb",
+        )
+        return (e[0], g[0] if grads else None) if single else (e, g)
 
     def _frames(self, pos, box):
         """``martini_frames`` of positions that are this system's: its dtype, device and number of beads."""
@@ -641,7 +670,8 @@ class MartiniSystem(_lib.Handle):
 
 class MartiniLangevinIntegrator(_MdIntegrator):
     """BAOAB Langevin dynamics of a :class:`MartiniSystem` (mythos_martini_sim_t): LJ over a device-built Verlet
-    list, bonds, angles; units nm, ps, amu, kJ/mol.  ``gamma`` is the friction rate in 1/ps."""
+    list, bonds, angles, and reaction-field Coulomb when the system holds charges; units nm, ps, amu, kJ/mol.
+    ``gamma`` is the friction rate in 1/ps."""
 
     KB = 0.0083144626  # kJ/mol/K
     _prefix = "mythos_martini_langevin"
@@ -722,12 +752,14 @@ class MartiniLangevinIntegrator(_MdIntegrator):
         s = self.system
         ns = n_steps // save_every if save_every > 0 else 0
         traj = torch.empty((ns, s.n, 3), dtype=s.dtype, device=s.device) if ns else None
-        et = torch.zeros((ns, 4), dtype=torch.float64, device=s.device) if (ns and want_energy) else None
+        # (a fifth column, the Coulomb energy, when the system holds charges: include/mythos_hip.h)
+        et = torch.zeros((ns, 5 if s.charged else 4), dtype=torch.float64, device=s.device) if (ns and want_energy) else None
         return traj, et
 
     def run(self, pos, vel, box, n_steps: int, save_every: int = 0, want_energy: bool = True):
         """Advance ``pos`` / ``vel`` (n, 3) in place -> (traj_pos (S, n, 3) or None, e_trace (S, 4) float64 or None);
-        e_trace columns: lj, bond, angle, kinetic (kJ/mol) at the saved steps (``want_energy=False``: positions only)."""
+        e_trace columns: lj, bond, angle, kinetic (kJ/mol) at the saved steps (``want_energy=False``: positions only), and
+        a fifth, the reaction-field Coulomb energy, when the system holds charges (``MartiniSystem.set_charges``)."""
         s = self.system
         self._check_state(pos, vel)
         box = np.ascontiguousarray(np.asarray(box, dtype=np.float64).reshape(3))

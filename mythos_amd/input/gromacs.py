@@ -80,6 +80,8 @@ class MartiniTopology:
     # per bead the running number of its residue, non-decreasing (where one residue ends and the next of the same name
     # begins); None on a topology built without it - the membrane observables then refuse it
     residue_index: np.ndarray | None = None
+    # per bead its charge in e (the charge column of [atoms], q of the .tpr); None: a topology built without charges
+    charges: np.ndarray | None = None
 
     @property
     def bond_names(self) -> tuple:
@@ -112,21 +114,23 @@ class MartiniTopology:
                 cur = {"atoms": [], "bonds": [], "angles": []}
                 mols[tok[0]] = cur
             elif section == "atoms" and cur is not None:
-                cur["atoms"].append((tok[1], tok[3], tok[4], int(tok[2])))  # type, residue, atom name, residue number
+                # type, residue, atom name, residue number, charge (column 7; 0 where the line stops short of it)
+                cur["atoms"].append((tok[1], tok[3], tok[4], int(tok[2]), float(tok[6]) if len(tok) > 6 else 0.0))
             elif section == "bonds" and cur is not None:
                 cur["bonds"].append((int(tok[0]) - 1, int(tok[1]) - 1))
             elif section == "angles" and cur is not None:
                 cur["angles"].append((int(tok[0]) - 1, int(tok[1]) - 1, int(tok[2]) - 1))
             elif section == "molecules":
                 order.append((tok[0], int(tok[1])))
-        types, names, res, resid, bonds, angles = [], [], [], [], [], []
+        types, names, res, resid, bonds, angles, charges = [], [], [], [], [], [], []
         base, running = 0, -1
         for name, count in order:
             mol = mols[name]
             for _ in range(count):
                 last = None  # a new molecule instance starts a new residue, whatever its residue numbers
-                for t, r, a, nr in mol["atoms"]:
+                for t, r, a, nr, q in mol["atoms"]:
                     types.append(t)
+                    charges.append(q)
                     res.append(r)
                     names.append(a)
                     if nr != last:
@@ -140,6 +144,7 @@ class MartiniTopology:
             angles=np.array(angles, dtype=np.int32).reshape(-1, 3),
             bonded_neighbors=np.array(bonds, dtype=np.int32).reshape(-1, 2),
             residue_index=np.array(resid, dtype=np.int32),
+            charges=np.array(charges, dtype=np.float64),
         )
 
     @classmethod
@@ -148,7 +153,8 @@ class MartiniTopology:
         MDAnalysis.Universe(tpr), mythos/energy/martini/base.py:76-84)."""
         t = read_tpr_topology(path)
         return cls(atom_types=t["atom_types"], atom_names=t["atom_names"], residue_names=t["residue_names"],
-                   angles=t["angles"], bonded_neighbors=t["bonds"], residue_index=t["residue_index"])
+                   angles=t["angles"], bonded_neighbors=t["bonds"], residue_index=t["residue_index"],
+                   charges=t["charges"])
 
     def tile(self, reps: int) -> "MartiniTopology":
         """The same molecules repeated ``reps`` times (for tiled boxes)."""
@@ -159,6 +165,7 @@ class MartiniTopology:
             bonded_neighbors=np.concatenate([self.bonded_neighbors + k * n for k in range(reps)]),
             residue_index=None if self.residue_index is None else np.concatenate(
                 [np.asarray(self.residue_index, dtype=np.int32) + k * (int(self.residue_index[-1]) + 1) for k in range(reps)]),
+            charges=None if self.charges is None else np.tile(np.asarray(self.charges, dtype=np.float64), reps),
         )
 
 
@@ -257,9 +264,11 @@ def read_tpr_topology(path) -> dict:
     for _ in range(r.i4()):
         r.i4()  # molecule type name
         nat, nres = r.i4(), r.i4()
-        resind = []
+        resind, charge = [], []
         for _ in range(nat):
-            r.o += 16      # m, q, mB, qB
+            r.f4()         # m
+            charge.append(r.f4())
+            r.o += 8       # mB, qB
             r.u2(), r.u2()  # type, typeB
             r.i4()         # particle type
             resind.append(r.i4())
@@ -278,8 +287,8 @@ def read_tpr_topology(path) -> dict:
         bonds = [tuple(il[k + 1:k + 3]) for ft in (_F_BONDS, _F_G96BONDS, _F_HARMONIC) for il in [ilists[ft]] for k in range(0, len(il), 3)]
         angles = [tuple(il[k + 1:k + 4]) for ft in (_F_ANGLES, _F_G96ANGLES) for il in [ilists[ft]] for k in range(0, len(il), 4)]
         moltypes.append({"names": names, "types": types, "res": [resnames[k] for k in resind], "resind": resind, "nres": nres,
-                         "bonds": bonds, "angles": angles})
-    out = {"atom_types": [], "atom_names": [], "residue_names": [], "residue_index": [], "bonds": [], "angles": []}
+                         "charges": charge, "bonds": bonds, "angles": angles})
+    out = {"atom_types": [], "atom_names": [], "residue_names": [], "residue_index": [], "charges": [], "bonds": [], "angles": []}
     base, res_base = 0, 0
     for _ in range(r.i4()):
         mt, nmol, nat_mol = moltypes[r.i4()], r.i4(), r.i4()
@@ -292,6 +301,7 @@ def read_tpr_topology(path) -> dict:
             out["residue_names"] += mt["res"]
             out["residue_index"] += [res_base + k for k in mt["resind"]]
             res_base += mt["nres"]
+            out["charges"] += mt["charges"]
             out["bonds"] += [(base + i, base + j) for i, j in mt["bonds"]]
             out["angles"] += [(base + i, base + j, base + k) for i, j, k in mt["angles"]]
             base += nat_mol
@@ -299,6 +309,7 @@ def read_tpr_topology(path) -> dict:
         raise ValueError(f"{path}: {base} atoms in the molecule blocks, {natoms} in the header")
     return {"atom_types": tuple(out["atom_types"]), "atom_names": tuple(out["atom_names"]), "residue_names": tuple(out["residue_names"]),
             "residue_index": np.array(out["residue_index"], dtype=np.int32),
+            "charges": np.array(out["charges"], dtype=np.float64),
             "bonds": np.array(out["bonds"], dtype=np.int32).reshape(-1, 2), "angles": np.array(out["angles"], dtype=np.int32).reshape(-1, 3)}
 
 

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """dev: is the device code of two builds of libmythos_hip.so the same?  The gate of a refactor that moves device text.
 
-usage: isa_diff.py [--table] parent.so branch.so      exit code 0: identical, 1: something differs (listed)
+usage: isa_diff.py [--table] [--alias REGEX=REPL] parent.so branch.so      exit code 0: identical, 1: something differs (listed)
        --table: first a markdown table of the kernels that differ - registers, scratch, instruction counts of both
+       --alias: rename the (mangled) symbols of the SECOND library that match REGEX before comparing, for a kernel template
+                that gained a defaulted parameter: its old instantiations carry the default in their names, e.g.
+                --alias 'martini_md_step_kernelI(.)Lb(.)ELb(.)ELb0EEE=martini_md_step_kernelI\1Lb\2ELb\3EEE'
 
 Compared PER CODE OBJECT (one per translation unit, in link order), not per library: an fp64 kernel that leaked into the
 fp32 unit would hide behind an identical name in a per-library comparison.  For every function symbol of a code object:
@@ -72,13 +75,15 @@ def metadata(elf):
     return out
 
 
-def describe(lib):
+def describe(lib, alias=None):
     objs = []
     with tempfile.TemporaryDirectory() as tmp:
         for k, obj in enumerate(code_objects(lib)):
             f = Path(tmp) / f"co{k}.elf"
             f.write_bytes(obj)
             objs.append((functions(f), metadata(f)))
+            if alias is not None:
+                objs[-1] = tuple({alias[0].sub(alias[1], name): v for name, v in d.items()} for d in objs[-1])
             if set(objs[-1][1]) - set(objs[-1][0]) or (objs[-1][0] and not objs[-1][1]):
                 raise SystemExit(f"isa_diff: code object {k} of {lib}: kernels in the notes and functions in the disassembly do not match")
     return objs
@@ -109,10 +114,16 @@ def main():
     want_table = "--table" in sys.argv
     if want_table:
         sys.argv.remove("--table")
+    alias = None
+    if "--alias" in sys.argv:
+        k = sys.argv.index("--alias")
+        pattern, repl = sys.argv[k + 1].split("=", 1)
+        alias = (re.compile(pattern), repl)
+        del sys.argv[k:k + 2]
     if len(sys.argv) != 3:
         print(__doc__)
         return 2
-    a, b = describe(sys.argv[1]), describe(sys.argv[2])
+    a, b = describe(sys.argv[1]), describe(sys.argv[2], alias)
     if want_table and len(a) == len(b):
         broken = table(a, b)
         print(f"\n{broken} kernel(s) with more scratch, other LDS bytes or another kernarg size")
