@@ -560,6 +560,12 @@ mythos_martini_t* mythos_martini_create(int n, const int32_t* types, int n_types
                                         const double* angle_k, const double* angle_t0, int angle_kind, double r_cut,
                                         int dtype, int device);
 void mythos_martini_destroy(mythos_martini_t* m);
+/* New values for the parameter tables of mythos_martini_create, shapes as there, in place: the handle, and every integrator
+ * bound to it with its resident state and lists, stay (an integrator takes the new tables at the head of its next call).
+ * A NULL table keeps its values.  What the reference does by writing new GROMACS parameter files before every run
+ * (mythos/simulators/gromacs/gromacs.py:70-131).  Synchronises the device. */
+int mythos_martini_set_params(mythos_martini_t* m, const double* sigma, const double* eps, const double* bond_k, const double* bond_r0,
+                              const double* angle_k, const double* angle_t0);
 int mythos_martini_energy(mythos_martini_t* m, const void* pos, const void* box, int n_frames, double* e_terms,
                           void* dU_dpos, mythos_stream_t stream);
 
@@ -673,6 +679,40 @@ int mythos_martini_langevin_get_box(const mythos_martini_sim_t* sim, double box[
 /* The box of every row the last run / advance saved, host double[*n_rows][3] (the .gro / .trr box line of a GROMACS
  * trajectory).  A row saved at an event step holds the state before the event and its box.  boxes == NULL: only *n_rows. */
 int mythos_martini_langevin_last_boxes(const mythos_martini_sim_t* sim, double* boxes, int* n_rows);
+
+/* ---- MARTINI temperature ensemble: n_rep copies of one system, own kT, box, seed and barostat history, one launch per step
+ * Replaces the loop of the reference's reparameterisation over its simulation temperatures, one GROMACS run each under
+ * the same md.mdp with only ref-t changed (examples/scripts/martini_full_reparameterization.py:347-357 on
+ * mythos/simulators/gromacs/gromacs.py:70-131).  Call a copy a replica and n the beads of one (the system's).
+ *   kT host double[n_rep], seeds host uint64[n_rep] (NULL: all 0), mass host double[n] or NULL, shared by the replicas
+ * The handle is the single integrator's and takes its entry points.  Replica r is, bit for bit, the single integrator
+ * made with kT[r] and seeds[r] and loaded with box r, as long as no call reports a recovery (a bead of ANY replica that
+ * leaves its skin halts and rebuilds all of them, after which the sums run over rows built at another step).  Shapes:
+ *   load / run / store / init_velocities   pos, vel dev real[n_rep][n][3];  box host double[n_rep][3], each checked
+ *   advance / run                          traj_pos dev real[rows][n_rep][n][3];  e_trace dev double[rows][n_rep][4 | 5]
+ *   last_boxes                             host double[*n_rows][n_rep][3]
+ *   get_rows, neighbor_stats               over the n_rep n rows; entries are bead indices inside the replica
+ * set_neighbor_policy, set_inner_list, set_barostat, set_timing and the counters apply to all replicas alike; rebuild
+ * schedule and halt are global.  mythos_martini_set_charges on the system works as for one copy.  A coupling event is one
+ * pressure launch, the single copy's barostat kernel once per replica (noise normals6(seeds[r], 0, step, 2)), one scaling launch
+ * and ONE synchronisation; if it would make any replica's box shorter than 2 (r_cut + skin) the call ends with
+ * INVALID_ARGUMENT naming the replica, and no replica is scaled.
+ * mythos_martini_langevin_pressure / get_box have their shape in the prototype and refuse an ensemble handle; the
+ * _ensemble forms take out[n_rep][10] / boxes[n_rep][3], and serve a single-copy handle as n_rep = 1.
+ * Refused (NULL / INVALID_ARGUMENT, by name): n_rep < 1, a kT that is not finite and positive, n_rep n beyond
+ * INT_MAX / 256 (the initial row stride), at load a box that the single integrator refuses.
+ * mythos_martini_ensemble_check: those checks alone for n beads per replica, the cut-off and skin given and boxes
+ * host double[n_rep][3] or NULL; touches no device. */
+mythos_martini_sim_t* mythos_martini_langevin_create_ensemble(mythos_martini_t* sys, int n_rep, double dt, const double* kT,
+                                                              double gamma, const double* mass, const uint64_t* seeds);
+int mythos_martini_ensemble_check(int n, int n_rep, const double* kT, double r_cut, double skin, const double* boxes);
+int mythos_martini_langevin_n_replicas(const mythos_martini_sim_t* sim); /* 1 for a single-copy handle */
+/* A handle made new for another run: seeds host uint64[replicas] (one for a single-copy handle), the step counter set to
+ * `step`, the resident state dropped - the next call must be a load or a run.  Settings (list policy, barostat) and buffers stay.
+ * After it the handle computes what a handle created with these seeds computes, bit for bit. */
+int mythos_martini_langevin_restart(mythos_martini_sim_t* sim, const uint64_t* seeds, int64_t step);
+int mythos_martini_langevin_pressure_ensemble(mythos_martini_sim_t* sim, double* out, mythos_stream_t stream);
+int mythos_martini_langevin_get_box_ensemble(const mythos_martini_sim_t* sim, double* boxes);
 
 /* ---- MARTINI observables: named bond lengths and triplet angles ------------------------------
  * Replaces mythos/observables/bond_distances.py:15-17, 51-69 (BondDistances / BondDistancesMapped) and

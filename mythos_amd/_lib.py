@@ -92,6 +92,7 @@ _SIGS = {
          c_int_p, c_double_p, c_double_p, C.c_int, C.c_double, C.c_int, C.c_int],
     ),
     "mythos_martini_destroy": (None, [V]),
+    "mythos_martini_set_params": (C.c_int, [V, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "mythos_martini_energy": (C.c_int, [V, V, V, C.c_int, V, V, V]),
     "mythos_martini_param_grads": (C.c_int, [V, V, V, C.c_int, V, V, V, V, V, V, V]),
     "mythos_martini_set_charges": (C.c_int, [V, c_double_p, C.c_double, C.c_double]),
@@ -115,6 +116,12 @@ _SIGS = {
     "mythos_martini_langevin_pressure": (C.c_int, [V, c_double_p, V]),
     "mythos_martini_langevin_get_box": (C.c_int, [V, c_double_p]),
     "mythos_martini_langevin_last_boxes": (C.c_int, [V, c_double_p, C.POINTER(C.c_int)]),
+    "mythos_martini_langevin_create_ensemble": (V, [V, C.c_int, C.c_double, c_double_p, C.c_double, c_double_p, C.POINTER(C.c_uint64)]),
+    "mythos_martini_ensemble_check": (C.c_int, [C.c_int, C.c_int, c_double_p, C.c_double, C.c_double, c_double_p]),
+    "mythos_martini_langevin_n_replicas": (C.c_int, [V]),
+    "mythos_martini_langevin_restart": (C.c_int, [V, C.POINTER(C.c_uint64), C.c_int64]),
+    "mythos_martini_langevin_pressure_ensemble": (C.c_int, [V, c_double_p, V]),
+    "mythos_martini_langevin_get_box_ensemble": (C.c_int, [V, c_double_p]),
     "mythos_martini_obs_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int]),
     "mythos_martini_obs_destroy": (None, [V]),
     "mythos_martini_obs_count": (C.c_int64, [V]),

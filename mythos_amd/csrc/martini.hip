@@ -577,6 +577,29 @@ mythos_martini_t* mythos_martini_create(int n, const int32_t* types, int n_types
 
 void mythos_martini_destroy(mythos_martini_t* m) { delete m; }
 
+int mythos_martini_set_params(mythos_martini_t* m, const double* sigma, const double* eps, const double* bond_k, const double* bond_r0,
+                              const double* angle_k, const double* angle_t0) {
+  if (!m) {
+    set_error("mythos_martini_set_params: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  MYTHOS_HIP_TRY(hipSetDevice(m->device));
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());  // (launches that read the tables replaced below)
+  const size_t tt = (size_t)m->n_types * m->n_types;
+  if ((sigma && m->d_sigma.upload_real(m->dtype, sigma, tt)) || (eps && m->d_eps.upload_real(m->dtype, eps, tt)) ||
+      (bond_k && m->d_bond_k.upload_real(m->dtype, bond_k, m->n_bonds)) || (bond_r0 && m->d_bond_r0.upload_real(m->dtype, bond_r0, m->n_bonds)) ||
+      (angle_k && m->d_angle_k.upload_real(m->dtype, angle_k, m->n_angles)) ||
+      (angle_t0 && m->d_angle_t0.upload_real(m->dtype, angle_t0, m->n_angles))) {
+    set_error("mythos_martini_set_params: device allocation failed");
+    return MYTHOS_ERR_HIP;
+  }
+  if (sigma) m->h_sigma.assign(sigma, sigma + tt);
+  if (eps) m->h_eps.assign(eps, eps + tt);
+  if (angle_t0) m->h_angle_t0.assign(angle_t0, angle_t0 + m->n_angles);
+  ++m->param_gen;
+  return MYTHOS_OK;
+}
+
 int mythos_martini_energy(mythos_martini_t* m, const void* pos, const void* box, int n_frames, double* e_terms,
                           void* dU_dpos, mythos_stream_t stream) {
   if (!m || !pos || !box || !e_terms || n_frames < 0) {

@@ -44,6 +44,7 @@ struct mythos_martini {
   // caller's doubles: what the device holds is these rounded to the system's precision
   std::vector<int> h_types, h_bead_bonds, h_bead_angles, h_bonds, h_angles;
   std::vector<double> h_sigma, h_eps, h_angle_t0;
+  int param_gen = 0;  // counts mythos_martini_set_params: an integrator compares it with the value its tables were derived at
   // Reaction-field Coulomb (mythos_martini_set_charges): off while no bead carries a charge.  charge_gen counts the calls
   // that changed anything: an integrator compares it with the value it last derived its own tables from.
   bool has_charge = false;

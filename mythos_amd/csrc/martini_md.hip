@@ -16,7 +16,9 @@
 // Roofline: as for oxDNA the state is cache resident; algorithmic bytes per bead per step =
 // 2 x (pos 3 + vel 3) words + 4 B type + 4 B x nbar.
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -24,6 +26,7 @@
 #include <hip/hip_ext.h>
 
 #include "cell_list.h"
+#include "martini_ensemble_checks.h"
 #include "martini_internal.h"
 #include "md_driver.h"
 #include "philox.h"
@@ -82,6 +85,32 @@ struct MmConst {
 constexpr int kCoulPref = 0, kCoulKrf = 1, kCoulCrf = 2, kCoulSelf = 3, kCoulQ = 4;
 constexpr int kCoulRec = kCoulQ + kMaxChargeClasses;
 
+// Temperature ensemble (ENS instantiations; mythos_martini_langevin_create_ensemble): R copies of the system, replica r
+// owning beads [r n, (r + 1) n) of every per-bead array, rows in LOCAL indices, topology and type tables those of one copy.
+// As for COUL the kernels' arguments do not change: the replica table travels behind the Coulomb record, at the next
+// multiple of 8 bytes - the number of replicas, then one record per replica with what MmConst and `seed` hold for a
+// single copy.  A workgroup belongs to one replica, so its record is scalar data.
+template <typename R>
+struct MmRep {
+  R lx, ly, lz, ilx, ily, ilz, kT, pad;
+  uint64_t seed;
+};
+constexpr size_t kMmRepHead = 8;  // bytes: int n_rep, int unused
+__host__ __device__ constexpr size_t mm_rep_offset(int tt, size_t real_bytes) {
+  return (((size_t)tt + kCoulRec) * real_bytes + 7) & ~size_t(7);
+}
+// the replica record of workgroup `rep`, K's box and kT replaced by it
+template <typename R>
+__device__ __forceinline__ const MmRep<R>& mm_rep_record(const R* eps, int tt, int rep, int& n_rep) {
+  const unsigned char* t = reinterpret_cast<const unsigned char*>(eps) + mm_rep_offset(tt, sizeof(R));
+  n_rep = *reinterpret_cast<const int*>(t);
+  return reinterpret_cast<const MmRep<R>*>(t + kMmRepHead)[rep];
+}
+template <typename R>
+__device__ __forceinline__ void mm_rep_apply(MmConst<R>& K, const MmRep<R>& r) {
+  K.lx = r.lx, K.ly = r.ly, K.lz = r.lz, K.ilx = r.ilx, K.ily = r.ily, K.ilz = r.ilz, K.kT = r.kT;
+}
+
 // Wave priority by phase (see md_step_kernel, langevin_step.h): MYTHOS_MM_PRIO_MAP = three decimal digits, the s_setprio
 // level of the row loop, the bonded lists, and everything behind the barrier (0 = no s_setprio)
 // (20 480 beads: 64.7 k -> 65.3 k steps/s with 310)
@@ -108,9 +137,11 @@ constexpr int mm_prio_digit(int phase) {
 // COUL: reaction-field Coulomb on top (the record behind eps, above): the pair term inside the row walk's cut-off test,
 // the excluded-pair term on the bond slots.  The instantiations without it are, instruction for instruction, those from
 // before the flag existed (scripts/isa_diff.py --alias).
-template <typename R, bool SAVE, bool EMIT = false, bool COUL = false>
+// ENS: n is the bead count of ONE replica; workgroup bid serves beads [lb PPB, (lb + 1) PPB) of replica rep, through
+// per-bead pointers moved to that replica in the prologue - the body below is the single copy's.
+template <typename R, bool SAVE, bool EMIT = false, bool COUL = false, bool ENS = false>
 __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_kernel(
-    int n, const MmConst<R> K, const typename Real4<R>::type* __restrict__ in, typename Real4<R>::type* __restrict__ out,
+    int n, const MmConst<R> K0, const typename Real4<R>::type* __restrict__ in, typename Real4<R>::type* __restrict__ out,
     typename Real4<R>::type* __restrict__ vel, const int* __restrict__ rows, const int* __restrict__ row_len,
     int row_stride, const R* __restrict__ sigma, const R* __restrict__ eps, const int* __restrict__ bead_bonds,
     const int* __restrict__ bead_angles, const int* __restrict__ bonds, const R* __restrict__ bond_k,
@@ -123,6 +154,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
   constexpr int G = kMmG, PPB = kMmPPB;
   constexpr int NT = COUL ? kMmTraceCoul : kMmTrace;
   extern __shared__ unsigned char smem_raw[];
+  MmConst<R> K = K0;
   R* s_sig2 = reinterpret_cast<R*>(smem_raw);
   R* s_eps = s_sig2 + K.n_types * K.n_types;
   R* s_c = s_eps + K.n_types * K.n_types;  // (COUL) the Coulomb record
@@ -130,11 +162,31 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
   __shared__ R s_f[PPB][4];
   __shared__ double s_e[SAVE ? PPB : 1][NT];
 
-  const int n_blocks = (n + PPB - 1) / PPB;
+  int n_blocks = (n + PPB - 1) / PPB;
+  int n_rep = 1;
+  (void)n_rep;
+  if constexpr (ENS) {
+    (void)mm_rep_record<R>(eps, K.n_types * K.n_types, 0, n_rep);
+    n_blocks *= n_rep;
+  }
   const int bid = (int)(blockIdx.x & 7) * ((n_blocks + 7) >> 3) + (int)(blockIdx.x >> 3);  // XCD-aware order
   if (bid >= n_blocks) return;
+  int lb = bid;  // the workgroup's index inside its replica
+  if constexpr (ENS) {
+    const int bpr = (n + PPB - 1) / PPB;
+    const int rep = bid / bpr;
+    lb = bid - rep * bpr;
+    const MmRep<R>& rr = mm_rep_record<R>(eps, K.n_types * K.n_types, rep, n_rep);
+    mm_rep_apply(K, rr);
+    seed = rr.seed;
+    const size_t b0 = (size_t)rep * n;
+    in += b0, out += b0, vel += b0, ref_pos += b0;
+    rows += b0 * row_stride, row_len += b0;
+    if (traj) traj += 3 * b0;
+    if constexpr (EMIT) emit_rows += b0 * row_stride, emit_len += b0;
+  }
   const int grp = threadIdx.x / G, lane = threadIdx.x % G;
-  const int i = bid * PPB + grp;
+  const int i = lb * PPB + grp;
   const bool valid = i < n;
   const int ii = valid ? i : n - 1;
   // Halt word (see md_drive, md_driver.h): set by the step that moved a bead out of its skin, or by a
@@ -327,7 +379,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
   //      (the oxDNA step kernel's arrangement, langevin_step.h).  pin_vgpr keeps the values on this side of the barrier.
   const int int_wave = (bid >> 2) & (kMmBlock / 64 - 1) & 3;
   const int il = threadIdx.x & 63;
-  const int ib = bid * PPB + il;
+  const int ib = lb * PPB + il;
   const bool integrates = (int)(threadIdx.x >> 6) == int_wave && il < PPB && ib < n;
   R z[6] = {R(0), R(0), R(0), R(0), R(0), R(0)};
   V4 x0{}, vv{}, r0{};
@@ -390,7 +442,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_md_step_ker
       double s = 0.0;
       for (int g = 0; g < PPB; ++g) s += s_e[g][threadIdx.x];
       if constexpr (COUL)
-        if (bid == 0 && threadIdx.x == 4) s += double(s_c[kCoulSelf]);
+        if (lb == 0 && threadIdx.x == 4) s += double(s_c[kCoulSelf]);
       e_part[(size_t)bid * NT + threadIdx.x] = s;
     }
   }
@@ -412,6 +464,46 @@ template <typename R>
 __global__ void mm_retype_kernel(int n, const int* __restrict__ types, typename Real4<R>::type* __restrict__ frame) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) frame[i].w = R(types[i]);
+}
+
+// Ensemble forms of the two kernels above: n beads per replica, types and inverse masses those of one copy
+template <typename R>
+__global__ void mm_pack_ens_kernel(int n, int n_rep, const R* __restrict__ pos, const R* __restrict__ v, const int* __restrict__ types,
+                                   const R* __restrict__ inv_mass, typename Real4<R>::type* __restrict__ frame,
+                                   typename Real4<R>::type* __restrict__ vel) {
+  using V4 = typename Real4<R>::type;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * n_rep) return;
+  const int l = i % n;
+  frame[i] = V4{pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2], R(types[l])};
+  vel[i] = V4{v[3 * (size_t)i], v[3 * (size_t)i + 1], v[3 * (size_t)i + 2], inv_mass[l]};
+}
+
+template <typename R>
+__global__ void mm_retype_ens_kernel(int n, int n_rep, const int* __restrict__ types, typename Real4<R>::type* __restrict__ frame) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n * n_rep) frame[i].w = R(types[i % n]);
+}
+
+// Energy-trace rows of an ensemble: workgroup r sums the blocks_per_rep partials of replica r into row r, in the order
+// reduce_trace_kernel (md_driver.h) sums those of a single copy
+template <int WIDTH>
+static __global__ __launch_bounds__(256) void mm_reduce_trace_ens_kernel(const double* __restrict__ part, int blocks_per_rep,
+                                                                         double* __restrict__ out) {
+  __shared__ double acc[16][17];
+  const int k = threadIdx.x & 15, g = threadIdx.x >> 4;
+  part += (size_t)blockIdx.x * blocks_per_rep * WIDTH;
+  double s = 0.0;
+  if (k < WIDTH)
+    for (int b = g; b < blocks_per_rep; b += 16) s += part[(size_t)b * WIDTH + k];
+  acc[g][k] = s;
+  __syncthreads();
+  if (g == 0 && k < WIDTH && out) {
+    double t = 0.0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) t += acc[j][k];
+    out[(size_t)blockIdx.x * WIDTH + k] = t;
+  }
 }
 
 template <typename R>
@@ -644,6 +736,8 @@ struct mythos_martini_sim : mythos::MdRun {
   std::vector<int> h_ctypes;
   std::vector<double> h_ceps;
   int charge_gen = 0;
+  int param_gen = 0;         // the system's at the time the tables below were derived (mythos_martini_set_params, mm_sync_params)
+  std::vector<int> h_used;   // the force field's type of every compact type
   bool coul = false;
   int trace_width() const { return coul ? kMmTraceCoul : kMmTrace; }
   DeviceBytes d_csig2, d_ceps;
@@ -661,22 +755,46 @@ struct mythos_martini_sim : mythos::MdRun {
   DeviceBuf<double> d_epart;
   double box[3] = {0, 0, 0};  // of the resident state (mythos_martini_langevin_load / advance / store)
   MmBarostat baro;            // off until mythos_martini_langevin_set_barostat: box is then constant between two loads
-  ~mythos_martini_sim() { (void)hipSetDevice(device); }  // the members, MdRun's too, free themselves on that device
+  // Temperature ensemble (mythos_martini_langevin_create_ensemble): n_rep copies of the system in one set of arrays,
+  // replica-major; 0: the single copy above, whose kT, seed and box are then the only ones.  The replica table of the
+  // kernels sits behind d_ceps' Coulomb record; it is staged in pinned memory (h_reps) and uploaded by mm_upload_reps
+  // whenever a box moved.
+  int n_rep = 0;
+  std::vector<double> rep_kT, rep_box;  // [n_rep], [n_rep][3]
+  std::vector<uint64_t> rep_seed;
+  unsigned char* h_reps = nullptr;
+  int copies() const { return n_rep > 0 ? n_rep : 1; }
+  int n_all() const { return copies() * sys->n; }  // beads of all copies
+  const double* box_of(int r) const { return n_rep > 0 ? &rep_box[3 * (size_t)r] : box; }
+  ~mythos_martini_sim() {  // the members, MdRun's too, free themselves on that device
+    (void)hipSetDevice(device);
+    if (h_reps) (void)hipHostFree(h_reps);
+  }
 };
 
 namespace mythos {
 
 template <typename R>
-static int mm_rebuild(mythos_martini_sim* sim, const typename Real4<R>::type* pos, const MmConst<R>& K, const double box[3],
-                      hipStream_t st) {
+static MmConst<R> mm_const(const mythos_martini_sim* sim, const double* box);
+
+// the rows of copy `rep` (0 for a single copy) from its n beads at pos, in its box: local indices, its slice of the row store
+template <typename R>
+static int mm_rebuild_one(mythos_martini_sim* sim, int rep, const typename Real4<R>::type* pos, hipStream_t st) {
   mythos_martini* m = sim->sys;
   VerletRows& L = sim->list;
   const int n = m->n;
   const double rl = m->r_cut + sim->skin;
+  const double* box = sim->box_of(rep);
+  const MmConst<R> K = mm_const<R>(sim, box);
+  const size_t b0 = (size_t)rep * n;
+  int* d_rows = L.d_rows.get() + b0 * L.stride;
+  int* d_row_len = sim->d_row_len.get() + b0;
+  typename Real4<R>::type* d_ref = (typename Real4<R>::type*)sim->ref_pos.get() + b0;
+  pos += b0;
   CellGrid<R> g;
   if (!cell_grid(g, n, rl, box)) {
     hipLaunchKernelGGL(mm_build_rows_allpairs_kernel<R>, dim3((n + 3) / 4), dim3(256), 0, st, n, pos, K, R(rl * rl), m->d_excl.get(),
-                       L.d_rows.get(), sim->d_row_len.get(), L.stride, L.d_overflow.get(), (typename Real4<R>::type*)sim->ref_pos.get());
+                       d_rows, d_row_len, L.stride, L.d_overflow.get(), d_ref);
     return 0;
   }
   // one table slot per cell (no hashing) whenever the grid is not much larger than the system
@@ -689,7 +807,15 @@ static int mm_rebuild(mythos_martini_sim* sim, const typename Real4<R>::type* po
   cell_bins_build<R, true>(n, reinterpret_cast<const R*>(pos), g, bins, L.d_overflow.get(), true, st);
   hipLaunchKernelGGL((mm_build_rows_cells_kernel<R, kMmRowG>), dim3((n + 256 / kMmRowG - 1) / (256 / kMmRowG)), dim3(256), 0, st, n, pos, K, g,
                      R(rl * rl), m->d_excl.get(), bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H,
-                     L.d_rows.get(), sim->d_row_len.get(), L.stride, L.d_overflow.get(), (typename Real4<R>::type*)sim->ref_pos.get());
+                     d_rows, d_row_len, L.stride, L.d_overflow.get(), d_ref);
+  return 0;
+}
+
+// Every copy's rows, one after the other through the one cell table: each build is the single copy's, so are its rows.
+template <typename R>
+static int mm_rebuild(mythos_martini_sim* sim, const typename Real4<R>::type* pos, hipStream_t st) {
+  for (int r = 0; r < sim->copies(); ++r)
+    if (int rc = mm_rebuild_one<R>(sim, r, pos, st)) return rc;
   return 0;
 }
 
@@ -698,10 +824,10 @@ static bool mm_inner_on(const mythos_martini_sim* sim) {
   return sim->inner_margin > 0 && sim->inner_margin < sim->skin && sim->inner_every >= 2;
 }
 
+// (an ensemble's step and pressure kernels take box and kT from the replica table instead: box_of(0) stands in)
 template <typename R>
-static MmConst<R> mm_const(const mythos_martini_sim* sim) {
+static MmConst<R> mm_const(const mythos_martini_sim* sim, const double* box) {
   const mythos_martini* m = sim->sys;
-  const double* box = sim->box;
   MmConst<R> K;
   K.lx = R(box[0]), K.ly = R(box[1]), K.lz = R(box[2]);
   K.ilx = R(1.0 / box[0]), K.ily = R(1.0 / box[1]), K.ilz = R(1.0 / box[2]);
@@ -716,11 +842,102 @@ static MmConst<R> mm_const(const mythos_martini_sim* sim) {
   return K;
 }
 
+// Ensemble: the replica table (box, 1 / box, kT, seed per replica, as mm_const rounds them for a single copy) from the
+// pinned staging buffer to the device, behind st.  The host writes the staging buffer only while st is idle: at create,
+// at load, and behind the synchronisation of a coupling event.
+static int mm_upload_reps(mythos_martini_sim* sim, hipStream_t st) {
+  const int nr = sim->n_rep;
+  const bool f32 = sim->sys->dtype == MYTHOS_F32;
+  const size_t rec = f32 ? sizeof(MmRep<float>) : sizeof(MmRep<double>), tab = kMmRepHead + nr * rec;
+  if (!sim->h_reps) MYTHOS_HIP_TRY(hipHostMalloc((void**)&sim->h_reps, tab, hipHostMallocDefault));
+  unsigned char* h = sim->h_reps;
+  const int head[2] = {nr, 0};
+  std::memcpy(h, head, kMmRepHead);
+  for (int r = 0; r < nr; ++r) {
+    const double* b = sim->box_of(r);
+    const double kT = sim->rep_kT[r];
+    if (f32) {
+      const MmRep<float> q{float(b[0]), float(b[1]), float(b[2]), float(1.0 / b[0]), float(1.0 / b[1]), float(1.0 / b[2]), float(kT), 0.0f, sim->rep_seed[r]};
+      std::memcpy(h + kMmRepHead + r * rec, &q, rec);
+    } else {
+      const MmRep<double> q{b[0], b[1], b[2], 1.0 / b[0], 1.0 / b[1], 1.0 / b[2], kT, 0.0, sim->rep_seed[r]};
+      std::memcpy(h + kMmRepHead + r * rec, &q, rec);
+    }
+  }
+  const size_t off = mm_rep_offset(sim->n_ctypes * sim->n_ctypes, f32 ? sizeof(float) : sizeof(double));
+  MYTHOS_HIP_TRY(hipMemcpyAsync((unsigned char*)sim->d_ceps.get() + off, h, tab, hipMemcpyHostToDevice, st));
+  return MYTHOS_OK;
+}
+
+// The epsilon table with the Coulomb record behind it (ce: n_ctypes^2 + kCoulRec doubles) in the system's precision; for
+// an ensemble with room for the replica table behind that, filled at once.
+static int mm_upload_ceps(mythos_martini_sim* sim, const std::vector<double>& ce) {
+  const int dtype = sim->sys->dtype;
+  if (sim->n_rep == 0) return sim->d_ceps.upload_real(dtype, ce.data(), ce.size());
+  const bool f32 = dtype == MYTHOS_F32;
+  const size_t w = f32 ? sizeof(float) : sizeof(double), rec = f32 ? sizeof(MmRep<float>) : sizeof(MmRep<double>);
+  if (int rc = sim->d_ceps.alloc(mm_rep_offset(sim->n_ctypes * sim->n_ctypes, w) + kMmRepHead + sim->n_rep * rec)) return rc;
+  if (f32) {
+    const std::vector<float> tmp(ce.begin(), ce.end());
+    MYTHOS_HIP_TRY(hipMemcpy(sim->d_ceps.get(), tmp.data(), tmp.size() * w, hipMemcpyHostToDevice));
+  } else {
+    MYTHOS_HIP_TRY(hipMemcpy(sim->d_ceps.get(), ce.data(), ce.size() * w, hipMemcpyHostToDevice));
+  }
+  if (int rc = mm_upload_reps(sim, nullptr)) return rc;
+  MYTHOS_HIP_TRY(hipStreamSynchronize(nullptr));
+  return MYTHOS_OK;
+}
+
+// What the step kernels read in place of the system's own tables, derived from the system's reals AS THE DEVICE HOLDS
+// THEM (the caller's doubles rounded to the system's precision): sigma^2 and epsilon of the types that occur (cs, ce:
+// [C][C], C = max(1, used.size())), and per angle cos(theta0) for the G96 form, theta0 for the harmonic one.
+static void mm_param_tables(const mythos_martini* sys, const std::vector<int>& used, std::vector<double>& cs, std::vector<double>& ce,
+                            std::vector<double>& ref) {
+  const int dtype = sys->dtype, T = sys->n_types;
+  auto rounded = [dtype](double v) { return dtype == MYTHOS_F32 ? double(float(v)) : v; };
+  const size_t C = std::max<size_t>(1, used.size());
+  cs.assign(C * C, 0.0), ce.assign(C * C, 0.0);
+  for (size_t p = 0; p < used.size(); ++p)
+    for (size_t q = 0; q < used.size(); ++q) {
+      // (squared in the kernel's own precision, as the kernel did)
+      const double sg = rounded(sys->h_sigma[(size_t)used[p] * T + used[q]]);
+      cs[p * C + q] = dtype == MYTHOS_F32 ? double(float(sg) * float(sg)) : sg * sg;
+      ce[p * C + q] = rounded(sys->h_eps[(size_t)used[p] * T + used[q]]);
+    }
+  ref.resize(sys->h_angle_t0.size());
+  for (size_t a = 0; a < ref.size(); ++a) {
+    const double t0 = rounded(sys->h_angle_t0[a]);
+    ref[a] = sys->angle_kind == 0 ? std::cos(t0) : t0;
+  }
+}
+
+static int mm_upload_ceps(mythos_martini_sim* sim, const std::vector<double>& ce);
+
+// mythos_martini_set_params replaced the system's parameter tables: the integrator's own follow at the head of its next
+// call, in place - the handle, its resident state and its lists stay.  The epsilon table travels with the Coulomb record
+// (and an ensemble's replica table), so mm_sync_charges is made to lay all of it out again.  Rare: synchronises.
+static int mm_sync_params(mythos_martini_sim* sim, hipStream_t st) {
+  const mythos_martini* m = sim->sys;
+  if (sim->param_gen == m->param_gen) return MYTHOS_OK;
+  MYTHOS_HIP_TRY(hipStreamSynchronize(st));
+  std::vector<double> cs, ce, ref;
+  mm_param_tables(m, sim->h_used, cs, ce, ref);
+  if (sim->d_csig2.upload_real(m->dtype, cs.data(), cs.size()) || sim->d_angle_ref.upload_real(m->dtype, ref.data(), ref.size())) {
+    set_error("mythos_martini_langevin: device allocation failed");
+    return MYTHOS_ERR_HIP;
+  }
+  sim->h_ceps = ce;
+  sim->charge_gen = m->charge_gen - 1;
+  sim->param_gen = m->param_gen;
+  return MYTHOS_OK;
+}
+
 // The integrator's view of the system's charges, brought up to date at the head of every call (load, advance, store,
 // pressure) when mythos_martini_set_charges has changed them since: the charge classes, the packed types and the Coulomb
 // record behind the epsilon table.  A resident frame is retyped in place.  Rare: synchronises.
 static int mm_sync_charges(mythos_martini_sim* sim, hipStream_t st) {
   const mythos_martini* m = sim->sys;
+  if (int rc = mm_sync_params(sim, st)) return rc;
   if (sim->charge_gen == m->charge_gen) return MYTHOS_OK;
   MYTHOS_HIP_TRY(hipStreamSynchronize(st));  // (launches that read the tables replaced below)
   const int n = m->n;
@@ -749,12 +966,19 @@ static int mm_sync_charges(mythos_martini_sim* sim, hipStream_t st) {
     ce.insert(ce.end(), tab.begin(), tab.end());
   }
   ce.resize(sim->h_ceps.size() + kCoulRec, 0.0);
-  if (sim->d_ctypes.upload(packed) || sim->d_ceps.upload_real(m->dtype, ce.data(), ce.size())) {
+  if (sim->d_ctypes.upload(packed) || mm_upload_ceps(sim, ce)) {
     set_error("mythos_martini_langevin: device allocation failed");
     return MYTHOS_ERR_HIP;
   }
   sim->coul = m->has_charge;
-  if (sim->resident) {
+  if (sim->resident && sim->n_rep > 0) {
+    const int tb = (sim->n_all() + 255) / 256;
+    if (m->dtype == MYTHOS_F32)
+      hipLaunchKernelGGL(mm_retype_ens_kernel<float>, dim3(tb), dim3(256), 0, st, n, sim->n_rep, sim->d_ctypes.get(), (float4*)sim->frame[sim->cur].get());
+    else
+      hipLaunchKernelGGL(mm_retype_ens_kernel<double>, dim3(tb), dim3(256), 0, st, n, sim->n_rep, sim->d_ctypes.get(), (double4*)sim->frame[sim->cur].get());
+    MYTHOS_HIP_TRY(hipGetLastError());
+  } else if (sim->resident) {
     const int tb = (n + 255) / 256;
     if (m->dtype == MYTHOS_F32)
       hipLaunchKernelGGL(mm_retype_kernel<float>, dim3(tb), dim3(256), 0, st, n, sim->d_ctypes.get(), (float4*)sim->frame[sim->cur].get());
@@ -762,20 +986,28 @@ static int mm_sync_charges(mythos_martini_sim* sim, hipStream_t st) {
       hipLaunchKernelGGL(mm_retype_kernel<double>, dim3(tb), dim3(256), 0, st, n, sim->d_ctypes.get(), (double4*)sim->frame[sim->cur].get());
     MYTHOS_HIP_TRY(hipGetLastError());
   }
-  if (int rc = sim->d_epart.grow((size_t)((n + kMmPPB - 1) / kMmPPB) * kMmTraceCoul)) return rc;
+  if (int rc = sim->d_epart.grow((size_t)sim->copies() * ((n + kMmPPB - 1) / kMmPPB) * kMmTraceCoul)) return rc;
   sim->charge_gen = m->charge_gen;
   return MYTHOS_OK;
 }
 
 // caller's (n, 3) arrays -> the resident frame; the list of a previous state does not carry over
 template <typename R>
-static int mm_load_typed(mythos_martini_sim* sim, const R* pos, const R* v, const double box[3], hipStream_t st) {
+static int mm_load_typed(mythos_martini_sim* sim, const R* pos, const R* v, const double* box, hipStream_t st) {
   using V4 = typename Real4<R>::type;
   mythos_martini* m = sim->sys;
   const int n = m->n, tb = (n + 255) / 256;
-  for (int k = 0; k < 3; ++k) sim->box[k] = box[k];
-  hipLaunchKernelGGL(mm_pack_kernel<R>, dim3(tb), dim3(256), 0, st, n, pos, v, sim->d_ctypes.get(), (const R*)sim->d_inv_mass.get(),
-                     (V4*)sim->frame[0].get(), (V4*)sim->vel.get());
+  if (sim->n_rep > 0) {  // box: [n_rep][3]
+    MYTHOS_HIP_TRY(hipStreamSynchronize(st));  // (the staging buffer of the replica tables)
+    sim->rep_box.assign(box, box + 3 * (size_t)sim->n_rep);
+    if (int rc = mm_upload_reps(sim, st)) return rc;
+    hipLaunchKernelGGL(mm_pack_ens_kernel<R>, dim3((sim->n_all() + 255) / 256), dim3(256), 0, st, n, sim->n_rep, pos, v, sim->d_ctypes.get(),
+                       (const R*)sim->d_inv_mass.get(), (V4*)sim->frame[0].get(), (V4*)sim->vel.get());
+  } else {
+    for (int k = 0; k < 3; ++k) sim->box[k] = box[k];
+    hipLaunchKernelGGL(mm_pack_kernel<R>, dim3(tb), dim3(256), 0, st, n, pos, v, sim->d_ctypes.get(), (const R*)sim->d_inv_mass.get(),
+                       (V4*)sim->frame[0].get(), (V4*)sim->vel.get());
+  }
   MYTHOS_HIP_TRY(hipGetLastError());
   sim->cur = 0;
   sim->resident = true;
@@ -794,18 +1026,19 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
                             hipStream_t st) {
   using V4 = typename Real4<R>::type;
   mythos_martini* m = sim->sys;
-  const int n = m->n;
-  const int blocks = (n + kMmPPB - 1) / kMmPPB, grid = 8 * ((blocks + 7) / 8);
-  const MmConst<R> K = mm_const<R>(sim);
-  const double* box = sim->box;
+  const int n = m->n, n_all = sim->n_all();  // (the kernels take n, the beads of one copy)
+  const bool ens = sim->n_rep > 0;
+  const int blocks_per_rep = (n + kMmPPB - 1) / kMmPPB;
+  const int blocks = sim->copies() * blocks_per_rep, grid = 8 * ((blocks + 7) / 8);
+  const MmConst<R> K = mm_const<R>(sim, sim->box_of(0));
   V4* fr[2] = {(V4*)sim->frame[0].get(), (V4*)sim->frame[1].get()};
   V4* vel = (V4*)sim->vel.get();
   const bool inner_on = mm_inner_on(sim);
   // the pruned rows share the Verlet rows' stride (a pruned row is a subset of its row: it cannot overflow)
   auto ensure_inner = [&]() -> int {
     if (!inner_on) return 0;
-    if (int rc = sim->d_row_len_in.grow((size_t)n)) return rc;
-    return sim->d_rows_in.grow((size_t)n * sim->list.stride);  // (a stride only grows)
+    if (int rc = sim->d_row_len_in.grow((size_t)n_all)) return rc;
+    return sim->d_rows_in.grow((size_t)n_all * sim->list.stride);  // (a stride only grows)
   };
   if (int rc = ensure_inner()) return rc;
   const bool coul = sim->coul;
@@ -814,7 +1047,7 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
     const int cur = row.cur;
     const R kick_close = R(row.kick_close);
     const int do_step = row.do_step;
-    R* tp = ((row.save || row.save_next) && traj_pos) ? traj_pos + (size_t)row.sidx * n * 3 : nullptr;
+    R* tp = ((row.save || row.save_next) && traj_pos) ? traj_pos + (size_t)row.sidx * n_all * 3 : nullptr;
     // pruned rows: the launch d steps after the Verlet rows were built prunes when d is a multiple of inner_every (so
     // the first launch on new rows does) and walks the pruned rows otherwise
     const bool emit = inner_on && ((k - row.built_at) % sim->inner_every == 0);
@@ -829,22 +1062,33 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
       (const R*)sim->d_angle_ref.get(), kick_close, do_step, sim->seed, (uint64_t)(sim->step + k),                        \
       (const V4*)sim->ref_pos.get(), sim->d_flags.get(), tp, sim->d_epart.get(), sim->list.d_overflow.get(), k,           \
       emit_rows, emit_len, sim->d_bb_partner.get(), sim->d_ba_partner.get()
-    auto go_coul = [&](auto save_tag, auto emit_tag, auto coul_tag) {
+    auto go_ens = [&](auto save_tag, auto emit_tag, auto coul_tag, auto ens_tag) {
       constexpr bool SV = decltype(save_tag)::value, EM = decltype(emit_tag)::value, CL = decltype(coul_tag)::value;
+      constexpr bool EN = decltype(ens_tag)::value;
       if (row.ea) {
-        hipExtLaunchKernelGGL((martini_md_step_kernel<R, SV, EM, CL>), dim3(grid), dim3(kMmBlock), lds, st, row.ea, row.eb, 0, MM_ARGS);
+        hipExtLaunchKernelGGL((martini_md_step_kernel<R, SV, EM, CL, EN>), dim3(grid), dim3(kMmBlock), lds, st, row.ea, row.eb, 0, MM_ARGS);
       } else {
-        hipLaunchKernelGGL((martini_md_step_kernel<R, SV, EM, CL>), dim3(grid), dim3(kMmBlock), lds, st, MM_ARGS);
+        hipLaunchKernelGGL((martini_md_step_kernel<R, SV, EM, CL, EN>), dim3(grid), dim3(kMmBlock), lds, st, MM_ARGS);
       }
     };
 #undef MM_ARGS
+    // an ensemble: the instantiations that read the replica table
+    auto go_coul = [&](auto save_tag, auto emit_tag, auto coul_tag) {
+      if (ens) go_ens(save_tag, emit_tag, coul_tag, std::true_type{}); else go_ens(save_tag, emit_tag, coul_tag, std::false_type{});
+    };
     // the system holds charges: the instantiations with reaction-field Coulomb
     auto go = [&](auto save_tag, auto emit_tag) {
       if (coul) go_coul(save_tag, emit_tag, std::true_type{}); else go_coul(save_tag, emit_tag, std::false_type{});
     };
     if (row.save) {
       if (emit) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{});
-      if (coul)
+      if (ens && coul)
+        hipLaunchKernelGGL(mm_reduce_trace_ens_kernel<kMmTraceCoul>, dim3(sim->n_rep), dim3(256), 0, st, sim->d_epart.get(), blocks_per_rep,
+                           e_trace + (size_t)row.sidx * sim->n_rep * kMmTraceCoul);
+      else if (ens)
+        hipLaunchKernelGGL(mm_reduce_trace_ens_kernel<kMmTrace>, dim3(sim->n_rep), dim3(256), 0, st, sim->d_epart.get(), blocks_per_rep,
+                           e_trace + (size_t)row.sidx * sim->n_rep * kMmTrace);
+      else if (coul)
         hipLaunchKernelGGL(reduce_trace_kernel<kMmTraceCoul>, dim3(1), dim3(256), 0, st, sim->d_epart.get(), blocks,
                            e_trace + (size_t)row.sidx * kMmTraceCoul);
       else
@@ -868,10 +1112,10 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
                      std::to_string(sim->inner_every) + " steps";
   d.st = st;
   return md_drive(
-      *sim, d, launch_step, [&](int buf) { return mm_rebuild<R>(sim, fr[buf], K, box, st); },
+      *sim, d, launch_step, [&](int buf) { return mm_rebuild<R>(sim, fr[buf], st); },
       [&](int buf) -> int {
-        auto build = [&] { return mm_rebuild<R>(sim, fr[buf], K, box, st); };
-        if (int rc = list_build_until_fit(sim->list, n, build, true, "mythos_martini_langevin_run: neighbour build", st)) return rc;
+        auto build = [&] { return mm_rebuild<R>(sim, fr[buf], st); };
+        if (int rc = list_build_until_fit(sim->list, n_all, build, true, "mythos_martini_langevin_run: neighbour build", st)) return rc;
         return ensure_inner();  // (the rows may have grown)
       },
       [] { return 0; });  // (no MARTINI launch aborts)
@@ -881,7 +1125,7 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
 template <typename R>
 static int mm_store_typed(mythos_martini_sim* sim, R* pos, R* v, hipStream_t st) {
   using V4 = typename Real4<R>::type;
-  const int n = sim->sys->n;
+  const int n = sim->n_all();
   const int rc = sim->open ? mm_advance_typed<R>(sim, 0, 0, true, nullptr, nullptr, st) : MYTHOS_OK;
   hipLaunchKernelGGL(mm_unpack_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const V4*)sim->frame[sim->cur].get(), (const V4*)sim->vel.get(), pos, v);
   MYTHOS_HIP_TRY(hipGetLastError());
@@ -896,23 +1140,34 @@ extern "C" {
 
 void mythos_martini_langevin_destroy(mythos_martini_sim_t* s) { delete s; }
 
-mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, double dt, double kT, double gamma,
-                                                     const double* mass, uint64_t seed) {
-  if (!sys || !(dt > 0) || !(kT > 0) || !(gamma >= 0)) {
-    set_error("mythos_martini_langevin_create: invalid argument");
-    return nullptr;
-  }
-  if (select_device(sys->device, "mythos_martini_langevin_create")) return nullptr;
+}  // extern "C"
+
+namespace {
+
+// n_rep = 0: the single copy of mythos_martini_langevin_create (kT, seeds: one value each)
+mythos_martini_sim_t* mm_create(mythos_martini_t* sys, int n_rep, double dt, const double* kTs, double gamma, const double* mass,
+                                const uint64_t* seeds, const char* who) {
+  const double kT = kTs[0];
+  const uint64_t seed = seeds ? seeds[0] : 0;
+  if (select_device(sys->device, who)) return nullptr;
   auto s = std::make_unique<mythos_martini_sim>();
   s->sys = sys, s->device = sys->device, s->dt = dt, s->kT = kT, s->gamma = gamma, s->seed = seed;
   s->rebuild_every = 10;
+  if (n_rep > 0) {
+    s->n_rep = n_rep;
+    s->rep_kT.assign(kTs, kTs + n_rep);
+    s->rep_box.assign(3 * (size_t)n_rep, 0.0);
+    s->rep_seed.assign((size_t)n_rep, 0);
+    for (int r = 0; seeds && r < n_rep; ++r) s->rep_seed[r] = seeds[r];
+  }
+  const int copies = s->copies();
   const int n = sys->n, dtype = sys->dtype;
   const size_t w = dtype == MYTHOS_F32 ? sizeof(float) : sizeof(double);
   std::vector<double> im(n);
   for (int i = 0; i < n; ++i) {
     const double mi = mass ? mass[i] : 72.0;  // MARTINI's standard bead mass (amu)
     if (!(mi > 0)) {
-      set_error("mythos_martini_langevin_create: masses must be positive");
+      set_error(std::string(who) + ": masses must be positive");
       return nullptr;
     }
     im[i] = 1.0 / mi;
@@ -929,10 +1184,7 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
       const int role = ba[k] & 3;
       pa[k] = role == 0 ? int2{t[1], t[2]} : (role == 1 ? int2{t[0], t[2]} : int2{t[0], t[1]});
     }
-  // The tables below derive from the system's reals AS THE DEVICE HOLDS THEM: the caller's doubles rounded to the
-  // system's precision.
-  auto rounded = [dtype](double v) { return dtype == MYTHOS_F32 ? double(float(v)) : v; };
-  // the compact type tables
+  // the compact type tables (mm_param_tables)
   const int T = sys->n_types;
   std::vector<int> types = sys->h_types, cmap(T, -1), used;
   for (int t : types)
@@ -940,36 +1192,56 @@ mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, doub
   for (int t = 0; t < T; ++t)
     if (cmap[t] == 0) cmap[t] = (int)used.size(), used.push_back(t);
   const int C = std::max<int>(1, (int)used.size());
-  std::vector<double> cs((size_t)C * C, 0.0), ce((size_t)C * C, 0.0);
-  for (size_t p = 0; p < used.size(); ++p)
-    for (size_t q = 0; q < used.size(); ++q) {
-      // (squared in the kernel's own precision, as the kernel did)
-      const double sg = rounded(sys->h_sigma[(size_t)used[p] * T + used[q]]);
-      cs[p * C + q] = dtype == MYTHOS_F32 ? double(float(sg) * float(sg)) : sg * sg;
-      ce[p * C + q] = rounded(sys->h_eps[(size_t)used[p] * T + used[q]]);
-    }
+  std::vector<double> cs, ce, ref;
+  mm_param_tables(sys, used, cs, ce, ref);
   for (int& t : types) t = (t >= 0 && t < T) ? cmap[t] : 0;
   s->n_ctypes = C;
   s->h_ctypes = types;
-  for (double e : ce) s->h_ceps.push_back(rounded(e));
+  s->h_used = used;
+  s->h_ceps = ce;
+  s->param_gen = sys->param_gen;
   ce.resize(ce.size() + kCoulRec, 0.0);  // the Coulomb record, all zero until the system holds charges (mm_sync_charges)
-  std::vector<double> ref(sys->h_angle_t0.size());
-  for (size_t a = 0; a < ref.size(); ++a) {
-    const double t0 = rounded(sys->h_angle_t0[a]);
-    ref[a] = sys->angle_kind == 0 ? std::cos(t0) : t0;
-  }
-  const int blocks = (n + kMmPPB - 1) / kMmPPB;
-  if (!md_run_create(*s) || s->frame[0].alloc((size_t)n * 4 * w) || s->frame[1].alloc((size_t)n * 4 * w) || s->vel.alloc((size_t)n * 4 * w) ||
-      s->ref_pos.alloc((size_t)n * 4 * w) || rows_reserve(s->list, n, 256) || s->d_row_len.alloc((size_t)n) ||
+  const size_t na = (size_t)copies * n;  // per-bead state: every copy's
+  const int blocks = copies * ((n + kMmPPB - 1) / kMmPPB);
+  if (!md_run_create(*s) || s->frame[0].alloc(na * 4 * w) || s->frame[1].alloc(na * 4 * w) || s->vel.alloc(na * 4 * w) ||
+      s->ref_pos.alloc(na * 4 * w) || rows_reserve(s->list, (int)na, kMmStride0) || s->d_row_len.alloc(na) ||
       s->list.d_overflow.alloc(kOverflowWords) || s->d_epart.alloc((size_t)blocks * kMmTrace) ||
       s->d_inv_mass.upload_real(dtype, im.data(), im.size()) || s->d_bb_partner.upload(pb) || s->d_ba_partner.upload(pa) ||
       s->d_ctypes.upload(types) || s->d_csig2.upload_real(dtype, cs.data(), cs.size()) ||
-      s->d_ceps.upload_real(dtype, ce.data(), ce.size()) || s->d_angle_ref.upload_real(dtype, ref.data(), ref.size()) ||
+      mm_upload_ceps(s.get(), ce) || s->d_angle_ref.upload_real(dtype, ref.data(), ref.size()) ||
       hipMemset(s->list.d_overflow.get(), 0, kOverflowWords * sizeof(int)) != hipSuccess) {
-    set_error("mythos_martini_langevin_create: device allocation failed");
+    set_error(std::string(who) + ": device allocation failed");
     return nullptr;
   }
   return s.release();
+}
+
+}  // namespace
+
+extern "C" {
+
+mythos_martini_sim_t* mythos_martini_langevin_create(mythos_martini_t* sys, double dt, double kT, double gamma,
+                                                     const double* mass, uint64_t seed) {
+  if (!sys || !(dt > 0) || !(kT > 0) || !(gamma >= 0)) {
+    set_error("mythos_martini_langevin_create: invalid argument");
+    return nullptr;
+  }
+  return mm_create(sys, 0, dt, &kT, gamma, mass, &seed, "mythos_martini_langevin_create");
+}
+
+int mythos_martini_ensemble_check(int n, int n_rep, const double* kT, double r_cut, double skin, const double* boxes) {
+  return mm_ensemble_check(n, n_rep, kT, r_cut, skin, boxes, "mythos_martini_ensemble_check");
+}
+
+mythos_martini_sim_t* mythos_martini_langevin_create_ensemble(mythos_martini_t* sys, int n_rep, double dt, const double* kT, double gamma,
+                                                              const double* mass, const uint64_t* seeds) {
+  const char* who = "mythos_martini_langevin_create_ensemble";
+  if (!sys || !(dt > 0) || !(gamma >= 0)) {
+    set_error(std::string(who) + ": invalid argument");
+    return nullptr;
+  }
+  if (mm_ensemble_check(sys->n, n_rep, kT, sys->r_cut, 0.0, nullptr, who)) return nullptr;
+  return mm_create(sys, n_rep, dt, kT, gamma, mass, seeds, who);
 }
 
 int mythos_martini_langevin_set_neighbor_policy(mythos_martini_sim_t* s, double skin, int rebuild_every) {
@@ -1001,28 +1273,30 @@ int mythos_martini_langevin_init_velocities(mythos_martini_sim_t* s, void* vel, 
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
-  if (s->sys->dtype == MYTHOS_F32)
-    hipLaunchKernelGGL(mm_init_velocities_kernel<float>, dim3(1), dim3(256), 0, (hipStream_t)stream, s->sys->n, float(s->kT),
-                       (const float*)s->d_inv_mass.get(), s->seed, (float*)vel);
-  else
-    hipLaunchKernelGGL(mm_init_velocities_kernel<double>, dim3(1), dim3(256), 0, (hipStream_t)stream, s->sys->n, s->kT,
-                       (const double*)s->d_inv_mass.get(), s->seed, (double*)vel);
+  // (an ensemble: replica r's slice of vel [n_rep][n][3] is what a single integrator with its kT and seed draws)
+  for (int r = 0; r < s->copies(); ++r) {
+    const double kT = s->n_rep > 0 ? s->rep_kT[r] : s->kT;
+    const uint64_t seed = s->n_rep > 0 ? s->rep_seed[r] : s->seed;
+    const size_t off = 3 * (size_t)r * s->sys->n;
+    if (s->sys->dtype == MYTHOS_F32)
+      hipLaunchKernelGGL(mm_init_velocities_kernel<float>, dim3(1), dim3(256), 0, (hipStream_t)stream, s->sys->n, float(kT),
+                         (const float*)s->d_inv_mass.get(), seed, (float*)vel + off);
+    else
+      hipLaunchKernelGGL(mm_init_velocities_kernel<double>, dim3(1), dim3(256), 0, (hipStream_t)stream, s->sys->n, kT,
+                         (const double*)s->d_inv_mass.get(), seed, (double*)vel + off);
+  }
   MYTHOS_HIP_TRY(hipGetLastError());
   return MYTHOS_OK;
 }
 
 namespace {
 
+// (an ensemble: box [n_rep][3], every replica's checked, the message names the replica)
 int mm_check_box(const mythos_martini_sim_t* s, const double* box, const char* who) {
-  if (!box || !(box[0] > 0) || !(box[1] > 0) || !(box[2] > 0)) {
-    set_error(std::string(who) + ": invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
   const double rl = s->sys->r_cut + s->skin;
-  if (2.0 * rl > std::min(box[0], std::min(box[1], box[2]))) {
-    set_error(std::string(who) + ": the box is smaller than twice (r_cut + skin): minimum image breaks down");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
+  if (s->n_rep == 0) return mm_box_fits(box, rl, who);
+  for (int r = 0; r < s->n_rep; ++r)
+    if (int rc = mm_box_fits(box ? box + 3 * (size_t)r : nullptr, rl, std::string(who) + ": replica " + std::to_string(r))) return rc;
   return MYTHOS_OK;
 }
 
@@ -1107,6 +1381,20 @@ int mythos_martini_langevin_store(mythos_martini_sim_t* s, void* pos, void* vel,
 
 int64_t mythos_martini_langevin_get_step(const mythos_martini_sim_t* s) { return md_get_step(s); }
 
+int mythos_martini_langevin_restart(mythos_martini_sim_t* s, const uint64_t* seeds, int64_t step) {
+  if (!s || !seeds || step < 0) {
+    set_error("mythos_martini_langevin_restart: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  s->seed = seeds[0];
+  for (int r = 0; r < s->n_rep; ++r) s->rep_seed[r] = seeds[r];
+  s->step = step;
+  s->resident = false;  // (an ensemble's replica table takes the seeds at the load that has to follow)
+  s->list_valid = false;
+  s->open = false;
+  return MYTHOS_OK;
+}
+
 int mythos_martini_langevin_last_rebuilds(const mythos_martini_sim_t* s, int* scheduled) {
   return md_last_count(s, &MdRun::last_rebuilds, scheduled, "mythos_martini_langevin_last_rebuilds");
 }
@@ -1122,7 +1410,7 @@ int mythos_martini_langevin_neighbor_stats(const mythos_martini_sim_t* s, int* m
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
-  return row_stats(s->d_row_len.get(), s->sys->n, 0, max_row, mean_row);
+  return row_stats(s->d_row_len.get(), s->n_all(), 0, max_row, mean_row);
 }
 
 int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* s, int which, int32_t* rows, int32_t* row_len, int* stride) {
@@ -1141,8 +1429,8 @@ int mythos_martini_langevin_get_rows(const mythos_martini_sim_t* s, int which, i
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
   MYTHOS_HIP_TRY(hipDeviceSynchronize());
-  if (rows) MYTHOS_HIP_TRY(hipMemcpy(rows, d_rows, (size_t)s->sys->n * s->list.stride * sizeof(int), hipMemcpyDeviceToHost));
-  if (row_len) MYTHOS_HIP_TRY(hipMemcpy(row_len, d_len, (size_t)s->sys->n * sizeof(int), hipMemcpyDeviceToHost));
+  if (rows) MYTHOS_HIP_TRY(hipMemcpy(rows, d_rows, (size_t)s->n_all() * s->list.stride * sizeof(int), hipMemcpyDeviceToHost));
+  if (row_len) MYTHOS_HIP_TRY(hipMemcpy(row_len, d_len, (size_t)s->n_all() * sizeof(int), hipMemcpyDeviceToHost));
   return MYTHOS_OK;
 }
 

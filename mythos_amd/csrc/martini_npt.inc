@@ -31,9 +31,11 @@ enum { kRecBox = 0, kRecMu = 3, kRecP = 6, kRecK = 9, kRecW = 12, kRecV = 15, kR
 // angle -u_d dU/dx_id at its first and -v_d dU/dx_kd at its last bead.  Sums in R inside a lane, in double across groups.
 // COUL (the system holds charges; the record behind eps, martini_md.hip): the reaction-field pair term on the row walk and the excluded-pair term on the bond
 // slots that carry it, both central: -1/2 (dV/dr) / r dx_d^2 to either bead, as LJ and bonds.
-template <typename R, bool COUL>
+// ENS (the replica table behind the Coulomb record, martini_md.hip): n beads per replica, blocks_per_rep workgroups each,
+// pointers moved to the workgroup's replica; partials stay in workgroup order, so replica-major.
+template <typename R, bool COUL, bool ENS = false>
 __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_pressure_kernel(
-    int n, const MmConst<R> K, const typename Real4<R>::type* __restrict__ in, const typename Real4<R>::type* __restrict__ vel,
+    int n, const MmConst<R> K0, const typename Real4<R>::type* __restrict__ in, const typename Real4<R>::type* __restrict__ vel,
     const int* __restrict__ rows, const int* __restrict__ row_len, int row_stride, const R* __restrict__ sigma,
     const R* __restrict__ eps, const int* __restrict__ bead_bonds, const int* __restrict__ bead_angles,
     const R* __restrict__ bond_k, const R* __restrict__ bond_r0, const R* __restrict__ angle_k, const R* __restrict__ angle_t0,
@@ -41,6 +43,7 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_pressure_ke
   using V4 = typename Real4<R>::type;
   constexpr int G = kMmG, PPB = kMmPPB;
   extern __shared__ unsigned char smem_raw[];
+  MmConst<R> K = K0;
   R* s_sig2 = reinterpret_cast<R*>(smem_raw);
   R* s_eps = s_sig2 + K.n_types * K.n_types;
   R* s_c = s_eps + K.n_types * K.n_types;  // (COUL) the Coulomb record
@@ -48,8 +51,18 @@ __global__ __launch_bounds__(kMmBlock, 1024 / kMmBlock) void martini_pressure_ke
   __shared__ double s_p[PPB][kMmVir];
 
   const int bid = (int)blockIdx.x;  // (the grid is exactly the workgroups that hold beads)
+  int lb = bid;
+  if constexpr (ENS) {
+    const int bpr = (n + PPB - 1) / PPB;
+    const int rep = bid / bpr;
+    int n_rep;
+    lb = bid - rep * bpr;
+    mm_rep_apply(K, mm_rep_record<R>(eps, K.n_types * K.n_types, rep, n_rep));
+    const size_t b0 = (size_t)rep * n;
+    in += b0, vel += b0, rows += b0 * row_stride, row_len += b0;
+  }
   const int grp = threadIdx.x / G, lane = threadIdx.x % G;
-  const int i = bid * PPB + grp;
+  const int i = lb * PPB + grp;
   const bool valid = i < n;
   const int ii = valid ? i : n - 1;
   const int tt = K.n_types * K.n_types;
@@ -232,6 +245,26 @@ static __global__ __launch_bounds__(256) void mm_barostat_kernel(const double* _
   for (int c = 0; c < kNptRec; ++c) rec[c] = out[c], host_rec[c] = out[c];
 }
 
+// Ensemble: bead i of replica i / n by that replica's mu; an event at which ANY replica's new box fails scales nobody
+// (the call ends there with every replica at the state of that step)
+template <typename R>
+__global__ void mm_scale_ens_kernel(int n, int n_rep, const double* __restrict__ rec, int scale_vel,
+                                    typename Real4<R>::type* __restrict__ frame, typename Real4<R>::type* __restrict__ vel) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * n_rep) return;
+  for (int r = 0; r < n_rep; ++r)
+    if (rec[(size_t)r * kNptRec + kRecOk] == 0.0) return;
+  const double* mu = rec + (size_t)(i / n) * kNptRec + kRecMu;
+  auto x = frame[i];
+  x.x *= R(mu[0]), x.y *= R(mu[1]), x.z *= R(mu[2]);
+  frame[i] = x;
+  if (scale_vel) {
+    auto v = vel[i];
+    v.x *= R(1.0 / mu[0]), v.y *= R(1.0 / mu[1]), v.z *= R(1.0 / mu[2]);
+    vel[i] = v;
+  }
+}
+
 template <typename R>
 __global__ void mm_scale_kernel(int n, const double* __restrict__ rec, int scale_vel, typename Real4<R>::type* __restrict__ frame,
                                 typename Real4<R>::type* __restrict__ vel) {
@@ -252,19 +285,25 @@ static bool mm_barostat_on(const mythos_martini_sim* sim) {
   return b.kind != 0 && (b.beta[0] > 0 || (b.coupling == 1 && b.beta[1] > 0));
 }
 
+// the boxes of the resident state, one per copy, as a row of last_boxes
+static void mm_push_boxes(mythos_martini_sim* sim) {
+  const double* b = sim->box_of(0);  // (an ensemble's are contiguous)
+  sim->baro.last_boxes.insert(sim->baro.last_boxes.end(), b, b + 3 * (size_t)sim->copies());
+}
+
 // no barostat: every saved row has the box of the load
 static void mm_constant_boxes(mythos_martini_sim* sim, int rows) {
   sim->baro.last_boxes.clear();
-  for (int r = 0; r < rows; ++r) sim->baro.last_boxes.insert(sim->baro.last_boxes.end(), sim->box, sim->box + 3);
+  for (int r = 0; r < rows; ++r) mm_push_boxes(sim);
 }
 
 static int mm_npt_buffers(mythos_martini_sim* sim) {
   MmBarostat& b = sim->baro;
-  const int blocks = (sim->sys->n + kMmPPB - 1) / kMmPPB;
+  const int blocks = sim->copies() * ((sim->sys->n + kMmPPB - 1) / kMmPPB);
   if (int rc = b.d_part.grow((size_t)blocks * kMmVir)) return rc;
-  if (int rc = b.d_rec.grow(kNptRec)) return rc;
-  if (!b.h_rec) {
-    MYTHOS_HIP_TRY(hipHostMalloc((void**)&b.h_rec, kNptRec * sizeof(double), hipHostMallocDefault));
+  if (int rc = b.d_rec.grow((size_t)sim->copies() * kNptRec)) return rc;
+  if (!b.h_rec) {  // (the number of copies is fixed at create)
+    MYTHOS_HIP_TRY(hipHostMalloc((void**)&b.h_rec, (size_t)sim->copies() * kNptRec * sizeof(double), hipHostMallocDefault));
     MYTHOS_HIP_TRY(hipHostGetDevicePointer((void**)&b.d_hrec, b.h_rec, 0));
   }
   return MYTHOS_OK;
@@ -279,8 +318,9 @@ static int mm_pressure_typed(mythos_martini_sim* sim, bool event, hipStream_t st
   mythos_martini* m = sim->sys;
   MmBarostat& b = sim->baro;
   if (int rc = mm_npt_buffers(sim)) return rc;
-  const int n = m->n, blocks = (n + kMmPPB - 1) / kMmPPB;
-  const MmConst<R> K = mm_const<R>(sim);
+  const bool ens = sim->n_rep > 0;
+  const int n = m->n, blocks_per_rep = (n + kMmPPB - 1) / kMmPPB, blocks = sim->copies() * blocks_per_rep;
+  const MmConst<R> K = mm_const<R>(sim, sim->box_of(0));
   const size_t lds = ((size_t)2 * sim->n_ctypes * sim->n_ctypes + (sim->coul ? kCoulRec : 0)) * sizeof(R);
   V4* frame = (V4*)sim->frame[sim->cur].get();
 #define MM_P_ARGS                                                                                                          \
@@ -288,25 +328,62 @@ static int mm_pressure_typed(mythos_martini_sim* sim, bool event, hipStream_t st
       (const R*)sim->d_csig2.get(), (const R*)sim->d_ceps.get(), m->d_bead_bonds.get(), m->d_bead_angles.get(),             \
       (const R*)m->d_bond_k.get(), (const R*)m->d_bond_r0.get(), (const R*)m->d_angle_k.get(),                              \
       (const R*)sim->d_angle_ref.get(), sim->d_bb_partner.get(), sim->d_ba_partner.get(), b.d_part.get()
-  if (sim->coul)
+  if (ens && sim->coul)
+    hipLaunchKernelGGL((martini_pressure_kernel<R, true, true>), dim3(blocks), dim3(kMmBlock), lds, st, MM_P_ARGS);
+  else if (ens)
+    hipLaunchKernelGGL((martini_pressure_kernel<R, false, true>), dim3(blocks), dim3(kMmBlock), lds, st, MM_P_ARGS);
+  else if (sim->coul)
     hipLaunchKernelGGL((martini_pressure_kernel<R, true>), dim3(blocks), dim3(kMmBlock), lds, st, MM_P_ARGS);
   else
     hipLaunchKernelGGL((martini_pressure_kernel<R, false>), dim3(blocks), dim3(kMmBlock), lds, st, MM_P_ARGS);
 #undef MM_P_ARGS
   MmBaroArgs a;
-  for (int d = 0; d < 3; ++d) a.box[d] = sim->box[d];
+  for (int d = 0; d < 3; ++d) a.box[d] = sim->box_of(0)[d];  // (an ensemble: box, kTp and seed per replica, below)
   for (int d = 0; d < 2; ++d) a.ref_p[d] = b.ref_p[d], a.f[d] = b.beta[d] * b.every * sim->dt / b.tau_p;
   a.kTp = kBarPerKjMolNm3 * sim->kT;
   a.min_edge = 2.0 * (m->r_cut + sim->skin);
   a.seed = sim->seed, a.step = (uint64_t)sim->step;
   a.kind = event ? b.kind : 0, a.coupling = b.coupling;
-  hipLaunchKernelGGL(mm_barostat_kernel, dim3(1), dim3(256), 0, st, (const double*)b.d_part.get(), blocks, a, b.d_rec.get(), b.d_hrec);
-  if (event)
-    hipLaunchKernelGGL(mm_scale_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const double*)b.d_rec.get(), b.kind == 2 ? 1 : 0, frame,
-                       (V4*)sim->vel.get());
+  if (ens) {
+    // One launch of the single copy's kernel per replica, over that replica's partials, with its box, kT' and seed: the
+    // record is the single integrator's by construction, and so is the kernel's code (a second kernel around the same
+    // body changed the inlining of the first).  R tiny launches per event, next to the 3 R of the list build behind it.
+    for (int r = 0; r < sim->n_rep; ++r) {
+      for (int d = 0; d < 3; ++d) a.box[d] = sim->box_of(r)[d];
+      a.kTp = kBarPerKjMolNm3 * sim->rep_kT[r], a.seed = sim->rep_seed[r];
+      hipLaunchKernelGGL(mm_barostat_kernel, dim3(1), dim3(256), 0, st, (const double*)b.d_part.get() + (size_t)r * blocks_per_rep * kMmVir,
+                         blocks_per_rep, a, b.d_rec.get() + (size_t)r * kNptRec, b.d_hrec + (size_t)r * kNptRec);
+    }
+    if (event)
+      hipLaunchKernelGGL(mm_scale_ens_kernel<R>, dim3((sim->n_all() + 255) / 256), dim3(256), 0, st, n, sim->n_rep, (const double*)b.d_rec.get(),
+                         b.kind == 2 ? 1 : 0, frame, (V4*)sim->vel.get());
+  } else {
+    hipLaunchKernelGGL(mm_barostat_kernel, dim3(1), dim3(256), 0, st, (const double*)b.d_part.get(), blocks, a, b.d_rec.get(), b.d_hrec);
+    if (event)
+      hipLaunchKernelGGL(mm_scale_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const double*)b.d_rec.get(), b.kind == 2 ? 1 : 0, frame,
+                         (V4*)sim->vel.get());
+  }
   MYTHOS_HIP_TRY(hipGetLastError());
   MYTHOS_HIP_TRY(hipStreamSynchronize(st));
   if (!event) return MYTHOS_OK;
+  if (ens) {  // R boxes behind the one synchronisation; the replica tables follow them, queued in front of the next launch
+    for (int r = 0; r < sim->n_rep; ++r) {
+      const double* h = b.h_rec + (size_t)r * kNptRec;
+      if (h[kRecOk] == 0.0) {
+        set_error("mythos_martini_langevin_run: the pressure coupling at step " + std::to_string(sim->step) + " would make the box of replica " +
+                  std::to_string(r) + " smaller than twice (r_cut + skin), or not finite - edges " + std::to_string(h[kRecBox]) + ", " +
+                  std::to_string(h[kRecBox + 1]) + ", " + std::to_string(h[kRecBox + 2]) +
+                  ": minimum image breaks down (the state of that step stays resident, no replica scaled)");
+        return MYTHOS_ERR_INVALID_ARGUMENT;
+      }
+    }
+    for (int r = 0; r < sim->n_rep; ++r)
+      for (int d = 0; d < 3; ++d) sim->rep_box[3 * (size_t)r + d] = b.h_rec[(size_t)r * kNptRec + kRecBox + d];
+    if (int rc = mm_upload_reps(sim, st)) return rc;
+    sim->list_valid = false;
+    sim->since_build = 0;
+    return MYTHOS_OK;
+  }
   if (b.h_rec[kRecOk] == 0.0) {
     set_error("mythos_martini_langevin_run: the pressure coupling at step " + std::to_string(sim->step) +
               " would make the box smaller than twice (r_cut + skin), or not finite - edges " + std::to_string(b.h_rec[kRecBox]) + ", " +
@@ -330,20 +407,18 @@ static int mm_advance_npt(mythos_martini_sim* sim, int n_steps, int save_every, 
   MmBarostat& b = sim->baro;
   b.last_boxes.clear();
   if (n_steps == 0) return mm_advance_typed<R>(sim, 0, save_every, close, traj_pos, e_trace, st);
-  const size_t row_reals = (size_t)sim->sys->n * 3;
+  const size_t row_reals = (size_t)sim->n_all() * 3;
   int done = 0, rows = 0, rebuilds = 0, recoveries = 0, launches = 0;
   while (done < n_steps) {
-    const int to_event = b.every - (int)(sim->step % b.every);
-    const int to_save = save_every > 0 ? save_every - done % save_every : n_steps + 1;
-    const int len = std::min(std::min(to_event, to_save), n_steps - done);
-    const bool event = len == to_event, save = len == to_save;
-    const bool last = done + len == n_steps;
+    const MmNptChunk c = mm_npt_chunk(sim->step, b.every, done, n_steps, save_every);  // (martini_ensemble_checks.h)
+    const int len = c.len;
+    const bool event = c.event, save = c.save, last = c.last;
     const int rc = mm_advance_typed<R>(sim, len, save ? len : 0, event || (last && close), traj_pos ? traj_pos + rows * row_reals : nullptr,
-                                       e_trace ? e_trace + (size_t)rows * sim->trace_width() : nullptr, st);
+                                       e_trace ? e_trace + mm_row_offset(rows, sim->copies(), sim->trace_width()) : nullptr, st);
     rebuilds += sim->last_rebuilds, recoveries += sim->last_recoveries, launches += sim->last_launches;
     sim->last_rebuilds = rebuilds, sim->last_recoveries = recoveries, sim->last_launches = launches;
     if (rc) return rc;
-    if (save) b.last_boxes.insert(b.last_boxes.end(), sim->box, sim->box + 3), ++rows;
+    if (save) mm_push_boxes(sim), ++rows;
     if (event)
       if (int re = mm_pressure_typed<R>(sim, true, st)) return re;
     done += len;
@@ -377,7 +452,8 @@ int mythos_martini_langevin_set_barostat(mythos_martini_sim_t* s, int kind, int 
   return MYTHOS_OK;
 }
 
-int mythos_martini_langevin_pressure(mythos_martini_sim_t* s, double out[10], mythos_stream_t stream) {
+/* out[copies][10]: one record per replica (a single-copy handle: one) */
+int mythos_martini_langevin_pressure_ensemble(mythos_martini_sim_t* s, double* out, mythos_stream_t stream) {
   if (!s || !out) {
     set_error("mythos_martini_langevin_pressure: invalid argument");
     return MYTHOS_ERR_INVALID_ARGUMENT;
@@ -395,27 +471,48 @@ int mythos_martini_langevin_pressure(mythos_martini_sim_t* s, double out[10], my
     if (int rc = f32 ? mm_advance_typed<float>(s, 0, 0, true, nullptr, nullptr, st) : mm_advance_typed<double>(s, 0, 0, true, nullptr, nullptr, st))
       return rc;
   if (int rc = f32 ? mm_pressure_typed<float>(s, false, st) : mm_pressure_typed<double>(s, false, st)) return rc;
-  const double* r = s->baro.h_rec;
-  for (int d = 0; d < 3; ++d) out[d] = r[kRecK + d], out[3 + d] = r[kRecW + d], out[6 + d] = r[kRecP + d];
-  out[9] = r[kRecV];
+  for (int c = 0; c < s->copies(); ++c, out += 10) {
+    const double* r = s->baro.h_rec + (size_t)c * kNptRec;
+    for (int d = 0; d < 3; ++d) out[d] = r[kRecK + d], out[3 + d] = r[kRecW + d], out[6 + d] = r[kRecP + d];
+    out[9] = r[kRecV];
+  }
+  return MYTHOS_OK;
+}
+
+int mythos_martini_langevin_pressure(mythos_martini_sim_t* s, double out[10], mythos_stream_t stream) {
+  if (s && s->n_rep > 0) {
+    set_error("mythos_martini_langevin_pressure: an ensemble handle has one record per replica (mythos_martini_langevin_pressure_ensemble)");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  return mythos_martini_langevin_pressure_ensemble(s, out, stream);
+}
+
+/* boxes[copies][3] */
+int mythos_martini_langevin_get_box_ensemble(const mythos_martini_sim_t* s, double* boxes) {
+  if (!s || !boxes) {
+    set_error("mythos_martini_langevin_get_box: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  std::copy(s->box_of(0), s->box_of(0) + 3 * (size_t)s->copies(), boxes);
   return MYTHOS_OK;
 }
 
 int mythos_martini_langevin_get_box(const mythos_martini_sim_t* s, double box[3]) {
-  if (!s || !box) {
-    set_error("mythos_martini_langevin_get_box: invalid argument");
+  if (s && s->n_rep > 0) {
+    set_error("mythos_martini_langevin_get_box: an ensemble handle has one box per replica (mythos_martini_langevin_get_box_ensemble)");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  for (int d = 0; d < 3; ++d) box[d] = s->box[d];
-  return MYTHOS_OK;
+  return mythos_martini_langevin_get_box_ensemble(s, box);
 }
+
+int mythos_martini_langevin_n_replicas(const mythos_martini_sim_t* s) { return s ? s->copies() : -1; }
 
 int mythos_martini_langevin_last_boxes(const mythos_martini_sim_t* s, double* boxes, int* n_rows) {
   if (!s || (!boxes && !n_rows)) {
     set_error("mythos_martini_langevin_last_boxes: invalid argument");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  if (n_rows) *n_rows = (int)(s->baro.last_boxes.size() / 3);
+  if (n_rows) *n_rows = (int)(s->baro.last_boxes.size() / (3 * (size_t)s->copies()));  // (an ensemble: rows of [n_rep][3])
   if (boxes) std::copy(s->baro.last_boxes.begin(), s->baro.last_boxes.end(), boxes);
   return MYTHOS_OK;
 }

@@ -613,6 +613,21 @@ class MartiniSystem(_lib.Handle):
                                                         float(epsilon_r), float(epsilon_rf)), "martini_set_charges")
         self.charged = q is not None and bool(np.any(q != 0.0))
 
+    def set_params(self, sigma=None, eps=None, bond_k=None, bond_r0=None, angle_k=None, angle_t0=None) -> None:
+        """New values for the parameter tables, in place (mythos_martini_set_params; shapes as at creation, ``None`` keeps a
+        table): the handle stays, and so does every integrator bound to it, which takes the tables with its next call."""
+        shapes = ((self.n_types, self.n_types), (self.n_types, self.n_types), (self.n_bonds,), (self.n_bonds,), (self.n_angles,),
+                  (self.n_angles,))
+        arrs = []
+        for a, shape, name in zip((sigma, eps, bond_k, bond_r0, angle_k, angle_t0), shapes, ("sigma", "eps", "bond_k", "bond_r0", "angle_k", "angle_t0")):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != shape:
+                    raise ValueError(f"{name} must have shape {shape}")
+            arrs.append(a)
+        _lib.check(self._lib.mythos_martini_set_params(self._h, *(None if a is None else a.ctypes.data_as(_lib.c_double_p) for a in arrs)),
+                   "martini_set_params")
+
     def coulomb(self, pos: torch.Tensor, box: torch.Tensor, grads: bool = False):
         """pos (F, N, 3) or (N, 3); box (F, 3) or (3,) -> (reaction-field Coulomb energy (F,) float64 - pairs, excluded
         pairs and the self term -, dU/dpos or None).  Zero for a system without charges."""
@@ -807,3 +822,163 @@ class MartiniLangevinIntegrator(_MdIntegrator):
         mx, mean = C.c_int(0), C.c_double(0.0)
         _lib.check(self._lib.mythos_martini_langevin_neighbor_stats(self._h, C.byref(mx), C.byref(mean)), "neighbor_stats")
         return mx.value, mean.value
+
+
+class _MartiniEnsembleHandle(MartiniLangevinIntegrator):
+    """The handle behind :class:`MartiniEnsembleIntegrator` (mythos_martini_langevin_create_ensemble): the single
+    integrator's entry points on tensors with a leading replica axis."""
+
+    def __init__(self, system: MartiniSystem, dt, kT, gamma, mass=None, seeds=None):
+        kT = np.ascontiguousarray(np.atleast_1d(np.asarray(kT, dtype=np.float64)))
+        if kT.ndim != 1 or kT.size < 1:
+            raise ValueError("kT must be a non-empty sequence, one value per replica")
+        self.n_rep = int(kT.size)
+        if seeds is None or np.isscalar(seeds):
+            seeds = [(int(seeds or 0) + r) & (2**64 - 1) for r in range(self.n_rep)]
+        seeds = np.ascontiguousarray(np.asarray([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64))
+        if seeds.shape != (self.n_rep,):
+            raise ValueError(f"seeds must be an int or {self.n_rep} values, one per replica")
+        mptr = None
+        if mass is not None:
+            mass = np.ascontiguousarray(mass, dtype=np.float64)
+            if mass.shape != (system.n,):
+                raise ValueError(f"mass must have shape ({system.n},)")
+            mptr = mass.ctypes.data_as(_lib.c_double_p)
+        self.kT, self.seeds = kT.copy(), seeds.copy()
+        self.system = system
+        _lib.Handle.__init__(self, "mythos_martini_langevin_create_ensemble", system._h, self.n_rep, float(dt),
+                             kT.ctypes.data_as(_lib.c_double_p), float(gamma), mptr, seeds.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def _boxes(self, box) -> np.ndarray:
+        return MartiniEnsembleIntegrator.replica_boxes(box, self.n_rep)
+
+    def restart(self, seeds, step: int = 0) -> None:
+        """Make the handle new for another run (mythos_martini_langevin_restart): one seed per replica, the step counter set,
+        the resident state dropped - ``load`` or ``run`` comes next.  Settings and buffers stay."""
+        sd = np.ascontiguousarray(np.asarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64))
+        if sd.shape != (self.n_rep,):
+            raise ValueError(f"seeds must hold {self.n_rep} values, one per replica")
+        _lib.check(self._lib.mythos_martini_langevin_restart(self._h, sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(step)), "restart")
+        self.seeds = sd.copy()
+
+    def pressure(self) -> dict:
+        """As :meth:`MartiniLangevinIntegrator.pressure`, per replica: ``kinetic``, ``virial``, ``pressure`` (R, 3),
+        ``volume`` and ``p`` (R,)."""
+        out = np.zeros((self.n_rep, 10), dtype=np.float64)
+        _lib.check(self._lib.mythos_martini_langevin_pressure_ensemble(self._h, out.ctypes.data_as(_lib.c_double_p),
+                                                                       _lib.stream(self.system.device)), "martini_langevin_pressure")
+        return {"kinetic": out[:, 0:3].copy(), "virial": out[:, 3:6].copy(), "pressure": out[:, 6:9].copy(), "volume": out[:, 9].copy(),
+                "p": out[:, 6:9].mean(axis=1)}
+
+    @property
+    def box(self) -> np.ndarray:
+        """(R, 3) float64: every replica's box of the resident state."""
+        b = np.zeros((self.n_rep, 3), dtype=np.float64)
+        _lib.check(self._lib.mythos_martini_langevin_get_box_ensemble(self._h, b.ctypes.data_as(_lib.c_double_p)), "get_box")
+        return b
+
+    @property
+    def last_boxes(self) -> torch.Tensor:
+        """(S, R, 3) float64 on the system's device: every replica's box at every row the last call saved."""
+        n = C.c_int(0)
+        _lib.check(self._lib.mythos_martini_langevin_last_boxes(self._h, None, C.byref(n)), "last_boxes")
+        b = np.zeros((n.value, self.n_rep, 3), dtype=np.float64)
+        if n.value:
+            _lib.check(self._lib.mythos_martini_langevin_last_boxes(self._h, b.ctypes.data_as(_lib.c_double_p), C.byref(n)), "last_boxes")
+        return torch.as_tensor(b, device=self.system.device)
+
+    def init_velocities(self) -> torch.Tensor:
+        """(R, n, 3): replica r's are those a single integrator with ``seeds[r]`` and ``kT[r]`` draws."""
+        v = torch.empty((self.n_rep, self.system.n, 3), dtype=self.system.dtype, device=self.system.device)
+        _lib.check(self._lib.mythos_martini_langevin_init_velocities(self._h, _lib.ptr(v), _lib.stream(self.system.device)), "init_velocities")
+        return v
+
+    def _check_state(self, pos, vel):
+        s = self.system
+        shape = (self.n_rep, s.n, 3)
+        for t, name in ((pos, "pos"), (vel, "vel")):
+            if t.device != s.device or t.dtype != s.dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {s.dtype} tensor of shape {shape} on {s.device}")
+
+    def _rows(self, n_steps: int, save_every: int, want_energy: bool):
+        s = self.system
+        ns = n_steps // save_every if save_every > 0 else 0
+        traj = torch.empty((ns, self.n_rep, s.n, 3), dtype=s.dtype, device=s.device) if ns else None
+        et = torch.zeros((ns, self.n_rep, 5 if s.charged else 4), dtype=torch.float64, device=s.device) if (ns and want_energy) else None
+        return traj, et
+
+    def run(self, pos, vel, box, n_steps: int, save_every: int = 0, want_energy: bool = True):
+        """Advance ``pos`` / ``vel`` (R, n, 3) in place -> (traj (S, R, n, 3) or None, e_trace (S, R, 4 | 5) or None)."""
+        self._check_state(pos, vel)
+        box = self._boxes(box)
+        traj, et = self._rows(n_steps, save_every, want_energy)
+        rc = self._lib.mythos_martini_langevin_run(
+            self._h, _lib.ptr(pos), _lib.ptr(vel), box.ctypes.data_as(_lib.c_double_p), int(n_steps), int(save_every),
+            _lib.ptr(traj), _lib.ptr(et), _lib.stream(self.system.device))
+        _touched(pos, vel)
+        _lib.check(rc, "martini_langevin_run")
+        return traj, et
+
+    def load(self, pos, vel, box) -> None:
+        self._check_state(pos, vel)
+        box = self._boxes(box)
+        _lib.check(self._lib.mythos_martini_langevin_load(self._h, _lib.ptr(pos), _lib.ptr(vel), box.ctypes.data_as(_lib.c_double_p),
+                                                          _lib.stream(self.system.device)), "martini_langevin_load")
+
+    def rows(self, pruned: bool = False):
+        """(rows (R n, stride) int32 of bead indices inside the replica, lengths (R n,) int32), replica-major."""
+        stride = C.c_int(0)
+        which = 1 if pruned else 0
+        _lib.check(self._lib.mythos_martini_langevin_get_rows(self._h, which, None, None, C.byref(stride)), "get_rows")
+        rows = np.empty((self.n_rep * self.system.n, stride.value), dtype=np.int32)
+        lens = np.empty(self.n_rep * self.system.n, dtype=np.int32)
+        _lib.check(self._lib.mythos_martini_langevin_get_rows(self._h, which, rows.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                              lens.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(stride)), "get_rows")
+        return rows, lens
+
+
+class MartiniEnsembleIntegrator:
+    """R independent copies ("replicas") of one :class:`MartiniSystem`, each with its own ``kT``, box, seed and - when a
+    barostat is set - coupling history, advanced by ONE step launch per time step
+    (mythos_martini_langevin_create_ensemble).  Stands in for the reference's loop over simulation temperatures, one
+    GROMACS run each (examples/scripts/martini_full_reparameterization.py:347-357).
+
+    The methods are those of :class:`MartiniLangevinIntegrator` with a leading replica axis on every tensor: ``pos`` /
+    ``vel`` (R, n, 3), ``box`` (R, 3) or (3,) for all, ``traj`` (rows, R, n, 3), ``e_trace`` (rows, R, 4 | 5),
+    ``last_boxes`` (rows, R, 3), ``pressure()`` a dict of (R, ...) arrays, ``rows()`` over the R n rows (local bead
+    indices).  Neighbour policy, pruned rows, barostat settings and timing apply to all replicas alike.  Replica r is bit
+    for bit the single integrator made with ``kT[r]``, ``seeds[r]`` and loaded with ``box[r]`` while no call reports a
+    recovery.  ``seeds``: one per replica, an int s for s + r, None for 0 + r."""
+
+    KB = MartiniLangevinIntegrator.KB
+
+    def __init__(self, system: MartiniSystem, dt, kT, gamma, mass=None, seeds=None):
+        self._impl = _MartiniEnsembleHandle(system, dt, kT, gamma, mass=mass, seeds=seeds)
+
+    def __getattr__(self, name):
+        # everything else - set_neighbor_policy, set_inner_list, set_barostat, load, advance, run, store, pressure, box,
+        # last_boxes, rows, step, the counters, close - is the handle's
+        if name == "_impl":
+            raise AttributeError(name)
+        return getattr(self._impl, name)
+
+    @staticmethod
+    def replica_boxes(box, n_rep: int) -> np.ndarray:
+        """``box`` (R, 3), or (3,) for every replica -> contiguous (R, 3) float64; anything else is refused."""
+        box = np.asarray(box, dtype=np.float64)
+        if box.shape == (3,):
+            box = np.broadcast_to(box, (n_rep, 3))
+        if box.shape != (n_rep, 3):
+            raise ValueError(f"box must have shape ({n_rep}, 3), or (3,) for every replica")
+        return np.ascontiguousarray(box)
+
+    @staticmethod
+    def check(n: int, kT, r_cut: float = 1.1, skin: float = 0.2, boxes=None) -> None:
+        """What creation and ``load`` refuse, without a device (mythos_martini_ensemble_check): fewer than one replica, a
+        kT that is not finite and positive, more rows than the neighbour store indexes, a replica box under
+        2 (r_cut + skin).  Raises with the library's message."""
+        kT = np.ascontiguousarray(np.atleast_1d(np.asarray(kT, dtype=np.float64)))
+        b = None if boxes is None else MartiniEnsembleIntegrator.replica_boxes(boxes, int(kT.size))
+        _lib.check(_lib.load().mythos_martini_ensemble_check(
+            int(n), int(kT.size), kT.ctypes.data_as(_lib.c_double_p), float(r_cut), float(skin),
+            None if b is None else b.ctypes.data_as(_lib.c_double_p)), "martini_ensemble_check")
