@@ -714,6 +714,56 @@ int mythos_martini_langevin_restart(mythos_martini_sim_t* sim, const uint64_t* s
 int mythos_martini_langevin_pressure_ensemble(mythos_martini_sim_t* sim, double* out, mythos_stream_t stream);
 int mythos_martini_langevin_get_box_ensemble(const mythos_martini_sim_t* sim, double* boxes);
 
+/* ---- MARTINI temperature ensemble: replica exchange between the temperatures -----------------------------------
+ * Ensemble handles with n_rep >= 2.  The rule:
+ *   Rungs and slots  The ladder's rungs are the kT of create_ensemble in the order given, beta_t = 1 / kT_t in double.
+ *                    Slots are the replicas as they lie in memory: slot r keeps its beads, velocities, box, barostat
+ *                    history, neighbour rows and thermostat seed for the whole run.  An exchange swaps TEMPERATURES
+ *                    between slots; no bead data moves.  rung_of_slot is a permutation of 0 .. n_rep - 1, the identity
+ *                    at creation and after restart (load leaves it and the counts alone).
+ *   Events           With every = E >= 1 an event happens at the closed state (x_s, v_s) of every absolute step s > 0
+ *                    with s % E == 0; its attempt index is a = s / E.  It attempts the rung pairs (t, t + 1) for
+ *                    t = a mod 2, a mod 2 + 2, ... while t + 1 < n_rep: disjoint pairs.
+ *   Decision         For slot A on rung t and slot B on rung t + 1:  d = (beta_t - beta_t+1) (H_A - H_B),  H = U + p V,
+ *                    u = (c[0] + 0.5) 2^-32 of Philox4x32-10 keyed by the 64-bit exchange seed, counter
+ *                    {t, s lo, s hi, 5} (stream 5; 0/1 thermostat, 2/3 barostat, 4 umbrella, 7/8 initial velocities);
+ *                    accepted iff d >= 0 or u < exp(d).  All in double.
+ *   U                lj + bond + angle (+ coulomb while the system holds charges), added in that order, of the values an
+ *                    energy row of step s holds: if the call saves one there, U is that row's sum bit for bit.
+ *   V, p             V = (lx ly) lz of the slot's box at step s.  p = 0 without a barostat; with one p = p_ref / 16.6053907,
+ *                    p_ref = ref_p[0] for isotropic coupling, for semi-isotropic coupling the reference pressure of the
+ *                    axis set whose compressibility is non-zero; both non-zero needs ref_p[0] == ref_p[1], otherwise
+ *                    advance / run are refused by name (an anisotropic reference stress has no scalar work term).
+ *   On acceptance    A takes rung t + 1, B rung t.  A's velocities are multiplied by (real)sqrt(kT_t+1 / kT_t), B's by
+ *                    (real)sqrt(kT_t / kT_t+1): quotient and root in double, rounded once to the system's precision,
+ *                    the product in that precision.  From the next step on thermostat noise and the barostat's kT' use
+ *                    the slot's new kT.
+ *   After an event   The neighbour rows are dropped as after a coupling event, accepted or not: the segment behind an event
+ *                    is bit for bit the run of a plain ensemble, created with the slots' kT, restarted at step s and loaded
+ *                    with the stored state.  One list build per event.
+ *   With coupling    At a step with both the exchange comes first, on U and the box of (x_s, box_s); the coupling event
+ *                    follows with the new kT' and the rescaled velocities (two synchronisations at such a step).  A row
+ *                    saved at step s is the state before both.
+ * An event costs a closing launch of the energy-trace instantiation, a reduction, the decision kernel (one workgroup), one
+ * rescaling launch, one synchronisation and the list build behind it.  every = 0 switches exchange off: the handle then
+ * launches nothing it did not launch before this entry point existed.
+ *   set_ladder       rung_of_slot host int32[n_rep], a permutation (anything else is refused); rewrites the slots' kT;
+ *                    refused (NOT_READY) while the resident frame is open.  get_ladder: the current one.
+ *   last_ladder      host int32[*n_rows][n_rep]: rung_of_slot at every row the last call saved, each the state before the
+ *                    events of its step (as last_boxes); rows == NULL: only *n_rows.
+ *   last_exchanges   host double[*n][11], the last call's attempts in order: step, t, slot A, slot B, U_A, U_B, V_A, V_B,
+ *                    d, u, accepted (0 | 1); rec == NULL: only *n.
+ *   exchange_counts  host int64[n_rep - 1] each: attempts and acceptances per rung pair (t, t + 1) since restart.
+ * mythos_martini_exchange_check: the refusals that need no handle - n_rep < 2, every < 0, rung_of_slot (host
+ * int32[n_rep] or NULL: not checked) not a permutation; touches no device. */
+int mythos_martini_langevin_set_exchange(mythos_martini_sim_t* sim, int every, uint64_t seed);
+int mythos_martini_langevin_set_ladder(mythos_martini_sim_t* sim, const int32_t* rung_of_slot);
+int mythos_martini_langevin_get_ladder(const mythos_martini_sim_t* sim, int32_t* rung_of_slot);
+int mythos_martini_langevin_last_ladder(const mythos_martini_sim_t* sim, int32_t* rows, int* n_rows);
+int mythos_martini_langevin_last_exchanges(const mythos_martini_sim_t* sim, double* rec, int* n);
+int mythos_martini_langevin_exchange_counts(const mythos_martini_sim_t* sim, int64_t* attempts, int64_t* accepts);
+int mythos_martini_exchange_check(int n_rep, int every, const int32_t* rung_of_slot);
+
 /* ---- MARTINI observables: named bond lengths and triplet angles ------------------------------
  * Replaces mythos/observables/bond_distances.py:15-17, 51-69 (BondDistances / BondDistancesMapped) and
  * triplet_angles.py:15-31, 73-92 (TripletAngles / TripletAnglesMapped) with the angle of

@@ -122,6 +122,13 @@ _SIGS = {
     "mythos_martini_langevin_restart": (C.c_int, [V, C.POINTER(C.c_uint64), C.c_int64]),
     "mythos_martini_langevin_pressure_ensemble": (C.c_int, [V, c_double_p, V]),
     "mythos_martini_langevin_get_box_ensemble": (C.c_int, [V, c_double_p]),
+    "mythos_martini_langevin_set_exchange": (C.c_int, [V, C.c_int, C.c_uint64]),
+    "mythos_martini_langevin_set_ladder": (C.c_int, [V, C.POINTER(C.c_int32)]),
+    "mythos_martini_langevin_get_ladder": (C.c_int, [V, C.POINTER(C.c_int32)]),
+    "mythos_martini_langevin_last_ladder": (C.c_int, [V, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "mythos_martini_langevin_last_exchanges": (C.c_int, [V, c_double_p, C.POINTER(C.c_int)]),
+    "mythos_martini_langevin_exchange_counts": (C.c_int, [V, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mythos_martini_exchange_check": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "mythos_martini_obs_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int]),
     "mythos_martini_obs_destroy": (None, [V]),
     "mythos_martini_obs_count": (C.c_int64, [V]),

@@ -27,6 +27,7 @@
 
 #include "cell_list.h"
 #include "martini_ensemble_checks.h"
+#include "martini_exchange_checks.h"
 #include "martini_internal.h"
 #include "md_driver.h"
 #include "philox.h"
@@ -720,6 +721,28 @@ struct MmBarostat {
   }
 };
 
+// Temperature replica exchange of an ensemble (martini_exchange.inc): what mythos_martini_langevin_set_exchange set, the
+// ladder - which rung's kT every slot runs at -, the counts since restart, and ladder rows and attempt log of the last call.
+struct MmExchange {
+  int every = 0;      // 0: off
+  uint64_t seed = 0;  // of the decisions' uniforms, a Philox stream of its own
+  std::vector<double> ladder_kT;      // [n_rep]: the kT given at creation, in their order
+  std::vector<int32_t> rung_of_slot;  // [n_rep]: a permutation, the identity at creation and after restart
+  std::vector<int64_t> attempts, accepts;  // [n_rep - 1], per rung pair (t, t + 1)
+  std::vector<int32_t> last_ladder;   // [rows][n_rep]
+  std::vector<double> last_log;       // [attempted pairs][kXchgRec]
+  mythos::DeviceBuf<double> d_etrace, d_fac;  // energy rows of an event whose step is not saved [n_rep][5]; velocity factors [n_rep]
+  double *h_d = nullptr, *d_hd = nullptr;  // pinned, and its device address: in boxes [n_rep][3], kT [n_rep]; out log [n_rep / 2][kXchgRec]
+  int *h_i = nullptr, *d_hi = nullptr;     // pinned: in rung_of_slot [n_rep]; out the new one [n_rep]
+  MmExchange() = default;
+  MmExchange(const MmExchange&) = delete;
+  MmExchange& operator=(const MmExchange&) = delete;
+  ~MmExchange() {  // (the owner's destructor has selected the device)
+    if (h_d) (void)hipHostFree(h_d);
+    if (h_i) (void)hipHostFree(h_i);
+  }
+};
+
 struct mythos_martini_sim : mythos::MdRun {
   mythos_martini* sys = nullptr;
   double dt = 0.02, kT = 2.27, gamma = 1.0;
@@ -763,6 +786,7 @@ struct mythos_martini_sim : mythos::MdRun {
   std::vector<double> rep_kT, rep_box;  // [n_rep], [n_rep][3]
   std::vector<uint64_t> rep_seed;
   unsigned char* h_reps = nullptr;
+  MmExchange xchg;  // off until mythos_martini_langevin_set_exchange
   int copies() const { return n_rep > 0 ? n_rep : 1; }
   int n_all() const { return copies() * sys->n; }  // beads of all copies
   const double* box_of(int r) const { return n_rep > 0 ? &rep_box[3 * (size_t)r] : box; }
@@ -1135,6 +1159,7 @@ static int mm_store_typed(mythos_martini_sim* sim, R* pos, R* v, hipStream_t st)
 }  // namespace mythos
 
 #include "martini_npt.inc"
+#include "martini_exchange.inc"
 
 extern "C" {
 
@@ -1159,6 +1184,11 @@ mythos_martini_sim_t* mm_create(mythos_martini_t* sys, int n_rep, double dt, con
     s->rep_box.assign(3 * (size_t)n_rep, 0.0);
     s->rep_seed.assign((size_t)n_rep, 0);
     for (int r = 0; seeds && r < n_rep; ++r) s->rep_seed[r] = seeds[r];
+    s->xchg.ladder_kT = s->rep_kT;
+    s->xchg.rung_of_slot.resize((size_t)n_rep);
+    for (int r = 0; r < n_rep; ++r) s->xchg.rung_of_slot[r] = r;
+    s->xchg.attempts.assign((size_t)std::max(0, n_rep - 1), 0);
+    s->xchg.accepts.assign((size_t)std::max(0, n_rep - 1), 0);
   }
   const int copies = s->copies();
   const int n = sys->n, dtype = sys->dtype;
@@ -1307,12 +1337,19 @@ int mm_load(mythos_martini_sim_t* s, const void* pos, const void* vel, const dou
 }
 int mm_advance(mythos_martini_sim_t* s, int n_steps, int save_every, bool close, void* traj, double* e_trace, hipStream_t st) {
   if (int rc = mm_sync_charges(s, st)) return rc;
-  if (mm_barostat_on(s))  // chunks that end at coupling events (martini_npt.inc); off: the call below, as ever
-    return s->sys->dtype == MYTHOS_F32 ? mm_advance_npt<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
-                                       : mm_advance_npt<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+  if (mm_exchange_on(s))  // chunks that end at exchange and coupling events (martini_exchange.inc)
+    return s->sys->dtype == MYTHOS_F32 ? mm_advance_events<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
+                                       : mm_advance_events<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+  if (mm_barostat_on(s)) {  // chunks that end at coupling events (martini_npt.inc); off: the call below, as ever
+    const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_npt<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
+                                               : mm_advance_npt<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+    mm_constant_ladder(s);
+    return rc;
+  }
   const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_typed<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
                                              : mm_advance_typed<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
   mm_constant_boxes(s, rc == MYTHOS_OK && save_every > 0 ? n_steps / save_every : 0);
+  mm_constant_ladder(s);
   return rc;
 }
 int mm_store(mythos_martini_sim_t* s, void* pos, void* vel, hipStream_t st) {
@@ -1388,6 +1425,12 @@ int mythos_martini_langevin_restart(mythos_martini_sim_t* s, const uint64_t* see
   }
   s->seed = seeds[0];
   for (int r = 0; r < s->n_rep; ++r) s->rep_seed[r] = seeds[r];
+  if (s->n_rep > 0) {  // the ladder back to the identity, every slot at the kT it was created with; the counts to zero
+    for (int r = 0; r < s->n_rep; ++r) s->xchg.rung_of_slot[r] = r;
+    mm_apply_ladder(s);
+    std::fill(s->xchg.attempts.begin(), s->xchg.attempts.end(), 0);
+    std::fill(s->xchg.accepts.begin(), s->xchg.accepts.end(), 0);
+  }
   s->step = step;
   s->resident = false;  // (an ensemble's replica table takes the seeds at the load that has to follow)
   s->list_valid = false;

@@ -854,12 +854,79 @@ class _MartiniEnsembleHandle(MartiniLangevinIntegrator):
 
     def restart(self, seeds, step: int = 0) -> None:
         """Make the handle new for another run (mythos_martini_langevin_restart): one seed per replica, the step counter set,
-        the resident state dropped - ``load`` or ``run`` comes next.  Settings and buffers stay."""
+        the resident state dropped - ``load`` or ``run`` comes next.  Settings and buffers stay; the exchange ladder goes
+        back to the identity and the exchange counts to zero."""
         sd = np.ascontiguousarray(np.asarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64))
         if sd.shape != (self.n_rep,):
             raise ValueError(f"seeds must hold {self.n_rep} values, one per replica")
         _lib.check(self._lib.mythos_martini_langevin_restart(self._h, sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(step)), "restart")
         self.seeds = sd.copy()
+
+    # ---- replica exchange between the temperatures (mythos_martini_langevin_set_exchange, include/mythos_hip.h) ----
+    EXCHANGE_FIELDS = ("step", "rung", "slot_a", "slot_b", "u_a", "u_b", "v_a", "v_b", "d", "u", "accepted")
+
+    def set_exchange(self, every: int, seed: int = 0) -> None:
+        """An exchange event at every absolute step s > 0 with s % ``every`` == 0 (0: off); ``seed`` keys the decisions'
+        uniforms.  Handles with at least two replicas."""
+        _lib.check(self._lib.mythos_martini_langevin_set_exchange(self._h, int(every), int(seed) & (2**64 - 1)), "set_exchange")
+
+    @staticmethod
+    def _ladder_arg(rung_of_slot) -> np.ndarray:
+        return np.ascontiguousarray(np.asarray(rung_of_slot, dtype=np.int64).reshape(-1), dtype=np.int32)
+
+    def set_ladder(self, rung_of_slot) -> None:
+        """Which rung of the ladder - the ``kT`` of creation, in their order - every slot runs at: a permutation of
+        0 .. R - 1.  Rewrites the slots' kT; refused while the resident frame is open."""
+        a = self._ladder_arg(rung_of_slot)
+        if a.shape != (self.n_rep,):
+            raise ValueError(f"rung_of_slot must hold {self.n_rep} values, one per replica")
+        _lib.check(self._lib.mythos_martini_langevin_set_ladder(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), "set_ladder")
+
+    @property
+    def ladder(self) -> np.ndarray:
+        """(R,) int64: ``rung_of_slot`` of the resident state."""
+        a = np.zeros(self.n_rep, dtype=np.int32)
+        _lib.check(self._lib.mythos_martini_langevin_get_ladder(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), "get_ladder")
+        return a.astype(np.int64)
+
+    @property
+    def kT_now(self) -> np.ndarray:
+        """(R,) float64: the kT every slot runs at now."""
+        return self.kT[self.ladder]
+
+    @property
+    def last_ladder(self) -> torch.Tensor:
+        """(S, R) int64 on the system's device: ``rung_of_slot`` at every row the last call saved, each before the events of
+        its step."""
+        n = C.c_int(0)
+        _lib.check(self._lib.mythos_martini_langevin_last_ladder(self._h, None, C.byref(n)), "last_ladder")
+        a = np.zeros((n.value, self.n_rep), dtype=np.int32)
+        if n.value:
+            _lib.check(self._lib.mythos_martini_langevin_last_ladder(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "last_ladder")
+        return torch.as_tensor(a.astype(np.int64), device=self.system.device)
+
+    @property
+    def last_exchanges(self) -> dict:
+        """The last call's attempts in order, a dict of (A,) arrays: ``step``, ``rung`` (the pair is rung, rung + 1),
+        ``slot_a``, ``slot_b`` int64; ``u_a``, ``u_b`` (kJ/mol), ``v_a``, ``v_b`` (nm^3), ``d``, ``u`` float64; ``accepted``
+        bool."""
+        n = C.c_int(0)
+        _lib.check(self._lib.mythos_martini_langevin_last_exchanges(self._h, None, C.byref(n)), "last_exchanges")
+        rec = np.zeros((n.value, len(self.EXCHANGE_FIELDS)), dtype=np.float64)
+        if n.value:
+            _lib.check(self._lib.mythos_martini_langevin_last_exchanges(self._h, rec.ctypes.data_as(_lib.c_double_p), C.byref(n)), "last_exchanges")
+        out = {k: rec[:, j].copy() for j, k in enumerate(self.EXCHANGE_FIELDS)}
+        for k in ("step", "rung", "slot_a", "slot_b"):
+            out[k] = out[k].astype(np.int64)
+        out["accepted"] = out["accepted"] != 0.0
+        return out
+
+    def exchange_counts(self) -> tuple[np.ndarray, np.ndarray]:
+        """(attempts, accepts), (R - 1,) int64 each: per rung pair (t, t + 1) since ``restart``."""
+        att, acc = np.zeros(self.n_rep - 1, dtype=np.int64), np.zeros(self.n_rep - 1, dtype=np.int64)
+        _lib.check(self._lib.mythos_martini_langevin_exchange_counts(self._h, att.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                     acc.ctypes.data_as(C.POINTER(C.c_int64))), "exchange_counts")
+        return att, acc
 
     def pressure(self) -> dict:
         """As :meth:`MartiniLangevinIntegrator.pressure`, per replica: ``kinetic``, ``virial``, ``pressure`` (R, 3),
@@ -948,7 +1015,14 @@ class MartiniEnsembleIntegrator:
     ``last_boxes`` (rows, R, 3), ``pressure()`` a dict of (R, ...) arrays, ``rows()`` over the R n rows (local bead
     indices).  Neighbour policy, pruned rows, barostat settings and timing apply to all replicas alike.  Replica r is bit
     for bit the single integrator made with ``kT[r]``, ``seeds[r]`` and loaded with ``box[r]`` while no call reports a
-    recovery.  ``seeds``: one per replica, an int s for s + r, None for 0 + r."""
+    recovery - between exchange events, with the slot's current kT.  ``seeds``: one per replica, an int s for s + r,
+    None for 0 + r.
+
+    Replica exchange between the temperatures (``set_exchange(every, seed)``; the rule is in include/mythos_hip.h): the
+    replicas are *slots* that keep their beads, box and seed, ``kT`` is the ladder of *rungs*, and an accepted exchange
+    swaps the kT of two slots and rescales their velocities.  ``ladder`` / ``set_ladder`` give and take ``rung_of_slot``,
+    ``kT_now`` the slots' current kT, ``last_ladder`` (rows, R) the ladder at every saved row, ``last_exchanges`` the log of
+    the last call's attempts and ``exchange_counts()`` attempts and acceptances per rung pair since ``restart``."""
 
     KB = MartiniLangevinIntegrator.KB
 
@@ -982,3 +1056,15 @@ class MartiniEnsembleIntegrator:
         _lib.check(_lib.load().mythos_martini_ensemble_check(
             int(n), int(kT.size), kT.ctypes.data_as(_lib.c_double_p), float(r_cut), float(skin),
             None if b is None else b.ctypes.data_as(_lib.c_double_p)), "martini_ensemble_check")
+
+    @staticmethod
+    def check_exchange(n_rep: int, every: int = 0, rung_of_slot=None) -> None:
+        """What ``set_exchange`` and ``set_ladder`` refuse, without a device (mythos_martini_exchange_check): fewer than two
+        replicas, ``every`` < 0, a ``rung_of_slot`` of ``n_rep`` entries that is no permutation.  Raises with the library's message."""
+        a = None
+        if rung_of_slot is not None:
+            a = _MartiniEnsembleHandle._ladder_arg(rung_of_slot)
+            if a.shape != (int(n_rep),):
+                raise ValueError(f"rung_of_slot must hold {int(n_rep)} values, one per replica")
+        _lib.check(_lib.load().mythos_martini_exchange_check(int(n_rep), int(every), None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))),
+                   "martini_exchange_check")

@@ -118,7 +118,10 @@ def check_arguments(n: int, init_positions, box, temperatures, equilibration_ste
 @dc.dataclass(frozen=True, kw_only=True)
 class HipMartiniSimulator(Simulator):
     """See the module docstring.  ``temperatures`` in K (one is R = 1 on the same path); ``save_every`` is the reference's
-    ``nstxout``; ``neighbors = (skin, every)``; ``inner = (margin, every)`` or None; ``precision`` "float32" | "float64"."""
+    ``nstxout``; ``neighbors = (skin, every)``; ``inner = (margin, every)`` or None; ``precision`` "float32" | "float64".
+    ``exchange_every = E`` > 0: replica exchange between the temperatures every E steps, in equilibration and production
+    (exchange seed ``seed + R``, next seed ``seed + R + 1``); ``observables[t]`` is then the trajectory of temperature t,
+    gathered from the slots that held it, and ``state`` gains ``ladder`` and ``exchange``."""
 
     energy_fn: Any
     topology: Any = None
@@ -134,6 +137,7 @@ class HipMartiniSimulator(Simulator):
     neighbors: tuple = (0.5, 12)
     inner: tuple | None = None
     barostat: dict | None = None
+    exchange_every: int = 0
     precision: str = "float32"
     device: Any = None
     _resident: dict = dc.field(default_factory=dict, repr=False, compare=False)
@@ -141,6 +145,8 @@ class HipMartiniSimulator(Simulator):
     def __post_init__(self):
         if self.precision not in ("float32", "float64"):
             raise ValueError("precision must be 'float32' or 'float64'")
+        if int(self.exchange_every) < 0 or (int(self.exchange_every) > 0 and np.size(self.temperatures) < 2):
+            raise ValueError("exchange_every >= 0, and at least two temperatures to exchange between, required")
         n = len(lower_martini(self.energy_fn)["types"])
         check_arguments(n, self.init_positions, self.box, self.temperatures, self.equilibration_steps, self.simulation_steps,
                         self.save_every, self.barostat)
@@ -192,6 +198,11 @@ class HipMartiniSimulator(Simulator):
         r = len(temps)
         integ.restart([int(seed) + k for k in range(r)], 0)
         state = state or {}
+        exchange = int(self.exchange_every)
+        if exchange:  # equilibration and production both exchange; the decisions' seed follows the replicas'
+            integ.set_exchange(exchange, int(seed) + r)
+            if "ladder" in state:
+                integ.set_ladder(np.asarray(state["ladder"]))
         pos = torch.as_tensor(state["positions"] if "positions" in state else x0).to(device=system.device, dtype=system.dtype).contiguous().clone()
         vel = (torch.as_tensor(state["velocities"]).to(device=system.device, dtype=system.dtype).contiguous().clone()
                if "velocities" in state else integ.init_velocities())
@@ -201,6 +212,8 @@ class HipMartiniSimulator(Simulator):
         traj, _ = integ.advance(int(self.simulation_steps), save_every=int(self.save_every), want_energy=False)
         lb = integ.last_boxes
         integ.store(pos, vel)
+        if exchange:
+            return self._exchanged_output(integ, traj, lb, temps, pos, vel, int(seed) + r + 1)
         s = traj.shape[0]
         q = torch.zeros((s, n, 4), dtype=traj.dtype, device=traj.device)
         q[..., 0] = 1.0
@@ -208,3 +221,22 @@ class HipMartiniSimulator(Simulator):
                                    temperature=torch.full((s,), KB * float(temps[k]), dtype=torch.float64, device=traj.device))
                for k in range(r)]
         return SimulatorOutput(observables=out, state=dict(positions=pos, velocities=vel, boxes=integ.box, seed=int(seed) + r))
+
+    def _exchanged_output(self, integ, traj, lb, temps, pos, vel, next_seed) -> SimulatorOutput:
+        """``observables[t]`` is the trajectory OF TEMPERATURE t: frame k is the slot that held rung t at row k, with that
+        slot's box; gathered on the GPU.  The state stays slot-major and gains the ladder."""
+        from mythos_amd.energy.base import Quaternion
+        from mythos_amd.simulators.io import SimulatorTrajectory
+
+        s, r, n = traj.shape[0], traj.shape[1], traj.shape[2]
+        slot_of_rung = torch.argsort(integ.last_ladder, dim=1)  # (S, R): the inverse of each row's permutation
+        rows = torch.arange(s, device=traj.device)
+        q = torch.zeros((s, n, 4), dtype=traj.dtype, device=traj.device)
+        q[..., 0] = 1.0
+        out = [SimulatorTrajectory(center=traj[rows, slot_of_rung[:, k]].contiguous(), orientation=Quaternion(vec=q),
+                                   box_size=lb[rows, slot_of_rung[:, k]].contiguous(),
+                                   temperature=torch.full((s,), KB * float(temps[k]), dtype=torch.float64, device=traj.device))
+               for k in range(r)]
+        attempts, accepts = integ.exchange_counts()
+        return SimulatorOutput(observables=out, state=dict(positions=pos, velocities=vel, boxes=integ.box, seed=next_seed, ladder=integ.ladder,
+                                                           exchange=dict(attempts=attempts, accepts=accepts)))

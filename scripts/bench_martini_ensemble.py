@@ -10,7 +10,12 @@ synchronised calls (best of --repeats), and from the integrator's timing getters
 loop time per launch - their difference is what list builds, coupling events and gaps cost.
 
 usage: python scripts/bench_martini_ensemble.py [--steps 2000] [--replicas 1,2,4,8,16] [--dtypes f32,f64] [--out FILE.json]
-Prints one JSON line per configuration and a markdown table at the end."""
+Prints one JSON line per configuration and a markdown table at the end.
+
+--exchange-every 0,1000,100: the replica-exchange study instead (set_exchange; NVT, or NPT with --npt): for every R and every
+value E the ensemble's replica-steps / s (best of --repeats, every repeat's time kept to show the spread), the acceptance
+rate per rung pair, and the cost per event against the E = 0 run of the same build: (t_E - t_0) / events.  The sequential
+single integrators are not run."""
 import argparse
 import json
 import sys
@@ -37,6 +42,53 @@ def timed(fn, repeats):
     return best
 
 
+def timed_all(fn, repeats):
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append(time.perf_counter() - t0)
+    return out
+
+
+def exchange_study(args, sysm, dname, x, box):
+    from mythos_amd.hip_system import MartiniEnsembleIntegrator
+
+    results = []
+    for n_rep in (int(r) for r in args.replicas.split(",")):
+        kTs = KB * np.linspace(273.0, 320.0, n_rep)
+        base = None
+        for every in (int(e) for e in args.exchange_every.split(",")):
+            ens = MartiniEnsembleIntegrator(sysm, dt=0.02, kT=kTs, gamma=1.0, seeds=1)
+            ens.set_neighbor_policy(0.5, 12)
+            if args.npt:
+                ens.set_barostat(**BARO)
+            if every:
+                ens.set_exchange(every, 20260317)
+            pos = torch.tensor(np.broadcast_to(x[3], (n_rep, *x[3].shape)).copy(), dtype=sysm.dtype, device=sysm.device)
+            ens.load(pos, ens.init_velocities(), box[3])
+            ens.advance(args.warmup)
+            step0 = ens.step
+            times = timed_all(lambda: ens.advance(args.steps), args.repeats)
+            t = min(times)
+            events = ((step0 + args.steps) // every - step0 // every) if every else 0  # of the first repeat; the others' differ by at most one
+            att, acc = ens.exchange_counts()
+            row = dict(dtype=dname, ensemble="NPT" if args.npt else "NVT", replicas=n_rep, steps=args.steps, exchange_every=every,
+                       replica_steps_per_s=n_rep * args.steps / t, seconds=times, events_per_call=events, recoveries=ens.last_recoveries(),
+                       attempts=att.tolist(), accepts=acc.tolist(), acceptance=[(a / n if n else None) for a, n in zip(acc.tolist(), att.tolist())])
+            if every == 0:
+                base = t
+            if every and base is not None and events:
+                row["us_per_event"] = 1e6 * (t - base) / events
+                row["slowdown_vs_exchange_off"] = t / base - 1.0
+            print(json.dumps(row), flush=True)
+            results.append(row)
+            del ens
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=2000)
@@ -45,6 +97,8 @@ def main():
     ap.add_argument("--dtypes", default="f32,f64")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--exchange-every", default=None, help="e.g. 0,1000,100: the replica-exchange study (see the module docstring)")
+    ap.add_argument("--npt", action="store_true", help="the exchange study under the barostat")
     args = ap.parse_args()
     from mythos_amd.hip_system import MartiniEnsembleIntegrator, MartiniLangevinIntegrator, MartiniSystem
     from tests import martini_helpers as MH
@@ -58,6 +112,9 @@ def main():
     for dname in args.dtypes.split(","):
         dtype = torch.float32 if dname == "f32" else torch.float64
         sysm = MartiniSystem(*ff, dtype=dtype)
+        if args.exchange_every is not None:
+            results += exchange_study(args, sysm, dname, x, box)
+            continue
         for npt in (False, True):
             for n_rep in (int(r) for r in args.replicas.split(",")):
                 kTs = KB * np.linspace(273.0, 320.0, n_rep) if n_rep > 1 else np.array([KB * 273.0])
@@ -98,6 +155,18 @@ def main():
                 print(json.dumps(row), flush=True)
                 results.append(row)
                 del ens, singles
+    if args.exchange_every is not None:
+        print("\n| dtype | ensemble | R | exchange every | replica-steps/s | repeats (s) | us / event | against exchange off | acceptance per rung pair |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        for r in results:
+            acc = ", ".join("-" if a is None else f"{a:.2f}" for a in r["acceptance"])
+            print(f"| {r['dtype']} | {r['ensemble']} | {r['replicas']} | {r['exchange_every']} | {r['replica_steps_per_s']:.0f} | "
+                  f"{', '.join(f'{t:.4f}' for t in r['seconds'])} | {r.get('us_per_event', float('nan')):.1f} | "
+                  f"{100 * r.get('slowdown_vs_exchange_off', 0.0):+.2f} % | {acc} |")
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(json.dumps(results, indent=1))
+        return
     print("\n| dtype | ensemble | R | ensemble replica-steps/s | sequential replica-steps/s | ratio | step kernel ms | loop ms / launch | builds + events + gaps |")
     print("|---|---|---|---|---|---|---|---|---|")
     for r in results:
