@@ -877,6 +877,36 @@ void mythos_duplex_obs_destroy(mythos_duplex_obs_t* obs);
 int mythos_duplex_obs_eval(mythos_duplex_obs_t* obs, const void* center, const void* quat, int dtype, int n_frames, double* out,
                            mythos_stream_t stream);
 
+/* ---- radial distribution functions: pair-distance histograms of stored MARTINI frames ------------
+ * The counts behind g(r) of pairs of bead selections, every frame and every pair of selections in one launch
+ * (csrc/rdf.hip; definitions in DESIGN section 3.5m).  The reference has no such observable; the counting rule is that
+ * of MDAnalysis' InterRDF with an exclusion block.
+ *   n_a, n_b   host int32[n_groups]  beads in list A and list B of a group, each at least 1 and at most 2^22
+ *   index      host int32[sum (n_a + n_b)]  the lists back to back: A_0 B_0 A_1 B_1 ...; A and B of a group may be the
+ *              same list, disjoint or overlapping
+ *   block      host int32[n] exclusion id of every bead - a pair of beads that share one is not counted - or NULL
+ *   n_bins     1 ... 4096 bins of width r_max / n_bins on [0, r_max); r_max > 0, in the units of the positions
+ *   dims       MYTHOS_RDF_XYZ, or MYTHOS_RDF_XY: distances and minimum image in x and y alone (lateral RDF of a membrane)
+ * A group whose lists leave no admissible ordered pair is refused, as are indices outside [0, n). */
+#define MYTHOS_RDF_XY 2
+#define MYTHOS_RDF_XYZ 3
+typedef struct mythos_rdf mythos_rdf_t;
+mythos_rdf_t* mythos_rdf_create(int n, int n_groups, const int32_t* n_a, const int32_t* n_b, const int32_t* index,
+                                const int32_t* block, int n_bins, double r_max, int dims, int device);
+void mythos_rdf_destroy(mythos_rdf_t* rdf);
+/* n_pairs host int64[n_groups]: the admissible ordered pairs (i in A, j in B) of each group - those with i != j and,
+ * with blocks, block[i] != block[j] - the N_pairs of the normalisation g = counts V / (N_pairs v_bin). */
+int mythos_rdf_n_pairs(const mythos_rdf_t* rdf, int64_t* n_pairs);
+/*   pos, box  dev real[n_frames][n][3], dev real[n_frames][3]; dtype is that of both; promoted to double on load
+ *   counts    dev int64[n_frames][n_groups][n_bins], zeroed by the call: +1 for every admissible ordered pair whose
+ *             minimum-image distance r (per-frame orthorhombic box, masked dimensions only) is below r_max, in bin
+ *             floor(r n_bins / r_max), at most n_bins - 1
+ *   flags     dev int32[1]: -1, or the first frame with a box edge of a masked dimension below 2 r_max, where the
+ *             minimum image no longer finds the closest pair (the counts of such a frame are not to be used)
+ * Integer adds: the counts have the same bits from run to run. */
+int mythos_rdf_eval(mythos_rdf_t* rdf, const void* pos, const void* box, int dtype, int n_frames, int64_t* counts,
+                    int32_t* flags, mythos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

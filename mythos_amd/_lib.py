@@ -143,6 +143,10 @@ _SIGS = {
     "mythos_duplex_obs_create": (V, [C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, c_double_p, C.c_int]),
     "mythos_duplex_obs_destroy": (None, [V]),
     "mythos_duplex_obs_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V]),
+    "mythos_rdf_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, C.c_int, C.c_double, C.c_int, C.c_int]),
+    "mythos_rdf_destroy": (None, [V]),
+    "mythos_rdf_n_pairs": (C.c_int, [V, C.POINTER(C.c_int64)]),
+    "mythos_rdf_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V, V]),
 }
 
 

@@ -4,7 +4,8 @@ MARTINI bond-length / triplet-angle distributions with their weighted Wasserstei
 the membrane observables of a bilayer: thickness, area per lipid and the melting temperature fitted to it, and the
 duplex-mechanics set: helical diameter, extension, twist, RMSE to a target, the stretch / torsion moduli and the
 worm-like-chain fit, and the duplex melting temperature by histogram reweighting of an umbrella-sampled trajectory, with
-oxDNA's ``bond`` / ``mindistance`` order parameters of stored frames and the umbrella histogram and weights built on them."""
+oxDNA's ``bond`` / ``mindistance`` order parameters of stored frames and the umbrella histogram and weights built on them,
+and the radial distribution functions between selections of MARTINI beads."""
 
 from mythos_amd.observables.base import ObservableSet, get_duplex_quartets
 from mythos_amd.observables.bond_distances import BondDistances, BondDistancesMapped
@@ -19,6 +20,7 @@ from mythos_amd.observables.order_parameters import (OrderParameters, extrapolat
 from mythos_amd.observables.persistence_length import PersistenceLength, persistence_length_fit
 from mythos_amd.observables.pitch import PitchAngle, compute_pitch
 from mythos_amd.observables.propeller import PropellerTwist
+from mythos_amd.observables.rdf import RadialDistribution, RadialDistributionPair
 from mythos_amd.observables.rise import Rise
 from mythos_amd.observables.rmse import RMSE
 from mythos_amd.observables.stretch_torsion import ExtensionZ, TwistXY, stretch, stretch_torsion, torsion
@@ -27,7 +29,7 @@ from mythos_amd.observables.wasserstein import WassersteinDistance, WassersteinD
 from mythos_amd.observables.wlc import calculate_extension, coth, fit_wlc, loss
 
 __all__ = ["AreaPerLipid", "BondDistances", "BondDistancesMapped", "Diameter", "ExtensionZ", "MeltingTemp", "MembraneMeltingTemp", "MembraneThickness",
-           "ObservableSet", "OrderParameters", "PersistenceLength", "PitchAngle", "PropellerTwist", "RMSE", "Rise", "TripletAngles", "TripletAnglesMapped",
+           "ObservableSet", "OrderParameters", "PersistenceLength", "PitchAngle", "PropellerTwist", "RMSE", "RadialDistribution", "RadialDistributionPair", "Rise", "TripletAngles", "TripletAnglesMapped",
            "TwistXY", "WassersteinDistance", "WassersteinDistanceMapped", "apl_residual", "calculate_apl", "calculate_extension",
            "compute_membrane_tm", "compute_pitch", "coth", "fit_apl_sigmoid", "fit_wlc", "get_duplex_quartets", "get_initial_guess",
            "loss", "persistence_length_fit", "stretch", "stretch_torsion", "torsion", "wasserstein_1d", "TARGETS", "compute_curve_width",
