@@ -225,8 +225,9 @@ def test_row_builder_equals_a_kd_tree_on_random_clouds():
     """scripts/stress_rows.py: 24 random systems (600-6 000 particles, blobs in free space and periodic boxes with
     wrapped and unwrapped coordinates, fp32 and fp64, 8-45 neighbours per particle): the device-built rows hold exactly
     as many pairs as scipy's k-d tree finds (every pair in two rows) and their longest row is as long as the tree's -
-    with managed buckets and with buckets of five places.  (Counts, not the pairs themselves: rows compared entry for
-    entry are in tests/test_gpu_martini_shapes.py, forces over the oxDNA rows in tests/test_gpu_periodic_md.py.)"""
+    with managed buckets and with buckets of five places.  (Counts here; the pairs themselves, entry for entry and
+    segment by segment against a brute-force classification, are in tests/test_gpu_oxdna_rows.py - this builder and the
+    integrator's -, MARTINI's in tests/test_gpu_martini_shapes.py, forces over the oxDNA rows in tests/test_gpu_periodic_md.py.)"""
     import subprocess
     import sys
     from pathlib import Path
