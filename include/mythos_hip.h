@@ -764,6 +764,55 @@ int mythos_martini_langevin_last_exchanges(const mythos_martini_sim_t* sim, doub
 int mythos_martini_langevin_exchange_counts(const mythos_martini_sim_t* sim, int64_t* attempts, int64_t* accepts);
 int mythos_martini_exchange_check(int n_rep, int every, const int32_t* rung_of_slot);
 
+/* ---- MARTINI integrator: position restraints, flat-bottomed restraints, pulling between centres of mass ----------
+ * External forces on the beads of a MARTINI integrator (single copy or ensemble; R = its replicas, 1 for a single copy),
+ * applied as a velocity kick queued in front of every step launch: BAOAB with the total force.  Units nm, ps, kJ/mol, amu;
+ * every sum in double in both precisions.  s is the step count of the frame the force is taken at, t = s dt.
+ *   position restraints  GROMACS' [ position_restraints ] funct 1: U = 1/2 sum_a k_a (x_a - X_a)^2.
+ *     pr_index host int32[n_posres] distinct beads; pr_k host double[n_posres][3] >= 0; pr_ref host double[R][n_posres][3].
+ *   flat-bottomed restraints  GROMACS' [ position_restraints ] funct 2: U = 1/2 k (d - r)^2 where d > r (inverted: where
+ *     d < r), no force at d = 0.  fb_index host int32[n_flat]; fb_flags host int32[n_flat]: shape in bits 0-1 (0 sphere,
+ *     d = |x - X|; 1 cylinder, the distance from the axis through X; 2 layer, d = |x_a - X_a|), the axis in bits 2-3,
+ *     invert in bit 4; fb_param host double[R][n_flat][5]: k, r, X.xyz.
+ *   pull groups  GROMACS' pull-groupN-name / -pbcatom: g_first host int32[n_groups + 1] member ranges, g_member the members
+ *     (distinct within a group), g_pbc_ref host int32[n_groups]: a member relative to which the others are taken at their
+ *     minimum image, or -1.  Centres of mass are weighted with the integrator's masses.
+ *   pull coordinates  GROMACS' pull-coordN-*: p_groups host int32[n_pull][2] = (A, B), A = -1 for the absolute reference
+ *     `origin`; p_flags host int32[n_pull]: bit 0 constant-force (else umbrella), bit 1 geometry direction (else distance),
+ *     bit 2 periodic (minimum image of D = X_B - X_A in the replica's box), bits 4-6 the axes of dim (distance);
+ *     p_param host double[R][n_pull][9]: k, init, rate, vec.xyz (a unit vector), origin.xyz.  distance: xi = |D| over dim, no
+ *     force at xi = 0; direction: xi = D . vec.  umbrella U = 1/2 k (xi - init - rate t)^2; constant-force U = k xi (k is
+ *     the negative of the force).  Member j of B gets -U'(xi) e m_j / M_B, member j of A +U'(xi) e m_j / M_A.
+ *   boxes  host double[R][3], needed when a coordinate is periodic or a group has a pbc_ref (NULL otherwise); a later load
+ *     into other boxes is then refused.
+ * Coordinates are taken as the frame stores them, unfolded.  All counts zero clears the set: the integrator then launches
+ * what it launched before the set existed.  Refused by name (INVALID_ARGUMENT): index out of range, empty group, duplicate
+ * member, A = B, k < 0, non-finite value, zero vec, empty dim, r < 0, pbc_ref not a member, a set together with a barostat
+ * or with replica exchange in either order of the two calls (the restraint virial and the restraint energy in the
+ * exchange's H are not built); NOT_READY while the resident frame is open.
+ * mythos_martini_restraints_check: those checks alone for n beads per replica, barostat / exchange saying whether one is
+ * set; touches no device.
+ * mythos_martini_langevin_eval_external: the field at pos dev real[R][n][3] and step count `step` through the kernels the
+ * integrator kicks with: force dev real[R][n][3] (or NULL), energies dev double[R][4] - position, flat-bottom, umbrella,
+ * constant-force - (or NULL) and xi dev double[R][n_pull] (or NULL; written with energies).  Needs no resident state.
+ * mythos_martini_langevin_pull_values: xi of every coordinate of a stored trajectory, pos dev real[n_frames][R][n][3] ->
+ * out dev double[n_frames][R][n_pull]; the same centre-of-mass kernel and the same evaluation as the kick.
+ * mythos_martini_langevin_n_pull: coordinates of the installed set (0 without one). */
+int mythos_martini_restraints_check(int n, int n_rep, int n_posres, const int32_t* pr_index, const double* pr_k, const double* pr_ref,
+                                    int n_flat, const int32_t* fb_index, const int32_t* fb_flags, const double* fb_param, int n_groups,
+                                    const int32_t* g_first, const int32_t* g_member, const int32_t* g_pbc_ref, int n_pull,
+                                    const int32_t* p_flags, const int32_t* p_groups, const double* p_param, const double* boxes,
+                                    int barostat, int exchange);
+int mythos_martini_langevin_set_restraints(mythos_martini_sim_t* sim, int n_posres, const int32_t* pr_index, const double* pr_k,
+                                           const double* pr_ref, int n_flat, const int32_t* fb_index, const int32_t* fb_flags,
+                                           const double* fb_param, int n_groups, const int32_t* g_first, const int32_t* g_member,
+                                           const int32_t* g_pbc_ref, int n_pull, const int32_t* p_flags, const int32_t* p_groups,
+                                           const double* p_param, const double* boxes);
+int mythos_martini_langevin_n_pull(const mythos_martini_sim_t* sim);
+int mythos_martini_langevin_eval_external(mythos_martini_sim_t* sim, const void* pos, double step, void* force, double* energies,
+                                          double* xi, mythos_stream_t stream);
+int mythos_martini_langevin_pull_values(mythos_martini_sim_t* sim, const void* pos, int n_frames, double* out, mythos_stream_t stream);
+
 /* ---- MARTINI observables: named bond lengths and triplet angles ------------------------------
  * Replaces mythos/observables/bond_distances.py:15-17, 51-69 (BondDistances / BondDistancesMapped) and
  * triplet_angles.py:15-31, 73-92 (TripletAngles / TripletAnglesMapped) with the angle of

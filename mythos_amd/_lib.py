@@ -129,6 +129,14 @@ _SIGS = {
     "mythos_martini_langevin_last_exchanges": (C.c_int, [V, c_double_p, C.POINTER(C.c_int)]),
     "mythos_martini_langevin_exchange_counts": (C.c_int, [V, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mythos_martini_exchange_check": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "mythos_martini_restraints_check": (C.c_int, [C.c_int, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p, C.c_int, c_int_p, c_int_p,
+                                                  c_double_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, c_double_p,
+                                                  c_double_p, C.c_int, C.c_int]),
+    "mythos_martini_langevin_set_restraints": (C.c_int, [V, C.c_int, c_int_p, c_double_p, c_double_p, C.c_int, c_int_p, c_int_p, c_double_p,
+                                                         C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p]),
+    "mythos_martini_langevin_n_pull": (C.c_int, [V]),
+    "mythos_martini_langevin_eval_external": (C.c_int, [V, V, C.c_double, V, V, V, V]),
+    "mythos_martini_langevin_pull_values": (C.c_int, [V, V, C.c_int, V, V]),
     "mythos_martini_obs_create": (V, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int]),
     "mythos_martini_obs_destroy": (None, [V]),
     "mythos_martini_obs_count": (C.c_int64, [V]),

@@ -29,6 +29,7 @@
 #include "martini_ensemble_checks.h"
 #include "martini_exchange_checks.h"
 #include "martini_internal.h"
+#include "martini_restraints.h"
 #include "md_driver.h"
 #include "philox.h"
 #include "wave_ops.h"
@@ -743,6 +744,23 @@ struct MmExchange {
   }
 };
 
+// External forces of the resident state (martini_restraints.h, martini_restraints.inc): the device arrays of the set
+// mythos_martini_langevin_set_restraints installed, the COM rows and the kick's stamp words.  installed = false: the
+// integrator launches nothing it did not launch before the set existed.
+struct MmRestraints {
+  bool installed = false;
+  bool uses_box = false;      // a periodic coordinate or a pbc_ref: the set holds the boxes it was lowered for
+  bool stamp_stale = true;    // the stamp words are cleared in front of the next kick (load, restart, set_restraints)
+  mythos::MrView view;
+  std::vector<double> h_boxes;
+  mythos::DeviceBuf<int> d_pr_index, d_fb_index, d_fb_flags, d_g_first, d_g_member, d_g_pbc_ref, d_p_flags, d_p_groups, d_e_index, d_e_first, d_e_term;
+  mythos::DeviceBuf<double> d_pr_k, d_pr_ref, d_fb_param, d_p_param, d_boxes, d_mass, d_rows, d_eval_rows;
+  mythos::DeviceBuf<unsigned long long> d_stamp, d_eval_stamp;
+  mythos::DeviceBuf<int> d_eval_flags;
+  mythos::DeviceBytes d_eval_vel;
+  int kick_blocks() const { return (int)(((long long)view.n_rep * view.n_entries + 255) / 256); }
+};
+
 struct mythos_martini_sim : mythos::MdRun {
   mythos_martini* sys = nullptr;
   double dt = 0.02, kT = 2.27, gamma = 1.0;
@@ -787,6 +805,8 @@ struct mythos_martini_sim : mythos::MdRun {
   std::vector<uint64_t> rep_seed;
   unsigned char* h_reps = nullptr;
   MmExchange xchg;  // off until mythos_martini_langevin_set_exchange
+  MmRestraints rst;  // none until mythos_martini_langevin_set_restraints
+  std::vector<double> h_mass;  // [n] as given at creation (the COM weights of the pull groups)
   int copies() const { return n_rep > 0 ? n_rep : 1; }
   int n_all() const { return copies() * sys->n; }  // beads of all copies
   const double* box_of(int r) const { return n_rep > 0 ? &rep_box[3 * (size_t)r] : box; }
@@ -1015,6 +1035,21 @@ static int mm_sync_charges(mythos_martini_sim* sim, hipStream_t st) {
   return MYTHOS_OK;
 }
 
+// The external kick of view v on the velocities `vel`, forces taken at pos: the COM rows of the pull groups, then the
+// gather-and-kick with one stamp word per workgroup.  The one place these two kernels are launched - in front of a step
+// launch, and by mythos_martini_langevin_eval_external with c_dt < 0 (factor 1) on zeroed velocities.  A set without pull
+// coordinates has no COM launch.
+template <typename R>
+static void mr_launch_kick(const MrView& v, const R* pos, int stride, double* rows, double c_dt, double step, typename Real4<R>::type* vel,
+                           const int* flags, const int* halt_words, int k, unsigned long long stamp, unsigned long long* stamps,
+                           hipStream_t st) {
+  if (v.n_pull > 0) hipLaunchKernelGGL(mr_com_kernel<R>, dim3(v.n_rep * v.n_groups), dim3(256), 0, st, v, pos, stride, rows);
+  const int blocks = (int)(((long long)v.n_rep * v.n_entries + 255) / 256);
+  if (blocks > 0)
+    hipLaunchKernelGGL((mr_kick_kernel<R, typename Real4<R>::type>), dim3(blocks), dim3(256), 0, st, v, pos, stride, (const double*)rows, c_dt,
+                       step, vel, flags, halt_words, k, stamp, stamps);
+}
+
 // caller's (n, 3) arrays -> the resident frame; the list of a previous state does not carry over
 template <typename R>
 static int mm_load_typed(mythos_martini_sim* sim, const R* pos, const R* v, const double* box, hipStream_t st) {
@@ -1038,6 +1073,7 @@ static int mm_load_typed(mythos_martini_sim* sim, const R* pos, const R* v, cons
   sim->list_valid = false;
   sim->open = false;
   sim->since_build = 0;
+  sim->rst.stamp_stale = true;
   return MYTHOS_OK;
 }
 
@@ -1069,8 +1105,8 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
   const size_t lds = ((size_t)2 * sim->n_ctypes * sim->n_ctypes + (coul ? kCoulRec : 0)) * sizeof(R);
   auto launch_step = [&](int k, const LaunchRow& row) {
     const int cur = row.cur;
-    const R kick_close = R(row.kick_close);
-    const int do_step = row.do_step;
+    R kick_close = R(row.kick_close);
+    int do_step = row.do_step;
     R* tp = ((row.save || row.save_next) && traj_pos) ? traj_pos + (size_t)row.sidx * n_all * 3 : nullptr;
     // pruned rows: the launch d steps after the Verlet rows were built prunes when d is a multiple of inner_every (so
     // the first launch on new rows does) and walks the pruned rows otherwise
@@ -1079,6 +1115,26 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
     const int* walk_len = (inner_on && !emit) ? sim->d_row_len_in.get() : sim->d_row_len.get();
     int* emit_rows = emit ? sim->d_rows_in.get() : nullptr;
     int* emit_len = emit ? sim->d_row_len_in.get() : nullptr;
+    // the external kick c dt F_ext / m of this launch (martini_restraints.h), queued in front of it, outside the dispatch's event pair
+    auto ext_kick = [&](double c, bool closing) {
+      MmRestraints& q = sim->rst;
+      if (q.stamp_stale) {
+        (void)hipMemsetAsync(q.d_stamp.get(), 0, sizeof(unsigned long long) * (size_t)q.kick_blocks(), st);
+        q.stamp_stale = false;
+      }
+      const unsigned long long stamp = 2ull * (unsigned long long)(sim->step + k) + (closing ? 1ull : 0ull) + 1ull;
+      mr_launch_kick<R>(q.view, (const R*)fr[cur], 4, q.d_rows.get(), c * sim->dt, double(sim->step + k), vel, sim->d_flags.get(),
+                        sim->list.d_overflow.get(), k, stamp, q.d_stamp.get(), st);
+    };
+    // A launch that saves an energy row takes the row's kinetic energy behind its closing half kick.  Under a set of
+    // restraints the external kick of a whole launch - closing and opening half together - would already be in those
+    // velocities, so such a launch is issued as the two launches a call that closes and the call behind it issue at this
+    // step index: close with the row (kick_close, no step), then open (no closing kick, the step), each behind its own
+    // external half kick, whose stamps differ in the closing bit as they do across two calls.  The forces are evaluated
+    // twice, on rows with energies only; both launches walk the same rows, read frame cur and test the same halt words.
+    const bool split = sim->rst.installed && row.save && row.do_step != 0;
+    if (sim->rst.installed) ext_kick(split ? double(row.kick_close) : double(row.kick_close) + 0.5 * row.do_step, row.kick_close != 0.0f);
+    if (split) do_step = 0;
 #define MM_ARGS                                                                                                           \
   n, K, (const V4*)fr[cur], fr[cur ^ 1], vel, walk_rows, walk_len, sim->list.stride, (const R*)sim->d_csig2.get(),        \
       (const R*)sim->d_ceps.get(), m->d_bead_bonds.get(), m->d_bead_angles.get(), m->d_bonds.get(),                       \
@@ -1121,6 +1177,11 @@ static int mm_advance_typed(mythos_martini_sim* sim, int n_steps, int save_every
     } else {
       if (emit) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{});
     }
+    if (split) {
+      ext_kick(0.5, false);
+      kick_close = R(0), do_step = 1, tp = nullptr;
+      if (emit) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{});
+    }
   };
   MdDrive d;
   d.who = "mythos_martini_langevin_run";
@@ -1160,6 +1221,7 @@ static int mm_store_typed(mythos_martini_sim* sim, R* pos, R* v, hipStream_t st)
 
 #include "martini_npt.inc"
 #include "martini_exchange.inc"
+#include "martini_restraints.inc"
 
 extern "C" {
 
@@ -1201,6 +1263,7 @@ mythos_martini_sim_t* mm_create(mythos_martini_t* sys, int n_rep, double dt, con
       return nullptr;
     }
     im[i] = 1.0 / mi;
+    s->h_mass.push_back(mi);
   }
   // partners per incidence slot
   const std::vector<int>&bb = sys->h_bead_bonds, &ba = sys->h_bead_angles;
@@ -1331,6 +1394,7 @@ int mm_check_box(const mythos_martini_sim_t* s, const double* box, const char* w
 }
 
 int mm_load(mythos_martini_sim_t* s, const void* pos, const void* vel, const double* box, hipStream_t st) {
+  if (int rc = mr_check_load_box(s, box)) return rc;
   if (int rc = mm_sync_charges(s, st)) return rc;
   return s->sys->dtype == MYTHOS_F32 ? mm_load_typed<float>(s, (const float*)pos, (const float*)vel, box, st)
                                      : mm_load_typed<double>(s, (const double*)pos, (const double*)vel, box, st);
@@ -1432,6 +1496,7 @@ int mythos_martini_langevin_restart(mythos_martini_sim_t* s, const uint64_t* see
     std::fill(s->xchg.accepts.begin(), s->xchg.accepts.end(), 0);
   }
   s->step = step;
+  s->rst.stamp_stale = true;
   s->resident = false;  // (an ensemble's replica table takes the seeds at the load that has to follow)
   s->list_valid = false;
   s->open = false;

@@ -442,6 +442,11 @@ int mythos_martini_langevin_set_barostat(mythos_martini_sim_t* s, int kind, int 
     b.kind = 0;
     return MYTHOS_OK;
   }
+  if (s->rst.installed) {
+    set_error("mythos_martini_langevin_set_barostat: a barostat together with restraints is refused: the restraint virial and reference "
+              "scaling are not built (clear the set with mythos_martini_langevin_set_restraints first)");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
   const bool finite = std::isfinite(ref_p[0]) && std::isfinite(ref_p[1]) && std::isfinite(compressibility[0]) && std::isfinite(compressibility[1]);
   if (!finite || !(compressibility[0] >= 0) || !(compressibility[1] >= 0) || !(tau_p > 0) || !std::isfinite(tau_p) || every < 1) {
     set_error("mythos_martini_langevin_set_barostat: finite ref_p, compressibility >= 0, tau_p > 0 and every >= 1 required");

@@ -823,6 +823,65 @@ class MartiniLangevinIntegrator(_MdIntegrator):
         _lib.check(self._lib.mythos_martini_langevin_neighbor_stats(self._h, C.byref(mx), C.byref(mean)), "neighbor_stats")
         return mx.value, mean.value
 
+    # ---- position restraints, flat-bottomed restraints, pulling (mythos_amd.simulators.martini_restraints) ---------
+    _replicas = 1      # leading replica axis of the tensors below: none for the single integrator
+    restraints = None  # the set last handed to set_restraints
+
+    def _lead(self) -> tuple:
+        return ()
+
+    def set_restraints(self, restraints=None, reference_pos=None, *, box=None, topology=None) -> None:
+        """External forces on the beads (mythos_martini_langevin_set_restraints): a ``MartiniRestraints`` set of position
+        restraints, flat-bottomed restraints and pull coordinates between centres of mass.  ``reference_pos``: the state
+        that references left ``None`` take their positions from; ``box``: the box(es) of the state, for periodic
+        coordinates and ``pbc_ref`` (default: those of the resident state); ``topology``: for groups given by a selection.
+        None, or an empty set, clears them: the integrator then launches what it launched before.  Refused together with
+        a barostat or replica exchange, and between ``advance`` and ``store`` (an open frame)."""
+        from mythos_amd.simulators import martini_restraints as mr
+
+        rs = mr.MartiniRestraints() if restraints is None else restraints
+        if isinstance(reference_pos, torch.Tensor):
+            reference_pos = reference_pos.detach().double().cpu().numpy()
+        if box is None and rs:
+            b = self.box
+            box = b if np.all(b > 0) else None
+        a = rs.lower(topology, n_rep=self._replicas, boxes=box, reference_pos=reference_pos)
+        _lib.check(self._lib.mythos_martini_langevin_set_restraints(self._h, *mr.c_args(a)), "martini_set_restraints")
+        self.restraints = rs
+
+    def _n_pull(self) -> int:
+        return int(self._lib.mythos_martini_langevin_n_pull(self._h))
+
+    def external_field(self, pos, step=None):
+        """The external field at ``pos`` and step count ``step`` (default: the integrator's), evaluated by the kernels the
+        integrator kicks with (mythos_martini_langevin_eval_external): -> (force like ``pos``, energies (4,) float64 -
+        position, flat-bottom, umbrella, constant-force -, xi (P,) float64: the pull coordinates).  The ensemble's carry
+        its leading replica axis.  Needs no resident state and changes none."""
+        s = self.system
+        shape = (*self._lead(), s.n, 3)
+        if pos.device != s.device or pos.dtype != s.dtype or tuple(pos.shape) != shape or not pos.is_contiguous():
+            raise ValueError(f"pos must be a contiguous {s.dtype} tensor of shape {shape} on {s.device}")
+        force = torch.empty_like(pos)
+        energies = torch.zeros((*self._lead(), 4), dtype=torch.float64, device=s.device)
+        xi = torch.zeros((*self._lead(), self._n_pull()), dtype=torch.float64, device=s.device)
+        _lib.check(self._lib.mythos_martini_langevin_eval_external(self._h, _lib.ptr(pos), float(self.step if step is None else step),
+                                                                   _lib.ptr(force), _lib.ptr(energies), _lib.ptr(xi), _lib.stream(s.device)),
+                   "martini_eval_external")
+        return force, energies, xi
+
+    def pull_values(self, pos) -> torch.Tensor:
+        """xi of every pull coordinate on a stored trajectory ``pos`` (rows, n, 3) - the ensemble's (rows, R, n, 3) -
+        -> (rows, P) / (rows, R, P) float64 on the device (mythos_martini_langevin_pull_values)."""
+        s = self.system
+        tail = (*self._lead(), s.n, 3)
+        if pos.device != s.device or pos.dtype != s.dtype or pos.dim() != len(tail) + 1 or tuple(pos.shape[1:]) != tail:
+            raise ValueError(f"pos must be a {s.dtype} tensor of shape (rows, {', '.join(map(str, tail))}) on {s.device}")
+        pos = pos.contiguous()
+        out = torch.zeros((pos.shape[0], *self._lead(), self._n_pull()), dtype=torch.float64, device=s.device)
+        _lib.check(self._lib.mythos_martini_langevin_pull_values(self._h, _lib.ptr(pos), int(pos.shape[0]), _lib.ptr(out),
+                                                                 _lib.stream(s.device)), "martini_pull_values")
+        return out
+
 
 class _MartiniEnsembleHandle(MartiniLangevinIntegrator):
     """The handle behind :class:`MartiniEnsembleIntegrator` (mythos_martini_langevin_create_ensemble): the single
@@ -851,6 +910,11 @@ class _MartiniEnsembleHandle(MartiniLangevinIntegrator):
 
     def _boxes(self, box) -> np.ndarray:
         return MartiniEnsembleIntegrator.replica_boxes(box, self.n_rep)
+
+    _replicas = property(lambda self: self.n_rep)
+
+    def _lead(self) -> tuple:
+        return (self.n_rep,)
 
     def restart(self, seeds, step: int = 0) -> None:
         """Make the handle new for another run (mythos_martini_langevin_restart): one seed per replica, the step counter set,

@@ -5,8 +5,9 @@ temperature under one md.mdp (examples/scripts/martini_full_reparameterization.p
 
 ``run(opt_params, seed=...)`` lowers ``energy_fn.with_params(opt_params)`` to the tables of one ``MartiniSystem``, uploads
 them into the resident handles (made at the first run and kept, as ``HipMDSimulator`` keeps its), equilibrates without
-output, runs production and returns one ``SimulatorTrajectory`` per temperature, on the GPU.  Not built: gradients through
-the run, a bias, restraints."""
+output, runs production and returns one ``SimulatorTrajectory`` per temperature, on the GPU.  ``restraints``: a
+``MartiniRestraints`` set (mythos_amd.simulators.martini_restraints), repeated per temperature.  Not built: gradients
+through the run, the restraints' bias as a term of the energy functions."""
 
 from __future__ import annotations
 
@@ -121,7 +122,11 @@ class HipMartiniSimulator(Simulator):
     ``nstxout``; ``neighbors = (skin, every)``; ``inner = (margin, every)`` or None; ``precision`` "float32" | "float64".
     ``exchange_every = E`` > 0: replica exchange between the temperatures every E steps, in equilibration and production
     (exchange seed ``seed + R``, next seed ``seed + R + 1``); ``observables[t]`` is then the trajectory of temperature t,
-    gathered from the slots that held it, and ``state`` gains ``ladder`` and ``exchange``."""
+    gathered from the slots that held it, and ``state`` gains ``ladder`` and ``exchange``.
+    ``restraints``: a ``MartiniRestraints`` set, the same for every temperature except where a pull coordinate's ``init`` /
+    ``k`` hold (R,) values - ``temperatures=[T] * R`` with ``init`` of shape (R,) are R umbrella windows in one launch;
+    references left None are the positions the run starts from.  ``state["pull"]`` is then the (rows, R, P) float64 tensor
+    of the pull coordinates of the saved frames, on the GPU.  Refused with a barostat or exchange."""
 
     energy_fn: Any
     topology: Any = None
@@ -138,6 +143,7 @@ class HipMartiniSimulator(Simulator):
     inner: tuple | None = None
     barostat: dict | None = None
     exchange_every: int = 0
+    restraints: Any = None
     precision: str = "float32"
     device: Any = None
     _resident: dict = dc.field(default_factory=dict, repr=False, compare=False)
@@ -147,6 +153,9 @@ class HipMartiniSimulator(Simulator):
             raise ValueError("precision must be 'float32' or 'float64'")
         if int(self.exchange_every) < 0 or (int(self.exchange_every) > 0 and np.size(self.temperatures) < 2):
             raise ValueError("exchange_every >= 0, and at least two temperatures to exchange between, required")
+        if self.restraints and (barostat_settings(self.barostat) or int(self.exchange_every) > 0):
+            raise ValueError("restraints together with a barostat or replica exchange are not built (the restraint virial, the "
+                             "restraint energy in the exchange's H)")
         n = len(lower_martini(self.energy_fn)["types"])
         check_arguments(n, self.init_positions, self.box, self.temperatures, self.equilibration_steps, self.simulation_steps,
                         self.save_every, self.barostat)
@@ -206,6 +215,8 @@ class HipMartiniSimulator(Simulator):
         pos = torch.as_tensor(state["positions"] if "positions" in state else x0).to(device=system.device, dtype=system.dtype).contiguous().clone()
         vel = (torch.as_tensor(state["velocities"]).to(device=system.device, dtype=system.dtype).contiguous().clone()
                if "velocities" in state else integ.init_velocities())
+        if self.restraints or integ.restraints:  # (the references left None follow the state this run starts from)
+            integ.set_restraints(self.restraints, reference_pos=pos, box=state.get("boxes", boxes), topology=self.topology)
         integ.load(pos, vel, state.get("boxes", boxes))
         if self.equilibration_steps:
             integ.advance(int(self.equilibration_steps))
@@ -220,7 +231,10 @@ class HipMartiniSimulator(Simulator):
         out = [SimulatorTrajectory(center=traj[:, k].contiguous(), orientation=Quaternion(vec=q), box_size=lb[:, k].contiguous(),
                                    temperature=torch.full((s,), KB * float(temps[k]), dtype=torch.float64, device=traj.device))
                for k in range(r)]
-        return SimulatorOutput(observables=out, state=dict(positions=pos, velocities=vel, boxes=integ.box, seed=int(seed) + r))
+        st = dict(positions=pos, velocities=vel, boxes=integ.box, seed=int(seed) + r)
+        if self.restraints:
+            st["pull"] = integ.pull_values(traj)
+        return SimulatorOutput(observables=out, state=st)
 
     def _exchanged_output(self, integ, traj, lb, temps, pos, vel, next_seed) -> SimulatorOutput:
         """``observables[t]`` is the trajectory OF TEMPERATURE t: frame k is the slot that held rung t at row k, with that
