@@ -524,7 +524,7 @@ int mythos_oxdna_write_trajectory(const char* path, int n, int n_frames, const d
  * No counterpart in the reference.  The GPU tests use them to reach code paths that physical inputs reach only by
  * chance (a cell bucket that overflows, a row walk in several segments, a list rebuild that overflows in front of the
  * first launch of a segment).  Process-wide, read when a list is built / a call starts (never per launch); a value of 0
- * restores the default.  Nothing in the library reads the environment. */
+ * restores the default (MYTHOS_DEBUG_ROWS_FILTER excepted: its default is 1).  Nothing in the library reads the environment. */
 enum mythos_debug_key {
   MYTHOS_DEBUG_CELL_BUCKET_CAP = 0, /* places per cell bucket, fixed (no growth): exercises the spill list */
   MYTHOS_DEBUG_ENERGY_LIST_CAP = 1, /* entries per segment of the energy kernel's row walk (8 ... 192); used by
@@ -538,7 +538,11 @@ enum mythos_debug_key {
                                        through an aborted launch */
   MYTHOS_DEBUG_MD_LANES = 6,        /* 8 | 16: lanes per nucleotide of the oxDNA step launches, fixed when a state is loaded
                                        (normally 16 where n / 16 workgroups are at most two per CU, 8 otherwise) */
-  MYTHOS_DEBUG_KEYS = 7
+  MYTHOS_DEBUG_ROWS_FILTER = 7,     /* DEFAULT 1 (the one key whose default is not 0): scheduled oxDNA list rebuilds filter candidate
+                                       rows where the cell builder makes the rows; 0: the full builder makes every one */
+  MYTHOS_DEBUG_ROWS_CAND_EVERY = 8, /* list rebuilds per candidate (wide) build; 0: kCandEvery (csrc/row_filter_plan.h) */
+  MYTHOS_DEBUG_ROWS_CAND_MARGIN = 9, /* how far beyond the list range the candidates reach, in thousandths; 0: kCandMarginMilli */
+  MYTHOS_DEBUG_KEYS = 10
 };
 int mythos_debug_set(int key, int64_t value);
 int64_t mythos_debug_get(int key);

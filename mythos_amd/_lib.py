@@ -205,11 +205,12 @@ def check(rc: int, what: str = "") -> None:
 
 
 # keys of mythos_debug_set (include/mythos_hip.h: enum mythos_debug_key) - test and diagnostic switches
-DEBUG_KEYS = {"cell_bucket_cap": 0, "energy_list_cap": 1, "md_segment": 2, "md_overflow_at": 3, "md_dense": 4, "md_items_big": 5, "md_lanes": 6}
+DEBUG_KEYS = {"cell_bucket_cap": 0, "energy_list_cap": 1, "md_segment": 2, "md_overflow_at": 3, "md_dense": 4, "md_items_big": 5, "md_lanes": 6,
+              "rows_filter": 7, "rows_cand_every": 8, "rows_cand_margin": 9}  # (rows_filter alone defaults to 1)
 
 
 def debug_set(key: str, value: int) -> None:
-    """Process-wide test / diagnostic switch of the library; 0 restores the default."""
+    """Process-wide test / diagnostic switch of the library; 0 restores the default (rows_filter: 1 does)."""
     check(load().mythos_debug_set(DEBUG_KEYS[key], int(value)), f"debug_set({key})")
 
 

@@ -19,6 +19,8 @@ int hip_fail(hipError_t e, const char* what) {
 }
 
 static std::atomic<long long> g_debug[MYTHOS_DEBUG_KEYS];
+// (every key starts at 0 but the row filter's switch, which is on)
+static const bool g_debug_defaults = (g_debug[MYTHOS_DEBUG_ROWS_FILTER].store(1, std::memory_order_relaxed), true);
 
 long long debug_value(int key) { return (key >= 0 && key < MYTHOS_DEBUG_KEYS) ? g_debug[key].load(std::memory_order_relaxed) : 0; }
 void debug_clear(int key) {

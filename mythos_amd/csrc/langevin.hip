@@ -102,6 +102,7 @@ int mythos_langevin_set_neighbor_policy(mythos_sim_t* s, double r_cut, double sk
   s->rebuild_every = every;
   s->list_fitted = false;  // another list range: size rows and buckets again at the next run
   s->list_valid = false;
+  s->sys->cand_unfit = false;  // (and find out again whether its candidate rows fit)
   return MYTHOS_OK;
 }
 

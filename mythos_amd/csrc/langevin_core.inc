@@ -229,12 +229,38 @@ static int advance_typed(mythos_sim* sim, int n_steps, int save_every, bool clos
       hipLaunchKernelGGL(reduce_trace_kernel<kTraceWidth>, dim3(1), dim3(256), 0, st, sim->d_epart.get(), blocks,
                          e_trace + (size_t)row.sidx * kTraceWidth);
   };
+  // Where the cell builder makes the rows, a rebuild filters candidate rows instead (neighbors.hip: filter_rows_kernel),
+  // behind a wide build where row_filter_plan.h says so: the first build of a list, every kCandEvery-th rebuild, every
+  // recovery.  The rows are the builder's either way; mythos_debug_set(MYTHOS_DEBUG_ROWS_FILTER, 0) has the builder make
+  // them all, as do systems the all-pairs kernel serves.
+  const int cand_every = cand_every_for(debug_value(MYTHOS_DEBUG_ROWS_CAND_EVERY));
+  const double cand_margin = cand_margin_for(debug_value(MYTHOS_DEBUG_ROWS_CAND_MARGIN));
+  const int cand_margin_milli = (int)std::lround(1e3 * cand_margin);
+  bool filter_rows = dynamic_list && debug_value(MYTHOS_DEBUG_ROWS_FILTER) != 0 && !sys->cand_unfit &&
+                     rows_filter_applies(sys, sim->r_cut, sim->skin, cand_margin);
   auto rebuild = [&](int buf) -> int {
     if ((++sim->builds & 63) == 0)
       if (int rc = update_chunk_order<R>(sim, fr[buf].p0, blocks, st)) return rc;
-    return rows_build_device(sys, fr[buf].p0, true, sim->r_cut, sim->skin, fr[buf].p3, fr[buf].p1, true, st);
+    if (!filter_rows) {
+      sim->cand = cand_none();
+      return rows_build_device(sys, fr[buf].p0, true, sim->r_cut, sim->skin, fr[buf].p3, fr[buf].p1, true, st);
+    }
+    const bool wide = cand_rebuild_is_wide(sim->cand, sim->list_valid, cand_every, cand_margin_milli);
+    if (wide) {
+      sim->cand = cand_none();  // (should the build fail)
+      if (int rc = rows_wide_build_device(sys, fr[buf].p0, sim->r_cut, sim->skin, cand_margin, st)) return rc;
+    }
+    sim->cand = cand_after(wide, sim->cand, cand_margin_milli);
+    return rows_filter_device(sys, fr[buf].p0, fr[buf].p3, fr[buf].p1, sim->r_cut, sim->skin, cand_margin, st);
   };
   auto rebuild_until_fit = [&](int buf) -> int {
+    sim->cand = cand_none();
+    if (filter_rows) {
+      const int rc = rows_filter_until_fit(sys, fr[buf].p0, fr[buf].p3, fr[buf].p1, sim->r_cut, sim->skin, cand_margin, st);
+      if (rc == MYTHOS_OK) sim->cand = cand_after(true, sim->cand, cand_margin_milli);
+      if (!sys->cand_unfit) return rc;
+      filter_rows = false;  // (candidate rows too long for this system: the full builder from here on)
+    }
     return rows_build_until_fit(sys, fr[buf].p0, true, sim->r_cut, sim->skin, fr[buf].p3, fr[buf].p1, true, true, st);
   };
   auto on_abort = [&]() -> int {

@@ -11,6 +11,7 @@
 #include "ext_field.h"
 #include "langevin_step.h"
 #include "md_driver.h"
+#include "row_filter_plan.h"
 #include "umbrella.h"
 
 struct mythos_sim : mythos::MdRun {
@@ -24,6 +25,7 @@ struct mythos_sim : mythos::MdRun {
   mythos::DeviceBytes frame[2][kFrameArrays];
   int builds = 0;          // scheduled rebuilds so far (the chunk order is refreshed every 64th)
   int list_epoch = 0;      // sys->list_epoch the rows in use belong to
+  mythos::CandState cand;  // the candidate rows behind the scheduled rebuilds (row_filter_plan.h); carries over like since_build
   // centres as the last run handed them out (hi) and the low parts that went with them (fp32 systems)
   mythos::DeviceBytes keep_hi, keep_lo;
   bool keep_valid = false;

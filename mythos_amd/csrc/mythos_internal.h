@@ -90,6 +90,14 @@ struct mythos_system {
   mythos::DeviceBytes d_ref_pos;  // [n] real4 positions at the last build (MD displacement check)
   mythos::DeviceBytes d_ref_off;  // [n] real4 backbone offsets at the last build
   mythos::DeviceBytes d_ref_a1;   // [n] real4 base vectors at the last build
+  // Candidate store of an MD run (neighbors.hip: rows_wide_build_device fills it, filter_rows_kernel reads it): rows of
+  // every unbonded neighbour whose centre lay within list range + margin at the candidate frame, one index-sorted
+  // segment each, with their own stride, overflow words and cell table, and the centres they were built from.
+  // Allocated at the first wide build.
+  mythos::VerletRows cand{32};
+  mythos::DeviceBuf<int> d_cand_len;   // [n] used slots | [n] end of the close segment (= used slots: one segment)
+  mythos::DeviceBytes d_cand_ref;      // [n] real4 centres at the candidate frame
+  bool cand_unfit = false;             // the candidates of this system need longer rows than the builder's LDS holds: no filter
   int reserve_refs() {
     const size_t v4 = (dtype == MYTHOS_F32 ? sizeof(float4) : sizeof(double4)) * (size_t)n;
     for (mythos::DeviceBytes* b : {&d_ref_pos, &d_ref_off, &d_ref_a1})
@@ -243,5 +251,19 @@ int rows_build_device(mythos_system* sys, const void* center, bool center_is_vec
 int rows_build_until_fit(mythos_system* sys, const void* center, bool center_is_vec4, double r_cut, double skin,
                          const void* backbone_offsets, const void* base_vectors, bool write_refs, bool headroom,
                          hipStream_t stream);
+// The candidate rows of an MD run and the rows filtered from them (row_filter_plan.h).  p0, p3, p1: the
+// frame's centres, backbone offsets and base vectors, real4 per nucleotide.
+// rows_filter_applies: the cell builder would build both the rows and the candidates (cell_grid at either range).
+bool rows_filter_applies(const mythos_system* sys, double r_cut, double skin, double margin);
+// wide build: the cell builder at r_cut + skin + margin, centre criterion only, into sys->cand
+int rows_wide_build_device(mythos_system* sys, const void* p0, double r_cut, double skin, double margin, hipStream_t stream);
+// filter: sys->cand -> sys->list at the frame (p0, p3, p1), entry for entry what rows_build_device writes there - or a
+// non-zero first overflow word of sys->list, which halts the step launches (stale candidates, rows over a stride)
+int rows_filter_device(mythos_system* sys, const void* p0, const void* p3, const void* p1, double r_cut, double skin, double margin,
+                       hipStream_t stream);
+// wide build until the candidates fit, then filter until the rows fit (synchronising; both with headroom).  Candidate rows
+// beyond kCandStrideMax slots (a system far denser than a duplex) set sys->cand_unfit and fail: the caller builds in full
+int rows_filter_until_fit(mythos_system* sys, const void* p0, const void* p3, const void* p1, double r_cut, double skin, double margin,
+                          hipStream_t stream);
 
 }  // namespace mythos

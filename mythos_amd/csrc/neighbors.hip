@@ -9,6 +9,7 @@
 
 #include "cell_list.h"
 #include "oxdna_gather.h"
+#include "row_filter_plan.h"
 
 namespace mythos {
 
@@ -318,16 +319,9 @@ __global__ __launch_bounds__(256) void build_rows_cells_kernel(int n, const R* _
   }
 }
 
+// The site criteria of a build at list range rl: what build_cells_typed classifies with, and the row filter after it
 template <typename R>
-static int build_cells_typed(mythos_system* sys, const R* pos, bool vec4, double rl, double skin, const R* off,
-                             const R* a1, bool write_refs, hipStream_t st) {
-  R* ref_pos = write_refs ? (R*)sys->d_ref_pos.get() : nullptr;
-  R* ref_off = write_refs ? (R*)sys->d_ref_off.get() : nullptr;
-  R* ref_a1 = write_refs ? (R*)sys->d_ref_a1.get() : nullptr;
-  const int n = sys->n;
-  // classification radius of the leading "close" segment (everything is close until parameters exist)
-  const double rcl = sys->params_set ? std::min(rl, oxdna_close_range(sys) + skin) : rl;
-  int* d_close = row_close_of(sys);
+static SiteCrit<R> site_crit_for(const mythos_system* sys, double rl, double skin, const R* off, const R* a1) {
   // range of the backbone-backbone terms (excluded volume, and Debye-Hueckel in oxDNA2) for the far segment
   double rbb = rl;
   if (off && sys->params_set) {
@@ -351,9 +345,30 @@ static int build_cells_typed(mythos_system* sys, const R* pos, bool vec4, double
     sc.g_ba = R(0.5 * (Pd[GEO_BASE] + Pr[GEO_BASE]));
     sc.g_st = R(0.5 * (Pd[GEO_STACK] + Pr[GEO_STACK]));
   }
-  VerletRows& L = sys->list;
+  return sc;
+}
+
+// wide: the candidate store of an MD run (sys->cand, its lengths and reference centres) instead of the rows - the
+// caller passes neither offsets nor base vectors, and the close range is the list range: one index-sorted segment
+template <typename R>
+static int build_cells_typed(mythos_system* sys, const R* pos, bool vec4, double rl, double skin, const R* off,
+                             const R* a1, bool write_refs, hipStream_t st, bool wide = false) {
+  R* ref_pos = write_refs ? (R*)(wide ? sys->d_cand_ref.get() : sys->d_ref_pos.get()) : nullptr;
+  R* ref_off = write_refs ? (R*)sys->d_ref_off.get() : nullptr;  // (written with site criteria only: never by a wide build)
+  R* ref_a1 = write_refs ? (R*)sys->d_ref_a1.get() : nullptr;
+  const int n = sys->n;
+  // classification radius of the leading "close" segment (everything is close until parameters exist)
+  const double rcl = (sys->params_set && !wide) ? std::min(rl, oxdna_close_range(sys) + skin) : rl;
+  int* d_len = wide ? sys->d_cand_len.get() : sys->d_row_len.get();
+  int* d_close = wide ? d_len + n : row_close_of(sys);
+  const SiteCrit<R> sc = site_crit_for<R>(sys, rl, skin, off, a1);
+  VerletRows& L = wide ? sys->cand : sys->list;
   CellGrid<R> g;
   const bool cells = cell_grid(g, n, rl, sys->has_box ? sys->box : nullptr);
+  if (wide && !cells) {  // (rows_filter_applies said otherwise)
+    set_error("candidate build: the system does not take the cell builder");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
   const int blocks_ap = (n * 64 + 255) / 256;
   int* d_partners = sys->d_row_len.get() + n;
   const BoxT<R> box = make_box<R>(sys);
@@ -389,13 +404,202 @@ static int build_cells_typed(mythos_system* sys, const R* pos, bool vec4, double
   const size_t far_lds = (size_t)kPerBlock * 2 * L.stride * sizeof(int);
   if (vec4)
     hipLaunchKernelGGL((build_rows_cells_kernel<R, true, kRowG>), dim3(wb), dim3(256), far_lds, st, n, pos, box, g, R(rl * rl),
-                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows.get(), sys->d_row_len.get(), d_close, L.stride,
+                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows.get(), d_len, d_close, L.stride,
                        L.d_overflow.get(), ref_pos, ref_off, ref_a1);
   else
     hipLaunchKernelGGL((build_rows_cells_kernel<R, false, kRowG>), dim3(wb), dim3(256), far_lds, st, n, pos, box, g, R(rl * rl),
-                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows.get(), sys->d_row_len.get(), d_close, L.stride,
+                       R(rcl * rcl), sc, d_partners, bins.cnt_cur, (const typename CellPlace<R>::type*)bins.place, bins.cap, bins.spill, bins.H, site_stride, L.d_rows.get(), d_len, d_close, L.stride,
                        L.d_overflow.get(), ref_pos, ref_off, ref_a1);
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Row filter: the rows of an MD frame from the candidate rows of an earlier one (a wide build: every unbonded neighbour
+// whose centre lay within list range + margin, one index-sorted segment per nucleotide) instead of from the cell table.
+// G lanes per nucleotide as the builder has; the chain of dependent reads is own state -> candidate indices -> their
+// centres, backbone offsets and base vectors from the frame (kFilterBatch x G candidates requested together) -> row.
+// A candidate is classified by the builder's functions on the builder's operands (min_image, the centre ranges,
+// site_close_v, far_in_range_v), and ballot compaction keeps the candidates' index order, so close and far segment come
+// out as the builder's rank sort leaves them: while the candidates are a superset of what the builder would sweep into
+// range, the rows are the builder's entry for entry.  They are a superset while no centre has moved more than half the
+// margin since the wide build; a nucleotide that has says so in the first overflow word of the rows, as does a row that
+// outgrows its stride (the builder's own report) or a candidate store whose build overflowed: the step launches behind
+// halt on that word and the host repairs with a synchronising wide build and filter (rows_filter_until_fit).
+// ------------------------------------------------------------------------------------------------
+constexpr int kFilterBatch = 4;
+constexpr int kRowsUnvouched = 1;  // first overflow word: no row is this short, so it names no stride to grow to
+
+template <typename R, int G>
+__global__ __launch_bounds__(256) void filter_rows_kernel(int n, const typename Vec4T<R>::type* __restrict__ p0,
+                                                          const typename Vec4T<R>::type* __restrict__ p3,
+                                                          const typename Vec4T<R>::type* __restrict__ p1, const BoxT<R> box,
+                                                          R rc2, R rcl2, const SiteCrit<R> sc,
+                                                          const int* __restrict__ partners,
+                                                          const int* __restrict__ cand_rows, const int* __restrict__ cand_len,
+                                                          int cand_stride,
+                                                          const typename Vec4T<R>::type* __restrict__ cand_ref, R stale2,
+                                                          const int* __restrict__ cand_overflow, int* __restrict__ rows,
+                                                          int* __restrict__ row_len, int* __restrict__ row_close,
+                                                          int row_stride, int* __restrict__ overflow,
+                                                          typename Vec4T<R>::type* __restrict__ ref_pos,
+                                                          typename Vec4T<R>::type* __restrict__ ref_off,
+                                                          typename Vec4T<R>::type* __restrict__ ref_a1) {
+  using V4 = typename Vec4T<R>::type;
+  constexpr int NG = 256 / G;
+  extern __shared__ int s_far_all[];  // [NG][cand_stride]: the far entries of a row until its close segment is complete
+  const int grp = threadIdx.x / G, l = threadIdx.x % G;
+  const int gshift = (threadIdx.x & 63) & ~(G - 1);
+  const int i = blockIdx.x * NG + grp;
+  if (i >= n) return;
+  int* s_far = s_far_all + (size_t)grp * cand_stride;
+  const V4 c4 = p0[i], o4 = p3[i], a4 = p1[i], r4 = cand_ref[i];
+  const int ncand = min(cand_len[i], cand_stride) - ROW_BONDED_SLOTS;
+  const int* crow = cand_rows + (size_t)i * cand_stride + ROW_BONDED_SLOTS;
+  const V3<R> ci{c4.x, c4.y, c4.z};
+  const R oi[3] = {o4.x, o4.y, o4.z}, ai[3] = {a4.x, a4.y, a4.z};
+  int* row = rows + (size_t)i * row_stride;
+  int out_c = 0, out_f = 0;
+  constexpr unsigned int kGroupMask = (G == 32) ? 0xffffffffu : ((1u << G) - 1u);
+  const unsigned int below = (1u << l) - 1u;
+  for (int t0 = 0; t0 < ncand; t0 += kFilterBatch * G) {
+    int e[kFilterBatch];
+    V4 cj[kFilterBatch], oj4[kFilterBatch], aj4[kFilterBatch];
+#pragma unroll
+    for (int b = 0; b < kFilterBatch; ++b) {
+      const int t = t0 + b * G + l;
+      e[b] = (t < ncand) ? crow[t] : -1;
+    }
+#pragma unroll
+    for (int b = 0; b < kFilterBatch; ++b) {
+      const int j = (e[b] >= 0) ? (e[b] & ROW_INDEX_MASK) : i;  // (idle lanes read their own record: in bounds, and cached)
+      cj[b] = p0[j], oj4[b] = p3[j], aj4[b] = p1[j];
+    }
+#pragma unroll
+    for (int b = 0; b < kFilterBatch; ++b) {
+      if (t0 + b * G >= ncand) break;  // (uniform over the group)
+      bool hit_c = false, hit_f = false;
+      if (e[b] >= 0) {
+        const R oj[3] = {oj4[b].x, oj4[b].y, oj4[b].z}, aj[3] = {aj4[b].x, aj4[b].y, aj4[b].z};
+        V3<R> d{cj[b].x - ci.x, cj[b].y - ci.y, cj[b].z - ci.z};
+        d = min_image(d, box);
+        const R r2 = dot(d, d);
+        if (r2 < rc2) {
+          hit_c = r2 < rcl2 && site_close_v(sc, ai, oi, aj, oj, d);
+          hit_f = !hit_c && far_in_range_v(sc, oi, oj, d);
+        }
+      }
+      const unsigned int mc = (unsigned int)(__ballot(hit_c) >> gshift) & kGroupMask;
+      const unsigned int mf = (unsigned int)(__ballot(hit_f) >> gshift) & kGroupMask;
+      if (hit_c) {
+        const int k = ROW_BONDED_SLOTS + out_c + __popc(mc & below);
+        if (k < row_stride) row[k] = e[b];
+      }
+      if (hit_f) s_far[out_f + __popc(mf & below)] = e[b];  // (at most ncand < cand_stride of them)
+      out_c += __popc(mc);
+      out_f += __popc(mf);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  const int n_close = ROW_BONDED_SLOTS + out_c;
+  int out = n_close + out_f;
+  for (int k = l; k < out_f; k += G)
+    if (n_close + k < row_stride) row[n_close + k] = s_far[k];
+  if (l == 0) {
+    const int* bq = partners + (size_t)ROW_BONDED_SLOTS * i;
+    row[0] = bq[0], row[1] = bq[1], row[2] = bq[2], row[3] = bq[3];
+    if (out > row_stride) {
+      atomicMax(overflow, out);
+      out = row_stride;
+    }
+    row_len[i] = out;
+    row_close[i] = min(n_close, out);
+    V4 rp = c4;
+    ref_pos[i] = rp, ref_off[i] = o4, ref_a1[i] = a4;
+    // do the candidates still vouch for this row?
+    V3<R> dr{ci.x - r4.x, ci.y - r4.y, ci.z - r4.z};
+    dr = min_image(dr, box);
+    bool unvouched = !(dot(dr, dr) <= stale2);
+    if (i == 0) unvouched = unvouched || (cand_overflow[0] | cand_overflow[1]) != 0;
+    if (unvouched) atomicMax(overflow, kRowsUnvouched);
+  }
+}
+
+bool rows_filter_applies(const mythos_system* sys, double r_cut, double skin, double margin) {
+  CellGrid<double> g;
+  return sys->params_set && cell_grid(g, sys->n, r_cut + skin + margin, sys->has_box ? sys->box : nullptr) &&
+         cell_grid(g, sys->n, r_cut + skin, sys->has_box ? sys->box : nullptr);
+}
+
+// the candidate store's buffers (first use; the rows start at a stride of 96: ~60 candidates of a duplex)
+static int cand_reserve(mythos_system* sys) {
+  const int n = sys->n;
+  if (!sys->cand.d_overflow) {
+    if (int rc = sys->cand.d_overflow.alloc(kOverflowWords)) return rc;
+    MYTHOS_HIP_TRY(hipMemset(sys->cand.d_overflow.get(), 0, kOverflowWords * sizeof(int)));
+  }
+  if (!sys->d_cand_len)
+    if (int rc = sys->d_cand_len.alloc(2 * (size_t)n)) return rc;
+  if (int rc = sys->d_cand_ref.grow((sys->dtype == MYTHOS_F32 ? sizeof(float4) : sizeof(double4)) * (size_t)n)) return rc;
+  if (sys->cand.stride == 0)
+    if (int rc = rows_reserve(sys->cand, n, 96)) return rc;
+  return 0;
+}
+
+int rows_wide_build_device(mythos_system* sys, const void* p0, double r_cut, double skin, double margin, hipStream_t stream) {
+  if (int rc = cand_reserve(sys)) return rc;
+  const double rl = r_cut + skin + margin;
+  const int rc = with_real(sys->dtype, [&](auto real) {
+    using R = decltype(real);
+    return build_cells_typed<R>(sys, (const R*)p0, true, rl, skin + margin, nullptr, nullptr, true, stream, true);
+  });
+  if (rc) return rc;
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int rows_filter_device(mythos_system* sys, const void* p0, const void* p3, const void* p1, double r_cut, double skin, double margin,
+                       hipStream_t stream) {
+  if (sys->list.stride == 0)
+    if (int rc = rows_reserve(sys->list, sys->n, 64)) return rc;
+  const int n = sys->n;
+  const double rl = r_cut + skin;
+  const double rcl = std::min(rl, oxdna_close_range(sys) + skin);  // (as build_cells_typed: parameters are set)
+  constexpr int kPerBlock = 256 / kRowG;
+  const VerletRows& C = sys->cand;
+  VerletRows& L = sys->list;
+  with_real(sys->dtype, [&](auto real) {
+    using R = decltype(real);
+    using V4 = typename Vec4T<R>::type;
+    const SiteCrit<R> sc = site_crit_for<R>(sys, rl, skin, (const R*)p3, (const R*)p1);
+    hipLaunchKernelGGL((filter_rows_kernel<R, kRowG>), dim3((n + kPerBlock - 1) / kPerBlock), dim3(256),
+                       (size_t)kPerBlock * C.stride * sizeof(int), stream, n, (const V4*)p0, (const V4*)p3, (const V4*)p1, make_box<R>(sys),
+                       R(rl * rl), R(rcl * rcl), sc, (const int*)(sys->d_row_len.get() + n), (const int*)C.d_rows.get(),
+                       (const int*)sys->d_cand_len.get(), C.stride, (const V4*)sys->d_cand_ref.get(), R(cand_stale_sq(margin)),
+                       (const int*)C.d_overflow.get(), L.d_rows.get(), sys->d_row_len.get(), row_close_of(sys), L.stride,
+                       L.d_overflow.get(), (V4*)sys->d_ref_pos.get(), (V4*)sys->d_ref_off.get(), (V4*)sys->d_ref_a1.get());
+  });
+  MYTHOS_HIP_TRY(hipGetLastError());
+  sys->nbrs_set = true;
+  return 0;
+}
+
+int rows_filter_until_fit(mythos_system* sys, const void* p0, const void* p3, const void* p1, double r_cut, double skin, double margin,
+                          hipStream_t stream) {
+  if (int rc = cand_reserve(sys)) return rc;
+  // (the builder keeps two segments of a row's stride per nucleotide in LDS, 128 B per slot of a workgroup's 64 KB)
+  constexpr int kCandStrideMax = 384;
+  auto wide = [&]() -> int {
+    if (sys->cand.stride > kCandStrideMax) {
+      sys->cand_unfit = true;
+      set_error("candidate build: more than " + std::to_string(kCandStrideMax) + " candidates in a row");
+      return MYTHOS_ERR_OVERFLOW;
+    }
+    return rows_wide_build_device(sys, p0, r_cut, skin, margin, stream);
+  };
+  if (int rc = list_build_until_fit(sys->cand, sys->n, wide, true, "candidate build", stream)) return rc;
+  return list_build_until_fit(
+      sys->list, sys->n, [&] { return rows_filter_device(sys, p0, p3, p1, r_cut, skin, margin, stream); }, true, "neighbour build", stream);
 }
 
 int rows_build_device(mythos_system* sys, const void* center, bool center_is_vec4, double r_cut, double skin,
