@@ -960,6 +960,45 @@ int mythos_rdf_n_pairs(const mythos_rdf_t* rdf, int64_t* n_pairs);
 int mythos_rdf_eval(mythos_rdf_t* rdf, const void* pos, const void* box, int dtype, int n_frames, int64_t* counts,
                     int32_t* flags, mythos_stream_t stream);
 
+/* ---- MBAR: unbiasing weights of frames pooled from biased windows, and the sums behind a PMF --------
+ * The binless multistate estimator (csrc/mbar.hip; definitions in DESIGN section 3.5o).  The reference has none.  N frames
+ * are pooled from K windows, window k contributed n_k[k] >= 1 of them (sum = N); b_k(n) is the reduced bias of window k at
+ * frame n.  One iteration is
+ *     L_n = ln sum_j N_j exp(f_j - b_j(n)),    f_k' = f_k - ln(sum_n t_kn / N_k),  t_kn = N_k exp(f_k - b_k(n) - L_n)
+ * re-gauged to f_0 = 0; the per-frame log-weights are -L_n.  All arithmetic is double; fixed summation order, no atomics:
+ * the same bits from run to run.
+ * The bias comes from one of two sources, whichever was set last:
+ *   set_windows  the table path.  table host double[K][P][4] = kind (0 umbrella U = 1/2 k (xi - init)^2, 1 constant force
+ *                U = k xi), k, init, rate of every window and coordinate - what p_flags bit 0 and p_param[.][.][0..2] of
+ *                the restraints entry point hold for replica k; b_k(n) = sum_p U_kp(xi[n][p]) / kT.  kT host double[K], all
+ *                equal.  xi dev double[N][P], BORROWED: it must stay alive and unchanged while the handle uses it.  The
+ *                K x N matrix is never stored.
+ *   set_matrix   the general path: u_kn dev double[K][N] row-major, BORROWED, any reduced energies (a temperature ladder's
+ *                beta_k (U_n + p V_n), for instance).
+ * Refused by name (INVALID_ARGUMENT): K < 1, N_k < 1, sum N_k != N, non-finite k or init, rate != 0 (moving windows are not
+ * built), windows at different kT in the table path, K (3 P + 6) > 8192 (the table lives in 64 KB of LDS).
+ * mythos_mbar_check: those checks alone, plus - where the pointers are given - non-finite xi (host double[N][P]) and
+ * non-increasing or non-finite bin edges (host double[n_edges]); table, kT, xi and edges may be NULL.  Touches no device.
+ * mythos_mbar_iterate: n_iter iterations queued on the stream without a synchronisation; f_inout dev double[K] is
+ * advanced in place, delta_out dev double[1] receives max_k |f' - f| of the last one (NaN if the iteration diverged).
+ * mythos_mbar_log_weights: log_weights dev double[N] = -L_n at the given f (dev double[K]).
+ * mythos_mbar_binned_sum: order dev int64[N] the frames sorted by bin (a permutation: the caller's duty; memory stays in
+ * bounds if it is not), seg_start dev int64[n_bins + 1] the bins' segments of it (frames outside every bin behind the
+ * last), weights dev double[N] or NULL for 1.  sums dev double[n_bins + 1]: sum over the bin's frames of
+ * weights[n] exp(log_weights[n] - shift), and in the last place the same sum over all N frames. */
+typedef struct mythos_mbar mythos_mbar_t;
+int mythos_mbar_check(int n_windows, int64_t n_frames, int n_coords, const double* table, const double* kT, const int64_t* n_k,
+                      const double* xi, int n_edges, const double* edges);
+mythos_mbar_t* mythos_mbar_create(int64_t n_frames, int n_windows, int device);
+void mythos_mbar_destroy(mythos_mbar_t* mbar);
+int mythos_mbar_set_windows(mythos_mbar_t* mbar, int n_coords, const double* table, const double* kT, const int64_t* n_k,
+                            const double* xi);
+int mythos_mbar_set_matrix(mythos_mbar_t* mbar, const double* u_kn, const int64_t* n_k);
+int mythos_mbar_iterate(mythos_mbar_t* mbar, double* f_inout, int n_iter, double* delta_out, mythos_stream_t stream);
+int mythos_mbar_log_weights(mythos_mbar_t* mbar, const double* f, double* log_weights, mythos_stream_t stream);
+int mythos_mbar_binned_sum(mythos_mbar_t* mbar, int n_bins, const int64_t* seg_start, const int64_t* order, const double* log_weights,
+                           const double* weights, double shift, double* sums, mythos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,14 @@ _SIGS = {
     "mythos_rdf_destroy": (None, [V]),
     "mythos_rdf_n_pairs": (C.c_int, [V, C.POINTER(C.c_int64)]),
     "mythos_rdf_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V, V]),
+    "mythos_mbar_check": (C.c_int, [C.c_int, C.c_int64, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int64), c_double_p, C.c_int, c_double_p]),
+    "mythos_mbar_create": (V, [C.c_int64, C.c_int, C.c_int]),
+    "mythos_mbar_destroy": (None, [V]),
+    "mythos_mbar_set_windows": (C.c_int, [V, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int64), V]),
+    "mythos_mbar_set_matrix": (C.c_int, [V, V, C.POINTER(C.c_int64)]),
+    "mythos_mbar_iterate": (C.c_int, [V, V, C.c_int, V, V]),
+    "mythos_mbar_log_weights": (C.c_int, [V, V, V, V]),
+    "mythos_mbar_binned_sum": (C.c_int, [V, C.c_int, V, V, V, V, C.c_double, V, V]),
 }
 
 

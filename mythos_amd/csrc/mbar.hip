@@ -1,0 +1,331 @@
+// MBAR, the binless form of WHAM: per-frame unbiasing weights of N frames pooled from K biased windows, and the binned
+// sums behind a free-energy profile over them.  Definitions and the measured timings: DESIGN section 3.5o.  The reference
+// has no such estimator; the equations are those of Shirts and Chodera (J. Chem. Phys. 129, 124105, 2008), iterated as
+//
+//     L_n  = ln sum_j N_j exp(f_j - b_j(n))            t_kn = N_k exp(f_k - b_k(n) - L_n)  in (0, 1],  sum_k t_kn = 1
+//     f_k' = f_k - ln(sum_n t_kn / N_k)                gauge f_0 = 0
+//
+// which is f_k' = -ln sum_n exp(-b_k(n) - L_n) written with the responsibilities t_kn: only L_n needs a running maximum,
+// the per-window sums are plain sums of numbers <= 1.  All arithmetic is double.
+//
+// mbar_iterate_kernel<SRC>: a workgroup of 256 threads takes chunks of 1024 frames, four per thread (four independent
+// exp chains: the kernel is bound by K N exponentials, twice per iteration), at most 1024 workgroups striding the chunks.
+// SRC = 0 forms b_k(n) = sum_p A_kp (xi_np - C_kp)^2 + B_kp xi_np from the frames' coordinates and the lowered window
+// table in LDS - umbrella: A = beta k / 2, C = init, B = 0; constant force: A = 0, B = beta k - and never stores the K x N
+// matrix; SRC = 1 reads the caller's u[k][n].  Pass 1 over k is an online log-sum-exp per frame and writes L_n; pass 2
+// forms t_kn again and sums it per window: over the four frames of a thread, over the wavefront in a fixed DPP / readlane
+// order, into the wavefront's own LDS row chunk after chunk, and at the end the four rows in order into one partial per
+// (workgroup, window).  No atomics: the same bits run after run.  No per-thread array indexed by k: no scratch.
+// mbar_finish_kernel: one workgroup of 1024; a wavefront adds the partials of a window - lane l those of workgroups l,
+// l + 64, ... in order, then the wavefront sum above - and the workgroup writes f' with f'_0 = 0 in place and
+// max_k |f' - f| into one device word - the only thing the host reads, once per check_every iterations.
+// mbar_binned_sum_kernel: one workgroup per bin sums w_n exp(lw_n - shift) over the bin's segment of a frame order sorted
+// by bin, thread-strided then block_sum; one more workgroup sums every frame the same way (the normalisation).
+#include <cmath>
+#include <memory>
+#include <vector>
+
+#include "device_buf.h"
+#include "mbar_checks.h"
+#include "wave_ops.h"
+
+struct mythos_mbar {
+  int K = 0, P = 0, device = 0, src = -1;  // src: -1 nothing set, 0 window table + xi, 1 matrix
+  int64_t N = 0;
+  int n_chunks = 0, n_blocks = 0;
+  const double* xi = nullptr;  // borrowed: dev double[N][P]
+  const double* u = nullptr;   // borrowed: dev double[K][N]
+  mythos::DeviceBuf<double> d_table;    // [K][P][3] A, B, C
+  mythos::DeviceBuf<double> d_ln_nk;    // [K]
+  mythos::DeviceBuf<double> d_L;        // [N]
+  mythos::DeviceBuf<double> d_partial;  // [K][n_blocks]
+  ~mythos_mbar() { (void)hipSetDevice(device); }  // the members free themselves, on the handle's device
+};
+
+namespace mythos {
+
+constexpr int kMbarBlock = 256;
+constexpr int kMbarFpt = 4;                         // frames per thread and chunk
+constexpr int kMbarChunk = kMbarBlock * kMbarFpt;   // frames per chunk
+constexpr int kMbarMaxBlocks = 1024;                // the grid's cap: four workgroups per CU; the rest is strided
+constexpr int kMbarWaves = kMbarBlock / 64;
+constexpr int kMbarFinishBlock = 1024;              // the one workgroup of the finish kernel: sixteen windows at a time
+
+// Sum over the wavefront, wave-uniform, in a fixed order: DPP butterfly inside each row of 16, then the four rows in order.
+// Every lane must be enabled.
+__device__ __forceinline__ double mbar_wave_sum(double v) {
+  v = group_sum<16>(v);
+  return ((read_lane(v, 0) + read_lane(v, 16)) + read_lane(v, 32)) + read_lane(v, 48);
+}
+
+// max that keeps a NaN once it has one (a diverged iteration must not look converged)
+__device__ __forceinline__ double mbar_max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
+
+template <int SRC>
+__global__ __launch_bounds__(kMbarBlock) void mbar_iterate_kernel(int K, int P, long long N, int n_chunks, const double* __restrict__ xi,
+                                                                   const double* __restrict__ table, const double* __restrict__ u,
+                                                                   const double* __restrict__ ln_nk, const double* __restrict__ f,
+                                                                   double* __restrict__ L_out, double* __restrict__ lw_out,
+                                                                   double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) double mbar_lds[];
+  double* __restrict__ s_tab = mbar_lds;                  // [K][P][3]
+  double* __restrict__ s_a = s_tab + 3 * (size_t)K * P;   // [K] ln N_k + f_k
+  double* __restrict__ s_part = s_a + K;                  // [kMbarWaves][K]
+  const int tid = (int)threadIdx.x, wave = tid >> 6;
+  if (SRC == 0)
+    for (int i = tid; i < 3 * K * P; i += kMbarBlock) s_tab[i] = table[i];
+  for (int k = tid; k < K; k += kMbarBlock) s_a[k] = ln_nk[k] + f[k];
+  for (int i = tid; i < kMbarWaves * K; i += kMbarBlock) s_part[i] = 0.0;
+  __syncthreads();
+
+  // b_k(n) of frame slot j: its first coordinate from a register, further ones through the cache
+  auto bias = [&](int k, long long n, double x0) {
+    if constexpr (SRC == 1) return u[(size_t)k * (size_t)N + (size_t)n];
+    const double* __restrict__ q = s_tab + 3 * (size_t)k * P;
+    double b = 0.0;
+    for (int p = 0; p < P; ++p) {
+      const double x = p == 0 ? x0 : xi[(size_t)n * P + p];
+      const double d = x - q[3 * p + 2];
+      b += q[3 * p] * d * d + q[3 * p + 1] * x;
+    }
+    return b;
+  };
+
+  for (int chunk = (int)blockIdx.x; chunk < n_chunks; chunk += (int)gridDim.x) {
+    long long n[kMbarFpt];
+    bool own[kMbarFpt];
+    double x0[kMbarFpt], m[kMbarFpt], s[kMbarFpt], L[kMbarFpt];
+#pragma unroll
+    for (int j = 0; j < kMbarFpt; ++j) {
+      const long long at = (long long)chunk * kMbarChunk + j * kMbarBlock + tid;
+      own[j] = at < N;
+      n[j] = own[j] ? at : N - 1;  // a slot past the end reads the last frame and adds nothing
+      x0[j] = SRC == 0 ? xi[(size_t)n[j] * P] : 0.0;
+      m[j] = s_a[0] - bias(0, n[j], x0[j]);
+      s[j] = 1.0;
+    }
+    for (int k = 1; k < K; ++k) {
+      const double a0 = s_a[k];
+#pragma unroll
+      for (int j = 0; j < kMbarFpt; ++j) {
+        const double a = a0 - bias(k, n[j], x0[j]);
+        const double e = exp(-fabs(a - m[j]));
+        s[j] = a > m[j] ? s[j] * e + 1.0 : s[j] + e;
+        m[j] = fmax(a, m[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kMbarFpt; ++j) {
+      L[j] = m[j] + log(s[j]);
+      if (own[j]) {
+        L_out[n[j]] = L[j];
+        if (lw_out) lw_out[n[j]] = -L[j];
+      }
+    }
+    if (!partial) continue;  // the log-weights alone (uniform over the launch)
+    for (int k = 0; k < K; ++k) {
+      const double a0 = s_a[k];
+      double acc = 0.0;
+#pragma unroll
+      for (int j = 0; j < kMbarFpt; ++j) {
+        const double t = exp(a0 - bias(k, n[j], x0[j]) - L[j]);
+        acc += own[j] ? t : 0.0;
+      }
+      const double w = mbar_wave_sum(acc);
+      if ((tid & 63) == 0) s_part[(size_t)wave * K + k] += w;
+    }
+  }
+  if (!partial) return;
+  __syncthreads();
+  for (int k = tid; k < K; k += kMbarBlock) {
+    double t = s_part[k];
+#pragma unroll
+    for (int w = 1; w < kMbarWaves; ++w) t += s_part[(size_t)w * K + k];
+    partial[(size_t)k * gridDim.x + blockIdx.x] = t;  // window-major: the finish kernel reads a window's row
+  }
+}
+
+__global__ __launch_bounds__(kMbarFinishBlock) void mbar_finish_kernel(int K, int n_blocks, const double* __restrict__ partial,
+                                                                        const double* __restrict__ ln_nk, double* __restrict__ f,
+                                                                        double* __restrict__ delta) {
+  extern __shared__ __attribute__((aligned(16))) double s_raw[];  // [K] f' before the gauge
+  __shared__ double s_max[kMbarFinishBlock];
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  // a wavefront per window: its lanes stride the window's row of workgroup partials (independent, coalesced loads - one
+  // thread per window was a chain of n_blocks dependent loads, as long as the iterate kernel itself), then the fixed-order sum
+  for (int k = tid >> 6; k < K; k += kMbarFinishBlock / 64) {
+    double t = 0.0;
+    for (int b = lane; b < n_blocks; b += 64) t += partial[(size_t)k * n_blocks + b];
+    t = mbar_wave_sum(t);
+    if (lane == 0) s_raw[k] = f[k] - (log(t) - ln_nk[k]);  // f_k - ln(sum_n t_kn / N_k)
+  }
+  __syncthreads();
+  const double f0 = s_raw[0];
+  double d = 0.0;
+  for (int k = tid; k < K; k += kMbarFinishBlock) {
+    const double g = s_raw[k] - f0;
+    d = mbar_max_nan(d, fabs(g - f[k]));
+    f[k] = g;
+  }
+  s_max[tid] = d;
+  __syncthreads();
+  for (int o = kMbarFinishBlock / 2; o > 0; o >>= 1) {
+    if (tid < o) s_max[tid] = mbar_max_nan(s_max[tid], s_max[tid + o]);
+    __syncthreads();
+  }
+  if (tid == 0) *delta = s_max[0];
+}
+
+__global__ __launch_bounds__(kMbarBlock) void mbar_binned_sum_kernel(int n_bins, long long N, const long long* __restrict__ seg,
+                                                                      const long long* __restrict__ order, const double* __restrict__ lw,
+                                                                      const double* __restrict__ weights, double shift,
+                                                                      double* __restrict__ out) {
+  __shared__ double s_red[kMbarWaves];
+  const int b = (int)blockIdx.x;
+  long long lo = 0, hi = N;  // workgroup n_bins: every frame
+  if (b < n_bins) lo = min(max(seg[b], 0ll), N), hi = min(max(seg[b + 1], lo), N);
+  double acc = 0.0;
+  for (long long i = lo + (int)threadIdx.x; i < hi; i += kMbarBlock) {
+    const long long n = order[i];
+    if (n < 0 || n >= N) continue;  // (not a permutation: the caller's fault, memory stays in bounds)
+    acc += (weights ? weights[n] : 1.0) * exp(lw[n] - shift);
+  }
+  const double total = block_sum(acc, s_red);
+  if (threadIdx.x == 0) out[b] = total;
+}
+
+static int mbar_ready(const mythos_mbar* h, const char* who) {
+  if (h->src < 0) {
+    set_error(std::string(who) + ": neither windows nor a matrix are set");
+    return MYTHOS_ERR_NOT_READY;
+  }
+  return MYTHOS_OK;
+}
+
+static int mbar_set_counts(mythos_mbar* h, const int64_t* n_k) {
+  std::vector<double> ln((size_t)h->K);
+  for (int k = 0; k < h->K; ++k) ln[k] = std::log((double)n_k[k]);
+  return h->d_ln_nk.upload(ln);
+}
+
+static void mbar_launch(const mythos_mbar* h, const double* f, double* lw_out, double* partial, hipStream_t st) {
+  const size_t lds = sizeof(double) * mbar_lds_doubles(h->K, h->P);
+  auto kernel = h->src == 0 ? mbar_iterate_kernel<0> : mbar_iterate_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(h->n_blocks), dim3(kMbarBlock), lds, st, h->K, h->P, (long long)h->N, h->n_chunks, h->xi,
+                     h->d_table.get(), h->u, h->d_ln_nk.get(), f, h->d_L.get(), lw_out, partial);
+}
+
+}  // namespace mythos
+
+using namespace mythos;
+
+extern "C" {
+
+int mythos_mbar_check(int n_windows, int64_t n_frames, int n_coords, const double* table, const double* kT, const int64_t* n_k,
+                      const double* xi, int n_edges, const double* edges) {
+  return mbar_check("mythos_mbar_check", n_windows, n_frames, n_coords, table, kT, n_k, xi, n_edges, edges);
+}
+
+mythos_mbar_t* mythos_mbar_create(int64_t n_frames, int n_windows, int device) {
+  if (n_windows < 1) {
+    set_error("mythos_mbar_create: K < 1 (at least one window)");
+    return nullptr;
+  }
+  if (n_frames < 1 || n_frames >= ((int64_t)1 << 31) || mbar_lds_doubles(n_windows, 0) > (size_t)kMbarLdsDoubles) {
+    set_error("mythos_mbar_create: 1 <= N < 2^31 frames and at most " + std::to_string(kMbarLdsDoubles / 6) + " windows");
+    return nullptr;
+  }
+  if (select_device(device, "mythos_mbar_create")) return nullptr;
+  auto h = std::make_unique<mythos_mbar>();
+  h->K = n_windows, h->N = n_frames, h->device = device;
+  h->n_chunks = (int)((n_frames + kMbarChunk - 1) / kMbarChunk);
+  h->n_blocks = std::min(h->n_chunks, kMbarMaxBlocks);
+  if (h->d_L.alloc((size_t)n_frames) || h->d_partial.alloc((size_t)h->n_blocks * n_windows) ||
+      h->d_ln_nk.alloc((size_t)n_windows) || h->d_table.alloc(1)) {
+    set_error("mythos_mbar_create: device allocation failed");
+    return nullptr;
+  }
+  return h.release();
+}
+
+void mythos_mbar_destroy(mythos_mbar_t* h) { delete h; }
+
+int mythos_mbar_set_windows(mythos_mbar_t* h, int n_coords, const double* table, const double* kT, const int64_t* n_k, const double* xi) {
+  if (!h || !table || !kT || !n_k || !xi) {
+    set_error("mythos_mbar_set_windows: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (int rc = mbar_check("mythos_mbar_set_windows", h->K, h->N, n_coords, table, kT, n_k, nullptr, 0, nullptr)) return rc;
+  const double beta = 1.0 / kT[0];
+  std::vector<double> abc(3 * (size_t)h->K * n_coords);
+  for (size_t i = 0; i < (size_t)h->K * n_coords; ++i) {
+    const double* q = table + i * kMbarRow;
+    const bool umbrella = q[0] == MBAR_UMBRELLA;
+    abc[3 * i] = umbrella ? 0.5 * beta * q[1] : 0.0;
+    abc[3 * i + 1] = umbrella ? 0.0 : beta * q[1];
+    abc[3 * i + 2] = umbrella ? q[2] : 0.0;
+  }
+  MYTHOS_HIP_TRY(hipSetDevice(h->device));
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());  // no launch in flight reads a table that is being replaced
+  if (int rc = h->d_table.upload(abc)) return rc;
+  if (int rc = mbar_set_counts(h, n_k)) return rc;
+  h->P = n_coords, h->xi = xi, h->u = nullptr, h->src = 0;
+  return MYTHOS_OK;
+}
+
+int mythos_mbar_set_matrix(mythos_mbar_t* h, const double* u_kn, const int64_t* n_k) {
+  if (!h || !u_kn || !n_k) {
+    set_error("mythos_mbar_set_matrix: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (int rc = mbar_check("mythos_mbar_set_matrix", h->K, h->N, 0, nullptr, nullptr, n_k, nullptr, 0, nullptr)) return rc;
+  MYTHOS_HIP_TRY(hipSetDevice(h->device));
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());
+  if (int rc = mbar_set_counts(h, n_k)) return rc;
+  h->P = 0, h->xi = nullptr, h->u = u_kn, h->src = 1;
+  return MYTHOS_OK;
+}
+
+int mythos_mbar_iterate(mythos_mbar_t* h, double* f_inout, int n_iter, double* delta_out, mythos_stream_t stream) {
+  if (!h || !f_inout || !delta_out || n_iter < 0) {
+    set_error("mythos_mbar_iterate: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (int rc = mbar_ready(h, "mythos_mbar_iterate")) return rc;
+  MYTHOS_HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  for (int it = 0; it < n_iter; ++it) {
+    mbar_launch(h, f_inout, nullptr, h->d_partial.get(), st);
+    hipLaunchKernelGGL(mbar_finish_kernel, dim3(1), dim3(kMbarFinishBlock), sizeof(double) * (size_t)h->K, st, h->K, h->n_blocks,
+                       h->d_partial.get(), h->d_ln_nk.get(), f_inout, delta_out);
+  }
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return MYTHOS_OK;
+}
+
+int mythos_mbar_log_weights(mythos_mbar_t* h, const double* f, double* log_weights, mythos_stream_t stream) {
+  if (!h || !f || !log_weights) {
+    set_error("mythos_mbar_log_weights: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (int rc = mbar_ready(h, "mythos_mbar_log_weights")) return rc;
+  MYTHOS_HIP_TRY(hipSetDevice(h->device));
+  mbar_launch(h, f, log_weights, nullptr, (hipStream_t)stream);
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return MYTHOS_OK;
+}
+
+int mythos_mbar_binned_sum(mythos_mbar_t* h, int n_bins, const int64_t* seg_start, const int64_t* order, const double* log_weights,
+                           const double* weights, double shift, double* sums, mythos_stream_t stream) {
+  if (!h || n_bins < 1 || n_bins > (1 << 20) || !seg_start || !order || !log_weights || !sums || !std::isfinite(shift)) {
+    set_error("mythos_mbar_binned_sum: invalid argument (1 <= n_bins <= 2^20, a finite shift)");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  MYTHOS_HIP_TRY(hipSetDevice(h->device));
+  hipLaunchKernelGGL(mbar_binned_sum_kernel, dim3(n_bins + 1), dim3(kMbarBlock), 0, (hipStream_t)stream, n_bins, (long long)h->N,
+                     (const long long*)seg_start, (const long long*)order, log_weights, weights, shift, sums);
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return MYTHOS_OK;
+}
+
+}  // extern "C"
