@@ -985,7 +985,18 @@ int mythos_rdf_eval(mythos_rdf_t* rdf, const void* pos, const void* box, int dty
  * mythos_mbar_binned_sum: order dev int64[N] the frames sorted by bin (a permutation: the caller's duty; memory stays in
  * bounds if it is not), seg_start dev int64[n_bins + 1] the bins' segments of it (frames outside every bin behind the
  * last), weights dev double[N] or NULL for 1.  sums dev double[n_bins + 1]: sum over the bin's frames of
- * weights[n] exp(log_weights[n] - shift), and in the last place the same sum over all N frames. */
+ * weights[n] exp(log_weights[n] - shift), and in the last place the same sum over all N frames.
+ * The window weights W_nk = exp(f_k - b_k(n) - L_n) = t_kn / N_k (N x K, never stored) enter two more entry points.  Both
+ * take f dev double[K], queue the pass that makes L_n current at this f in front of their own kernels on the caller's
+ * stream, work for either source, and do not synchronise (the first call allocates its partial sums on the handle).
+ * mythos_mbar_gram: gram dev double[K][K] = the full, exactly symmetric G_ij = sum_n W_ni W_nj - the Hessian of a Newton
+ * step is [diag(N_k s_k) - N_i N_j G_ij] / N, the estimator's asymptotic covariance a function of G -; colsum dev double[K]
+ * = s_k = sum_n W_nk, or NULL.  Refused by name where the table rows of 128 windows leave no LDS for a strip of W (few
+ * windows with some thousand coordinates each).
+ * mythos_mbar_segment_moments: out dev double[n_seg][K], out[b][k] = sum over the frames n of segment b of v[n] W_nk;
+ * order and seg_start (dev int64[N], dev int64[n_seg + 1]) as for mythos_mbar_binned_sum - an entry of order outside
+ * [0, N) is skipped and never dereferenced -; order NULL: one segment (n_seg = 1) over all frames, seg_start unused.  v dev
+ * double[N] or NULL for 1.  Refused: NULL handle or output, nothing set (NOT_READY), n_seg < 1 or > 2^20. */
 typedef struct mythos_mbar mythos_mbar_t;
 int mythos_mbar_check(int n_windows, int64_t n_frames, int n_coords, const double* table, const double* kT, const int64_t* n_k,
                       const double* xi, int n_edges, const double* edges);
@@ -998,6 +1009,9 @@ int mythos_mbar_iterate(mythos_mbar_t* mbar, double* f_inout, int n_iter, double
 int mythos_mbar_log_weights(mythos_mbar_t* mbar, const double* f, double* log_weights, mythos_stream_t stream);
 int mythos_mbar_binned_sum(mythos_mbar_t* mbar, int n_bins, const int64_t* seg_start, const int64_t* order, const double* log_weights,
                            const double* weights, double shift, double* sums, mythos_stream_t stream);
+int mythos_mbar_gram(mythos_mbar_t* mbar, const double* f, double* gram, double* colsum, mythos_stream_t stream);
+int mythos_mbar_segment_moments(mythos_mbar_t* mbar, const double* f, int n_seg, const int64_t* seg_start, const int64_t* order,
+                                const double* v, double* out, mythos_stream_t stream);
 
 #ifdef __cplusplus
 }

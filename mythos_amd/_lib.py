@@ -163,6 +163,8 @@ _SIGS = {
     "mythos_mbar_iterate": (C.c_int, [V, V, C.c_int, V, V]),
     "mythos_mbar_log_weights": (C.c_int, [V, V, V, V]),
     "mythos_mbar_binned_sum": (C.c_int, [V, C.c_int, V, V, V, V, C.c_double, V, V]),
+    "mythos_mbar_gram": (C.c_int, [V, V, V, V, V]),
+    "mythos_mbar_segment_moments": (C.c_int, [V, V, C.c_int, V, V, V, V, V]),
 }
 
 

@@ -21,6 +21,25 @@
 // max_k |f' - f| into one device word - the only thing the host reads, once per check_every iterations.
 // mbar_binned_sum_kernel: one workgroup per bin sums w_n exp(lw_n - shift) over the bin's segment of a frame order sorted
 // by bin, thread-strided then block_sum; one more workgroup sums every frame the same way (the normalisation).
+//
+// The Gram matrix G = W^T W of the window weights W_nk = exp(f_k - b_k(n) - L_n) = t_kn / N_k - the Hessian of a Newton step
+// and the asymptotic covariance both are functions of it - and the segment moments sum_{n in segment} v_n W_nk.  W is N x K
+// and, like the bias matrix, never stored.  Both entry points queue the L-pass (the iterate kernel without partials) first.
+// mbar_gram_kernel<SRC>: the windows in tiles of 64, the upper-triangle tile pairs only.  A workgroup of 256 takes one tile
+// pair (blockIdx.y) and the frame chunks blockIdx.x, blockIdx.x + gridDim.x, ...; per step of F <= 32 frames it forms the two
+// 64-column strips of W in LDS (one strip on a diagonal pair) - entry e of the step is frame e % F, column e / F, so xi, L
+// and the matrix rows are read along the frames and the table row of a column is an LDS broadcast; the strip rows are padded
+// by two doubles against the bank conflict of that store - and then every thread adds the F outer products into its 4 x 4
+// block of the tile, in registers, by fma in frame order (a diagonal tile is exactly symmetric: the product commutes).  Only
+// the table rows of the pair's windows are staged, so F follows from what K (3 P + 1) leaves of the 64 KB.  One partial
+// tile per (frame block, tile pair); the number of frame blocks is at most 1024 / pairs: the partials stay below 32 MB.
+// mbar_gram_finish_kernel: a thread per tile entry adds the frame blocks' partials in index order and writes the entry and,
+// off the diagonal tiles, its mirror image.
+// mbar_segment_kernel<SRC>: the iterate kernel's pass 2 over a segment of a frame order - 256 x 4 frames per round, per
+// window the threads' four terms v_n W_nk, mbar_wave_sum, the wavefront's LDS row, the four rows in order.  blockIdx.x is the
+// segment; the rounds of a segment are dealt to gridDim.y workgroups (as many as keep segments x splits <= 1024: one segment
+// over all frames - the column sums a Newton step needs at every candidate - is not left to one workgroup), whose partials
+// mbar_segment_finish_kernel adds in index order.  The split is a function of N and the number of segments alone.
 #include <cmath>
 #include <memory>
 #include <vector>
@@ -39,6 +58,8 @@ struct mythos_mbar {
   mythos::DeviceBuf<double> d_ln_nk;    // [K]
   mythos::DeviceBuf<double> d_L;        // [N]
   mythos::DeviceBuf<double> d_partial;  // [K][n_blocks]
+  mythos::DeviceBuf<double> d_gram_partial;  // [frame blocks][tile pairs][64][64]: allocated by the first mythos_mbar_gram
+  mythos::DeviceBuf<double> d_seg_partial;   // [segments][splits][K]: grown by mythos_mbar_segment_moments where splits > 1
   ~mythos_mbar() { (void)hipSetDevice(device); }  // the members free themselves, on the handle's device
 };
 
@@ -50,6 +71,12 @@ constexpr int kMbarChunk = kMbarBlock * kMbarFpt;   // frames per chunk
 constexpr int kMbarMaxBlocks = 1024;                // the grid's cap: four workgroups per CU; the rest is strided
 constexpr int kMbarWaves = kMbarBlock / 64;
 constexpr int kMbarFinishBlock = 1024;              // the one workgroup of the finish kernel: sixteen windows at a time
+constexpr int kGramTile = 64;                       // windows per tile: 16 x 16 threads own 4 x 4 entries each
+constexpr int kGramTileSize = kGramTile * kGramTile;
+constexpr int kGramPad = 2;                         // doubles behind a strip row in LDS
+constexpr int kGramLog2Frames = 5;                  // at most 32 frames per strip step
+constexpr int kGramMaxPartials = 1024;              // (frame block, tile pair) partial tiles of 32 KB each
+constexpr int kSegMaxSplits = 1024;                 // segments x splits of the segment kernel
 
 // Sum over the wavefront, wave-uniform, in a fixed order: DPP butterfly inside each row of 16, then the four rows in order.
 // Every lane must be enabled.
@@ -194,6 +221,167 @@ __global__ __launch_bounds__(kMbarBlock) void mbar_binned_sum_kernel(int n_bins,
   if (threadIdx.x == 0) out[b] = total;
 }
 
+// b_k(n) for the Gram and segment kernels: q the window's table row [P][3] in LDS, x0 the frame's first coordinate
+template <int SRC>
+__device__ __forceinline__ double mbar_bias(const double* __restrict__ q, const double* __restrict__ xi, const double* __restrict__ u,
+                                            int P, long long N, int k, long long n, double x0) {
+  if constexpr (SRC == 1) return u[(size_t)k * (size_t)N + (size_t)n];
+  double b = 0.0;
+  for (int p = 0; p < P; ++p) {
+    const double x = p == 0 ? x0 : xi[(size_t)n * P + p];
+    const double d = x - q[3 * p + 2];
+    b += q[3 * p] * d * d + q[3 * p + 1] * x;
+  }
+  return b;
+}
+
+// tile pair `pair` of the upper triangle, row by row: (0,0) (0,1) ... (0,T-1) (1,1) ...
+__device__ __forceinline__ void mbar_tile_pair(int T, int pair, int& ti, int& tj) {
+  ti = 0;
+  while (pair >= T - ti) pair -= T - ti, ++ti;
+  tj = ti + pair;
+}
+
+// what the host and the kernel agree on: columns of a strip step, staged table rows, doubles in front of the strips (even)
+constexpr int mbar_gram_width(int K) { return K > kGramTile ? 2 * kGramTile : kGramTile; }
+constexpr int mbar_gram_rows(int K) { return K < mbar_gram_width(K) ? K : mbar_gram_width(K); }
+constexpr size_t mbar_gram_head(int K, int P, int src) {
+  const size_t d = (size_t)mbar_gram_rows(K) * ((src == 0 ? 3 * (size_t)P : 0) + 1);
+  return d + (d & 1);
+}
+
+template <int SRC>
+__global__ __launch_bounds__(kMbarBlock) void mbar_gram_kernel(int K, int P, long long N, int n_chunks, int log2_frames,
+                                                                const double* __restrict__ xi, const double* __restrict__ table,
+                                                                const double* __restrict__ u, const double* __restrict__ f,
+                                                                const double* __restrict__ L, double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) double mbar_lds[];
+  const int tid = (int)threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  int ti, tj;
+  mbar_tile_pair((K + kGramTile - 1) / kGramTile, (int)blockIdx.y, ti, tj);
+  const bool diag = ti == tj;
+  // a pair's valid columns are the first n_cols: only the last tile is short, and it is tile j or the diagonal's own
+  const int n_cols = min(kGramTile, K - kGramTile * ti) + (diag ? 0 : min(kGramTile, K - kGramTile * tj));
+  const int width = diag ? kGramTile : 2 * kGramTile, stride = mbar_gram_width(K) + kGramPad, frames = 1 << log2_frames;
+  const int row = SRC == 0 ? 3 * P : 0;
+  double* __restrict__ s_tab = mbar_lds;                               // [rows][P][3]
+  double* __restrict__ s_f = s_tab + (size_t)mbar_gram_rows(K) * row;  // [rows]
+  double* __restrict__ s_w = mbar_lds + mbar_gram_head(K, P, SRC);     // [frames][stride]
+  auto window = [&](int c) { return c < kGramTile ? kGramTile * ti + c : kGramTile * tj + c - kGramTile; };
+  if constexpr (SRC == 0)
+    for (int i = tid; i < n_cols * row; i += kMbarBlock) s_tab[i] = table[(size_t)window(i / row) * row + i % row];
+  for (int c = tid; c < n_cols; c += kMbarBlock) s_f[c] = f[window(c)];
+  __syncthreads();
+
+  double acc[4][4] = {};
+  for (int chunk = (int)blockIdx.x; chunk < n_chunks; chunk += (int)gridDim.x) {
+    const long long end = min((long long)(chunk + 1) * kMbarChunk, N);
+    for (long long base = (long long)chunk * kMbarChunk; base < end; base += frames) {
+      for (int e = tid; e < width << log2_frames; e += kMbarBlock) {
+        const int fr = e & (frames - 1), c = e >> log2_frames;
+        const long long n = base + fr;
+        double w = 0.0;  // a column past K, a frame past N: a zero that adds nothing
+        if (c < n_cols && n < N) {
+          const double x0 = SRC == 0 ? xi[(size_t)n * P] : 0.0;
+          w = exp(s_f[c] - mbar_bias<SRC>(s_tab + (size_t)c * row, xi, u, P, N, window(c), n, x0) - L[n]);
+        }
+        s_w[fr * stride + c] = w;
+      }
+      __syncthreads();
+      const int n_fr = (int)min((long long)frames, end - base);
+      for (int fr = 0; fr < n_fr; ++fr) {
+        const double* __restrict__ a = s_w + fr * stride + 4 * ty;
+        const double* __restrict__ b = s_w + fr * stride + (diag ? 0 : kGramTile) + 4 * tx;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = fma(a[i], b[j], acc[i][j]);
+      }
+      __syncthreads();
+    }
+  }
+  double* __restrict__ dst = partial + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * kGramTileSize;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dst[(4 * ty + i) * kGramTile + 4 * tx + j] = acc[i][j];
+}
+
+// grid (tile pairs, kGramTileSize / kMbarBlock)
+__global__ __launch_bounds__(kMbarBlock) void mbar_gram_finish_kernel(int K, int n_fb, const double* __restrict__ partial,
+                                                                       double* __restrict__ gram) {
+  int ti, tj;
+  mbar_tile_pair((K + kGramTile - 1) / kGramTile, (int)blockIdx.x, ti, tj);
+  const int e = (int)blockIdx.y * kMbarBlock + (int)threadIdx.x;
+  double t = 0.0;
+  for (int b = 0; b < n_fb; ++b) t += partial[((size_t)b * gridDim.x + blockIdx.x) * kGramTileSize + e];
+  const int gi = kGramTile * ti + e / kGramTile, gj = kGramTile * tj + e % kGramTile;
+  if (gi >= K || gj >= K) return;
+  gram[(size_t)gi * K + gj] = t;
+  if (ti != tj) gram[(size_t)gj * K + gi] = t;  // (a diagonal tile holds both of its triangles, bit for bit)
+}
+
+// grid (segments, splits); dst [segment][split][K]
+template <int SRC>
+__global__ __launch_bounds__(kMbarBlock) void mbar_segment_kernel(int K, int P, long long N, const long long* __restrict__ seg,
+                                                                   const long long* __restrict__ order, const double* __restrict__ v,
+                                                                   const double* __restrict__ xi, const double* __restrict__ table,
+                                                                   const double* __restrict__ u, const double* __restrict__ f,
+                                                                   const double* __restrict__ L, double* __restrict__ dst) {
+  extern __shared__ __attribute__((aligned(16))) double mbar_lds[];
+  double* __restrict__ s_tab = mbar_lds;                  // [K][P][3]
+  double* __restrict__ s_a = s_tab + 3 * (size_t)K * P;   // [K] f_k
+  double* __restrict__ s_part = s_a + K;                  // [kMbarWaves][K]
+  const int tid = (int)threadIdx.x, wave = tid >> 6;
+  if (SRC == 0)
+    for (int i = tid; i < 3 * K * P; i += kMbarBlock) s_tab[i] = table[i];
+  for (int k = tid; k < K; k += kMbarBlock) s_a[k] = f[k];
+  for (int i = tid; i < kMbarWaves * K; i += kMbarBlock) s_part[i] = 0.0;
+  __syncthreads();
+  long long lo = 0, hi = N;  // no order: every frame, in natural order
+  if (order) lo = min(max(seg[blockIdx.x], 0ll), N), hi = min(max(seg[blockIdx.x + 1], lo), N);
+  for (long long at = lo + (long long)blockIdx.y * kMbarChunk; at < hi; at += (long long)gridDim.y * kMbarChunk) {
+    long long n[kMbarFpt];
+    double x0[kMbarFpt], vn[kMbarFpt], Ln[kMbarFpt];
+#pragma unroll
+    for (int j = 0; j < kMbarFpt; ++j) {
+      const long long i = at + j * kMbarBlock + tid;
+      long long m = i < hi ? (order ? order[i] : i) : -1;
+      const bool own = m >= 0 && m < N;  // (not a permutation: the entry is skipped, memory stays in bounds)
+      n[j] = own ? m : 0;                // a slot without a frame reads frame 0 and adds 0 times its weight
+      vn[j] = own ? (v ? v[n[j]] : 1.0) : 0.0;
+      x0[j] = SRC == 0 ? xi[(size_t)n[j] * P] : 0.0;
+      Ln[j] = L[n[j]];
+    }
+    for (int k = 0; k < K; ++k) {
+      const double a0 = s_a[k];
+      double acc = 0.0;
+#pragma unroll
+      for (int j = 0; j < kMbarFpt; ++j)
+        acc += vn[j] * exp(a0 - mbar_bias<SRC>(s_tab + 3 * (size_t)k * P, xi, u, P, N, k, n[j], x0[j]) - Ln[j]);
+      const double w = mbar_wave_sum(acc);
+      if ((tid & 63) == 0) s_part[(size_t)wave * K + k] += w;
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < K; k += kMbarBlock) {
+    double t = s_part[k];
+#pragma unroll
+    for (int w = 1; w < kMbarWaves; ++w) t += s_part[(size_t)w * K + k];
+    dst[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * K + k] = t;
+  }
+}
+
+// grid (segments)
+__global__ __launch_bounds__(kMbarBlock) void mbar_segment_finish_kernel(int K, int splits, const double* __restrict__ partial,
+                                                                          double* __restrict__ out) {
+  for (int k = (int)threadIdx.x; k < K; k += kMbarBlock) {
+    double t = 0.0;
+    for (int s = 0; s < splits; ++s) t += partial[((size_t)blockIdx.x * splits + s) * K + k];
+    out[(size_t)blockIdx.x * K + k] = t;
+  }
+}
+
 static int mbar_ready(const mythos_mbar* h, const char* who) {
   if (h->src < 0) {
     set_error(std::string(who) + ": neither windows nor a matrix are set");
@@ -213,6 +401,24 @@ static void mbar_launch(const mythos_mbar* h, const double* f, double* lw_out, d
   auto kernel = h->src == 0 ? mbar_iterate_kernel<0> : mbar_iterate_kernel<1>;
   hipLaunchKernelGGL(kernel, dim3(h->n_blocks), dim3(kMbarBlock), lds, st, h->K, h->P, (long long)h->N, h->n_chunks, h->xi,
                      h->d_table.get(), h->u, h->d_ln_nk.get(), f, h->d_L.get(), lw_out, partial);
+}
+
+// The segment kernel and, where a segment's rounds are split, its finish.  d_L must be current on the stream.
+static int mbar_segment_launch(mythos_mbar* h, const double* f, int n_seg, const int64_t* seg_start, const int64_t* order,
+                               const double* v, double* out, hipStream_t st) {
+  const int splits = std::min(h->n_chunks, std::max(1, kSegMaxSplits / n_seg));
+  double* dst = out;
+  if (splits > 1) {
+    if (int rc = h->d_seg_partial.grow((size_t)n_seg * splits * h->K)) return rc;
+    dst = h->d_seg_partial.get();
+  }
+  const size_t lds = sizeof(double) * mbar_lds_doubles(h->K, h->P);
+  auto kernel = h->src == 0 ? mbar_segment_kernel<0> : mbar_segment_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(n_seg, splits), dim3(kMbarBlock), lds, st, h->K, h->P, (long long)h->N, (const long long*)seg_start,
+                     (const long long*)order, v, h->xi, h->d_table.get(), h->u, f, h->d_L.get(), dst);
+  if (splits > 1)
+    hipLaunchKernelGGL(mbar_segment_finish_kernel, dim3(n_seg), dim3(kMbarBlock), 0, st, h->K, splits, dst, out);
+  return MYTHOS_OK;
 }
 
 }  // namespace mythos
@@ -324,6 +530,52 @@ int mythos_mbar_binned_sum(mythos_mbar_t* h, int n_bins, const int64_t* seg_star
   MYTHOS_HIP_TRY(hipSetDevice(h->device));
   hipLaunchKernelGGL(mbar_binned_sum_kernel, dim3(n_bins + 1), dim3(kMbarBlock), 0, (hipStream_t)stream, n_bins, (long long)h->N,
                      (const long long*)seg_start, (const long long*)order, log_weights, weights, shift, sums);
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return MYTHOS_OK;
+}
+
+int mythos_mbar_gram(mythos_mbar_t* h, const double* f, double* gram, double* colsum, mythos_stream_t stream) {
+  if (!h || !f || !gram) {
+    set_error("mythos_mbar_gram: invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (int rc = mbar_ready(h, "mythos_mbar_gram")) return rc;
+  const int tiles = (h->K + kGramTile - 1) / kGramTile, pairs = tiles * (tiles + 1) / 2;
+  const size_t head = mbar_gram_head(h->K, h->P, h->src), step = (size_t)mbar_gram_width(h->K) + kGramPad;
+  int log2_frames = kGramLog2Frames;
+  while (log2_frames >= 0 && head + (step << log2_frames) > (size_t)kMbarLdsDoubles) --log2_frames;
+  if (log2_frames < 0) {
+    set_error("mythos_mbar_gram: the window table leaves no LDS for a strip of W (" + std::to_string(head) + " + " +
+              std::to_string(step) + " doubles do not fit 64 KB)");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  MYTHOS_HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int n_fb = std::min(h->n_chunks, std::max(1, kGramMaxPartials / pairs));
+  if (int rc = h->d_gram_partial.grow((size_t)n_fb * pairs * kGramTileSize)) return rc;
+  mbar_launch(h, f, nullptr, nullptr, st);  // L_n at this f
+  auto kernel = h->src == 0 ? mbar_gram_kernel<0> : mbar_gram_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(n_fb, pairs), dim3(kMbarBlock), sizeof(double) * (head + (step << log2_frames)), st, h->K, h->P,
+                     (long long)h->N, h->n_chunks, log2_frames, h->xi, h->d_table.get(), h->u, f, h->d_L.get(), h->d_gram_partial.get());
+  hipLaunchKernelGGL(mbar_gram_finish_kernel, dim3(pairs, kGramTileSize / kMbarBlock), dim3(kMbarBlock), 0, st, h->K, n_fb,
+                     h->d_gram_partial.get(), gram);
+  if (colsum)
+    if (int rc = mbar_segment_launch(h, f, 1, nullptr, nullptr, nullptr, colsum, st)) return rc;
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return MYTHOS_OK;
+}
+
+int mythos_mbar_segment_moments(mythos_mbar_t* h, const double* f, int n_seg, const int64_t* seg_start, const int64_t* order,
+                                const double* v, double* out, mythos_stream_t stream) {
+  if (!h || !f || !out || n_seg < 1 || n_seg > (1 << 20) || (order && !seg_start) || (!order && n_seg != 1)) {
+    set_error("mythos_mbar_segment_moments: invalid argument (1 <= n_seg <= 2^20; seg_start with an order, one segment without)");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (int rc = mbar_ready(h, "mythos_mbar_segment_moments")) return rc;
+  MYTHOS_HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  mbar_launch(h, f, nullptr, nullptr, st);  // L_n at this f
+  if (int rc = mbar_segment_launch(h, f, n_seg, seg_start, order, v, out, st)) return rc;
   MYTHOS_HIP_TRY(hipGetLastError());
   return MYTHOS_OK;
 }
