@@ -817,6 +817,48 @@ int mythos_martini_langevin_eval_external(mythos_martini_sim_t* sim, const void*
                                           double* xi, mythos_stream_t stream);
 int mythos_martini_langevin_pull_values(mythos_martini_sim_t* sim, const void* pos, int n_frames, double* out, mythos_stream_t stream);
 
+/* ---- MARTINI ensemble: window exchange (Hamiltonian replica exchange between umbrella windows) -----------------------
+ * A mode of its own beside temperature exchange: every replica at the SAME kT, the rungs are the parameter rows of the
+ * installed set of restraints.
+ *   Windows and slots  The window of rung w is the whole per-replica row set_restraints was given for replica w: pr_ref[w],
+ *                    fb_param[w], p_param[w].  Slots are the replicas as they lie in memory and keep beads, velocities,
+ *                    box, seed and kT.  window_of_slot is a permutation, the identity after set_restraints.  An accepted
+ *                    exchange SWAPS THE TWO ROWS in device memory: slot s always runs under row s, and the step path and the
+ *                    restraint kick are what they are without exchange.
+ *   Energy           E_w(x_s, t): position + flat-bottom + umbrella + constant-force energy of the configuration of slot s,
+ *                    in slot s's box, under window w, at t = step dt (moving windows included); sums in double.
+ *   Event            every = E > 0: at the closed state of every absolute step that is a multiple of E.  Attempt a = step / E
+ *                    tries the pairs of temperature exchange's schedule.  For slot A in window t and slot B in window t + 1
+ *                        d = -(1 / kT) [ (E_t+1(x_A) + E_t(x_B)) - (E_t(x_A) + E_t+1(x_B)) ],   accept iff d >= 0 or u < exp(d),
+ *                    u = (c[0] + 0.5) 2^-32 of Philox4x32-10 keyed by the 64-bit seed, counter {t, step lo, step hi, 6}.  The
+ *                    physical energy cancels at equal kT: no energy row, no rescale.  One centre-of-mass launch, one
+ *                    decision launch (a workgroup per pair), one synchronisation; the neighbour rows are dropped, so what
+ *                    follows is bit for bit the run of an ensemble loaded with this state and set_restraints with these
+ *                    rows.  A row saved at an event step is the state before the event.  every = 0 switches it off: the
+ *                    handle then launches exactly what it launched before.
+ * Refused by name (INVALID_ARGUMENT): n_rep < 2, every < 0, replicas whose kT differ, temperature exchange or a barostat in
+ * either order of the two calls, a set whose pull vec or origin differ between replicas (windows may differ in k, init,
+ * rate, position-restraint references and flat-bottom parameters; xi is then a function of the configuration alone), a
+ * window_of_slot that is no permutation.  NOT_READY: advance with window exchange on and no set installed; set_windows on
+ * an open resident frame or without a set.
+ *   set_windows      window_of_slot host int32[n_rep]: permutes the rows from the current assignment to this one.
+ *   get_windows      the current assignment.  set_restraints resets it to the identity and clears the counts.
+ *   last_windows     host int32[*n_rows][n_rep]: window_of_slot at every row the last call saved, each before its event.
+ *   last_window_exchanges  host double[*n][11], the last call's attempts in order: step, t, slot A, slot B, E_t(x_A),
+ *                    E_t+1(x_A), E_t(x_B), E_t+1(x_B), d, u, accepted (0 | 1).  rec / rows NULL: the count alone.
+ *   window_exchange_counts  host int64[n_rep - 1] each: attempts and acceptances per rung pair since set_restraints.
+ * mythos_martini_window_exchange_check: the refusals that need no handle; kT host double[n_rep], p_param host
+ * double[n_rep][n_pull][9] and window_of_slot may be NULL (not checked); temperature_exchange / barostat say whether one is
+ * set; touches no device. */
+int mythos_martini_window_exchange_check(int n_rep, int every, const double* kT, int temperature_exchange, int barostat, int n_pull,
+                                         const double* p_param, const int32_t* window_of_slot);
+int mythos_martini_langevin_set_window_exchange(mythos_martini_sim_t* sim, int every, uint64_t seed);
+int mythos_martini_langevin_set_windows(mythos_martini_sim_t* sim, const int32_t* window_of_slot);
+int mythos_martini_langevin_get_windows(const mythos_martini_sim_t* sim, int32_t* window_of_slot);
+int mythos_martini_langevin_last_windows(const mythos_martini_sim_t* sim, int32_t* rows, int* n_rows);
+int mythos_martini_langevin_last_window_exchanges(const mythos_martini_sim_t* sim, double* rec, int* n);
+int mythos_martini_langevin_window_exchange_counts(const mythos_martini_sim_t* sim, int64_t* attempts, int64_t* accepts);
+
 /* ---- MARTINI observables: named bond lengths and triplet angles ------------------------------
  * Replaces mythos/observables/bond_distances.py:15-17, 51-69 (BondDistances / BondDistancesMapped) and
  * triplet_angles.py:15-31, 73-92 (TripletAngles / TripletAnglesMapped) with the angle of

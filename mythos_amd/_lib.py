@@ -129,6 +129,13 @@ _SIGS = {
     "mythos_martini_langevin_last_exchanges": (C.c_int, [V, c_double_p, C.POINTER(C.c_int)]),
     "mythos_martini_langevin_exchange_counts": (C.c_int, [V, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mythos_martini_exchange_check": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "mythos_martini_window_exchange_check": (C.c_int, [C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, C.c_int, c_double_p, C.POINTER(C.c_int32)]),
+    "mythos_martini_langevin_set_window_exchange": (C.c_int, [V, C.c_int, C.c_uint64]),
+    "mythos_martini_langevin_set_windows": (C.c_int, [V, C.POINTER(C.c_int32)]),
+    "mythos_martini_langevin_get_windows": (C.c_int, [V, C.POINTER(C.c_int32)]),
+    "mythos_martini_langevin_last_windows": (C.c_int, [V, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "mythos_martini_langevin_last_window_exchanges": (C.c_int, [V, c_double_p, C.POINTER(C.c_int)]),
+    "mythos_martini_langevin_window_exchange_counts": (C.c_int, [V, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mythos_martini_restraints_check": (C.c_int, [C.c_int, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p, C.c_int, c_int_p, c_int_p,
                                                   c_double_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, c_double_p,
                                                   c_double_p, C.c_int, C.c_int]),

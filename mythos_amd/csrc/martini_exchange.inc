@@ -219,6 +219,8 @@ int mythos_martini_langevin_set_exchange(mythos_martini_sim_t* s, int every, uin
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
   if (int rc = mm_xchg_check_settings(s->n_rep, every, "mythos_martini_langevin_set_exchange")) return rc;
+  if (every > 0 && s->wx.every > 0)  // (martini_window_exchange_checks.h)
+    return mm_wx_check_partners(true, false, "mythos_martini_langevin_set_exchange");
   if (every > 0 && s->rst.installed) {
     set_error("mythos_martini_langevin_set_exchange: replica exchange together with restraints is refused: the restraint energy is not "
               "in the exchange's H (clear the set with mythos_martini_langevin_set_restraints first)");

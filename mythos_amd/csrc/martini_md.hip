@@ -30,6 +30,7 @@
 #include "martini_exchange_checks.h"
 #include "martini_internal.h"
 #include "martini_restraints.h"
+#include "martini_window_exchange_checks.h"
 #include "md_driver.h"
 #include "philox.h"
 #include "wave_ops.h"
@@ -744,6 +745,27 @@ struct MmExchange {
   }
 };
 
+// Window exchange of an ensemble (martini_window_exchange.inc): what mythos_martini_langevin_set_window_exchange set, the
+// assignment - which window's parameter row every slot holds -, the counts since set_restraints, and assignment rows and
+// attempt log of the last call.
+struct MmWindowExchange {
+  int every = 0;      // 0: off
+  uint64_t seed = 0;  // of the decisions' uniforms, a Philox stream of its own
+  std::vector<int32_t> window_of_slot;     // [n_rep]: a permutation, the identity at creation and after set_restraints
+  std::vector<int64_t> attempts, accepts;  // [n_rep - 1], per rung pair (t, t + 1)
+  std::vector<int32_t> last_windows;       // [rows][n_rep]
+  std::vector<double> last_log;            // [attempted pairs][kWxRec]
+  double *h_d = nullptr, *d_hd = nullptr;  // pinned, and its device address: out log [n_rep / 2][kWxRec]
+  int *h_i = nullptr, *d_hi = nullptr;     // pinned: in window_of_slot [n_rep]; out the new one [n_rep]
+  MmWindowExchange() = default;
+  MmWindowExchange(const MmWindowExchange&) = delete;
+  MmWindowExchange& operator=(const MmWindowExchange&) = delete;
+  ~MmWindowExchange() {  // (the owner's destructor has selected the device)
+    if (h_d) (void)hipHostFree(h_d);
+    if (h_i) (void)hipHostFree(h_i);
+  }
+};
+
 // External forces of the resident state (martini_restraints.h, martini_restraints.inc): the device arrays of the set
 // mythos_martini_langevin_set_restraints installed, the COM rows and the kick's stamp words.  installed = false: the
 // integrator launches nothing it did not launch before the set existed.
@@ -806,6 +828,7 @@ struct mythos_martini_sim : mythos::MdRun {
   unsigned char* h_reps = nullptr;
   MmExchange xchg;  // off until mythos_martini_langevin_set_exchange
   MmRestraints rst;  // none until mythos_martini_langevin_set_restraints
+  MmWindowExchange wx;  // off until mythos_martini_langevin_set_window_exchange
   std::vector<double> h_mass;  // [n] as given at creation (the COM weights of the pull groups)
   int copies() const { return n_rep > 0 ? n_rep : 1; }
   int n_all() const { return copies() * sys->n; }  // beads of all copies
@@ -1222,6 +1245,7 @@ static int mm_store_typed(mythos_martini_sim* sim, R* pos, R* v, hipStream_t st)
 #include "martini_npt.inc"
 #include "martini_exchange.inc"
 #include "martini_restraints.inc"
+#include "martini_window_exchange.inc"
 
 extern "C" {
 
@@ -1251,6 +1275,9 @@ mythos_martini_sim_t* mm_create(mythos_martini_t* sys, int n_rep, double dt, con
     for (int r = 0; r < n_rep; ++r) s->xchg.rung_of_slot[r] = r;
     s->xchg.attempts.assign((size_t)std::max(0, n_rep - 1), 0);
     s->xchg.accepts.assign((size_t)std::max(0, n_rep - 1), 0);
+    s->wx.window_of_slot = s->xchg.rung_of_slot;
+    s->wx.attempts = s->xchg.attempts;
+    s->wx.accepts = s->xchg.accepts;
   }
   const int copies = s->copies();
   const int n = sys->n, dtype = sys->dtype;
@@ -1401,19 +1428,30 @@ int mm_load(mythos_martini_sim_t* s, const void* pos, const void* vel, const dou
 }
 int mm_advance(mythos_martini_sim_t* s, int n_steps, int save_every, bool close, void* traj, double* e_trace, hipStream_t st) {
   if (int rc = mm_sync_charges(s, st)) return rc;
-  if (mm_exchange_on(s))  // chunks that end at exchange and coupling events (martini_exchange.inc)
-    return s->sys->dtype == MYTHOS_F32 ? mm_advance_events<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
-                                       : mm_advance_events<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+  if (mm_window_exchange_on(s)) {  // chunks that end at window-exchange events (martini_window_exchange.inc)
+    const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_windows<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
+                                               : mm_advance_windows<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+    mm_constant_ladder(s);
+    return rc;
+  }
+  if (mm_exchange_on(s)) {  // chunks that end at exchange and coupling events (martini_exchange.inc)
+    const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_events<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
+                                               : mm_advance_events<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+    mm_constant_windows(s);
+    return rc;
+  }
   if (mm_barostat_on(s)) {  // chunks that end at coupling events (martini_npt.inc); off: the call below, as ever
     const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_npt<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
                                                : mm_advance_npt<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
     mm_constant_ladder(s);
+    mm_constant_windows(s);
     return rc;
   }
   const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_typed<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
                                              : mm_advance_typed<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
   mm_constant_boxes(s, rc == MYTHOS_OK && save_every > 0 ? n_steps / save_every : 0);
   mm_constant_ladder(s);
+  mm_constant_windows(s);
   return rc;
 }
 int mm_store(mythos_martini_sim_t* s, void* pos, void* vel, hipStream_t st) {

@@ -442,6 +442,8 @@ int mythos_martini_langevin_set_barostat(mythos_martini_sim_t* s, int kind, int 
     b.kind = 0;
     return MYTHOS_OK;
   }
+  if (s->wx.every > 0)  // (martini_window_exchange_checks.h)
+    return mm_wx_check_partners(false, true, "mythos_martini_langevin_set_barostat");
   if (s->rst.installed) {
     set_error("mythos_martini_langevin_set_barostat: a barostat together with restraints is refused: the restraint virial and reference "
               "scaling are not built (clear the set with mythos_martini_langevin_set_restraints first)");

@@ -118,11 +118,13 @@ struct MrPull {
   double e[3];       // d xi / d X_B (zero where the coordinate has no direction)
 };
 
-// Pull coordinate p of replica rep from the COM rows of that replica (rows: its n_groups rows) at time t.  The one
-// evaluation of the law: the kick, the energy sum and the stored-frames launch all come here.
-__device__ inline MrPull mr_pull_eval(const MrView& v, int p, int rep, const double* __restrict__ rows, double t) {
+// Pull coordinate p of replica rep from the COM rows of that replica (rows: its n_groups rows) at time t, with the
+// parameters of row prow - rep itself everywhere but in the window-exchange event, which evaluates a configuration under
+// another replica's window; minimum images are always the configuration's, in the box of rep.  The one evaluation of the
+// law: the kick, the energy sum, the stored-frames launch and the exchange event all come here.
+__device__ inline MrPull mr_pull_eval(const MrView& v, int p, int rep, int prow, const double* __restrict__ rows, double t) {
   const int f = v.p_flags[p], A = v.p_groups[2 * p], B = v.p_groups[2 * p + 1];
-  const double* q = v.p_param + ((size_t)rep * v.n_pull + p) * kMrPullParams;
+  const double* q = v.p_param + ((size_t)prow * v.n_pull + p) * kMrPullParams;
   const double* L = v.boxes + 3 * (size_t)rep;
   const double* xb = rows + (size_t)B * kMrRow;
   double D[3];
@@ -157,10 +159,11 @@ __device__ inline MrPull mr_pull_eval(const MrView& v, int p, int rep, const dou
   return r;
 }
 
-// position restraint t of replica rep on a bead at x: its force added to F, its energy returned
-__device__ inline double mr_posres_term(const MrView& v, int t, int rep, const double (&x)[3], double (&F)[3]) {
+// position restraint t with the reference of parameter row prow (the bead's own replica, or in the window-exchange event
+// the other window's row) on a bead at x: its force added to F, its energy returned
+__device__ inline double mr_posres_term(const MrView& v, int t, int prow, const double (&x)[3], double (&F)[3]) {
   const double* k = v.pr_k + 3 * (size_t)t;
-  const double* X = v.pr_ref + ((size_t)rep * v.n_posres + t) * 3;
+  const double* X = v.pr_ref + ((size_t)prow * v.n_posres + t) * 3;
   double u = 0;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -171,10 +174,10 @@ __device__ inline double mr_posres_term(const MrView& v, int t, int rep, const d
   return 0.5 * u;
 }
 
-// flat-bottom term t of replica rep on a bead at x
-__device__ inline double mr_flat_term(const MrView& v, int t, int rep, const double (&x)[3], double (&F)[3]) {
+// flat-bottom term t with the parameters of row prow on a bead at x
+__device__ inline double mr_flat_term(const MrView& v, int t, int prow, const double (&x)[3], double (&F)[3]) {
   const int f = v.fb_flags[t], shape = mr_flat_shape(f), axis = mr_flat_axis(f);
-  const double* q = v.fb_param + ((size_t)rep * v.n_flat + t) * kMrFlatParams;
+  const double* q = v.fb_param + ((size_t)prow * v.n_flat + t) * kMrFlatParams;
   double rho[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -223,7 +226,7 @@ __global__ __launch_bounds__(256) void mr_kick_kernel(const MrView v, const R* _
         (void)mr_flat_term(v, idx, rep, x, F);
       } else {
         const int side = (code >> 2) & 1;
-        const MrPull pc = mr_pull_eval(v, idx, rep, rw, t);
+        const MrPull pc = mr_pull_eval(v, idx, rep, rep, rw, t);
         const int g = v.p_groups[2 * idx + side];
         const double w = (side ? -pc.du : pc.du) * (v.mass[il] / rw[(size_t)g * kMrRow + 3]);
         F[0] += w * pc.e[0], F[1] += w * pc.e[1], F[2] += w * pc.e[2];
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(256) void mr_energy_kernel(const MrView v, const R*
     acc[1] += mr_flat_term(v, t, rep, x, F);
   }
   for (int p = threadIdx.x; p < v.n_pull; p += 256) {
-    const MrPull pc = mr_pull_eval(v, p, rep, rw, s * v.dt);
+    const MrPull pc = mr_pull_eval(v, p, rep, rep, rw, s * v.dt);
     acc[mr_pull_constant(v.p_flags[p]) ? 3 : 2] += pc.u;
     if (xi) xi[(size_t)rep * v.n_pull + p] = pc.xi;
   }
@@ -276,7 +279,7 @@ __global__ __launch_bounds__(256) void mr_pull_values_kernel(const MrView v, int
   const int p = (int)(j % v.n_pull);
   const long long fr = j / v.n_pull;
   const int rep = (int)(fr % v.n_rep);
-  out[j] = mr_pull_eval(v, p, rep, rows + (size_t)fr * v.n_groups * kMrRow, 0.0).xi;
+  out[j] = mr_pull_eval(v, p, rep, rep, rows + (size_t)fr * v.n_groups * kMrRow, 0.0).xi;
 }
 
 // caller's (n_all, 3) positions need no packing (stride 3); the velocities of the scratch frame -> (n_all, 3) forces

@@ -146,12 +146,18 @@ int mythos_martini_langevin_set_restraints(mythos_martini_sim_t* s, int n_posres
   const MrArrays a = mr_arrays(n_posres, pr_index, pr_k, pr_ref, n_flat, fb_index, fb_flags, fb_param, n_groups, g_first, g_member,
                                g_pbc_ref, n_pull, p_flags, p_groups, p_param, boxes);
   if (int rc = mr_check(who, s->sys->n, s->copies(), a, s->baro.kind != 0, mm_exchange_on(s))) return rc;
+  if (s->wx.every > 0)  // window exchange: vec and origin are the coordinate's, not a window's (martini_window_exchange_checks.h)
+    if (int rc = mm_wx_check_set(s->n_rep, a.n_pull, a.p_param, who)) return rc;
   if (s->resident && s->open) {
     set_error(std::string(who) + ": the resident frame is open - its velocities wait for a closing half kick by the old field (store or load first)");
     return MYTHOS_ERR_NOT_READY;
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
   MYTHOS_HIP_TRY(hipDeviceSynchronize());  // (launches that read the arrays replaced below)
+  // the rows are the caller's again: window w lies in slot w, the window-exchange counts start over
+  for (int r = 0; r < s->n_rep; ++r) s->wx.window_of_slot[(size_t)r] = r;
+  std::fill(s->wx.attempts.begin(), s->wx.attempts.end(), 0);
+  std::fill(s->wx.accepts.begin(), s->wx.accepts.end(), 0);
   return mr_install(s, a);
 }
 

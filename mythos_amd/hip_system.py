@@ -992,6 +992,64 @@ class _MartiniEnsembleHandle(MartiniLangevinIntegrator):
                                                                      acc.ctypes.data_as(C.POINTER(C.c_int64))), "exchange_counts")
         return att, acc
 
+    # ---- window exchange between the rows of the installed restraints (mythos_martini_langevin_set_window_exchange) ----
+    WINDOW_EXCHANGE_FIELDS = ("step", "rung", "slot_a", "slot_b", "e_t_a", "e_t1_a", "e_t_b", "e_t1_b", "d", "u", "accepted")
+
+    def set_window_exchange(self, every: int, seed: int = 0) -> None:
+        """A window-exchange event at every absolute step s > 0 with s % ``every`` == 0 (0: off); ``seed`` keys the
+        decisions' uniforms.  Every replica at the same kT; refused together with temperature exchange or a barostat."""
+        _lib.check(self._lib.mythos_martini_langevin_set_window_exchange(self._h, int(every), int(seed) & (2**64 - 1)), "set_window_exchange")
+
+    def set_windows(self, window_of_slot) -> None:
+        """Which window - the parameter row ``set_restraints`` was given for that replica - every slot holds: a permutation
+        of 0 .. R - 1.  Moves the rows on the device; refused while the resident frame is open."""
+        a = self._ladder_arg(window_of_slot)
+        if a.shape != (self.n_rep,):
+            raise ValueError(f"window_of_slot must hold {self.n_rep} values, one per replica")
+        _lib.check(self._lib.mythos_martini_langevin_set_windows(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), "set_windows")
+
+    @property
+    def windows(self) -> np.ndarray:
+        """(R,) int64: ``window_of_slot`` of the resident state."""
+        a = np.zeros(self.n_rep, dtype=np.int32)
+        _lib.check(self._lib.mythos_martini_langevin_get_windows(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), "get_windows")
+        return a.astype(np.int64)
+
+    @property
+    def last_windows(self) -> torch.Tensor:
+        """(S, R) int64 on the system's device: ``window_of_slot`` at every row the last call saved, each before the event
+        of its step."""
+        n = C.c_int(0)
+        _lib.check(self._lib.mythos_martini_langevin_last_windows(self._h, None, C.byref(n)), "last_windows")
+        a = np.zeros((n.value, self.n_rep), dtype=np.int32)
+        if n.value:
+            _lib.check(self._lib.mythos_martini_langevin_last_windows(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "last_windows")
+        return torch.as_tensor(a.astype(np.int64), device=self.system.device)
+
+    @property
+    def last_window_exchanges(self) -> dict:
+        """The last call's attempts in order, a dict of (A,) arrays: ``step``, ``rung`` (the pair is rung, rung + 1),
+        ``slot_a``, ``slot_b`` int64; ``e_t_a``, ``e_t1_a``, ``e_t_b``, ``e_t1_b`` (kJ/mol: the restraint energy of slot
+        A's / slot B's configuration under window rung / rung + 1), ``d``, ``u`` float64; ``accepted`` bool."""
+        n = C.c_int(0)
+        _lib.check(self._lib.mythos_martini_langevin_last_window_exchanges(self._h, None, C.byref(n)), "last_window_exchanges")
+        rec = np.zeros((n.value, len(self.WINDOW_EXCHANGE_FIELDS)), dtype=np.float64)
+        if n.value:
+            _lib.check(self._lib.mythos_martini_langevin_last_window_exchanges(self._h, rec.ctypes.data_as(_lib.c_double_p), C.byref(n)),
+                       "last_window_exchanges")
+        out = {k: rec[:, j].copy() for j, k in enumerate(self.WINDOW_EXCHANGE_FIELDS)}
+        for k in ("step", "rung", "slot_a", "slot_b"):
+            out[k] = out[k].astype(np.int64)
+        out["accepted"] = out["accepted"] != 0.0
+        return out
+
+    def window_exchange_counts(self) -> tuple[np.ndarray, np.ndarray]:
+        """(attempts, accepts), (R - 1,) int64 each: per rung pair (t, t + 1) since ``set_restraints``."""
+        att, acc = np.zeros(self.n_rep - 1, dtype=np.int64), np.zeros(self.n_rep - 1, dtype=np.int64)
+        _lib.check(self._lib.mythos_martini_langevin_window_exchange_counts(self._h, att.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                            acc.ctypes.data_as(C.POINTER(C.c_int64))), "window_exchange_counts")
+        return att, acc
+
     def pressure(self) -> dict:
         """As :meth:`MartiniLangevinIntegrator.pressure`, per replica: ``kinetic``, ``virial``, ``pressure`` (R, 3),
         ``volume`` and ``p`` (R,)."""
@@ -1086,7 +1144,13 @@ class MartiniEnsembleIntegrator:
     replicas are *slots* that keep their beads, box and seed, ``kT`` is the ladder of *rungs*, and an accepted exchange
     swaps the kT of two slots and rescales their velocities.  ``ladder`` / ``set_ladder`` give and take ``rung_of_slot``,
     ``kT_now`` the slots' current kT, ``last_ladder`` (rows, R) the ladder at every saved row, ``last_exchanges`` the log of
-    the last call's attempts and ``exchange_counts()`` attempts and acceptances per rung pair since ``restart``."""
+    the last call's attempts and ``exchange_counts()`` attempts and acceptances per rung pair since ``restart``.
+
+    Window exchange (``set_window_exchange(every, seed)``; a mode of its own, every replica at the same kT): the rungs are
+    the per-replica parameter rows of the installed restraints, and an accepted exchange swaps the rows of two slots on the
+    device.  ``windows`` / ``set_windows`` give and take ``window_of_slot``, ``last_windows`` (rows, R) the assignment at
+    every saved row, ``last_window_exchanges`` the log of the last call's attempts and ``window_exchange_counts()``
+    attempts and acceptances per rung pair since ``set_restraints``."""
 
     KB = MartiniLangevinIntegrator.KB
 
@@ -1132,3 +1196,32 @@ class MartiniEnsembleIntegrator:
                 raise ValueError(f"rung_of_slot must hold {int(n_rep)} values, one per replica")
         _lib.check(_lib.load().mythos_martini_exchange_check(int(n_rep), int(every), None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))),
                    "martini_exchange_check")
+
+    @staticmethod
+    def check_window_exchange(n_rep: int, every: int = 0, kT=None, temperature_exchange: bool = False, barostat: bool = False,
+                              p_param=None, window_of_slot=None) -> None:
+        """What ``set_window_exchange``, ``set_windows`` and ``set_restraints`` under window exchange refuse, without a device
+        (mythos_martini_window_exchange_check): fewer than two replicas, ``every`` < 0, replicas whose ``kT`` differ,
+        temperature exchange or a barostat beside it, ``p_param`` (R, P, 9) of a lowered set whose vec or origin differ
+        between replicas, a ``window_of_slot`` that is no permutation.  Raises with the library's message."""
+        n_rep = int(n_rep)
+        k = None
+        if kT is not None:
+            k = np.ascontiguousarray(np.asarray(kT, dtype=np.float64).reshape(-1))
+            if k.shape != (n_rep,):
+                raise ValueError(f"kT must hold {n_rep} values, one per replica")
+        q, n_pull = None, 0
+        if p_param is not None:
+            q = np.ascontiguousarray(p_param, dtype=np.float64)
+            if q.ndim != 3 or q.shape[0] != n_rep or q.shape[2] != 9:
+                raise ValueError(f"p_param must have shape ({n_rep}, P, 9)")
+            n_pull = int(q.shape[1])
+        a = None
+        if window_of_slot is not None:
+            a = _MartiniEnsembleHandle._ladder_arg(window_of_slot)
+            if a.shape != (n_rep,):
+                raise ValueError(f"window_of_slot must hold {n_rep} values, one per replica")
+        _lib.check(_lib.load().mythos_martini_window_exchange_check(
+            n_rep, int(every), None if k is None else k.ctypes.data_as(_lib.c_double_p), int(bool(temperature_exchange)), int(bool(barostat)),
+            n_pull, None if q is None else q.ctypes.data_as(_lib.c_double_p), None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))),
+            "martini_window_exchange_check")

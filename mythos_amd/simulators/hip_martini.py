@@ -126,7 +126,13 @@ class HipMartiniSimulator(Simulator):
     ``restraints``: a ``MartiniRestraints`` set, the same for every temperature except where a pull coordinate's ``init`` /
     ``k`` hold (R,) values - ``temperatures=[T] * R`` with ``init`` of shape (R,) are R umbrella windows in one launch;
     references left None are the positions the run starts from.  ``state["pull"]`` is then the (rows, R, P) float64 tensor
-    of the pull coordinates of the saved frames, on the GPU.  Refused with a barostat or exchange."""
+    of the pull coordinates of the saved frames, on the GPU.  Refused with a barostat or exchange.
+    ``window_exchange_every = E`` > 0 (with ``restraints`` and equal temperatures): Hamiltonian replica exchange between
+    the windows every E steps, in equilibration and production (seeds as for ``exchange_every``); ``observables[w]`` and
+    ``state["pull"][:, w]`` are then the trajectory of WINDOW w, gathered from the slots that held it, so that
+    ``mbar_umbrella(state["pull"], restraints, kT)`` works unchanged; ``state`` gains ``windows`` (the slot-major
+    assignment, taken up again by ``run(state=...)``) and ``window_exchange``.  Refused with
+    ``exchange_every`` > 0 or a barostat."""
 
     energy_fn: Any
     topology: Any = None
@@ -144,6 +150,7 @@ class HipMartiniSimulator(Simulator):
     barostat: dict | None = None
     exchange_every: int = 0
     restraints: Any = None
+    window_exchange_every: int = 0
     precision: str = "float32"
     device: Any = None
     _resident: dict = dc.field(default_factory=dict, repr=False, compare=False)
@@ -153,6 +160,15 @@ class HipMartiniSimulator(Simulator):
             raise ValueError("precision must be 'float32' or 'float64'")
         if int(self.exchange_every) < 0 or (int(self.exchange_every) > 0 and np.size(self.temperatures) < 2):
             raise ValueError("exchange_every >= 0, and at least two temperatures to exchange between, required")
+        wx = int(self.window_exchange_every)
+        if wx < 0 or (wx > 0 and (not self.restraints or np.size(self.temperatures) < 2)):
+            raise ValueError("window_exchange_every >= 0, and restraints with at least two windows to exchange between, required")
+        if wx > 0 and int(self.exchange_every) > 0:
+            raise ValueError("window_exchange_every together with exchange_every is refused: exchange with different kT and windows is not built")
+        if wx > 0 and barostat_settings(self.barostat):
+            raise ValueError("window_exchange_every together with a barostat is refused: restraints under pressure coupling are not built")
+        if wx > 0 and np.unique(np.asarray(self.temperatures, dtype=np.float64)).size != 1:
+            raise ValueError("window_exchange_every needs every replica at the same temperature: exchange with different kT and windows is not built")
         if self.restraints and (barostat_settings(self.barostat) or int(self.exchange_every) > 0):
             raise ValueError("restraints together with a barostat or replica exchange are not built (the restraint virial, the "
                              "restraint energy in the exchange's H)")
@@ -215,8 +231,13 @@ class HipMartiniSimulator(Simulator):
         pos = torch.as_tensor(state["positions"] if "positions" in state else x0).to(device=system.device, dtype=system.dtype).contiguous().clone()
         vel = (torch.as_tensor(state["velocities"]).to(device=system.device, dtype=system.dtype).contiguous().clone()
                if "velocities" in state else integ.init_velocities())
+        windows = int(self.window_exchange_every)
+        if windows:  # as for the temperatures: both phases exchange, the decisions' seed follows the replicas'
+            integ.set_window_exchange(windows, int(seed) + r)
         if self.restraints or integ.restraints:  # (the references left None follow the state this run starts from)
             integ.set_restraints(self.restraints, reference_pos=pos, box=state.get("boxes", boxes), topology=self.topology)
+        if windows and "windows" in state:  # (set_restraints has put window w into slot w)
+            integ.set_windows(np.asarray(state["windows"]))
         integ.load(pos, vel, state.get("boxes", boxes))
         if self.equilibration_steps:
             integ.advance(int(self.equilibration_steps))
@@ -225,6 +246,8 @@ class HipMartiniSimulator(Simulator):
         integ.store(pos, vel)
         if exchange:
             return self._exchanged_output(integ, traj, lb, temps, pos, vel, int(seed) + r + 1)
+        if windows:
+            return self._window_output(integ, traj, lb, temps, pos, vel, int(seed) + r + 1)
         s = traj.shape[0]
         q = torch.zeros((s, n, 4), dtype=traj.dtype, device=traj.device)
         q[..., 0] = 1.0
@@ -236,14 +259,15 @@ class HipMartiniSimulator(Simulator):
             st["pull"] = integ.pull_values(traj)
         return SimulatorOutput(observables=out, state=st)
 
-    def _exchanged_output(self, integ, traj, lb, temps, pos, vel, next_seed) -> SimulatorOutput:
-        """``observables[t]`` is the trajectory OF TEMPERATURE t: frame k is the slot that held rung t at row k, with that
-        slot's box; gathered on the GPU.  The state stays slot-major and gains the ladder."""
+    @staticmethod
+    def _by_rung(rung_rows, traj, lb, temps):
+        """Slot-major rows -> one trajectory per rung: frame k of rung t is the slot that held t at row k, with that slot's
+        box.  -> (trajectories, slot_of_rung (S, R))."""
         from mythos_amd.energy.base import Quaternion
         from mythos_amd.simulators.io import SimulatorTrajectory
 
         s, r, n = traj.shape[0], traj.shape[1], traj.shape[2]
-        slot_of_rung = torch.argsort(integ.last_ladder, dim=1)  # (S, R): the inverse of each row's permutation
+        slot_of_rung = torch.argsort(rung_rows, dim=1)  # (S, R): the inverse of each row's permutation
         rows = torch.arange(s, device=traj.device)
         q = torch.zeros((s, n, 4), dtype=traj.dtype, device=traj.device)
         q[..., 0] = 1.0
@@ -251,6 +275,24 @@ class HipMartiniSimulator(Simulator):
                                    box_size=lb[rows, slot_of_rung[:, k]].contiguous(),
                                    temperature=torch.full((s,), KB * float(temps[k]), dtype=torch.float64, device=traj.device))
                for k in range(r)]
+        return out, slot_of_rung
+
+    def _window_output(self, integ, traj, lb, temps, pos, vel, next_seed) -> SimulatorOutput:
+        """``observables[w]`` and ``state["pull"][:, w]`` are the trajectory OF WINDOW w, gathered as ``_exchanged_output``
+        gathers the temperatures; xi depends on the configuration alone, so it is evaluated slot-major and gathered.  The
+        state stays slot-major and gains the assignment."""
+        out, slot_of_window = self._by_rung(integ.last_windows, traj, lb, temps)
+        rows = torch.arange(traj.shape[0], device=traj.device)
+        pull = integ.pull_values(traj)
+        pull = torch.stack([pull[rows, slot_of_window[:, k]] for k in range(traj.shape[1])], dim=1).contiguous()
+        attempts, accepts = integ.window_exchange_counts()
+        return SimulatorOutput(observables=out, state=dict(positions=pos, velocities=vel, boxes=integ.box, seed=next_seed, pull=pull,
+                                                           windows=integ.windows, window_exchange=dict(attempts=attempts, accepts=accepts)))
+
+    def _exchanged_output(self, integ, traj, lb, temps, pos, vel, next_seed) -> SimulatorOutput:
+        """``observables[t]`` is the trajectory OF TEMPERATURE t: frame k is the slot that held rung t at row k, with that
+        slot's box; gathered on the GPU.  The state stays slot-major and gains the ladder."""
+        out, _ = self._by_rung(integ.last_ladder, traj, lb, temps)
         attempts, accepts = integ.exchange_counts()
         return SimulatorOutput(observables=out, state=dict(positions=pos, velocities=vel, boxes=integ.box, seed=next_seed, ladder=integ.ladder,
                                                            exchange=dict(attempts=attempts, accepts=accepts)))

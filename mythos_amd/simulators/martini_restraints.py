@@ -260,6 +260,30 @@ def read_ndx(path) -> dict:
     return {k: np.asarray(v, dtype=np.int64) for k, v in groups.items()}
 
 
+def round_trips(window_rows) -> np.ndarray:
+    """For every slot of a ``(rows, R)`` history of ``window_of_slot`` (``last_windows`` of a run with window exchange, or
+    several runs' concatenated): the number of completed trips rung 0 -> rung R - 1 -> rung 0.  A trip starts counting at
+    the slot's first visit to rung 0; one that has not come back by the last row does not count.  Host only; -> (R,) int64."""
+    w = np.asarray(window_rows.cpu() if hasattr(window_rows, "cpu") else window_rows, dtype=np.int64)
+    if w.ndim != 2:
+        raise ValueError("window_rows must have shape (rows, R)")
+    top = w.shape[1] - 1
+    trips = np.zeros(w.shape[1], dtype=np.int64)
+    if top < 1:
+        return trips
+    for s in range(w.shape[1]):
+        state = 0  # 0: waiting for rung 0, 1: left rung 0, heading up, 2: reached the top, heading down
+        for g in w[:, s]:
+            if state == 0 and g == 0:
+                state = 1
+            elif state == 1 and g == top:
+                state = 2
+            elif state == 2 and g == 0:
+                trips[s] += 1
+                state = 1
+    return trips
+
+
 def check(n: int, arrays: dict, barostat: bool = False, exchange: bool = False) -> None:
     """What ``set_restraints`` refuses, without a device (mythos_martini_restraints_check), for ``arrays`` of ``lower`` and
     ``n`` beads per replica.  Raises ValueError with the library's message."""
