@@ -444,9 +444,26 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   constexpr int kSlots = 2 + ITEMS;
   // two work lists per nucleotide: 0 = base-pair terms (H-bond and / or cross-stacking: they share the base-base
   // vector and all six angles, so one evaluation serves both), 1 = coaxial stacking
-  __shared__ int items[2][PPB][ITEMS];  // the flagged row ENTRIES (index | role bit), not their slots
+  // Wave-dense lists (the fixed-row instantiations of the single sweep, ITEMS = 16: the 12 kbp kernel): every wavefront
+  // appends what its groups flag to ONE list per kind while the radial pass runs - position = the wavefront's running
+  // count + the flagged lanes below, both out of the ballot the per-nucleotide slot needs anyway - so the angular pass
+  // finds its items with two LDS round trips (the four counts, the item) where the per-nucleotide lists take a prefix
+  // scan over the 32 counts and a binary search: fourteen dependent round trips in front of the first neighbour load of
+  // the base-pair wavefronts, the longest chain of the kernel.  An item is 8 bytes: the row entry, and p | k << 8 - the
+  // owner and the slot within the owner's list, which fix the result row exactly as the per-nucleotide lists do.
+  // kWaveCap per wavefront and kind (a duplex has 25 - 35 base-pair items per wavefront); a fuller wavefront aborts the
+  // launch like an over-full nucleotide, and the ITEMS = 32 instantiation (per-nucleotide lists: 8 x ITEMS items per
+  // wavefront would take 16 KB) repeats the step.  2 x 4 x 64 x 8 B = 4 KB in place of items (4 KB) + item_pre (0.5 KB).
+  // (oxRNA2, MODEL 3, keeps the per-nucleotide lists: with the dense ones md_step_kernel<float, 3, false, 16> took 52 B of
+  // scratch where it had none; oxNA, MODEL 4, and the 16-lane instantiations walk their rows in two pipelines whose trip
+  // counts differ between the groups of a wavefront, so a wavefront-wide running count has no place there)
+  constexpr bool kWaveLists = sizeof(R) == 4 && !DENSE && ITEMS == kMdItems && MODEL <= 2 && GL == kMdG;
+  constexpr int kWaveCap = 64;
+  __shared__ int items[kWaveLists ? 1 : 2][kWaveLists ? 1 : PPB][kWaveLists ? 1 : ITEMS];  // the flagged row ENTRIES (index | role bit), not their slots
   __shared__ int item_cnt[2][PPB];
-  __shared__ int item_pre[4][PPB + 1];  // per WAVEFRONT: the prefix of the list that wavefront will walk
+  __shared__ int item_pre[kWaveLists ? 1 : 4][kWaveLists ? 1 : PPB + 1];  // per WAVEFRONT: the prefix of the list that wavefront will walk
+  __shared__ int2 wave_items[kWaveLists ? 2 : 1][kWaveLists ? 4 : 1][kWaveLists ? kWaveCap : 1];
+  __shared__ __attribute__((aligned(16))) int wave_cnt[2][4];  // items of every wavefront's list, final at the barrier
   __shared__ R self_lds[PPB][13];
   __shared__ R rad_lds[PPB][7];  // radial-pass site gradients (backbone, base) of each nucleotide
   // result rows, [nucleotide][slot][RW] with the nucleotide stride padded to an odd word count: the 32
@@ -542,6 +559,8 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
   const RadSet<R> rs1 = (MODEL == 4) ? radset_from<R, 2>(Prna, cut_from<R>(Prna, cut.rcom2)) : rs0;
   const RadSet<R> rs2 = (MODEL == 4) ? radset_from<R, 2>(Pdrh, cut_from<R>(Pdrh, cut.rcom2)) : rs0;
   int n_items[2] = {0, 0};
+  const int wave_s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int wave_n[2] = {0, 0};  // (wave-dense lists) items of this wavefront's two lists so far: wave-uniform
   const int row_room = ITEMS - (extra_bonds ? ROW_BONDED_SLOTS - 2 : 0);  // result rows left for flagged neighbours
   const int lane64 = threadIdx.x & 63;
   const int gshift = lane64 & ~(G - 1);
@@ -680,9 +699,15 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
       const unsigned int gm = (unsigned int)(bal >> gshift) & ((1u << G) - 1u);
       if (flag[t]) {
         const int pos = n_items[t] + __popc(gm & ((1u << lane) - 1u));
-        if (pos < ITEMS) items[t][grp][pos] = entry;  // (row_room <= ITEMS; an over-full nucleotide aborts the launch below)
+        if constexpr (kWaveLists) {
+          const int wpos = wave_n[t] + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+          if (wpos < kWaveCap) wave_items[t][wave_s][wpos] = make_int2(entry, grp | (pos << 8));  // (a fuller list aborts the launch below)
+        } else {
+          if (pos < ITEMS) items[t][grp][pos] = entry;  // (row_room <= ITEMS; an over-full nucleotide aborts the launch below)
+        }
       }
       n_items[t] += __popc(gm);
+      if constexpr (kWaveLists) wave_n[t] = __builtin_amdgcn_readfirstlane(wave_n[t] + __popcll(bal));  // (a scalar register, not one per lane)
     }
   };
   // oxNA (MODEL 4) keeps the two separate pipelines - close segment, then far segment - it had before the single sweep:
@@ -784,9 +809,14 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
       }
     }
   }
-  if (n_items[0] + n_items[1] > row_room) {  // result rows of one nucleotide exhausted: this launch does not count
+  bool lists_over = n_items[0] + n_items[1] > row_room;  // result rows of one nucleotide exhausted: this launch does not count
+  // (wave-dense lists: ... or a wavefront's list is full.  Either way the WHOLE wavefront hands in nothing: its items
+  // cannot be told apart by owner any more, and an item of an over-full nucleotide would point past its result rows)
+  if constexpr (kWaveLists) lists_over = __any(lists_over) || wave_n[0] > kWaveCap || wave_n[1] > kWaveCap;
+  if (lists_over) {
     if (lane == 0) atomicMax(flags + 3, k_index + 1);
     n_items[0] = n_items[1] = 0;
+    wave_n[0] = wave_n[1] = 0;
   }
   // The radial sums are folded over the group now and parked in LDS: nothing computed so far stays in
   // registers across the angular pass (whose pair functions need the whole register budget).
@@ -797,6 +827,9 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     rl[0] = gbk.x, rl[1] = gbk.y, rl[2] = gbk.z, rl[3] = gba.x, rl[4] = gba.y, rl[5] = gba.z;
 #pragma unroll
     for (int t = 0; t < 2; ++t) item_cnt[t][grp] = valid ? n_items[t] : 0;
+  }
+  if constexpr (kWaveLists) {
+    if (lane64 == 0) wave_cnt[0][wave_s] = wave_n[0], wave_cnt[1][wave_s] = wave_n[1];
   }
   if (threadIdx.x == 0) s_halt = halt_word;
   __syncthreads();  // self_lds, rad_lds and item_cnt are visible
@@ -819,7 +852,15 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     const int pw = threadIdx.x >> 6;
     // rows 2, 3 (second-bond slots) exist only in systems with circular strands
     const int n_bonded_rows = extra_bonds ? ROW_BONDED_SLOTS : 2;
-    {
+    // wave-dense lists: the list of this wavefront's role is the four wavefronts' lists one after the other - item q is
+    // found from the four counts (one 16-byte read) with three compares; no scan, no search, no second barrier
+    int wl_b1 = 0, wl_b2 = 0, wl_b3 = 0, wl_n = 0;
+    if constexpr (kWaveLists) {
+      const int4 wc = *reinterpret_cast<const int4*>(wave_cnt[lst]);
+      const int c0 = __builtin_amdgcn_readfirstlane(wc.x), c1 = __builtin_amdgcn_readfirstlane(wc.y);
+      const int c2 = __builtin_amdgcn_readfirstlane(wc.z), c3 = __builtin_amdgcn_readfirstlane(wc.w);
+      wl_b1 = c0, wl_b2 = wl_b1 + c1, wl_b3 = wl_b2 + c2, wl_n = wl_b3 + c3;  // (scalars: the pair functions need every vector register)
+    } else {
       const int l = threadIdx.x & 63;
       int inc = (l < PPB) ? item_cnt[lst][l] : 0;
       // ... and (pooled rows) of the rows every nucleotide takes from the result pool: its bonded slots, then its two lists
@@ -846,7 +887,7 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
     // evaluated or folded, the launch is marked as not counting and the host goes on with the big instantiation
     const bool pool_over = kPooled && row_base[kPooled ? pw : 0][PPB] > kPool;
     if (pool_over && threadIdx.x == 0) atomicMax(flags + 3, k_index + 1);
-    const int n_list = pool_over ? 0 : item_pre[pw][PPB];
+    const int n_list = kWaveLists ? wl_n : (pool_over ? 0 : item_pre[kWaveLists ? 0 : pw][kWaveLists ? 0 : PPB]);
     const int half = (n_list + 1) >> 1;
     const int q_lo = wave == 2 ? half : 0;                      // this wavefront's slice [q_lo, q_hi) of the list
     const int q_hi = wave == 1 ? half : n_list;
@@ -866,14 +907,23 @@ __global__ __launch_bounds__(kMdBlock, (md_blocks_per_cu<R, SAVE, ITEMS, DENSE, 
       } else {
         const int q = q_lo + sweep * 64 + (threadIdx.x & 63);
         active = q < q_hi;
+        int k;
+        if constexpr (kWaveLists) {
+          const int src = (q >= wl_b1) + (q >= wl_b2) + (q >= wl_b3);  // the wavefront that appended item q
+          const int at = q - (q >= wl_b3 ? wl_b3 : q >= wl_b2 ? wl_b2 : q >= wl_b1 ? wl_b1 : 0);
+          const int2 it = wave_items[lst][src][at & (kWaveCap - 1)];  // (a lane past the end reads a slot nobody uses)
+          p = it.y & (PPB - 1), k = it.y >> 8;  // (masked: what a lane past the end read is not an owner)
+          sl = active ? it.x : -1;
+        } else {
         int lo = 0, hi = PPB;  // owner: largest p with item_pre[pw][p] <= q
         while (hi - lo > 1) {
           const int mid = (lo + hi) >> 1;
           if (item_pre[pw][mid] <= q) lo = mid; else hi = mid;
         }
         p = lo;
-        const int k = q - item_pre[pw][lo];
+        k = q - item_pre[pw][lo];
         sl = active ? items[lst][p][k] : -1;  // for these waves sl carries the row entry itself
+        }
         // result row: the bonded slots, then the nucleotide's H-bond, cross-stacking and coaxial items
         idx = n_bonded_rows + k + (lst >= 1 ? item_cnt[0][p] : 0);
       }
