@@ -1054,6 +1054,40 @@ int mythos_mbar_binned_sum(mythos_mbar_t* mbar, int n_bins, const int64_t* seg_s
 int mythos_mbar_gram(mythos_mbar_t* mbar, const double* f, double* gram, double* colsum, mythos_stream_t stream);
 int mythos_mbar_segment_moments(mythos_mbar_t* mbar, const double* f, int n_seg, const int64_t* seg_start, const int64_t* order,
                                 const double* v, double* out, mythos_stream_t stream);
+/* The block bootstrap's weighted sums.  Replicate b = 0 ... n_boot - 1 weights frame n by the integer multiplicity
+ * mult[b][n] (dev uint16[n_boot][N]) and is delta[b][k] = f_bk - f_hat[k] away from the solved f_hat (dev double[K],
+ * dev double[n_boot][K]).  With t_jn = N_j W_nj at f_hat and D_bn = sum_j t_jn exp(delta_bj), the replicate's window weights are
+ * W_bnk = W_nk exp(delta_bk) / D_bn and its frame weights exp(-L_n) / D_bn: the exponentials of a frame are formed once
+ * for a tile of 32 replicates, W and D are never stored.  Both queue the L-pass at f_hat first, work for either source, do not
+ * synchronise, and return the same bits call after call.
+ * mythos_mbar_boot_colsums: out_s dev double[n_boot][K], s_bk = sum_n mult[b][n] W_bnk (1 at a replicate's solution).
+ * mythos_mbar_boot_binned: out dev double[n_boot][n_seg][max(n_cols, 1)] = sum over the frames n of a segment of
+ * mult[b][n] v[n][e] exp(-L_n - shift) / D_bn; v dev double[N][n_cols], or n_cols = 0 for 1; order and seg_start as for
+ * mythos_mbar_segment_moments (order NULL: one segment over all frames).
+ * Refused by name: n_boot < 1 or > 65 536, n_cols > 8, a non-finite shift, and K (3 P + 65) + 1 376 > 8 192 doubles (the
+ * table, 32 rows of exp(delta) and a strip of 32 frames share 64 KB of LDS: about 100 windows of one coordinate). */
+int mythos_mbar_boot_colsums(mythos_mbar_t* mbar, const double* f_hat, int n_boot, const double* delta, const uint16_t* mult,
+                             double* out_s, mythos_stream_t stream);
+int mythos_mbar_boot_binned(mythos_mbar_t* mbar, const double* f_hat, int n_boot, const double* delta, const uint16_t* mult, int n_seg,
+                            const int64_t* seg_start, const int64_t* order, int n_cols, const double* v, double shift, double* out,
+                            mythos_stream_t stream);
+
+/* ---- time series: autocorrelation functions for the statistical inefficiency (csrc/timeseries.hip) --------
+ * K series are the row segments offsets[k] ... offsets[k + 1] - 1 of x, dev double[n_rows][n_cols], time-ordered; every
+ * column is a series of its own, T its length.  offsets is given twice, host int64[K + 1] (checked) and dev int64[K + 1].
+ *     mu = mean x, v = mean (x - mu)^2, C(t) = sum_{i < T - t} (x_i - mu)(x_{i+t} - mu) / ((T - t) v)
+ * mythos_timeseries_moments: mean and var, dev double[K][n_cols].
+ * mythos_timeseries_autocorr: out dev double[K][n_cols][n_lags], out[k][e][j] = C(t0 + j); 0 where t0 + j >= T or v = 0.
+ * Fixed summation order, no atomics: the same bits call after call.  Neither synchronises.
+ * Refused by name (INVALID_ARGUMENT): n_cols < 1, offsets that do not increase from 0 to n_rows, n_lags < 1 or > 65 536.
+ * mythos_timeseries_check: those checks alone, plus - where x (HOST double[n_rows][n_cols]) is given - non-finite values.
+ * Touches no device. */
+int mythos_timeseries_check(int64_t n_rows, int n_cols, int n_series, const int64_t* offsets, const double* x);
+int mythos_timeseries_moments(const double* x, int64_t n_rows, int n_cols, int n_series, const int64_t* offsets,
+                              const int64_t* offsets_dev, double* mean, double* var, int device, mythos_stream_t stream);
+int mythos_timeseries_autocorr(const double* x, int64_t n_rows, int n_cols, int n_series, const int64_t* offsets,
+                               const int64_t* offsets_dev, const double* mean, const double* var, int64_t t0, int n_lags,
+                               double* out, int device, mythos_stream_t stream);
 
 #ifdef __cplusplus
 }

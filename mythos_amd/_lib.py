@@ -172,6 +172,11 @@ _SIGS = {
     "mythos_mbar_binned_sum": (C.c_int, [V, C.c_int, V, V, V, V, C.c_double, V, V]),
     "mythos_mbar_gram": (C.c_int, [V, V, V, V, V]),
     "mythos_mbar_segment_moments": (C.c_int, [V, V, C.c_int, V, V, V, V, V]),
+    "mythos_mbar_boot_colsums": (C.c_int, [V, V, C.c_int, V, V, V, V]),
+    "mythos_mbar_boot_binned": (C.c_int, [V, V, C.c_int, V, V, C.c_int, V, V, C.c_int, V, C.c_double, V, V]),
+    "mythos_timeseries_check": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), c_double_p]),
+    "mythos_timeseries_moments": (C.c_int, [V, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), V, V, V, C.c_int, V]),
+    "mythos_timeseries_autocorr": (C.c_int, [V, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), V, V, V, C.c_int64, C.c_int, V, C.c_int, V]),
 }
 
 

@@ -40,6 +40,20 @@
 // segment; the rounds of a segment are dealt to gridDim.y workgroups (as many as keep segments x splits <= 1024: one segment
 // over all frames - the column sums a Newton step needs at every candidate - is not left to one workgroup), whose partials
 // mbar_segment_finish_kernel adds in index order.  The split is a function of N and the number of segments alone.
+//
+// The block bootstrap's weighted sums (mythos_mbar_boot_colsums, mythos_mbar_boot_binned).  Replicate b weights frame n by an
+// integer multiplicity m_bn and solves sum_n m_bn W_bnk = 1; about the solved f^ with delta_b = f_b - f^ and the
+// responsibilities t^_jn = N_j exp(f^_j - b_j(n) - L^_n) at f^ (sum_j t^_jn = 1),
+//     D_bn = sum_j t^_jn e^{delta_bj}       W_bnk = t^_kn e^{delta_bk} / (N_k D_bn)       e^{lw_bn} = e^{-L^_n} / D_bn
+// mbar_boot_kernel<SRC, MODE>: a workgroup of 256 takes a tile of 32 replicates and walks its frames 32 at a time.  Per step
+// it forms the 32 x K strip of t^ in LDS - the step's only exponentials, shared by the tile's replicates: K / 32 per frame
+// and replicate -, then D of its 32 x 32 (replicate, frame) pairs, four per thread over one read of the strip, a dot
+// product of K fmas in window order against the tile's e^{delta} rows in LDS, and q_bn = m_bn / D_bn into LDS.  MODE 0 (the
+// column sums): thread (window k of a tile of 64, eight replicates) adds q_bn t^_kn of the step's frames into eight registers
+// by fma in frame order; the k tiles and the replicate tiles are blockIdx.z.  MODE 1 (the binned sums): thread (replicate,
+// column e) adds q_bn e^{-L^_n - shift} v_ne.  Frames are dealt in rounds of 1 024 to gridDim.y workgroups as in the segment
+// kernel, whose partials the finish kernels add in index order (and scale by e^{delta_bk} / N_k).  Plain fma, no MFMA: see
+// DESIGN.  W, D and the bias matrix are never stored; no atomics, no per-thread array indexed at run time.
 #include <cmath>
 #include <memory>
 #include <vector>
@@ -60,6 +74,8 @@ struct mythos_mbar {
   mythos::DeviceBuf<double> d_partial;  // [K][n_blocks]
   mythos::DeviceBuf<double> d_gram_partial;  // [frame blocks][tile pairs][64][64]: allocated by the first mythos_mbar_gram
   mythos::DeviceBuf<double> d_seg_partial;   // [segments][splits][K]: grown by mythos_mbar_segment_moments where splits > 1
+  mythos::DeviceBuf<double> d_boot_exp;      // [B][K] e^{delta}: grown by the bootstrap entry points
+  mythos::DeviceBuf<double> d_boot_partial;  // [splits][B][K] or [B][segments][splits][E]
   ~mythos_mbar() { (void)hipSetDevice(device); }  // the members free themselves, on the handle's device
 };
 
@@ -382,6 +398,155 @@ __global__ __launch_bounds__(kMbarBlock) void mbar_segment_finish_kernel(int K, 
   }
 }
 
+// ---- the block bootstrap's weighted sums ------------------------------------------------------------------------------
+constexpr int kBootTile = 32;     // replicates per workgroup
+constexpr int kBootFrames = 32;   // frames per step
+constexpr int kBootCols = 64;     // windows per workgroup of the column sums
+constexpr int kBootMaxE = 8;      // columns of v per call of the binned sums: kBootTile * kBootMaxE threads own one sum each
+constexpr int kBootMaxB = 1 << 16;
+constexpr int boot_stride(int K) { return K | 1; }  // odd: the strip's rows start in different banks
+// doubles of LDS: table, ln N + f^, e^{delta} rows, strip, q, e^{-L - shift}, v, and the step's frame indices
+constexpr size_t mbar_boot_lds_doubles(int K, int P, int src) {
+  return (size_t)K * ((src == 0 ? 3 * (size_t)P : 0) + 1) + (size_t)kBootTile * K + (size_t)kBootFrames * boot_stride(K) +
+         (size_t)kBootTile * kBootFrames + kBootFrames + (size_t)kBootFrames * kBootMaxE + kBootFrames;
+}
+
+__global__ __launch_bounds__(kMbarBlock) void mbar_boot_exp_kernel(long long count, const double* __restrict__ delta, double* __restrict__ ed) {
+  const long long i = (long long)blockIdx.x * kMbarBlock + threadIdx.x;
+  if (i < count) ed[i] = exp(delta[i]);
+}
+
+// grid (segments, splits, tiles).  MODE 0: dst [split][B][K], tiles = replicate tiles x window tiles, one segment;
+// MODE 1: dst [B][segments][splits][E], tiles = replicate tiles.
+template <int SRC, int MODE>
+__global__ __launch_bounds__(kMbarBlock) void mbar_boot_kernel(int K, int P, long long N, int B, int E, const long long* __restrict__ seg,
+                                                                const long long* __restrict__ order, const double* __restrict__ v,
+                                                                double shift, const double* __restrict__ xi,
+                                                                const double* __restrict__ table, const double* __restrict__ u,
+                                                                const double* __restrict__ ln_nk, const double* __restrict__ f,
+                                                                const double* __restrict__ L, const double* __restrict__ ed,
+                                                                const unsigned short* __restrict__ mult, double* __restrict__ dst) {
+  extern __shared__ __attribute__((aligned(16))) double mbar_lds[];
+  const int row = SRC == 0 ? 3 * P : 0, stride = boot_stride(K);
+  double* __restrict__ s_tab = mbar_lds;                               // [K][P][3]
+  double* __restrict__ s_a = s_tab + (size_t)K * row;                  // [K] ln N_k + f^_k
+  double* __restrict__ s_e = s_a + K;                                  // [kBootTile][K] e^{delta}
+  double* __restrict__ s_w = s_e + (size_t)kBootTile * K;              // [kBootFrames][stride] t^
+  double* __restrict__ s_q = s_w + (size_t)kBootFrames * stride;       // [kBootTile][kBootFrames] m / D
+  double* __restrict__ s_x = s_q + kBootTile * kBootFrames;            // [kBootFrames] e^{-L - shift}
+  double* __restrict__ s_v = s_x + kBootFrames;                        // [kBootFrames][E]
+  long long* __restrict__ s_n = (long long*)(s_v + kBootFrames * kBootMaxE);  // [kBootFrames] the frames, -1 for none
+  const int tid = (int)threadIdx.x;
+  const int k_tiles = (K + kBootCols - 1) / kBootCols;
+  const int b0 = kBootTile * (MODE == 0 ? (int)blockIdx.z / k_tiles : (int)blockIdx.z);
+  const int k0 = MODE == 0 ? kBootCols * ((int)blockIdx.z % k_tiles) : 0;
+  if constexpr (SRC == 0)
+    for (int i = tid; i < K * row; i += kMbarBlock) s_tab[i] = table[i];
+  for (int k = tid; k < K; k += kMbarBlock) s_a[k] = ln_nk[k] + f[k];
+  for (int i = tid; i < kBootTile * K; i += kMbarBlock) s_e[i] = b0 + i / K < B ? ed[(size_t)b0 * K + i] : 0.0;
+  long long lo = 0, hi = N;  // no order: every frame, in natural order
+  if (order) lo = min(max(seg[blockIdx.x], 0ll), N), hi = min(max(seg[blockIdx.x + 1], lo), N);
+  double acc[8] = {};  // MODE 0: replicates (tid >> 6) + 4 i of window k0 + (tid & 63); MODE 1: acc[0] of (replicate, column)
+  for (long long at = lo + (long long)blockIdx.y * kMbarChunk; at < hi; at += (long long)gridDim.y * kMbarChunk) {
+    const long long end = min(at + kMbarChunk, hi);
+    for (long long base = at; base < end; base += kBootFrames) {
+      if (tid < kBootFrames) {
+        const long long i = base + tid;
+        const long long m = i < end ? (order ? order[i] : i) : -1;
+        const bool own = m >= 0 && m < N;  // (not a permutation: the entry is skipped, memory stays in bounds)
+        s_n[tid] = own ? m : -1;
+        if constexpr (MODE == 1) s_x[tid] = own ? exp(-L[m] - shift) : 0.0;
+      }
+      __syncthreads();
+      for (int e = tid; e < kBootFrames * K; e += kMbarBlock) {
+        const int fr = e & (kBootFrames - 1), c = e / kBootFrames;
+        const long long n = s_n[fr];
+        double w = 0.0;  // a slot without a frame: a zero that adds nothing
+        if (n >= 0) {
+          const double x0 = SRC == 0 ? xi[(size_t)n * P] : 0.0;
+          w = exp(s_a[c] - mbar_bias<SRC>(s_tab + (size_t)c * row, xi, u, P, N, c, n, x0) - L[n]);
+        }
+        s_w[fr * stride + c] = w;
+      }
+      if constexpr (MODE == 1)
+        for (int i = tid; i < kBootFrames * E; i += kMbarBlock) {
+          const long long n = s_n[i / E];
+          s_v[i] = n >= 0 ? (v ? v[(size_t)n * E + i % E] : 1.0) : 0.0;
+        }
+      __syncthreads();
+      {
+        const int fr = tid & (kBootFrames - 1), r0 = tid / kBootFrames;  // replicates r0 + 8 i of the tile
+        const double* __restrict__ w = s_w + fr * stride;
+        const double* __restrict__ e = s_e + (size_t)r0 * K;
+        const size_t step = (size_t)(kMbarBlock / kBootFrames) * K;
+        double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
+        for (int j = 0; j < K; ++j) {
+          const double t = w[j];
+          d0 = fma(t, e[j], d0), d1 = fma(t, e[step + j], d1), d2 = fma(t, e[2 * step + j], d2), d3 = fma(t, e[3 * step + j], d3);
+        }
+        const double d[4] = {d0, d1, d2, d3};
+        const long long n = s_n[fr];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = r0 + (kMbarBlock / kBootFrames) * i;
+          const unsigned m = (n >= 0 && b0 + r < B) ? mult[(size_t)(b0 + r) * (size_t)N + (size_t)n] : 0u;
+          double q = m ? (double)m / d[i] : 0.0;
+          if constexpr (MODE == 1) q *= s_x[fr];
+          s_q[r * kBootFrames + fr] = q;
+        }
+      }
+      __syncthreads();
+      if constexpr (MODE == 0) {
+        const double* __restrict__ w = s_w + min(k0 + (tid & (kBootCols - 1)), K - 1);  // a window past K: computed, not written
+        const double* __restrict__ q = s_q + (tid / kBootCols) * kBootFrames;
+        for (int fr = 0; fr < kBootFrames; ++fr) {
+          const double t = w[fr * stride];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) acc[i] = fma(q[(kMbarBlock / kBootCols) * kBootFrames * i + fr], t, acc[i]);
+        }
+      } else if (tid < kBootTile * E) {
+        const double* __restrict__ q = s_q + (tid / E) * kBootFrames;
+        const double* __restrict__ c = s_v + tid % E;
+        for (int fr = 0; fr < kBootFrames; ++fr) acc[0] = fma(q[fr], c[fr * E], acc[0]);
+      }
+      // (the next step writes s_n and s_x, which nobody reads behind the last barrier, and the rest behind its own first barrier)
+    }
+  }
+  if constexpr (MODE == 0) {
+    const int k = k0 + (tid & (kBootCols - 1));
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int b = b0 + tid / kBootCols + (kMbarBlock / kBootCols) * i;
+      if (k < K && b < B) dst[((size_t)blockIdx.y * B + b) * K + k] = acc[i];
+    }
+  } else if (tid < kBootTile * E && b0 + tid / E < B) {
+    dst[(((size_t)(b0 + tid / E) * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y) * E + tid % E] = acc[0];
+  }
+}
+
+// s_bk = e^{delta_bk} / N_k times the splits' partials in index order; a thread per (b, k)
+__global__ __launch_bounds__(kMbarBlock) void mbar_boot_colsums_finish_kernel(long long count, int K, int splits,
+                                                                               const double* __restrict__ partial,
+                                                                               const double* __restrict__ delta,
+                                                                               const double* __restrict__ ln_nk, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * kMbarBlock + threadIdx.x;
+  if (i >= count) return;
+  double t = 0.0;
+  for (int s = 0; s < splits; ++s) t += partial[(size_t)s * count + i];
+  out[i] = t * exp(delta[i] - ln_nk[i % K]);
+}
+
+// out[i] = the splits' partials of entry i = (b, segment, e) in index order, E values each
+__global__ __launch_bounds__(kMbarBlock) void mbar_boot_binned_finish_kernel(long long count, int E, int splits,
+                                                                              const double* __restrict__ partial, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * kMbarBlock + threadIdx.x;
+  if (i >= count) return;
+  const long long cell = i / E;
+  double t = 0.0;
+  for (int s = 0; s < splits; ++s) t += partial[((size_t)cell * splits + s) * E + i % E];
+  out[i] = t;
+}
+
 static int mbar_ready(const mythos_mbar* h, const char* who) {
   if (h->src < 0) {
     set_error(std::string(who) + ": neither windows nor a matrix are set");
@@ -576,6 +741,74 @@ int mythos_mbar_segment_moments(mythos_mbar_t* h, const double* f, int n_seg, co
   hipStream_t st = (hipStream_t)stream;
   mbar_launch(h, f, nullptr, nullptr, st);  // L_n at this f
   if (int rc = mbar_segment_launch(h, f, n_seg, seg_start, order, v, out, st)) return rc;
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return MYTHOS_OK;
+}
+
+// What both bootstrap entry points check and queue first: L^ at f^ and e^{delta}.
+static int mbar_boot_begin(mythos_mbar* h, const char* who, const double* f_hat, int B, const double* delta, const uint16_t* mult,
+                           const void* out, hipStream_t st) {
+  if (!h || !f_hat || !delta || !mult || !out || B < 1 || B > kBootMaxB) {
+    set_error(std::string(who) + ": invalid argument (1 <= B <= " + std::to_string(kBootMaxB) + " replicates)");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  if (int rc = mbar_ready(h, who)) return rc;
+  if (mbar_boot_lds_doubles(h->K, h->P, h->src) > (size_t)kMbarLdsDoubles) {
+    set_error(std::string(who) + ": the window table, " + std::to_string(kBootTile) + " rows of e^delta and a strip of " +
+              std::to_string(kBootFrames) + " frames (" + std::to_string(mbar_boot_lds_doubles(h->K, h->P, h->src)) +
+              " doubles) do not fit 64 KB of LDS");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  MYTHOS_HIP_TRY(hipSetDevice(h->device));
+  const long long count = (long long)B * h->K;
+  if (int rc = h->d_boot_exp.grow((size_t)count)) return rc;
+  mbar_launch(h, f_hat, nullptr, nullptr, st);  // L_n at f^
+  hipLaunchKernelGGL(mbar_boot_exp_kernel, dim3((unsigned)((count + kMbarBlock - 1) / kMbarBlock)), dim3(kMbarBlock), 0, st, count, delta,
+                     h->d_boot_exp.get());
+  return MYTHOS_OK;
+}
+
+int mythos_mbar_boot_colsums(mythos_mbar_t* h, const double* f_hat, int n_boot, const double* delta, const uint16_t* mult, double* out_s,
+                             mythos_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mbar_boot_begin(h, "mythos_mbar_boot_colsums", f_hat, n_boot, delta, mult, out_s, st)) return rc;
+  const int tiles = ((n_boot + kBootTile - 1) / kBootTile) * ((h->K + kBootCols - 1) / kBootCols);
+  const int splits = std::min(h->n_chunks, std::max(1, kSegMaxSplits / tiles));
+  const long long count = (long long)n_boot * h->K;
+  if (int rc = h->d_boot_partial.grow((size_t)splits * count)) return rc;
+  auto kernel = h->src == 0 ? mbar_boot_kernel<0, 0> : mbar_boot_kernel<1, 0>;
+  hipLaunchKernelGGL(kernel, dim3(1, splits, tiles), dim3(kMbarBlock), sizeof(double) * mbar_boot_lds_doubles(h->K, h->P, h->src), st, h->K,
+                     h->P, (long long)h->N, n_boot, 0, (const long long*)nullptr, (const long long*)nullptr, (const double*)nullptr, 0.0,
+                     h->xi, h->d_table.get(), h->u, h->d_ln_nk.get(), f_hat, h->d_L.get(), h->d_boot_exp.get(), mult,
+                     h->d_boot_partial.get());
+  hipLaunchKernelGGL(mbar_boot_colsums_finish_kernel, dim3((unsigned)((count + kMbarBlock - 1) / kMbarBlock)), dim3(kMbarBlock), 0, st, count,
+                     h->K, splits, h->d_boot_partial.get(), delta, h->d_ln_nk.get(), out_s);
+  MYTHOS_HIP_TRY(hipGetLastError());
+  return MYTHOS_OK;
+}
+
+int mythos_mbar_boot_binned(mythos_mbar_t* h, const double* f_hat, int n_boot, const double* delta, const uint16_t* mult, int n_seg,
+                            const int64_t* seg_start, const int64_t* order, int n_cols, const double* v, double shift, double* out,
+                            mythos_stream_t stream) {
+  if (n_seg < 1 || n_seg > (1 << 20) || (order && !seg_start) || (!order && n_seg != 1) || n_cols < 0 || n_cols > kBootMaxE ||
+      (n_cols > 0 && !v) || !std::isfinite(shift)) {
+    set_error("mythos_mbar_boot_binned: invalid argument (1 <= n_seg <= 2^20; seg_start with an order, one segment without; 0 <= E <= " +
+              std::to_string(kBootMaxE) + " with v where E > 0; a finite shift)");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mbar_boot_begin(h, "mythos_mbar_boot_binned", f_hat, n_boot, delta, mult, out, st)) return rc;
+  const int E = std::max(n_cols, 1), tiles = (n_boot + kBootTile - 1) / kBootTile;
+  const int splits = (int)std::min<long long>(h->n_chunks, std::max<long long>(1, kSegMaxSplits / ((long long)n_seg * tiles)));
+  const long long count = (long long)n_boot * n_seg * E;
+  if (int rc = h->d_boot_partial.grow((size_t)count * splits)) return rc;
+  auto kernel = h->src == 0 ? mbar_boot_kernel<0, 1> : mbar_boot_kernel<1, 1>;
+  hipLaunchKernelGGL(kernel, dim3(n_seg, splits, tiles), dim3(kMbarBlock), sizeof(double) * mbar_boot_lds_doubles(h->K, h->P, h->src), st,
+                     h->K, h->P, (long long)h->N, n_boot, E, (const long long*)seg_start, (const long long*)order, n_cols > 0 ? v : nullptr,
+                     shift, h->xi, h->d_table.get(), h->u, h->d_ln_nk.get(), f_hat, h->d_L.get(), h->d_boot_exp.get(), mult,
+                     h->d_boot_partial.get());
+  hipLaunchKernelGGL(mbar_boot_binned_finish_kernel, dim3((unsigned)((count + kMbarBlock - 1) / kMbarBlock)), dim3(kMbarBlock), 0, st, count,
+                     E, splits, h->d_boot_partial.get(), out);
   MYTHOS_HIP_TRY(hipGetLastError());
   return MYTHOS_OK;
 }

@@ -11,7 +11,8 @@ free-energy profile along a pull coordinate."""
 from mythos_amd.observables.base import ObservableSet, get_duplex_quartets
 from mythos_amd.observables.bond_distances import BondDistances, BondDistancesMapped
 from mythos_amd.observables.diameter import Diameter
-from mythos_amd.observables.mbar import MbarNotConverged, MbarResult, UmbrellaPMF, mbar, mbar_umbrella
+from mythos_amd.observables.mbar import (BlockResample, MbarNotConverged, MbarResult, UmbrellaPMF, auto_block, block_resample, mbar, mbar_umbrella,
+                                         statistical_inefficiency, subsample_correlated)
 from mythos_amd.observables.melting_temp import (TARGETS, MeltingTemp, compute_curve_width, compute_finf, extrapolated_ratios,
                                                  find_melting_temp, interp1d)
 from mythos_amd.observables.membrane import AreaPerLipid, MembraneThickness
@@ -30,7 +31,8 @@ from mythos_amd.observables.triplet_angles import TripletAngles, TripletAnglesMa
 from mythos_amd.observables.wasserstein import WassersteinDistance, WassersteinDistanceMapped, wasserstein_1d
 from mythos_amd.observables.wlc import calculate_extension, coth, fit_wlc, loss
 
-__all__ = ["MbarNotConverged", "MbarResult", "UmbrellaPMF", "mbar", "mbar_umbrella", "AreaPerLipid", "BondDistances", "BondDistancesMapped", "Diameter", "ExtensionZ", "MeltingTemp", "MembraneMeltingTemp", "MembraneThickness",
+__all__ = ["BlockResample", "MbarNotConverged", "MbarResult", "UmbrellaPMF", "auto_block", "block_resample", "mbar", "mbar_umbrella",
+           "statistical_inefficiency", "subsample_correlated", "AreaPerLipid", "BondDistances", "BondDistancesMapped", "Diameter", "ExtensionZ", "MeltingTemp", "MembraneMeltingTemp", "MembraneThickness",
            "ObservableSet", "OrderParameters", "PersistenceLength", "PitchAngle", "PropellerTwist", "RMSE", "RadialDistribution", "RadialDistributionPair", "Rise", "TripletAngles", "TripletAnglesMapped",
            "TwistXY", "WassersteinDistance", "WassersteinDistanceMapped", "apl_residual", "calculate_apl", "calculate_extension",
            "compute_membrane_tm", "compute_pitch", "coth", "fit_apl_sigmoid", "fit_wlc", "get_duplex_quartets", "get_initial_guess",
