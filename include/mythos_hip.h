@@ -1002,6 +1002,42 @@ int mythos_rdf_n_pairs(const mythos_rdf_t* rdf, int64_t* n_pairs);
 int mythos_rdf_eval(mythos_rdf_t* rdf, const void* pos, const void* box, int dtype, int n_frames, int64_t* counts,
                     int32_t* flags, mythos_stream_t stream);
 
+/* ---- lateral pressure profile: the diagonal virial of stored MARTINI frames, resolved in slabs along z --------
+ * Every frame of a trajectory in one call, on the tables, exclusions, incidence lists and charges the system handle holds
+ * (csrc/stress_profile.hip; definitions in DESIGN section 3.5q).  The reference has no such observable.
+ * Bead i of a frame gets a diagonal virial share w_i, the decomposition of mythos_martini_langevin_pressure term for term:
+ * an LJ pair, a bond, a reaction-field pair and an excluded reaction-field pair give -1/2 (dV/dr) / r dx_d^2 to either bead,
+ * an angle -u_d dU/dx_id to its first and -v_d dU/dx_kd to its last bead (nothing to its centre), over minimum-image
+ * vectors; sum_i w_i is that entry point's W.  The share sits at the bead's own z (a Harasima-type contour): the lateral
+ * components are what the profile is for, P_zz(z) of this contour is not constant in z and only its sum over the slabs is
+ * physical.
+ *   pos, box   dev real[n_frames][n][3], dev real[n_frames][3] of the SYSTEM's precision; every edge at least 2 r_cut
+ *   n_bins     1 ... 1024 slabs of thickness lz / n_bins of the frame's own box
+ *   center     host int32[n_center] beads, or n_center = 0.  Without: slab = min(n_bins - 1, floor(u n_bins)) with
+ *              u = z / lz - floor(z / lz), fixed to the box.  With: mid = the mean stored z of those beads (the midpoint of
+ *              mythos_membrane_eval, and as there wrong for a bilayer that lies across the z boundary),
+ *              u = (z - mid) / lz - floor((z - mid) / lz + 1/2), slab = floor((u + 1/2) n_bins) clamped to [0, n_bins - 1]:
+ *              slab n_bins / 2 starts at the midplane.  In double from positions promoted on load: an fp32 frame lands in
+ *              the slabs of the fp64 call on the same values.
+ *   out        dev double[n_frames][n_bins][MYTHOS_STRESS_ROW]: bead count, W_x, W_y, W_z (kJ/mol) of the slab; with by_term
+ *              [MYTHOS_STRESS_ROW_BY_TERM]: count, then W_xyz of lj, bond, angle, coulomb (zero without charges).  The
+ *              un-split W is ((lj + bond) + angle) + coulomb of those columns, bitwise.
+ * The local pressure is P_d = (count kT + W_d) n_bins / (lx ly lz) x mythos_martini_bar_per_kj_mol_nm3() bar: stored frames
+ * hold no velocities, the kinetic part is its equipartition value.  The caller forms it.
+ * Sums inside a bead's tile of partners in the system's precision, everything behind in double, in a fixed order, no
+ * atomics: a frame's row has the same bits alone, in any batch and call after call.  Does not synchronise, except where a
+ * new centre list replaces the one of the call before.
+ * Refused by name (INVALID_ARGUMENT): n_bins < 1 or > 1024, a centre index outside [0, n).
+ * mythos_martini_stress_profile_check: those checks alone for n beads, plus - where boxes (HOST double[n_frames][3]) is given -
+ * a box edge that is not positive and finite, or below 2 r_cut, naming the frame.  Touches no device. */
+#define MYTHOS_STRESS_ROW 4
+#define MYTHOS_STRESS_ROW_BY_TERM 13
+double mythos_martini_bar_per_kj_mol_nm3(void);
+int mythos_martini_stress_profile_check(int n, double r_cut, int n_frames, const double* boxes, int n_center, const int32_t* center,
+                                        int n_bins);
+int mythos_martini_stress_profile(mythos_martini_t* martini, const void* pos, const void* box, int n_frames, int n_center,
+                                  const int32_t* center, int n_bins, int by_term, double* out, mythos_stream_t stream);
+
 /* ---- MBAR: unbiasing weights of frames pooled from biased windows, and the sums behind a PMF --------
  * The binless multistate estimator (csrc/mbar.hip; definitions in DESIGN section 3.5o).  The reference has none.  N frames
  * are pooled from K windows, window k contributed n_k[k] >= 1 of them (sum = N); b_k(n) is the reduced bias of window k at

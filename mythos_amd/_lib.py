@@ -162,6 +162,9 @@ _SIGS = {
     "mythos_rdf_destroy": (None, [V]),
     "mythos_rdf_n_pairs": (C.c_int, [V, C.POINTER(C.c_int64)]),
     "mythos_rdf_eval": (C.c_int, [V, V, V, C.c_int, C.c_int, V, V, V]),
+    "mythos_martini_bar_per_kj_mol_nm3": (C.c_double, []),
+    "mythos_martini_stress_profile_check": (C.c_int, [C.c_int, C.c_double, C.c_int, c_double_p, C.c_int, c_int_p, C.c_int]),
+    "mythos_martini_stress_profile": (C.c_int, [V, V, V, C.c_int, C.c_int, c_int_p, C.c_int, C.c_int, V, V]),
     "mythos_mbar_check": (C.c_int, [C.c_int, C.c_int64, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int64), c_double_p, C.c_int, c_double_p]),
     "mythos_mbar_create": (V, [C.c_int64, C.c_int, C.c_int]),
     "mythos_mbar_destroy": (None, [V]),
@@ -208,6 +211,8 @@ DECLARED_SYMBOLS = tuple(_SIGS)
 
 
 MEMBRANE_ROW = 7  # MYTHOS_MEMBRANE_ROW of include/mythos_hip.h: doubles per frame of mythos_membrane_eval
+STRESS_ROW, STRESS_ROW_BY_TERM = 4, 13  # MYTHOS_STRESS_ROW, MYTHOS_STRESS_ROW_BY_TERM: doubles per slab of mythos_martini_stress_profile
+STRESS_MAX_BINS = 1024  # kStressMaxBins of csrc/stress_profile_checks.h
 
 
 def last_error() -> str:

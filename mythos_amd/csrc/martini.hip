@@ -10,7 +10,7 @@
 // fixed-order reduction (no atomics, reproducible).  Bonded pairs are excluded through a short
 // per-bead list that is consulted only inside the cut-off.  Every pair is visited from both ends
 // (energy weight 1/2).  Bonds and angles are gathered per bead from incidence lists.  The terms are martini_terms.h's;
-// the energy and the LJ parameter-gradient kernel run the same sweep (lj_tile_sweep) with their own per-pair work.
+// the energy and the LJ parameter-gradient kernel run the same sweep (lj_tile_sweep, martini_internal.h) with their own per-pair work.
 // Reaction-field Coulomb of stored frames (mythos_martini_set_charges / mythos_martini_coulomb; the reference evaluates no
 // Coulomb term, its GROMACS runs do) is a third kernel on the same sweep, with its own term for the excluded pairs.
 // Roofline: the sweep is ALU/LDS bound, not HBM bound: 16 B per bead per tile pass from L2/HBM versus
@@ -23,58 +23,6 @@
 #include "martini_internal.h"
 
 namespace mythos {
-
-// The sweep of one thread over its share of the partner tiles (tile js, js + n_js, ...): stages each tile in LDS
-// (s_x: 3 kLjBlock reals and kLjBlock ints behind the caller's tables; the first barrier also publishes those), wraps,
-// tests the cut-off, and calls pair(tp, j, excluded, dx, dy, dz, r2) for every partner j != i inside it - tp indexes the
-// type-pair tables, excluded: j is on the bead's exclusion list (LJ drops those, reaction-field Coulomb has a term for
-// them) - and tile_done() behind each tile.
-template <typename R, typename Pair, typename TileDone>
-__device__ __forceinline__ void lj_tile_sweep(int n, const R* __restrict__ p, const R* __restrict__ box,
-                                              const int* __restrict__ types, const int* __restrict__ excl, R rc2,
-                                              int n_types, int n_tiles, R* s_x, Pair pair, TileDone tile_done) {
-  R *s_y = s_x + kLjBlock, *s_z = s_y + kLjBlock;
-  int* s_t = reinterpret_cast<int*>(s_z + kLjBlock);
-  const int js = blockIdx.y, n_js = gridDim.y;
-  const int i = blockIdx.x * kLjBlock + threadIdx.x;
-  const R lx = box[0], ly = box[1], lz = box[2];
-  const R ilx = R(1) / lx, ily = R(1) / ly, ilz = R(1) / lz;
-  R xi = 0, yi = 0, zi = 0;
-  int ti = 0;
-  int ex[kMaxExcl];
-#pragma unroll
-  for (int k = 0; k < kMaxExcl; ++k) ex[k] = -1;
-  if (i < n) {
-    xi = p[3 * i], yi = p[3 * i + 1], zi = p[3 * i + 2];
-    ti = types[i] * n_types;
-#pragma unroll
-    for (int k = 0; k < kMaxExcl; ++k) ex[k] = excl[(size_t)i * kMaxExcl + k];
-  }
-  for (int tile = js; tile < n_tiles; tile += n_js) {
-    __syncthreads();
-    const int j0 = tile * kLjBlock, jl = j0 + threadIdx.x;
-    if (jl < n) {
-      s_x[threadIdx.x] = p[3 * jl], s_y[threadIdx.x] = p[3 * jl + 1], s_z[threadIdx.x] = p[3 * jl + 2];
-      s_t[threadIdx.x] = types[jl];
-    }
-    __syncthreads();
-    const int cnt = min(kLjBlock, n - j0);
-    if (i < n) {
-      for (int k = 0; k < cnt; ++k) {
-        const R dx = wrap(xi - s_x[k], lx, ilx), dy = wrap(yi - s_y[k], ly, ily), dz = wrap(zi - s_z[k], lz, ilz);
-        const R r2 = dx * dx + dy * dy + dz * dz;
-        if (r2 < rc2) {
-          const int j = j0 + k;
-          bool excluded = false;
-#pragma unroll
-          for (int q = 0; q < kMaxExcl; ++q) excluded = excluded || (ex[q] == j);
-          if (j != i) pair(ti + s_t[k], j, excluded, dx, dy, dz, r2);
-        }
-      }
-      tile_done();
-    }
-  }
-}
 
 template <typename R>
 __global__ __launch_bounds__(kLjBlock) void martini_lj_kernel(

@@ -1,4 +1,5 @@
-// Shared by martini.hip (energy path) and martini_md.hip (Langevin MD): limits, constants, the system struct.
+// Shared by martini.hip (energy path), martini_md.hip (Langevin MD) and stress_profile.hip (stress profile of stored
+// frames): limits, constants, the all-pairs tile sweep, the system struct.
 #ifndef MYTHOS_MARTINI_INTERNAL_H
 #define MYTHOS_MARTINI_INTERNAL_H
 
@@ -19,6 +20,7 @@ constexpr int kMaxTypes = 64;
 // .w and look the neighbour's charge up in a table of this size in LDS (martini_md.hip); DMPC in water uses three.
 constexpr int kMaxChargeClasses = 8;
 constexpr double kCoulombF = 138.935458;  // kJ mol^-1 nm e^-2 (GROMACS' ONE_4PI_EPS0)
+constexpr double kBarPerKjMolNm3 = 16.6053907;  // kJ mol^-1 nm^-3 -> bar (martini_npt.inc, mythos_martini_bar_per_kj_mol_nm3)
 
 // Reaction-field constants in the kernels' precision: pref = f / eps_r, V = pref q_i q_j (1/r + k_rf r^2 - c_rf)
 template <typename R>
@@ -32,6 +34,58 @@ struct MartiniConst {
   int n_types;
   int angle_kind;  // 0 = G96 cosine, 1 = harmonic
 };
+
+// The sweep of one thread over its share of the partner tiles (tile js, js + n_js, ...): stages each tile in LDS
+// (s_x: 3 kLjBlock reals and kLjBlock ints behind the caller's tables; the first barrier also publishes those), wraps,
+// tests the cut-off, and calls pair(tp, j, excluded, dx, dy, dz, r2) for every partner j != i inside it - tp indexes the
+// type-pair tables, excluded: j is on the bead's exclusion list (LJ drops those, reaction-field Coulomb has a term for
+// them) - and tile_done() behind each tile.
+template <typename R, typename Pair, typename TileDone>
+__device__ __forceinline__ void lj_tile_sweep(int n, const R* __restrict__ p, const R* __restrict__ box,
+                                              const int* __restrict__ types, const int* __restrict__ excl, R rc2,
+                                              int n_types, int n_tiles, R* s_x, Pair pair, TileDone tile_done) {
+  R *s_y = s_x + kLjBlock, *s_z = s_y + kLjBlock;
+  int* s_t = reinterpret_cast<int*>(s_z + kLjBlock);
+  const int js = blockIdx.y, n_js = gridDim.y;
+  const int i = blockIdx.x * kLjBlock + threadIdx.x;
+  const R lx = box[0], ly = box[1], lz = box[2];
+  const R ilx = R(1) / lx, ily = R(1) / ly, ilz = R(1) / lz;
+  R xi = 0, yi = 0, zi = 0;
+  int ti = 0;
+  int ex[kMaxExcl];
+#pragma unroll
+  for (int k = 0; k < kMaxExcl; ++k) ex[k] = -1;
+  if (i < n) {
+    xi = p[3 * i], yi = p[3 * i + 1], zi = p[3 * i + 2];
+    ti = types[i] * n_types;
+#pragma unroll
+    for (int k = 0; k < kMaxExcl; ++k) ex[k] = excl[(size_t)i * kMaxExcl + k];
+  }
+  for (int tile = js; tile < n_tiles; tile += n_js) {
+    __syncthreads();
+    const int j0 = tile * kLjBlock, jl = j0 + threadIdx.x;
+    if (jl < n) {
+      s_x[threadIdx.x] = p[3 * jl], s_y[threadIdx.x] = p[3 * jl + 1], s_z[threadIdx.x] = p[3 * jl + 2];
+      s_t[threadIdx.x] = types[jl];
+    }
+    __syncthreads();
+    const int cnt = min(kLjBlock, n - j0);
+    if (i < n) {
+      for (int k = 0; k < cnt; ++k) {
+        const R dx = wrap(xi - s_x[k], lx, ilx), dy = wrap(yi - s_y[k], ly, ily), dz = wrap(zi - s_z[k], lz, ilz);
+        const R r2 = dx * dx + dy * dy + dz * dz;
+        if (r2 < rc2) {
+          const int j = j0 + k;
+          bool excluded = false;
+#pragma unroll
+          for (int q = 0; q < kMaxExcl; ++q) excluded = excluded || (ex[q] == j);
+          if (j != i) pair(ti + s_t[k], j, excluded, dx, dy, dz, r2);
+        }
+      }
+      tile_done();
+    }
+  }
+}
 
 }  // namespace mythos
 
@@ -60,6 +114,12 @@ struct mythos_martini {
   }
   mythos::DeviceBytes d_fpart;
   mythos::DeviceBuf<double> d_epart, d_ebpart, d_ljpart;  // d_ljpart: per-workgroup dU/dsigma | dU/deps tables
+  // stress profile of stored frames (stress_profile.hip), allocated at its first call: per-bead virial shares of the sweep
+  // [frames][n_js][n][3 or 6], of bonds and angles [frames][n][6], slab of every bead [frames][n], midpoints [frames], and
+  // the centre selection of the last call with its host copy
+  mythos::DeviceBuf<double> d_sp_part, d_sp_bonded, d_sp_mid;
+  mythos::DeviceBuf<int> d_sp_bin, d_sp_center;
+  std::vector<int> h_sp_center;
   ~mythos_martini() { (void)hipSetDevice(device); }  // the members free themselves, on the system's device
 };
 

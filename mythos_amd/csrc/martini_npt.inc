@@ -21,7 +21,7 @@
 
 namespace mythos {
 
-constexpr double kBarPerKjMolNm3 = 16.6053907;
+// (kBarPerKjMolNm3: martini_internal.h)
 constexpr int kMmVir = 6;    // Kx Ky Kz Wx Wy Wz
 constexpr int kNptRec = 20;  // box[3] mu[3] P[3] K[3] W[3] V ok
 enum { kRecBox = 0, kRecMu = 3, kRecP = 6, kRecK = 9, kRecW = 12, kRecV = 15, kRecOk = 16 };

@@ -588,6 +588,7 @@ class MartiniSystem(_lib.Handle):
         bonds = np.ascontiguousarray(bonds, dtype=np.int32).reshape(-1, 2)
         angles = np.ascontiguousarray(angles, dtype=np.int32).reshape(-1, 3)
         self.n_types, self.n_bonds, self.n_angles = n_types, int(bonds.shape[0]), int(angles.shape[0])
+        self.r_cut = float(r_cut)
         f = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
         bond_k, bond_r0, angle_k, angle_t0 = f(bond_k), f(bond_r0), f(angle_k), f(angle_t0)
         dp = lambda a: a.ctypes.data_as(_lib.c_double_p)  # noqa: E731
@@ -660,6 +661,36 @@ class MartiniSystem(_lib.Handle):
             "martini_energy",
         )
         return (e[0], g[0] if grads else None) if single else (e, g)
+
+    @staticmethod
+    def check_stress_profile(n: int, r_cut: float, boxes, n_bins: int, center_index=None) -> None:
+        """The host-side refusals of ``stress_profile`` alone (mythos_martini_stress_profile_check; no GPU): ``n_bins``
+        outside [1, 1024], a centre index outside [0, n), a box edge (``boxes`` (F, 3) on the host, or None) that is not
+        positive and finite or is below 2 ``r_cut`` - ``ValueError`` naming the offender."""
+        b = None if boxes is None else np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 3))
+        c = np.ascontiguousarray([] if center_index is None else center_index, dtype=np.int32).reshape(-1)
+        _lib.check(_lib.load().mythos_martini_stress_profile_check(
+            int(n), float(r_cut), 0 if b is None else int(b.shape[0]), None if b is None else b.ctypes.data_as(_lib.c_double_p),
+            int(c.size), c.ctypes.data_as(_lib.c_int_p), int(n_bins)), "martini_stress_profile_check")
+
+    def stress_profile(self, pos: torch.Tensor, box: torch.Tensor, n_bins: int, center_index=None, by_term: bool = False,
+                       check_boxes: bool = True) -> torch.Tensor:
+        """Raw rows of the lateral pressure profile (mythos_martini_stress_profile): pos (F, N, 3) or
+        (N, 3), box (F, 3) or (3,) -> (F, n_bins, 4) float64 on the device - bead count, W_x, W_y, W_z (kJ/mol) of every
+        slab along z - or with ``by_term`` (F, n_bins, 13): the count, then W of lj, bond, angle, coulomb.
+        ``center_index``: beads whose mean stored z is the frame's midplane (slab n_bins / 2 starts there); None: slabs
+        fixed to the box.  Reading the boxes for the edge checks is one host synchronisation per call;
+        ``check_boxes=False`` leaves them on the device - for boxes already validated (``check_stress_profile``) - and the call
+        then queues its launches without synchronising, as the C entry point does."""
+        pos, box = self._frames(pos, box)
+        nf = pos.shape[0]
+        c = np.ascontiguousarray([] if center_index is None else center_index, dtype=np.int32).reshape(-1)
+        self.check_stress_profile(self.n, self.r_cut, box.detach().to("cpu", torch.float64).numpy() if check_boxes else None, n_bins, c)
+        out = torch.empty((nf, int(n_bins), _lib.STRESS_ROW_BY_TERM if by_term else _lib.STRESS_ROW), dtype=torch.float64, device=self.device)
+        _lib.check(self._lib.mythos_martini_stress_profile(self._h, _lib.ptr(pos), _lib.ptr(box), nf, int(c.size), c.ctypes.data_as(_lib.c_int_p),
+                                                           int(n_bins), 1 if by_term else 0, _lib.ptr(out), _lib.stream(self.device)),
+                   "martini_stress_profile")
+        return out
 
     def param_grads(self, pos: torch.Tensor, box: torch.Tensor, lj: bool = True, bonds: bool = True, angles: bool = True):
         """Per-frame parameter gradients (float64, on the device): dict with ``sigma``/``eps`` (F, T, T) for the

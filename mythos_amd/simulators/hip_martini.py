@@ -29,20 +29,26 @@ _MDP_KEYS = {"pcoupl": "kind", "pcoupltype": "coupling", "ref-p": "ref_p", "ref_
 def lower_martini(energy_fn) -> dict:
     """The tables of ONE ``MartiniSystem`` from the current parameters of a ``MartiniComposedEnergyFunction`` of LJ, Bond,
     Angle / Angle3 and optionally Coulomb: every term contributes the tables it owns, exactly as it hands them to its own
-    system (``_tables`` for the types, ``_theta`` for the reals)."""
+    system (``_tables`` for the types, ``_theta`` for the reals).  A single term (the stress profile of one term) stands for
+    all three: it hands out neutral values for the tables it does not own, as it does to its own system."""
     from mythos_amd.energy import martini as M
 
-    fns = getattr(energy_fn, "energy_fns", None)
-    if not fns:
-        raise TypeError("energy_fn must be a MartiniComposedEnergyFunction")
     by = {}
-    for fn in fns:
-        kind = "coulomb" if isinstance(fn, M.Coulomb) else "lj" if isinstance(fn, M.LJ) else "bond" if isinstance(fn, M.Bond) else \
-            "angle" if isinstance(fn, M.Angle) else None
-        if kind is None or kind in by:
-            raise ValueError(f"energy_fn must hold one LJ, one Bond, one Angle / Angle3 and at most one Coulomb term, not {type(fn).__name__}"
-                             + (" twice" if kind else ""))
-        by[kind] = fn
+    if isinstance(energy_fn, M.MartiniEnergyFunction):
+        by = {"lj": energy_fn, "bond": energy_fn, "angle": energy_fn}
+        if isinstance(energy_fn, M.Coulomb):
+            by["coulomb"] = energy_fn
+    else:
+        fns = getattr(energy_fn, "energy_fns", None)
+        if not fns:
+            raise TypeError("energy_fn must be a MartiniComposedEnergyFunction or a single MARTINI term")
+        for fn in fns:
+            kind = "coulomb" if isinstance(fn, M.Coulomb) else "lj" if isinstance(fn, M.LJ) else "bond" if isinstance(fn, M.Bond) else \
+                "angle" if isinstance(fn, M.Angle) else None
+            if kind is None or kind in by:
+                raise ValueError(f"energy_fn must hold one LJ, one Bond, one Angle / Angle3 and at most one Coulomb term, not {type(fn).__name__}"
+                                 + (" twice" if kind else ""))
+            by[kind] = fn
     missing = {"lj", "bond", "angle"} - set(by)
     if missing:
         raise ValueError(f"energy_fn lacks the terms {sorted(missing)}")
