@@ -1,6 +1,7 @@
-// Ownership of device memory: the one place of the library that allocates and frees it.  Also home of the error
-// plumbing every translation unit shares (set_error / hip_fail / MYTHOS_HIP_TRY) and of select_device, so that this
-// header stands on <hip/hip_runtime.h> alone (the host test of oracle/cpu_port compiles it against a malloc-backed one).
+// Ownership of device memory and of pinned host memory: the one place of the library that allocates and frees them.
+// Also home of the error plumbing every translation unit shares (set_error / hip_fail / MYTHOS_HIP_TRY) and of
+// select_device, so that this header stands on <hip/hip_runtime.h> alone (the host test of oracle/cpu_port compiles it
+// against a malloc-backed one).
 #ifndef MYTHOS_DEVICE_BUF_H
 #define MYTHOS_DEVICE_BUF_H
 
@@ -109,6 +110,57 @@ class DeviceBuf {
 };
 
 using DeviceBytes = DeviceBuf<void>;
+
+// Move-only owner of one allocation of pinned host memory (hipHostMalloc) of `capacity()` elements of T, with the address
+// the device reads and writes the same memory at: what a kernel publishes to the host, or the host stages for a kernel,
+// without a copy command.  The rules of DeviceBuf: never a zero-byte allocation, 0 or an error code, and the calling
+// thread's device is the one the buffer was made on, also when it is destroyed.
+template <typename T>
+class PinnedBuf {
+ public:
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  PinnedBuf(PinnedBuf&& o) noexcept : h_(o.h_), d_(o.d_), cap_(o.cap_) { o.h_ = o.d_ = nullptr, o.cap_ = 0; }
+  PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      h_ = o.h_, d_ = o.d_, cap_ = o.cap_;
+      o.h_ = o.d_ = nullptr, o.cap_ = 0;
+    }
+    return *this;
+  }
+  ~PinnedBuf() { reset(); }
+
+  T* host() const { return h_; }
+  T* dev() const { return d_; }
+  size_t capacity() const { return cap_; }
+  explicit operator bool() const { return h_ != nullptr; }
+
+  void reset() {
+    if (h_) (void)hipHostFree(h_);
+    h_ = d_ = nullptr, cap_ = 0;
+  }
+  // a new allocation of max(count, 1) elements; the old one is freed first and its contents are gone
+  int alloc(size_t count) {
+    reset();
+    count = std::max<size_t>(count, 1);
+    MYTHOS_HIP_TRY(hipHostMalloc((void**)&h_, count * sizeof(T), hipHostMallocDefault));
+    if (const hipError_t e = hipHostGetDevicePointer((void**)&d_, h_, 0); e != hipSuccess) {
+      reset();
+      return hip_fail(e, "hipHostGetDevicePointer");
+    }
+    cap_ = count;
+    return 0;
+  }
+  // allocated once, or again - contents not kept - when more than capacity() elements are needed
+  int grow(size_t need) { return need <= cap_ ? 0 : alloc(need); }
+
+ private:
+  T* h_ = nullptr;
+  T* d_ = nullptr;
+  size_t cap_ = 0;
+};
 
 }  // namespace mythos
 

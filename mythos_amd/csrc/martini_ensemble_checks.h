@@ -1,7 +1,7 @@
 // Host bookkeeping of the MARTINI temperature ensemble that needs no device: what mythos_martini_langevin_create_ensemble and
-// load refuse, and how an advance under a barostat is cut into chunks.  In the style of host_checks.h - it stands on the
-// standard library and set_error alone, so tests/host/martini_ensemble_checks_main.cpp compiles it as it is, under the
-// host sanitizers.
+// load refuse.  (How an advance with events is cut into chunks: mm_event_chunk, martini_exchange_checks.h.)  In the style
+// of host_checks.h - it stands on the standard library and set_error alone, so tests/host/martini_ensemble_checks_main.cpp
+// compiles it as it is, under the host sanitizers.
 #ifndef MYTHOS_MARTINI_ENSEMBLE_CHECKS_H
 #define MYTHOS_MARTINI_ENSEMBLE_CHECKS_H
 
@@ -51,22 +51,6 @@ inline int mm_ensemble_check(int n, int n_rep, const double* kT, double r_cut, d
     if (int rc = mm_box_fits(boxes + 3 * (size_t)r, r_cut + skin, std::string(who) + ": replica " + std::to_string(r))) return rc;
   return 0;
 }
-
-// The next chunk of an advance under a barostat (mm_advance_npt): it ends at the next coupling event (absolute step counter),
-// the next saved row (counted from the call's first step) or the end of the call, whichever comes first.
-struct MmNptChunk {
-  int len;
-  bool event, save, last;
-};
-inline MmNptChunk mm_npt_chunk(int64_t step, int every, int done, int n_steps, int save_every) {
-  const int to_event = every - (int)(step % every);
-  const int to_save = save_every > 0 ? save_every - done % save_every : n_steps + 1;
-  const int len = std::min(std::min(to_event, to_save), n_steps - done);
-  return {len, len == to_event, len == to_save, done + len == n_steps};
-}
-
-// Row r of a per-event, per-row array of `copies` records of `width` values each: where chunked output lands
-inline size_t mm_row_offset(int row, int copies, size_t width) { return (size_t)row * copies * width; }
 
 }  // namespace mythos
 

@@ -1,12 +1,14 @@
 // Temperature replica exchange between the replicas of a MARTINI ensemble; included by martini_md.hip behind martini_npt.inc.
 //
 // The rule is stated in include/mythos_hip.h (mythos_martini_langevin_set_exchange) and DESIGN.md section 3.5l; what needs
-// no device - the pair schedule, the decision, the chunking, the refusals - is martini_exchange_checks.h.  Here: the decision
-// kernel, the velocity rescale, and mm_advance_events, which is mm_advance_npt with two kinds of event.
+// no device - the pair schedule, the decision, the chunking and its plan, the refusals - is martini_exchange_checks.h.
+// Here: the decision kernel, the velocity rescale, the event, and what the event and the C entry points share with window
+// exchange (MmPairExchange, martini_md.hip).  The loop that cuts an advance at the events is mm_advance_chunked (martini_md.hip).
 //
 // Slots are the replicas as they lie in memory; an exchange swaps the TEMPERATURES of two slots, no bead data moves.  An
 // event needs U(x_s) of every slot: the chunk in front of it ends on a closing launch of the energy-trace instantiation and
-// mm_reduce_trace_ens_kernel, into the caller's row if step s is saved, into MmExchange::d_etrace otherwise.
+// mm_reduce_trace_ens_kernel, into the caller's row if step s is saved with energies, into MmLadder::d_etrace otherwise
+// (mm_chunk_plan).
 
 namespace mythos {
 
@@ -94,22 +96,36 @@ __global__ __launch_bounds__(256) void mm_rescale_vel_ens_kernel(int n, int n_re
 static bool mm_exchange_on(const mythos_martini_sim* sim) { return sim->n_rep >= 2 && sim->xchg.every > 0; }
 
 static int mm_exchange_buffers(mythos_martini_sim* sim) {
-  MmExchange& x = sim->xchg;
-  const size_t nr = (size_t)sim->n_rep;
-  if (int rc = x.d_etrace.grow(nr * kMmTraceCoul)) return rc;
-  if (int rc = x.d_fac.grow(nr)) return rc;
-  if (!x.h_d) {  // (the number of replicas is fixed at create) in: boxes 3 R, kT R; out: R / 2 records
-    MYTHOS_HIP_TRY(hipHostMalloc((void**)&x.h_d, (4 * nr + (nr / 2) * kXchgRec) * sizeof(double), hipHostMallocDefault));
-    MYTHOS_HIP_TRY(hipHostGetDevicePointer((void**)&x.d_hd, x.h_d, 0));
-    MYTHOS_HIP_TRY(hipHostMalloc((void**)&x.h_i, 2 * nr * sizeof(int), hipHostMallocDefault));  // in: rung R; out: rung R
-    MYTHOS_HIP_TRY(hipHostGetDevicePointer((void**)&x.d_hi, x.h_i, 0));
-  }
-  return MYTHOS_OK;
+  const size_t nr = (size_t)sim->n_rep;  // (fixed at create)
+  if (int rc = sim->ladder.d_etrace.grow(nr * kMmTraceCoul)) return rc;
+  if (int rc = sim->ladder.d_fac.grow(nr)) return rc;
+  if (int rc = sim->xchg.h_d.grow(4 * nr + (nr / 2) * kXchgRec)) return rc;  // in: boxes 3 R, kT R; out: R / 2 records
+  return sim->xchg.h_i.grow(2 * nr);                                        // in: rung R; out: rung R
 }
 
 // the ladder as it stands -> every slot's kT; the replica table follows at the next mm_upload_reps
 static void mm_apply_ladder(mythos_martini_sim* sim) {
-  for (int r = 0; r < sim->n_rep; ++r) sim->rep_kT[r] = sim->xchg.ladder_kT[(size_t)sim->xchg.rung_of_slot[r]];
+  for (int r = 0; r < sim->n_rep; ++r) sim->rep_kT[r] = sim->ladder.kT[(size_t)sim->xchg.of_slot[r]];
+}
+
+// The host half of an exchange event of either kind, behind the event's synchronisation: the permutation the kernel left
+// in the upper half of h_i and the n_pairs records at h_log, both pinned, become the slots' permutation, the call's log
+// and the counts per rung pair.  what: "exchange" or "window-exchange", as the message names the event.
+static int mm_pair_exchange_take(mythos_martini_sim* sim, MmPairExchange& x, const double* h_log, int n_pairs, const char* what) {
+  const int nr = sim->n_rep;
+  const int* out = x.h_i.host() + nr;
+  if (!mm_is_permutation(out, nr)) {  // (defensive: the kernel swaps pairs of a permutation)
+    set_error(std::string("mythos_martini_langevin_run: the ") + what + " event at step " + std::to_string(sim->step) + " did not return a permutation");
+    return MYTHOS_ERR_HIP;
+  }
+  std::copy(out, out + nr, x.of_slot.begin());
+  x.last_log.insert(x.last_log.end(), h_log, h_log + (size_t)n_pairs * kXchgRec);
+  for (int q = 0; q < n_pairs; ++q) {
+    const int t = (int)h_log[(size_t)q * kXchgRec + 1];
+    ++x.attempts[(size_t)t];
+    if (h_log[(size_t)q * kXchgRec + 10] != 0.0) ++x.accepts[(size_t)t];
+  }
+  return MYTHOS_OK;
 }
 
 // The exchange event at the closed state of step sim->step, from the energy rows e_rows [n_rep][width] queued on st:
@@ -119,34 +135,23 @@ static void mm_apply_ladder(mythos_martini_sim* sim) {
 template <typename R>
 static int mm_exchange_event(mythos_martini_sim* sim, const double* e_rows, double p, hipStream_t st) {
   using V4 = typename Real4<R>::type;
-  MmExchange& x = sim->xchg;
+  MmPairExchange& x = sim->xchg;
   const int nr = sim->n_rep, n = sim->sys->n;
   const int64_t attempt = sim->step / x.every;
   const int n_pairs = mm_xchg_n_pairs(nr, attempt);
   // (the stream is idle behind the last event's synchronisation, or nothing queued on it reads these)
-  std::copy(sim->rep_box.begin(), sim->rep_box.end(), x.h_d);
-  std::copy(x.ladder_kT.begin(), x.ladder_kT.end(), x.h_d + 3 * (size_t)nr);
-  std::copy(x.rung_of_slot.begin(), x.rung_of_slot.end(), x.h_i);
-  double* h_log = x.h_d + 4 * (size_t)nr;
+  std::copy(sim->rep_box.begin(), sim->rep_box.end(), x.h_d.host());
+  std::copy(sim->ladder.kT.begin(), sim->ladder.kT.end(), x.h_d.host() + 3 * (size_t)nr);
+  std::copy(x.of_slot.begin(), x.of_slot.end(), x.h_i.host());
   MmXchgArgs a;
   a.n_rep = nr, a.width = sim->trace_width(), a.p = p, a.seed = x.seed, a.step = sim->step, a.attempt = attempt;
-  hipLaunchKernelGGL(mm_exchange_kernel, dim3(1), dim3(256), 0, st, e_rows, (const double*)x.d_hd, (const int*)x.d_hi, a, x.d_fac.get(),
-                     x.d_hi + nr, x.d_hd + 4 * (size_t)nr);
-  hipLaunchKernelGGL(mm_rescale_vel_ens_kernel<R>, dim3((sim->n_all() + 255) / 256), dim3(256), 0, st, n, nr, (const double*)x.d_fac.get(),
+  hipLaunchKernelGGL(mm_exchange_kernel, dim3(1), dim3(256), 0, st, e_rows, (const double*)x.h_d.dev(), (const int*)x.h_i.dev(), a,
+                     sim->ladder.d_fac.get(), x.h_i.dev() + nr, x.h_d.dev() + 4 * (size_t)nr);
+  hipLaunchKernelGGL(mm_rescale_vel_ens_kernel<R>, dim3((sim->n_all() + 255) / 256), dim3(256), 0, st, n, nr, (const double*)sim->ladder.d_fac.get(),
                      (V4*)sim->vel.get());
   MYTHOS_HIP_TRY(hipGetLastError());
   MYTHOS_HIP_TRY(hipStreamSynchronize(st));
-  if (!mm_is_permutation(x.h_i + nr, nr)) {  // (defensive: the kernel swaps pairs of a permutation)
-    set_error("mythos_martini_langevin_run: the exchange event at step " + std::to_string(sim->step) + " did not return a permutation");
-    return MYTHOS_ERR_HIP;
-  }
-  std::copy(x.h_i + nr, x.h_i + 2 * (size_t)nr, x.rung_of_slot.begin());
-  x.last_log.insert(x.last_log.end(), h_log, h_log + (size_t)n_pairs * kXchgRec);
-  for (int q = 0; q < n_pairs; ++q) {
-    const int t = (int)h_log[(size_t)q * kXchgRec + 1];
-    ++x.attempts[(size_t)t];
-    if (h_log[(size_t)q * kXchgRec + 10] != 0.0) ++x.accepts[(size_t)t];
-  }
+  if (int rc = mm_pair_exchange_take(sim, x, x.h_d.host() + 4 * (size_t)nr, n_pairs, "exchange")) return rc;
   mm_apply_ladder(sim);
   if (int rc = mm_upload_reps(sim, st)) return rc;
   sim->list_valid = false;
@@ -154,53 +159,43 @@ static int mm_exchange_event(mythos_martini_sim* sim, const double* e_rows, doub
   return MYTHOS_OK;
 }
 
-// the ladder of the resident state as a row of last_ladder
-static void mm_push_ladder(mythos_martini_sim* sim) {
-  sim->xchg.last_ladder.insert(sim->xchg.last_ladder.end(), sim->xchg.rung_of_slot.begin(), sim->xchg.rung_of_slot.end());
-}
-// no exchange in this call: every saved row has the ladder as it stands
-static void mm_constant_ladder(mythos_martini_sim* sim) {
-  sim->xchg.last_ladder.clear();
-  sim->xchg.last_log.clear();
-  if (sim->n_rep == 0) return;
-  const size_t rows = sim->baro.last_boxes.size() / (3 * (size_t)sim->n_rep);
-  for (size_t r = 0; r < rows; ++r) mm_push_ladder(sim);
-}
-
-// n_steps with exchange events and, under a barostat, coupling events: mm_advance_npt with the chunks of mm_event_chunk.  A
-// chunk that ends at either event closes; one that ends at an exchange event carries an energy row at its last step.  At a
-// step with both the exchange comes first - on U and the box of (x_s, box_s), no second energy evaluation - and the coupling
-// follows with the new kT' and the rescaled velocities, each with its own synchronisation.  A saved row is the state before
-// both.
-template <typename R>
-static int mm_advance_events(mythos_martini_sim* sim, int n_steps, int save_every, bool close, R* traj_pos, double* e_trace, hipStream_t st) {
-  MmBarostat& b = sim->baro;
-  MmExchange& x = sim->xchg;
-  const bool baro = mm_barostat_on(sim);
-  double p = 0.0;
-  if (int rc = mm_xchg_pressure(baro, b.coupling, b.ref_p, b.beta, &p, "mythos_martini_langevin_advance")) return rc;
-  if (int rc = mm_exchange_buffers(sim)) return rc;
-  b.last_boxes.clear();
-  x.last_ladder.clear();
-  x.last_log.clear();
-  if (n_steps == 0) return mm_advance_typed<R>(sim, 0, save_every, close, traj_pos, e_trace, st);
-  const size_t row_reals = (size_t)sim->n_all() * 3;
-  int done = 0, rows = 0, rebuilds = 0, recoveries = 0, launches = 0;
-  while (done < n_steps) {
-    const MmEventChunk c = mm_event_chunk(sim->step, baro ? b.every : 0, x.every, done, n_steps, save_every);
-    double* e_row = (c.save && e_trace) ? e_trace + mm_row_offset(rows, sim->copies(), sim->trace_width()) : (c.exchange ? x.d_etrace.get() : nullptr);
-    const int rc = mm_advance_typed<R>(sim, c.len, (c.save || c.exchange) ? c.len : 0, c.couple || c.exchange || (c.last && close),
-                                       (c.save && traj_pos) ? traj_pos + rows * row_reals : nullptr, e_row, st);
-    rebuilds += sim->last_rebuilds, recoveries += sim->last_recoveries, launches += sim->last_launches;
-    sim->last_rebuilds = rebuilds, sim->last_recoveries = recoveries, sim->last_launches = launches;
-    if (rc) return rc;
-    if (c.save) mm_push_boxes(sim), mm_push_ladder(sim), ++rows;
-    if (c.exchange)
-      if (int re = mm_exchange_event<R>(sim, e_row, p, st)) return re;
-    if (c.couple)
-      if (int re = mm_pressure_typed<R>(sim, true, st)) return re;
-    done += c.len;
+// ---- what the C entry points of the two exchanges share; `which` is &mythos_martini_sim::xchg or ::wx
+using MmWhich = MmPairExchange mythos_martini_sim::*;
+static int mm_pair_get(const mythos_martini_sim* s, MmWhich which, int32_t* of_slot, const char* who) {
+  if (!s || !of_slot || s->n_rep < 1) {
+    set_error(std::string(who) + ": an ensemble handle and an array of n_rep entries required");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
   }
+  std::copy((s->*which).of_slot.begin(), (s->*which).of_slot.end(), of_slot);
+  return MYTHOS_OK;
+}
+static int mm_pair_last_rows(const mythos_martini_sim* s, MmWhich which, int32_t* rows, int* n_rows, const char* who) {
+  if (!s || s->n_rep < 1 || (!rows && !n_rows)) {
+    set_error(std::string(who) + ": invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  const std::vector<int32_t>& last = (s->*which).last_rows;
+  if (n_rows) *n_rows = (int)(last.size() / (size_t)s->n_rep);
+  if (rows) std::copy(last.begin(), last.end(), rows);
+  return MYTHOS_OK;
+}
+static int mm_pair_last_log(const mythos_martini_sim* s, MmWhich which, double* rec, int* n, const char* who) {
+  if (!s || (!rec && !n)) {
+    set_error(std::string(who) + ": invalid argument");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  const std::vector<double>& log = (s->*which).last_log;
+  if (n) *n = (int)(log.size() / kXchgRec);
+  if (rec) std::copy(log.begin(), log.end(), rec);
+  return MYTHOS_OK;
+}
+static int mm_pair_counts(const mythos_martini_sim* s, MmWhich which, int64_t* attempts, int64_t* accepts, const char* who) {
+  if (!s || s->n_rep < 2 || !attempts || !accepts) {
+    set_error(std::string(who) + ": an ensemble handle with n_rep >= 2 and two arrays of n_rep - 1 entries required");
+    return MYTHOS_ERR_INVALID_ARGUMENT;
+  }
+  std::copy((s->*which).attempts.begin(), (s->*which).attempts.end(), attempts);
+  std::copy((s->*which).accepts.begin(), (s->*which).accepts.end(), accepts);
   return MYTHOS_OK;
 }
 
@@ -244,7 +239,7 @@ int mythos_martini_langevin_set_ladder(mythos_martini_sim_t* s, const int32_t* r
   }
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
   MYTHOS_HIP_TRY(hipDeviceSynchronize());  // (launches that read the replica table)
-  std::copy(rung_of_slot, rung_of_slot + s->n_rep, s->xchg.rung_of_slot.begin());
+  std::copy(rung_of_slot, rung_of_slot + s->n_rep, s->xchg.of_slot.begin());
   mm_apply_ladder(s);
   if (int rc = mm_upload_reps(s, nullptr)) return rc;
   MYTHOS_HIP_TRY(hipStreamSynchronize(nullptr));
@@ -252,42 +247,19 @@ int mythos_martini_langevin_set_ladder(mythos_martini_sim_t* s, const int32_t* r
 }
 
 int mythos_martini_langevin_get_ladder(const mythos_martini_sim_t* s, int32_t* rung_of_slot) {
-  if (!s || !rung_of_slot || s->n_rep < 1) {
-    set_error("mythos_martini_langevin_get_ladder: an ensemble handle and an array of n_rep entries required");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  std::copy(s->xchg.rung_of_slot.begin(), s->xchg.rung_of_slot.end(), rung_of_slot);
-  return MYTHOS_OK;
+  return mm_pair_get(s, &mythos_martini_sim::xchg, rung_of_slot, "mythos_martini_langevin_get_ladder");
 }
 
 int mythos_martini_langevin_last_ladder(const mythos_martini_sim_t* s, int32_t* rows, int* n_rows) {
-  if (!s || s->n_rep < 1 || (!rows && !n_rows)) {
-    set_error("mythos_martini_langevin_last_ladder: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  if (n_rows) *n_rows = (int)(s->xchg.last_ladder.size() / (size_t)s->n_rep);
-  if (rows) std::copy(s->xchg.last_ladder.begin(), s->xchg.last_ladder.end(), rows);
-  return MYTHOS_OK;
+  return mm_pair_last_rows(s, &mythos_martini_sim::xchg, rows, n_rows, "mythos_martini_langevin_last_ladder");
 }
 
 int mythos_martini_langevin_last_exchanges(const mythos_martini_sim_t* s, double* rec, int* n) {
-  if (!s || (!rec && !n)) {
-    set_error("mythos_martini_langevin_last_exchanges: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  if (n) *n = (int)(s->xchg.last_log.size() / kXchgRec);
-  if (rec) std::copy(s->xchg.last_log.begin(), s->xchg.last_log.end(), rec);
-  return MYTHOS_OK;
+  return mm_pair_last_log(s, &mythos_martini_sim::xchg, rec, n, "mythos_martini_langevin_last_exchanges");
 }
 
 int mythos_martini_langevin_exchange_counts(const mythos_martini_sim_t* s, int64_t* attempts, int64_t* accepts) {
-  if (!s || s->n_rep < 2 || !attempts || !accepts) {
-    set_error("mythos_martini_langevin_exchange_counts: an ensemble handle with n_rep >= 2 and two arrays of n_rep - 1 entries required");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  std::copy(s->xchg.attempts.begin(), s->xchg.attempts.end(), attempts);
-  std::copy(s->xchg.accepts.begin(), s->xchg.accepts.end(), accepts);
-  return MYTHOS_OK;
+  return mm_pair_counts(s, &mythos_martini_sim::xchg, attempts, accepts, "mythos_martini_langevin_exchange_counts");
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Host bookkeeping of temperature replica exchange in the MARTINI ensemble (mythos_martini_langevin_set_exchange) that needs
-// no device: which rung pairs an event attempts, the decision, how an advance is cut at coupling events, exchange events and
-// saved rows, the permutation check of a ladder, the scalar reference pressure of the work term, and what is refused.  In the
+// no device: which rung pairs an event attempts, the decision, how every advance with events - coupling, temperature
+// exchange, window exchange - is cut at them and at saved rows and what the one loop passes on for each chunk
+// (mm_event_chunk, mm_chunk_plan), the permutation check of a ladder, the scalar reference pressure of the work term, and what is refused.  In the
 // style of martini_ensemble_checks.h - the standard library and set_error alone, so tests/host/martini_exchange_main.cpp
 // compiles it as it is under the host sanitizers.  What mm_exchange_kernel shares with the host (the pair schedule, the
 // decision) is marked MYTHOS_XHD: __host__ __device__ under hipcc, nothing otherwise.
@@ -52,9 +53,10 @@ MYTHOS_XHD inline bool mm_xchg_accept(double d, double u) { return d >= 0.0 || u
 // what a slot's velocities are multiplied by when its kT goes from kT_old to kT_new (rounded once more to the system's reals)
 MYTHOS_XHD inline double mm_xchg_vel_factor(double kT_old, double kT_new) { return sqrt(kT_new / kT_old); }
 
-// ---- chunks of an advance with two kinds of event (mm_npt_chunk of martini_ensemble_checks.h generalised): the next chunk
-// ends at the next coupling event, the next exchange event (both on the absolute step counter; every == 0: none), the next
-// saved row (counted from the call's first step) or the end of the call, whichever comes first
+// ---- chunks of an advance with events (mm_advance_chunked, martini_md.hip: under a barostat, temperature exchange or
+// window exchange): the next chunk ends at the next coupling event, the next exchange event (both on the absolute step
+// counter; every == 0: none), the next saved row (counted from the call's first step) or the end of the call, whichever
+// comes first
 struct MmEventChunk {
   int len;
   bool couple, exchange, save, last;
@@ -67,6 +69,26 @@ inline MmEventChunk mm_event_chunk(int64_t step, int couple_every, int exchange_
   const int len = std::min(std::min(to_couple, to_exchange), std::min(to_save, n_steps - done));
   return {len, len == to_couple, len == to_exchange, len == to_save, done + len == n_steps};
 }
+
+// What the integrator's one call for a chunk is given.  An event needs the closed state, so a chunk that ends at one
+// closes; the last chunk closes if the caller's call does.  A temperature event needs U(x_s) of every slot, so its chunk
+// ends on an energy row whether the caller saves that step or not: the caller's row if it saves the step with energies,
+// the exchange's scratch row otherwise.  A window event needs no energy row.
+enum MmExchangeKind { kMmNoExchange = 0, kMmTemperatureExchange, kMmWindowExchange };
+enum MmEnergyRow { kMmNoEnergyRow = 0, kMmCallerRow, kMmScratchRow };
+struct MmChunkPlan {
+  bool close;
+  int save_every;      // c.len: the chunk's last step is a row; 0: the chunk saves nothing
+  MmEnergyRow energy;  // where that row's energies go
+};
+inline MmChunkPlan mm_chunk_plan(const MmEventChunk& c, bool close, MmExchangeKind kind, bool caller_energies) {
+  const bool needs_u = c.exchange && kind == kMmTemperatureExchange;
+  const MmEnergyRow energy = (c.save && caller_energies) ? kMmCallerRow : (needs_u ? kMmScratchRow : kMmNoEnergyRow);
+  return {c.couple || c.exchange || (c.last && close), (c.save || needs_u) ? c.len : 0, energy};
+}
+
+// Row r of a per-row array of `copies` records of `width` values each: where chunked output lands
+inline size_t mm_row_offset(int row, int copies, size_t width) { return (size_t)row * copies * width; }
 
 inline bool mm_is_permutation(const int32_t* p, int n) {
   if (!p || n < 1) return false;

@@ -712,58 +712,36 @@ struct MmBarostat {
   double ref_p[2] = {1.0, 1.0}, beta[2] = {0.0, 0.0}, tau_p = 1.0;  // bar, 1/bar, ps
   int every = 10;
   mythos::DeviceBuf<double> d_part, d_rec;  // per-workgroup partials [blocks][6]; the record the scale kernel reads
-  double* h_rec = nullptr;                  // the same record in pinned host memory, written by the device
-  double* d_hrec = nullptr;                 // device address of h_rec
+  mythos::PinnedBuf<double> rec;            // the same record in pinned host memory, written by the device
   std::vector<double> last_boxes;           // [rows][3] of the last run / advance
-  MmBarostat() = default;
-  MmBarostat(const MmBarostat&) = delete;
-  MmBarostat& operator=(const MmBarostat&) = delete;
-  ~MmBarostat() {  // (the owner's destructor has selected the device)
-    if (h_rec) (void)hipHostFree(h_rec);
-  }
 };
 
-// Temperature replica exchange of an ensemble (martini_exchange.inc): what mythos_martini_langevin_set_exchange set, the
-// ladder - which rung's kT every slot runs at -, the counts since restart, and ladder rows and attempt log of the last call.
-struct MmExchange {
+// An exchange between the replicas of an ensemble, temperature exchange (xchg, martini_exchange.inc) and window exchange
+// (wx, martini_window_exchange.inc) alike: what set_exchange / set_window_exchange set, the permutation - which rung's kT
+// every slot runs at, which window's parameter row it holds -, the counts since restart / set_restraints, and the
+// permutation rows and attempt log of the last call.
+static_assert(kXchgRec == 11 && kWxRec == kXchgRec, "one log record for both exchanges: column 1 the rung, column 10 accepted");
+struct MmPairExchange {
   int every = 0;      // 0: off
   uint64_t seed = 0;  // of the decisions' uniforms, a Philox stream of its own
-  std::vector<double> ladder_kT;      // [n_rep]: the kT given at creation, in their order
-  std::vector<int32_t> rung_of_slot;  // [n_rep]: a permutation, the identity at creation and after restart
+  std::vector<int32_t> of_slot;            // [n_rep]: rung_of_slot / window_of_slot, the identity at creation
   std::vector<int64_t> attempts, accepts;  // [n_rep - 1], per rung pair (t, t + 1)
-  std::vector<int32_t> last_ladder;   // [rows][n_rep]
-  std::vector<double> last_log;       // [attempted pairs][kXchgRec]
+  std::vector<int32_t> last_rows;          // [rows][n_rep]: of_slot at every row the last call saved
+  std::vector<double> last_log;            // [attempted pairs][kXchgRec]
+  // pinned, allocated at the first advance with the exchange on.  h_d: out the log [n_rep / 2][kXchgRec]; temperature
+  // exchange has in boxes [n_rep][3], kT [n_rep] in front of it.  h_i: in of_slot [n_rep], out the new one [n_rep].
+  mythos::PinnedBuf<double> h_d;
+  mythos::PinnedBuf<int> h_i;
+  void identity() {
+    for (size_t r = 0; r < of_slot.size(); ++r) of_slot[r] = (int32_t)r;
+    std::fill(attempts.begin(), attempts.end(), 0);
+    std::fill(accepts.begin(), accepts.end(), 0);
+  }
+};
+// what temperature exchange needs on top: the ladder, and the device buffers of an event
+struct MmLadder {
+  std::vector<double> kT;                     // [n_rep]: the kT given at creation, in their order
   mythos::DeviceBuf<double> d_etrace, d_fac;  // energy rows of an event whose step is not saved [n_rep][5]; velocity factors [n_rep]
-  double *h_d = nullptr, *d_hd = nullptr;  // pinned, and its device address: in boxes [n_rep][3], kT [n_rep]; out log [n_rep / 2][kXchgRec]
-  int *h_i = nullptr, *d_hi = nullptr;     // pinned: in rung_of_slot [n_rep]; out the new one [n_rep]
-  MmExchange() = default;
-  MmExchange(const MmExchange&) = delete;
-  MmExchange& operator=(const MmExchange&) = delete;
-  ~MmExchange() {  // (the owner's destructor has selected the device)
-    if (h_d) (void)hipHostFree(h_d);
-    if (h_i) (void)hipHostFree(h_i);
-  }
-};
-
-// Window exchange of an ensemble (martini_window_exchange.inc): what mythos_martini_langevin_set_window_exchange set, the
-// assignment - which window's parameter row every slot holds -, the counts since set_restraints, and assignment rows and
-// attempt log of the last call.
-struct MmWindowExchange {
-  int every = 0;      // 0: off
-  uint64_t seed = 0;  // of the decisions' uniforms, a Philox stream of its own
-  std::vector<int32_t> window_of_slot;     // [n_rep]: a permutation, the identity at creation and after set_restraints
-  std::vector<int64_t> attempts, accepts;  // [n_rep - 1], per rung pair (t, t + 1)
-  std::vector<int32_t> last_windows;       // [rows][n_rep]
-  std::vector<double> last_log;            // [attempted pairs][kWxRec]
-  double *h_d = nullptr, *d_hd = nullptr;  // pinned, and its device address: out log [n_rep / 2][kWxRec]
-  int *h_i = nullptr, *d_hi = nullptr;     // pinned: in window_of_slot [n_rep]; out the new one [n_rep]
-  MmWindowExchange() = default;
-  MmWindowExchange(const MmWindowExchange&) = delete;
-  MmWindowExchange& operator=(const MmWindowExchange&) = delete;
-  ~MmWindowExchange() {  // (the owner's destructor has selected the device)
-    if (h_d) (void)hipHostFree(h_d);
-    if (h_i) (void)hipHostFree(h_i);
-  }
 };
 
 // External forces of the resident state (martini_restraints.h, martini_restraints.inc): the device arrays of the set
@@ -825,18 +803,16 @@ struct mythos_martini_sim : mythos::MdRun {
   int n_rep = 0;
   std::vector<double> rep_kT, rep_box;  // [n_rep], [n_rep][3]
   std::vector<uint64_t> rep_seed;
-  unsigned char* h_reps = nullptr;
-  MmExchange xchg;  // off until mythos_martini_langevin_set_exchange
-  MmRestraints rst;  // none until mythos_martini_langevin_set_restraints
-  MmWindowExchange wx;  // off until mythos_martini_langevin_set_window_exchange
+  mythos::PinnedBuf<unsigned char> h_reps;
+  MmPairExchange xchg;  // off until mythos_martini_langevin_set_exchange
+  MmLadder ladder;
+  MmRestraints rst;   // none until mythos_martini_langevin_set_restraints
+  MmPairExchange wx;  // off until mythos_martini_langevin_set_window_exchange
   std::vector<double> h_mass;  // [n] as given at creation (the COM weights of the pull groups)
   int copies() const { return n_rep > 0 ? n_rep : 1; }
   int n_all() const { return copies() * sys->n; }  // beads of all copies
   const double* box_of(int r) const { return n_rep > 0 ? &rep_box[3 * (size_t)r] : box; }
-  ~mythos_martini_sim() {  // the members, MdRun's too, free themselves on that device
-    (void)hipSetDevice(device);
-    if (h_reps) (void)hipHostFree(h_reps);
-  }
+  ~mythos_martini_sim() { (void)hipSetDevice(device); }  // the members, MdRun's too, free themselves on that device
 };
 
 namespace mythos {
@@ -916,8 +892,8 @@ static int mm_upload_reps(mythos_martini_sim* sim, hipStream_t st) {
   const int nr = sim->n_rep;
   const bool f32 = sim->sys->dtype == MYTHOS_F32;
   const size_t rec = f32 ? sizeof(MmRep<float>) : sizeof(MmRep<double>), tab = kMmRepHead + nr * rec;
-  if (!sim->h_reps) MYTHOS_HIP_TRY(hipHostMalloc((void**)&sim->h_reps, tab, hipHostMallocDefault));
-  unsigned char* h = sim->h_reps;
+  if (int rc = sim->h_reps.grow(tab)) return rc;  // (the number of replicas is fixed at create)
+  unsigned char* h = sim->h_reps.host();
   const int head[2] = {nr, 0};
   std::memcpy(h, head, kMmRepHead);
   for (int r = 0; r < nr; ++r) {
@@ -1247,6 +1223,59 @@ static int mm_store_typed(mythos_martini_sim* sim, R* pos, R* v, hipStream_t st)
 #include "martini_restraints.inc"
 #include "martini_window_exchange.inc"
 
+namespace mythos {
+
+// n_steps with events - coupling under a barostat, and temperature or window exchange: chunks that end at the next event
+// step (absolute step counter), the next saved row (counted from the call's first step) or the end of the call
+// (mm_event_chunk), each one call of mm_advance_typed - md_drive as it is - with what mm_chunk_plan says.  A chunk that
+// ends at an event closes (the event needs the closed state; a temperature event U(x_s) too); every other boundary
+// leaves the frame open, and the launches on either side of it are those of one longer call.  Inside a step: the saved
+// row - the state BEFORE the step's events, with the box, ladder and windows it was integrated under -, then the exchange
+// on U and the box of (x_s, box_s), then the coupling with the new kT' and the rescaled velocities, each event with its own
+// synchronisation.  What is refused comes first, then the events' buffers, allocated at the first call that needs them.
+template <typename R>
+static int mm_advance_chunked(mythos_martini_sim* sim, int n_steps, int save_every, bool close, R* traj_pos, double* e_trace, hipStream_t st) {
+  MmBarostat& b = sim->baro;
+  const bool baro = mm_barostat_on(sim);
+  const MmExchangeKind kind = mm_window_exchange_on(sim) ? kMmWindowExchange : (mm_exchange_on(sim) ? kMmTemperatureExchange : kMmNoExchange);
+  const int exchange_every = kind == kMmWindowExchange ? sim->wx.every : (kind == kMmTemperatureExchange ? sim->xchg.every : 0);
+  double p = 0.0;  // of the temperature exchange's work term
+  if (kind == kMmWindowExchange) {
+    if (!sim->rst.installed) {
+      set_error("mythos_martini_langevin_advance: window exchange is on and no set of restraints is installed: there are no windows to "
+                "exchange (mythos_martini_langevin_set_restraints first, or switch window exchange off)");
+      return MYTHOS_ERR_NOT_READY;
+    }
+    if (int rc = mm_wx_buffers(sim)) return rc;
+  } else if (kind == kMmTemperatureExchange) {
+    if (int rc = mm_xchg_pressure(baro, b.coupling, b.ref_p, b.beta, &p, "mythos_martini_langevin_advance")) return rc;
+    if (int rc = mm_exchange_buffers(sim)) return rc;
+  }
+  if (n_steps == 0) return mm_advance_typed<R>(sim, 0, save_every, close, traj_pos, e_trace, st);
+  const size_t row_reals = (size_t)sim->n_all() * 3;
+  int done = 0, rows = 0, rebuilds = 0, recoveries = 0, launches = 0;
+  while (done < n_steps) {
+    const MmEventChunk c = mm_event_chunk(sim->step, baro ? b.every : 0, exchange_every, done, n_steps, save_every);
+    const MmChunkPlan plan = mm_chunk_plan(c, close, kind, e_trace != nullptr);
+    double* e_row = plan.energy == kMmCallerRow    ? e_trace + mm_row_offset(rows, sim->copies(), sim->trace_width())
+                    : plan.energy == kMmScratchRow ? sim->ladder.d_etrace.get()
+                                                   : nullptr;
+    const int rc = mm_advance_typed<R>(sim, c.len, plan.save_every, plan.close, (c.save && traj_pos) ? traj_pos + rows * row_reals : nullptr, e_row, st);
+    rebuilds += sim->last_rebuilds, recoveries += sim->last_recoveries, launches += sim->last_launches;
+    sim->last_rebuilds = rebuilds, sim->last_recoveries = recoveries, sim->last_launches = launches;
+    if (rc) return rc;
+    if (c.save) mm_push_row(sim), ++rows;
+    if (c.exchange)
+      if (int re = kind == kMmWindowExchange ? mm_window_exchange_event<R>(sim, st) : mm_exchange_event<R>(sim, e_row, p, st)) return re;
+    if (c.couple)
+      if (int re = mm_pressure_typed<R>(sim, true, st)) return re;
+    done += c.len;
+  }
+  return MYTHOS_OK;
+}
+
+}  // namespace mythos
+
 extern "C" {
 
 void mythos_martini_langevin_destroy(mythos_martini_sim_t* s) { delete s; }
@@ -1270,14 +1299,13 @@ mythos_martini_sim_t* mm_create(mythos_martini_t* sys, int n_rep, double dt, con
     s->rep_box.assign(3 * (size_t)n_rep, 0.0);
     s->rep_seed.assign((size_t)n_rep, 0);
     for (int r = 0; seeds && r < n_rep; ++r) s->rep_seed[r] = seeds[r];
-    s->xchg.ladder_kT = s->rep_kT;
-    s->xchg.rung_of_slot.resize((size_t)n_rep);
-    for (int r = 0; r < n_rep; ++r) s->xchg.rung_of_slot[r] = r;
-    s->xchg.attempts.assign((size_t)std::max(0, n_rep - 1), 0);
-    s->xchg.accepts.assign((size_t)std::max(0, n_rep - 1), 0);
-    s->wx.window_of_slot = s->xchg.rung_of_slot;
-    s->wx.attempts = s->xchg.attempts;
-    s->wx.accepts = s->xchg.accepts;
+    s->ladder.kT = s->rep_kT;
+    for (MmPairExchange* x : {&s->xchg, &s->wx}) {
+      x->of_slot.resize((size_t)n_rep);
+      x->attempts.resize((size_t)std::max(0, n_rep - 1));
+      x->accepts.resize((size_t)std::max(0, n_rep - 1));
+      x->identity();
+    }
   }
   const int copies = s->copies();
   const int n = sys->n, dtype = sys->dtype;
@@ -1426,32 +1454,19 @@ int mm_load(mythos_martini_sim_t* s, const void* pos, const void* vel, const dou
   return s->sys->dtype == MYTHOS_F32 ? mm_load_typed<float>(s, (const float*)pos, (const float*)vel, box, st)
                                      : mm_load_typed<double>(s, (const double*)pos, (const double*)vel, box, st);
 }
+
+// Without events the call is ONE mm_advance_typed - one md_drive - with the caller's save_every; its rows all have the box,
+// ladder and windows of the load, and a call that failed has none.
 int mm_advance(mythos_martini_sim_t* s, int n_steps, int save_every, bool close, void* traj, double* e_trace, hipStream_t st) {
   if (int rc = mm_sync_charges(s, st)) return rc;
-  if (mm_window_exchange_on(s)) {  // chunks that end at window-exchange events (martini_window_exchange.inc)
-    const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_windows<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
-                                               : mm_advance_windows<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
-    mm_constant_ladder(s);
-    return rc;
-  }
-  if (mm_exchange_on(s)) {  // chunks that end at exchange and coupling events (martini_exchange.inc)
-    const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_events<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
-                                               : mm_advance_events<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
-    mm_constant_windows(s);
-    return rc;
-  }
-  if (mm_barostat_on(s)) {  // chunks that end at coupling events (martini_npt.inc); off: the call below, as ever
-    const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_npt<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
-                                               : mm_advance_npt<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
-    mm_constant_ladder(s);
-    mm_constant_windows(s);
-    return rc;
-  }
-  const int rc = s->sys->dtype == MYTHOS_F32 ? mm_advance_typed<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
-                                             : mm_advance_typed<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
-  mm_constant_boxes(s, rc == MYTHOS_OK && save_every > 0 ? n_steps / save_every : 0);
-  mm_constant_ladder(s);
-  mm_constant_windows(s);
+  mm_clear_logs(s);
+  const bool f32 = s->sys->dtype == MYTHOS_F32;
+  if (mm_barostat_on(s) || mm_exchange_on(s) || mm_window_exchange_on(s))
+    return f32 ? mm_advance_chunked<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
+               : mm_advance_chunked<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+  const int rc = f32 ? mm_advance_typed<float>(s, n_steps, save_every, close, (float*)traj, e_trace, st)
+                     : mm_advance_typed<double>(s, n_steps, save_every, close, (double*)traj, e_trace, st);
+  for (int r = 0; rc == MYTHOS_OK && save_every > 0 && r < n_steps / save_every; ++r) mm_push_row(s);
   return rc;
 }
 int mm_store(mythos_martini_sim_t* s, void* pos, void* vel, hipStream_t st) {
@@ -1528,10 +1543,8 @@ int mythos_martini_langevin_restart(mythos_martini_sim_t* s, const uint64_t* see
   s->seed = seeds[0];
   for (int r = 0; r < s->n_rep; ++r) s->rep_seed[r] = seeds[r];
   if (s->n_rep > 0) {  // the ladder back to the identity, every slot at the kT it was created with; the counts to zero
-    for (int r = 0; r < s->n_rep; ++r) s->xchg.rung_of_slot[r] = r;
+    s->xchg.identity();
     mm_apply_ladder(s);
-    std::fill(s->xchg.attempts.begin(), s->xchg.attempts.end(), 0);
-    std::fill(s->xchg.accepts.begin(), s->xchg.accepts.end(), 0);
   }
   s->step = step;
   s->rst.stamp_stale = true;

@@ -17,7 +17,9 @@
 // mu = exp(ln mu): GROMACS' Berendsen scales by the linear 1 - f (P0 - P) / 3, which differs from this at O(f^2).
 //
 // The pressure kernel reads a CLOSED frame (velocities after the closing half kick) and writes nothing but its partials:
-// the chunk in front of an event ends on the step kernel's closing launch (md_drive, close = true).
+// the chunk in front of an event ends on the step kernel's closing launch (md_drive, close = true).  The loop that cuts an
+// advance at the events is mm_advance_chunked (martini_md.hip), one for coupling and both exchanges; the row logs it keeps
+// are mm_clear_logs / mm_push_row below.
 
 namespace mythos {
 
@@ -285,16 +287,18 @@ static bool mm_barostat_on(const mythos_martini_sim* sim) {
   return b.kind != 0 && (b.beta[0] > 0 || (b.coupling == 1 && b.beta[1] > 0));
 }
 
-// the boxes of the resident state, one per copy, as a row of last_boxes
-static void mm_push_boxes(mythos_martini_sim* sim) {
+// The row logs of an advance - last_boxes, and for an ensemble handle the rows of ladder and windows - are kept here and
+// nowhere else: cleared, with both attempt logs, at the head of every advance, and pushed together at the moment a row is
+// saved, so all three always hold the same number of rows.
+static void mm_clear_logs(mythos_martini_sim* sim) {
+  sim->baro.last_boxes.clear();
+  for (MmPairExchange* x : {&sim->xchg, &sim->wx}) x->last_rows.clear(), x->last_log.clear();
+}
+static void mm_push_row(mythos_martini_sim* sim) {
   const double* b = sim->box_of(0);  // (an ensemble's are contiguous)
   sim->baro.last_boxes.insert(sim->baro.last_boxes.end(), b, b + 3 * (size_t)sim->copies());
-}
-
-// no barostat: every saved row has the box of the load
-static void mm_constant_boxes(mythos_martini_sim* sim, int rows) {
-  sim->baro.last_boxes.clear();
-  for (int r = 0; r < rows; ++r) mm_push_boxes(sim);
+  if (sim->n_rep == 0) return;  // a single copy has neither ladder nor windows
+  for (MmPairExchange* x : {&sim->xchg, &sim->wx}) x->last_rows.insert(x->last_rows.end(), x->of_slot.begin(), x->of_slot.end());
 }
 
 static int mm_npt_buffers(mythos_martini_sim* sim) {
@@ -302,11 +306,7 @@ static int mm_npt_buffers(mythos_martini_sim* sim) {
   const int blocks = sim->copies() * ((sim->sys->n + kMmPPB - 1) / kMmPPB);
   if (int rc = b.d_part.grow((size_t)blocks * kMmVir)) return rc;
   if (int rc = b.d_rec.grow((size_t)sim->copies() * kNptRec)) return rc;
-  if (!b.h_rec) {  // (the number of copies is fixed at create)
-    MYTHOS_HIP_TRY(hipHostMalloc((void**)&b.h_rec, (size_t)sim->copies() * kNptRec * sizeof(double), hipHostMallocDefault));
-    MYTHOS_HIP_TRY(hipHostGetDevicePointer((void**)&b.d_hrec, b.h_rec, 0));
-  }
-  return MYTHOS_OK;
+  return b.rec.grow((size_t)sim->copies() * kNptRec);  // (the number of copies is fixed at create)
 }
 
 // Pressure of the resident frame - closed, with rows built for it - into the records; with `event` the coupling
@@ -352,13 +352,13 @@ static int mm_pressure_typed(mythos_martini_sim* sim, bool event, hipStream_t st
       for (int d = 0; d < 3; ++d) a.box[d] = sim->box_of(r)[d];
       a.kTp = kBarPerKjMolNm3 * sim->rep_kT[r], a.seed = sim->rep_seed[r];
       hipLaunchKernelGGL(mm_barostat_kernel, dim3(1), dim3(256), 0, st, (const double*)b.d_part.get() + (size_t)r * blocks_per_rep * kMmVir,
-                         blocks_per_rep, a, b.d_rec.get() + (size_t)r * kNptRec, b.d_hrec + (size_t)r * kNptRec);
+                         blocks_per_rep, a, b.d_rec.get() + (size_t)r * kNptRec, b.rec.dev() + (size_t)r * kNptRec);
     }
     if (event)
       hipLaunchKernelGGL(mm_scale_ens_kernel<R>, dim3((sim->n_all() + 255) / 256), dim3(256), 0, st, n, sim->n_rep, (const double*)b.d_rec.get(),
                          b.kind == 2 ? 1 : 0, frame, (V4*)sim->vel.get());
   } else {
-    hipLaunchKernelGGL(mm_barostat_kernel, dim3(1), dim3(256), 0, st, (const double*)b.d_part.get(), blocks, a, b.d_rec.get(), b.d_hrec);
+    hipLaunchKernelGGL(mm_barostat_kernel, dim3(1), dim3(256), 0, st, (const double*)b.d_part.get(), blocks, a, b.d_rec.get(), b.rec.dev());
     if (event)
       hipLaunchKernelGGL(mm_scale_kernel<R>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const double*)b.d_rec.get(), b.kind == 2 ? 1 : 0, frame,
                          (V4*)sim->vel.get());
@@ -366,9 +366,10 @@ static int mm_pressure_typed(mythos_martini_sim* sim, bool event, hipStream_t st
   MYTHOS_HIP_TRY(hipGetLastError());
   MYTHOS_HIP_TRY(hipStreamSynchronize(st));
   if (!event) return MYTHOS_OK;
+  const double* h_rec = b.rec.host();
   if (ens) {  // R boxes behind the one synchronisation; the replica tables follow them, queued in front of the next launch
     for (int r = 0; r < sim->n_rep; ++r) {
-      const double* h = b.h_rec + (size_t)r * kNptRec;
+      const double* h = h_rec + (size_t)r * kNptRec;
       if (h[kRecOk] == 0.0) {
         set_error("mythos_martini_langevin_run: the pressure coupling at step " + std::to_string(sim->step) + " would make the box of replica " +
                   std::to_string(r) + " smaller than twice (r_cut + skin), or not finite - edges " + std::to_string(h[kRecBox]) + ", " +
@@ -378,51 +379,22 @@ static int mm_pressure_typed(mythos_martini_sim* sim, bool event, hipStream_t st
       }
     }
     for (int r = 0; r < sim->n_rep; ++r)
-      for (int d = 0; d < 3; ++d) sim->rep_box[3 * (size_t)r + d] = b.h_rec[(size_t)r * kNptRec + kRecBox + d];
+      for (int d = 0; d < 3; ++d) sim->rep_box[3 * (size_t)r + d] = h_rec[(size_t)r * kNptRec + kRecBox + d];
     if (int rc = mm_upload_reps(sim, st)) return rc;
     sim->list_valid = false;
     sim->since_build = 0;
     return MYTHOS_OK;
   }
-  if (b.h_rec[kRecOk] == 0.0) {
+  if (h_rec[kRecOk] == 0.0) {
     set_error("mythos_martini_langevin_run: the pressure coupling at step " + std::to_string(sim->step) +
-              " would make the box smaller than twice (r_cut + skin), or not finite - edges " + std::to_string(b.h_rec[kRecBox]) + ", " +
-              std::to_string(b.h_rec[kRecBox + 1]) + ", " + std::to_string(b.h_rec[kRecBox + 2]) +
+              " would make the box smaller than twice (r_cut + skin), or not finite - edges " + std::to_string(h_rec[kRecBox]) + ", " +
+              std::to_string(h_rec[kRecBox + 1]) + ", " + std::to_string(h_rec[kRecBox + 2]) +
               ": minimum image breaks down (the state of that step stays resident, unscaled)");
     return MYTHOS_ERR_INVALID_ARGUMENT;
   }
-  for (int d = 0; d < 3; ++d) sim->box[d] = b.h_rec[kRecBox + d];
+  for (int d = 0; d < 3; ++d) sim->box[d] = h_rec[kRecBox + d];
   sim->list_valid = false;
   sim->since_build = 0;
-  return MYTHOS_OK;
-}
-
-// n_steps with coupling events: chunks that end at the next event step (absolute step counter), the next saved row (counted
-// from the call's first step, as without a barostat) or the end of the call, each one call of mm_advance_typed - md_drive
-// as it is.  A chunk that ends at an event closes (the event needs p_s); every other boundary leaves the frame open, and
-// the launches on either side of it are those of one longer call.  A saved row is the state BEFORE the event of its step,
-// with the box it was integrated in.
-template <typename R>
-static int mm_advance_npt(mythos_martini_sim* sim, int n_steps, int save_every, bool close, R* traj_pos, double* e_trace, hipStream_t st) {
-  MmBarostat& b = sim->baro;
-  b.last_boxes.clear();
-  if (n_steps == 0) return mm_advance_typed<R>(sim, 0, save_every, close, traj_pos, e_trace, st);
-  const size_t row_reals = (size_t)sim->n_all() * 3;
-  int done = 0, rows = 0, rebuilds = 0, recoveries = 0, launches = 0;
-  while (done < n_steps) {
-    const MmNptChunk c = mm_npt_chunk(sim->step, b.every, done, n_steps, save_every);  // (martini_ensemble_checks.h)
-    const int len = c.len;
-    const bool event = c.event, save = c.save, last = c.last;
-    const int rc = mm_advance_typed<R>(sim, len, save ? len : 0, event || (last && close), traj_pos ? traj_pos + rows * row_reals : nullptr,
-                                       e_trace ? e_trace + mm_row_offset(rows, sim->copies(), sim->trace_width()) : nullptr, st);
-    rebuilds += sim->last_rebuilds, recoveries += sim->last_recoveries, launches += sim->last_launches;
-    sim->last_rebuilds = rebuilds, sim->last_recoveries = recoveries, sim->last_launches = launches;
-    if (rc) return rc;
-    if (save) mm_push_boxes(sim), ++rows;
-    if (event)
-      if (int re = mm_pressure_typed<R>(sim, true, st)) return re;
-    done += len;
-  }
   return MYTHOS_OK;
 }
 
@@ -479,7 +451,7 @@ int mythos_martini_langevin_pressure_ensemble(mythos_martini_sim_t* s, double* o
       return rc;
   if (int rc = f32 ? mm_pressure_typed<float>(s, false, st) : mm_pressure_typed<double>(s, false, st)) return rc;
   for (int c = 0; c < s->copies(); ++c, out += 10) {
-    const double* r = s->baro.h_rec + (size_t)c * kNptRec;
+    const double* r = s->baro.rec.host() + (size_t)c * kNptRec;
     for (int d = 0; d < 3; ++d) out[d] = r[kRecK + d], out[3 + d] = r[kRecW + d], out[6 + d] = r[kRecP + d];
     out[9] = r[kRecV];
   }

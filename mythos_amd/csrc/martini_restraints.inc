@@ -1,6 +1,7 @@
 // Host side of the MARTINI integrator's external forces (included by martini_md.hip; kernels: martini_restraints.h; the
 // checks and the lowering to per-bead term lists, which need no device: martini_restraint_checks.h).  Here: the upload of a
-// set, the evaluation path and the stored-frames launch.
+// set, the evaluation path and the stored-frames launch.  The kick itself is queued by mm_advance_typed's launches, so it runs
+// the same in the plain call and in every chunk of mm_advance_chunked (martini_md.hip).
 
 namespace mythos {
 
@@ -155,9 +156,7 @@ int mythos_martini_langevin_set_restraints(mythos_martini_sim_t* s, int n_posres
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
   MYTHOS_HIP_TRY(hipDeviceSynchronize());  // (launches that read the arrays replaced below)
   // the rows are the caller's again: window w lies in slot w, the window-exchange counts start over
-  for (int r = 0; r < s->n_rep; ++r) s->wx.window_of_slot[(size_t)r] = r;
-  std::fill(s->wx.attempts.begin(), s->wx.attempts.end(), 0);
-  std::fill(s->wx.accepts.begin(), s->wx.accepts.end(), 0);
+  s->wx.identity();
   return mr_install(s, a);
 }
 

@@ -3,7 +3,9 @@
 //
 // The rule is stated in include/mythos_hip.h (mythos_martini_langevin_set_window_exchange) and DESIGN.md section 3.5p; what
 // needs no device - the decision, the refusals, the row plan of set_windows - is martini_window_exchange_checks.h; pair
-// schedule, acceptance and chunking are those of temperature exchange (martini_exchange_checks.h).
+// schedule, acceptance and chunking are those of temperature exchange (martini_exchange_checks.h), and so are the record
+// (MmPairExchange, martini_md.hip), the host half of an event and the bodies of the C entry points (martini_exchange.inc).
+// The loop that cuts an advance at the events is mm_advance_chunked (martini_md.hip).
 //
 // Slots are the replicas as they lie in memory and keep beads, box, seed and kT.  The window of rung w is the parameter row
 // set_restraints was given for replica w: pr_ref[w], fb_param[w], p_param[w].  An accepted exchange SWAPS THE TWO ROWS in
@@ -108,15 +110,9 @@ __global__ __launch_bounds__(256) void mr_window_exchange_kernel(const MrView v,
 static bool mm_window_exchange_on(const mythos_martini_sim* sim) { return sim->n_rep >= 2 && sim->wx.every > 0; }
 
 static int mm_wx_buffers(mythos_martini_sim* sim) {
-  MmWindowExchange& w = sim->wx;
-  const size_t nr = (size_t)sim->n_rep;
-  if (!w.h_d) {  // (the number of replicas is fixed at create) out: R / 2 records; in: window R, out: window R
-    MYTHOS_HIP_TRY(hipHostMalloc((void**)&w.h_d, (nr / 2) * kWxRec * sizeof(double), hipHostMallocDefault));
-    MYTHOS_HIP_TRY(hipHostGetDevicePointer((void**)&w.d_hd, w.h_d, 0));
-    MYTHOS_HIP_TRY(hipHostMalloc((void**)&w.h_i, 2 * nr * sizeof(int), hipHostMallocDefault));
-    MYTHOS_HIP_TRY(hipHostGetDevicePointer((void**)&w.d_hi, w.h_i, 0));
-  }
-  return MYTHOS_OK;
+  const size_t nr = (size_t)sim->n_rep;  // (fixed at create)
+  if (int rc = sim->wx.h_d.grow((nr / 2) * kWxRec)) return rc;  // out: R / 2 records
+  return sim->wx.h_i.grow(2 * nr);                              // in: window R; out: window R
 }
 
 // The window-exchange event at the closed state of step sim->step: the centres of mass of the resident frame, the decision
@@ -124,7 +120,7 @@ static int mm_wx_buffers(mythos_martini_sim* sim) {
 // rows, as the temperature event does - what follows is the run of an ensemble loaded with this state and these rows.
 template <typename R>
 static int mm_window_exchange_event(mythos_martini_sim* sim, hipStream_t st) {
-  MmWindowExchange& w = sim->wx;
+  MmPairExchange& w = sim->wx;
   MmRestraints& q = sim->rst;
   const MrView& v = q.view;
   const int nr = sim->n_rep;
@@ -132,75 +128,20 @@ static int mm_window_exchange_event(mythos_martini_sim* sim, hipStream_t st) {
   const int n_pairs = mm_xchg_n_pairs(nr, attempt);
   if (n_pairs > 0) {
     // (the stream is idle behind the last event's synchronisation, or nothing queued on it reads these)
-    std::copy(w.window_of_slot.begin(), w.window_of_slot.end(), w.h_i);
-    std::copy(w.window_of_slot.begin(), w.window_of_slot.end(), w.h_i + nr);
+    std::copy(w.of_slot.begin(), w.of_slot.end(), w.h_i.host());
+    std::copy(w.of_slot.begin(), w.of_slot.end(), w.h_i.host() + nr);
     const R* frame = (const R*)sim->frame[sim->cur].get();
     if (v.n_pull > 0) hipLaunchKernelGGL(mr_com_kernel<R>, dim3(v.n_rep * v.n_groups), dim3(256), 0, st, v, frame, 4, q.d_rows.get());
     MmWxArgs a;
     a.n_rep = nr, a.kT = sim->rep_kT[0], a.s = double(sim->step), a.seed = w.seed, a.step = sim->step, a.attempt = attempt;
     hipLaunchKernelGGL(mr_window_exchange_kernel<R>, dim3(n_pairs), dim3(256), 0, st, v, frame, 4, (const double*)q.d_rows.get(), a,
-                       (const int*)w.d_hi, q.d_pr_ref.get(), q.d_fb_param.get(), q.d_p_param.get(), w.d_hi + nr, w.d_hd);
+                       (const int*)w.h_i.dev(), q.d_pr_ref.get(), q.d_fb_param.get(), q.d_p_param.get(), w.h_i.dev() + nr, w.h_d.dev());
     MYTHOS_HIP_TRY(hipGetLastError());
     MYTHOS_HIP_TRY(hipStreamSynchronize(st));
-    if (!mm_is_permutation(w.h_i + nr, nr)) {  // (defensive: the kernel swaps pairs of a permutation)
-      set_error("mythos_martini_langevin_run: the window-exchange event at step " + std::to_string(sim->step) + " did not return a permutation");
-      return MYTHOS_ERR_HIP;
-    }
-    std::copy(w.h_i + nr, w.h_i + 2 * (size_t)nr, w.window_of_slot.begin());
-    w.last_log.insert(w.last_log.end(), w.h_d, w.h_d + (size_t)n_pairs * kWxRec);
-    for (int p = 0; p < n_pairs; ++p) {
-      const int t = (int)w.h_d[(size_t)p * kWxRec + 1];
-      ++w.attempts[(size_t)t];
-      if (w.h_d[(size_t)p * kWxRec + 10] != 0.0) ++w.accepts[(size_t)t];
-    }
+    if (int rc = mm_pair_exchange_take(sim, w, w.h_d.host(), n_pairs, "window-exchange")) return rc;
   }
   sim->list_valid = false;
   sim->since_build = 0;
-  return MYTHOS_OK;
-}
-
-static void mm_push_windows(mythos_martini_sim* sim) {
-  sim->wx.last_windows.insert(sim->wx.last_windows.end(), sim->wx.window_of_slot.begin(), sim->wx.window_of_slot.end());
-}
-// no window exchange in this call: every saved row has the assignment as it stands
-static void mm_constant_windows(mythos_martini_sim* sim) {
-  sim->wx.last_windows.clear();
-  sim->wx.last_log.clear();
-  if (sim->n_rep == 0) return;
-  const size_t rows = sim->baro.last_boxes.size() / (3 * (size_t)sim->n_rep);
-  for (size_t r = 0; r < rows; ++r) mm_push_windows(sim);
-}
-
-// n_steps with window-exchange events: the chunks of mm_event_chunk without coupling.  A chunk that ends at an event
-// closes; it carries no energy row of its own.  A saved row is the state before the event.
-template <typename R>
-static int mm_advance_windows(mythos_martini_sim* sim, int n_steps, int save_every, bool close, R* traj_pos, double* e_trace, hipStream_t st) {
-  MmWindowExchange& w = sim->wx;
-  if (!sim->rst.installed) {
-    set_error("mythos_martini_langevin_advance: window exchange is on and no set of restraints is installed: there are no windows to "
-              "exchange (mythos_martini_langevin_set_restraints first, or switch window exchange off)");
-    return MYTHOS_ERR_NOT_READY;
-  }
-  if (int rc = mm_wx_buffers(sim)) return rc;
-  sim->baro.last_boxes.clear();
-  w.last_windows.clear();
-  w.last_log.clear();
-  if (n_steps == 0) return mm_advance_typed<R>(sim, 0, save_every, close, traj_pos, e_trace, st);
-  const size_t row_reals = (size_t)sim->n_all() * 3;
-  int done = 0, rows = 0, rebuilds = 0, recoveries = 0, launches = 0;
-  while (done < n_steps) {
-    const MmEventChunk c = mm_event_chunk(sim->step, 0, w.every, done, n_steps, save_every);
-    double* e_row = (c.save && e_trace) ? e_trace + mm_row_offset(rows, sim->copies(), sim->trace_width()) : nullptr;
-    const int rc = mm_advance_typed<R>(sim, c.len, c.save ? c.len : 0, c.exchange || (c.last && close),
-                                       (c.save && traj_pos) ? traj_pos + rows * row_reals : nullptr, e_row, st);
-    rebuilds += sim->last_rebuilds, recoveries += sim->last_recoveries, launches += sim->last_launches;
-    sim->last_rebuilds = rebuilds, sim->last_recoveries = recoveries, sim->last_launches = launches;
-    if (rc) return rc;
-    if (c.save) mm_push_boxes(sim), mm_push_windows(sim), ++rows;
-    if (c.exchange)
-      if (int re = mm_window_exchange_event<R>(sim, st)) return re;
-    done += c.len;
-  }
   return MYTHOS_OK;
 }
 
@@ -209,7 +150,7 @@ static int mm_wx_move_rows(mythos_martini_sim* sim, const int32_t* want) {
   MmRestraints& q = sim->rst;
   const MrView& v = q.view;
   const int nr = sim->n_rep;
-  const std::vector<int32_t> plan = mm_wx_row_plan(sim->wx.window_of_slot.data(), want, nr);
+  const std::vector<int32_t> plan = mm_wx_row_plan(sim->wx.of_slot.data(), want, nr);
   struct Rows {
     double* d;
     size_t len;
@@ -243,7 +184,7 @@ int mythos_martini_langevin_set_window_exchange(mythos_martini_sim_t* s, int eve
   }
   if (int rc = mm_wx_check_settings(s->n_rep, every, who)) return rc;
   if (every > 0) {
-    if (int rc = mm_wx_check_kT(s->n_rep, s->xchg.ladder_kT.data(), who)) return rc;
+    if (int rc = mm_wx_check_kT(s->n_rep, s->ladder.kT.data(), who)) return rc;
     if (int rc = mm_wx_check_partners(mm_exchange_on(s), s->baro.kind != 0, who)) return rc;
     if (s->rst.installed && s->rst.view.n_pull > 0) {
       // (the set is on the device; the rows may have moved, which changes nothing in what is compared)
@@ -277,47 +218,24 @@ int mythos_martini_langevin_set_windows(mythos_martini_sim_t* s, const int32_t* 
   MYTHOS_HIP_TRY(hipSetDevice(s->device));
   MYTHOS_HIP_TRY(hipDeviceSynchronize());  // (launches that read the rows)
   if (int rc = mm_wx_move_rows(s, window_of_slot)) return rc;
-  std::copy(window_of_slot, window_of_slot + s->n_rep, s->wx.window_of_slot.begin());
+  std::copy(window_of_slot, window_of_slot + s->n_rep, s->wx.of_slot.begin());
   return MYTHOS_OK;
 }
 
 int mythos_martini_langevin_get_windows(const mythos_martini_sim_t* s, int32_t* window_of_slot) {
-  if (!s || !window_of_slot || s->n_rep < 1) {
-    set_error("mythos_martini_langevin_get_windows: an ensemble handle and an array of n_rep entries required");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  std::copy(s->wx.window_of_slot.begin(), s->wx.window_of_slot.end(), window_of_slot);
-  return MYTHOS_OK;
+  return mm_pair_get(s, &mythos_martini_sim::wx, window_of_slot, "mythos_martini_langevin_get_windows");
 }
 
 int mythos_martini_langevin_last_windows(const mythos_martini_sim_t* s, int32_t* rows, int* n_rows) {
-  if (!s || s->n_rep < 1 || (!rows && !n_rows)) {
-    set_error("mythos_martini_langevin_last_windows: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  if (n_rows) *n_rows = (int)(s->wx.last_windows.size() / (size_t)s->n_rep);
-  if (rows) std::copy(s->wx.last_windows.begin(), s->wx.last_windows.end(), rows);
-  return MYTHOS_OK;
+  return mm_pair_last_rows(s, &mythos_martini_sim::wx, rows, n_rows, "mythos_martini_langevin_last_windows");
 }
 
 int mythos_martini_langevin_last_window_exchanges(const mythos_martini_sim_t* s, double* rec, int* n) {
-  if (!s || (!rec && !n)) {
-    set_error("mythos_martini_langevin_last_window_exchanges: invalid argument");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  if (n) *n = (int)(s->wx.last_log.size() / kWxRec);
-  if (rec) std::copy(s->wx.last_log.begin(), s->wx.last_log.end(), rec);
-  return MYTHOS_OK;
+  return mm_pair_last_log(s, &mythos_martini_sim::wx, rec, n, "mythos_martini_langevin_last_window_exchanges");
 }
 
 int mythos_martini_langevin_window_exchange_counts(const mythos_martini_sim_t* s, int64_t* attempts, int64_t* accepts) {
-  if (!s || s->n_rep < 2 || !attempts || !accepts) {
-    set_error("mythos_martini_langevin_window_exchange_counts: an ensemble handle with n_rep >= 2 and two arrays of n_rep - 1 entries required");
-    return MYTHOS_ERR_INVALID_ARGUMENT;
-  }
-  std::copy(s->wx.attempts.begin(), s->wx.attempts.end(), attempts);
-  std::copy(s->wx.accepts.begin(), s->wx.accepts.end(), accepts);
-  return MYTHOS_OK;
+  return mm_pair_counts(s, &mythos_martini_sim::wx, attempts, accepts, "mythos_martini_langevin_window_exchange_counts");
 }
 
 }  // extern "C"

@@ -31,8 +31,7 @@ struct MdRun {
   // control words as the device published them at the end of a segment: [0..3] d_flags, [4..6] the list builder's
   // overflow words.  Pinned host memory the publishing kernel writes directly: one stream synchronisation per segment
   // and no copy commands.
-  int* h_ctl = nullptr;
-  int* d_ctl = nullptr;  // device address of h_ctl
+  PinnedBuf<int> ctl;
   double last_avg_ms = 0;     // (ev1 - ev0) / launches: includes rebuilds and inter-kernel gaps
   double last_kernel_ms = 0;  // mean over the sampled single-launch intervals
   int last_launches = 0, last_samples = 0;
@@ -44,7 +43,6 @@ struct MdRun {
   MdRun& operator=(const MdRun&) = delete;
   // (the owner's destructor has selected the device; what md_run_create did not get to is null)
   ~MdRun() {
-    if (h_ctl) (void)hipHostFree(h_ctl);
     for (hipEvent_t e : {ev0, ev1})
       if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < kMaxSamples; ++k) {
@@ -57,10 +55,8 @@ struct MdRun {
 // events, control words (cleared) and their pinned host copy; false on failure (the destructor frees what was made)
 inline bool md_run_create(MdRun& r) {
   bool ok = r.d_flags.alloc(MdRun::kCtlWords) == 0 && hipMemset(r.d_flags.get(), 0, MdRun::kCtlWords * sizeof(int)) == hipSuccess &&
-            hipHostMalloc((void**)&r.h_ctl, 8 * sizeof(int), hipHostMallocDefault) == hipSuccess &&
-            hipHostGetDevicePointer((void**)&r.d_ctl, r.h_ctl, 0) == hipSuccess &&
-            hipEventCreate(&r.ev0) == hipSuccess && hipEventCreate(&r.ev1) == hipSuccess;
-  if (ok) std::fill(r.h_ctl, r.h_ctl + 8, 0);
+            r.ctl.alloc(8) == 0 && hipEventCreate(&r.ev0) == hipSuccess && hipEventCreate(&r.ev1) == hipSuccess;
+  if (ok) std::fill(r.ctl.host(), r.ctl.host() + 8, 0);
   for (int k = 0; ok && k < MdRun::kMaxSamples; ++k)
     ok = hipEventCreate(&r.sa[k]) == hipSuccess && hipEventCreate(&r.sb[k]) == hipSuccess;
   return ok;
@@ -233,10 +229,10 @@ static int md_drive(MdRun& run, const MdDrive& d, Launch&& launch, Rebuild&& reb
       cur ^= 1;
     }
     if (timing && k >= n_launch) MYTHOS_HIP_TRY(hipEventRecord(run.ev1, st));
-    hipLaunchKernelGGL(publish_ctl_kernel, dim3(1), dim3(1), 0, st, run.d_flags.get(), (const int*)d.halt_words, run.d_ctl);
+    hipLaunchKernelGGL(publish_ctl_kernel, dim3(1), dim3(1), 0, st, run.d_flags.get(), (const int*)d.halt_words, run.ctl.dev());
     MYTHOS_HIP_TRY(hipGetLastError());
     MYTHOS_HIP_TRY(hipStreamSynchronize(st));
-    const int* ctl = run.h_ctl;
+    const int* ctl = run.ctl.host();
     if (ctl[0] & 2) {  // NaN: the state is lost
       drop_list();
       run.resident = false;

@@ -957,6 +957,38 @@ class _MartiniEnsembleHandle(MartiniLangevinIntegrator):
         _lib.check(self._lib.mythos_martini_langevin_restart(self._h, sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(step)), "restart")
         self.seeds = sd.copy()
 
+    # ---- what the two exchanges' readers share: `name` is the C entry point behind "mythos_martini_langevin_" ----
+    def _permutation(self, name: str) -> np.ndarray:
+        a = np.zeros(self.n_rep, dtype=np.int32)
+        _lib.check(getattr(self._lib, "mythos_martini_langevin_" + name)(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), name)
+        return a.astype(np.int64)
+
+    def _counted(self, name: str, width: int, dtype, ctype) -> np.ndarray:
+        """The (rows, width) array behind a (handle, array or NULL, count) entry point: count, then fill."""
+        fn, n = getattr(self._lib, "mythos_martini_langevin_" + name), C.c_int(0)
+        _lib.check(fn(self._h, None, C.byref(n)), name)
+        a = np.zeros((n.value, width), dtype=dtype)
+        if n.value:
+            _lib.check(fn(self._h, a.ctypes.data_as(C.POINTER(ctype)), C.byref(n)), name)
+        return a
+
+    def _last_rows(self, name: str) -> torch.Tensor:
+        return torch.as_tensor(self._counted(name, self.n_rep, np.int32, C.c_int32).astype(np.int64), device=self.system.device)
+
+    def _last_log(self, name: str, fields: tuple) -> dict:
+        rec = self._counted(name, len(fields), np.float64, C.c_double)
+        out = {k: rec[:, j].copy() for j, k in enumerate(fields)}
+        for k in ("step", "rung", "slot_a", "slot_b"):
+            out[k] = out[k].astype(np.int64)
+        out["accepted"] = out["accepted"] != 0.0
+        return out
+
+    def _counts(self, name: str) -> tuple[np.ndarray, np.ndarray]:
+        att, acc = np.zeros(self.n_rep - 1, dtype=np.int64), np.zeros(self.n_rep - 1, dtype=np.int64)
+        _lib.check(getattr(self._lib, "mythos_martini_langevin_" + name)(self._h, att.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                         acc.ctypes.data_as(C.POINTER(C.c_int64))), name)
+        return att, acc
+
     # ---- replica exchange between the temperatures (mythos_martini_langevin_set_exchange, include/mythos_hip.h) ----
     EXCHANGE_FIELDS = ("step", "rung", "slot_a", "slot_b", "u_a", "u_b", "v_a", "v_b", "d", "u", "accepted")
 
@@ -980,9 +1012,7 @@ class _MartiniEnsembleHandle(MartiniLangevinIntegrator):
     @property
     def ladder(self) -> np.ndarray:
         """(R,) int64: ``rung_of_slot`` of the resident state."""
-        a = np.zeros(self.n_rep, dtype=np.int32)
-        _lib.check(self._lib.mythos_martini_langevin_get_ladder(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), "get_ladder")
-        return a.astype(np.int64)
+        return self._permutation("get_ladder")
 
     @property
     def kT_now(self) -> np.ndarray:
@@ -993,35 +1023,18 @@ class _MartiniEnsembleHandle(MartiniLangevinIntegrator):
     def last_ladder(self) -> torch.Tensor:
         """(S, R) int64 on the system's device: ``rung_of_slot`` at every row the last call saved, each before the events of
         its step."""
-        n = C.c_int(0)
-        _lib.check(self._lib.mythos_martini_langevin_last_ladder(self._h, None, C.byref(n)), "last_ladder")
-        a = np.zeros((n.value, self.n_rep), dtype=np.int32)
-        if n.value:
-            _lib.check(self._lib.mythos_martini_langevin_last_ladder(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "last_ladder")
-        return torch.as_tensor(a.astype(np.int64), device=self.system.device)
+        return self._last_rows("last_ladder")
 
     @property
     def last_exchanges(self) -> dict:
         """The last call's attempts in order, a dict of (A,) arrays: ``step``, ``rung`` (the pair is rung, rung + 1),
         ``slot_a``, ``slot_b`` int64; ``u_a``, ``u_b`` (kJ/mol), ``v_a``, ``v_b`` (nm^3), ``d``, ``u`` float64; ``accepted``
         bool."""
-        n = C.c_int(0)
-        _lib.check(self._lib.mythos_martini_langevin_last_exchanges(self._h, None, C.byref(n)), "last_exchanges")
-        rec = np.zeros((n.value, len(self.EXCHANGE_FIELDS)), dtype=np.float64)
-        if n.value:
-            _lib.check(self._lib.mythos_martini_langevin_last_exchanges(self._h, rec.ctypes.data_as(_lib.c_double_p), C.byref(n)), "last_exchanges")
-        out = {k: rec[:, j].copy() for j, k in enumerate(self.EXCHANGE_FIELDS)}
-        for k in ("step", "rung", "slot_a", "slot_b"):
-            out[k] = out[k].astype(np.int64)
-        out["accepted"] = out["accepted"] != 0.0
-        return out
+        return self._last_log("last_exchanges", self.EXCHANGE_FIELDS)
 
     def exchange_counts(self) -> tuple[np.ndarray, np.ndarray]:
         """(attempts, accepts), (R - 1,) int64 each: per rung pair (t, t + 1) since ``restart``."""
-        att, acc = np.zeros(self.n_rep - 1, dtype=np.int64), np.zeros(self.n_rep - 1, dtype=np.int64)
-        _lib.check(self._lib.mythos_martini_langevin_exchange_counts(self._h, att.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                                     acc.ctypes.data_as(C.POINTER(C.c_int64))), "exchange_counts")
-        return att, acc
+        return self._counts("exchange_counts")
 
     # ---- window exchange between the rows of the installed restraints (mythos_martini_langevin_set_window_exchange) ----
     WINDOW_EXCHANGE_FIELDS = ("step", "rung", "slot_a", "slot_b", "e_t_a", "e_t1_a", "e_t_b", "e_t1_b", "d", "u", "accepted")
@@ -1042,44 +1055,24 @@ class _MartiniEnsembleHandle(MartiniLangevinIntegrator):
     @property
     def windows(self) -> np.ndarray:
         """(R,) int64: ``window_of_slot`` of the resident state."""
-        a = np.zeros(self.n_rep, dtype=np.int32)
-        _lib.check(self._lib.mythos_martini_langevin_get_windows(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), "get_windows")
-        return a.astype(np.int64)
+        return self._permutation("get_windows")
 
     @property
     def last_windows(self) -> torch.Tensor:
         """(S, R) int64 on the system's device: ``window_of_slot`` at every row the last call saved, each before the event
         of its step."""
-        n = C.c_int(0)
-        _lib.check(self._lib.mythos_martini_langevin_last_windows(self._h, None, C.byref(n)), "last_windows")
-        a = np.zeros((n.value, self.n_rep), dtype=np.int32)
-        if n.value:
-            _lib.check(self._lib.mythos_martini_langevin_last_windows(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "last_windows")
-        return torch.as_tensor(a.astype(np.int64), device=self.system.device)
+        return self._last_rows("last_windows")
 
     @property
     def last_window_exchanges(self) -> dict:
         """The last call's attempts in order, a dict of (A,) arrays: ``step``, ``rung`` (the pair is rung, rung + 1),
         ``slot_a``, ``slot_b`` int64; ``e_t_a``, ``e_t1_a``, ``e_t_b``, ``e_t1_b`` (kJ/mol: the restraint energy of slot
         A's / slot B's configuration under window rung / rung + 1), ``d``, ``u`` float64; ``accepted`` bool."""
-        n = C.c_int(0)
-        _lib.check(self._lib.mythos_martini_langevin_last_window_exchanges(self._h, None, C.byref(n)), "last_window_exchanges")
-        rec = np.zeros((n.value, len(self.WINDOW_EXCHANGE_FIELDS)), dtype=np.float64)
-        if n.value:
-            _lib.check(self._lib.mythos_martini_langevin_last_window_exchanges(self._h, rec.ctypes.data_as(_lib.c_double_p), C.byref(n)),
-                       "last_window_exchanges")
-        out = {k: rec[:, j].copy() for j, k in enumerate(self.WINDOW_EXCHANGE_FIELDS)}
-        for k in ("step", "rung", "slot_a", "slot_b"):
-            out[k] = out[k].astype(np.int64)
-        out["accepted"] = out["accepted"] != 0.0
-        return out
+        return self._last_log("last_window_exchanges", self.WINDOW_EXCHANGE_FIELDS)
 
     def window_exchange_counts(self) -> tuple[np.ndarray, np.ndarray]:
         """(attempts, accepts), (R - 1,) int64 each: per rung pair (t, t + 1) since ``set_restraints``."""
-        att, acc = np.zeros(self.n_rep - 1, dtype=np.int64), np.zeros(self.n_rep - 1, dtype=np.int64)
-        _lib.check(self._lib.mythos_martini_langevin_window_exchange_counts(self._h, att.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                                            acc.ctypes.data_as(C.POINTER(C.c_int64))), "window_exchange_counts")
-        return att, acc
+        return self._counts("window_exchange_counts")
 
     def pressure(self) -> dict:
         """As :meth:`MartiniLangevinIntegrator.pressure`, per replica: ``kinetic``, ``virial``, ``pressure`` (R, 3),

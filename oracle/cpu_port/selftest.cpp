@@ -8,8 +8,9 @@
 // n_steps}, then types int32[n], bonds int32[n_bonds][2], angles int32[n_angles][3], box double[3], sigma and eps
 // double[n_types][n_types], bond k and r0 double[n_bonds], angle k and theta0 double[n_angles], mass, x and v double[n](,[3]);
 // evaluated and stepped once with G96 and once with harmonic angles.
-// `--device-buf` instead of a file: the owning buffer type of the library (mythos_amd/csrc/device_buf.h) over the shim's
-// malloc-backed runtime; prints what was read back and, after every scope, the live allocations (the test wants 0).
+// `--device-buf` instead of a file: the owning buffer types of the library (mythos_amd/csrc/device_buf.h: DeviceBuf, and
+// PinnedBuf for pinned host memory) over the shim's malloc-backed runtime; prints what was read back and, after every
+// scope, the live allocations (the test wants 0).
 // `--md-plan`: the launch plan of the oxDNA step kernel (mythos_amd/csrc/md_plan.h) for a fixed table of systems, one line
 // each: lanes per nucleotide, then nucleotides per workgroup, workgroups, grid, the DENSE choice and the priority switch.
 // `--index-lists`: the argument checks the *_create functions of the frame observables share (mythos_amd/csrc/host_checks.h):
@@ -111,6 +112,59 @@ struct FourBuffers {
   }
 };
 
+struct PinnedAndDevice {
+  mythos::DeviceBuf<int> a;
+  mythos::PinnedBuf<int> p, q;
+  int create() {
+    if (int rc = a.alloc(8)) return rc;
+    if (int rc = p.alloc(8)) return rc;
+    return q.alloc(8);
+  }
+};
+
+// the ownership rules of DeviceBuf again for PinnedBuf: 0, or the code of the first check that failed
+static int pinned_buf_checks() {
+  using mythos::PinnedBuf;
+  {
+    PinnedBuf<double> g;
+    if (g.grow(0) || g.host() != nullptr || g) return 70;  // nothing needed, nothing allocated
+    if (g.grow(16) || !g.host() || g.dev() != g.host()) return 71;  // (the shim's device reads at the host's address)
+    const double* p0 = g.host();
+    if (g.grow(16) || g.grow(7) || g.host() != p0 || g.capacity() != 16) return 72;
+    if (g.grow(17) || g.capacity() != 17) return 73;
+    memset(g.host(), 0, 17 * sizeof(double));  // (the sanitizer build checks the extent)
+    if (g.alloc(0) || !g.host() || g.capacity() != 1) return 74;  // never a zero-byte allocation
+    printf("PINNED grow cap %zu held %ld\n", g.capacity(), shim_live_allocations());
+  }
+  if (shim_live_allocations() != 0) return 75;
+  {
+    PinnedBuf<int> a;
+    if (a.alloc(4)) return 80;
+    int *pa = a.host(), *da = a.dev();
+    PinnedBuf<int> b(std::move(a));
+    if (a.host() != nullptr || a.dev() != nullptr || a.capacity() != 0 || b.host() != pa || b.dev() != da || b.capacity() != 4) return 81;
+    PinnedBuf<int> c;
+    if (c.alloc(2)) return 82;
+    c = std::move(b);  // frees c's own allocation
+    if (b.host() != nullptr || c.host() != pa || c.capacity() != 4) return 83;
+    printf("PINNED moved held %ld\n", shim_live_allocations());
+    c.reset();
+    if (c.host() != nullptr || c.dev() != nullptr || c.capacity() != 0 || c) return 84;
+    c.reset();  // twice: nothing to do
+    printf("PINNED reset held %ld\n", shim_live_allocations());
+  }
+  if (shim_live_allocations() != 0) return 85;
+  {
+    PinnedAndDevice h;
+    shim_fail_allocation_in() = 3;
+    const int rc = h.create();
+    printf("PINNED partial rc %d a %d p %d q %d held %ld: %s\n", rc, h.a ? 1 : 0, h.p ? 1 : 0, h.q ? 1 : 0, shim_live_allocations(),
+           mythos::g_error.c_str());
+    if (rc != MYTHOS_ERR_HIP || !h.p || h.q || h.q.dev() || h.q.capacity() != 0) return 90;
+  }
+  return shim_live_allocations() == 0 ? 0 : 91;
+}
+
 static int device_buf_case() {
   using mythos::DeviceBuf;
   using mythos::DeviceBytes;
@@ -180,6 +234,7 @@ static int device_buf_case() {
     if (rc != MYTHOS_ERR_HIP || h.c || h.d) return 50;
   }
   live("partial");
+  if (int rc = pinned_buf_checks()) return rc;
   {
     const int ok = mythos::select_device(0, "selftest"), bad = mythos::select_device(3, "selftest");
     printf("DEVBUF select %d %d: %s\n", ok, bad, mythos::g_error.c_str());

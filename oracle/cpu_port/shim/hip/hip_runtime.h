@@ -34,7 +34,7 @@ inline long& shim_live_allocations() {
   static long live = 0;
   return live;
 }
-inline long& shim_fail_allocation_in() {  // k > 0: the k-th hipMalloc from now fails (once); 0: none does
+inline long& shim_fail_allocation_in() {  // k > 0: the k-th hipMalloc / hipHostMalloc from now fails (once); 0: none does
   static long k = 0;
   return k;
 }
@@ -51,6 +51,14 @@ static inline hipError_t hipMalloc(void** p, size_t bytes) {
 static inline hipError_t hipFree(void* p) {
   if (p) free(p), --shim_live_allocations();
   return hipSuccess;
+}
+// pinned host memory: the same allocator, count and switch; the "device" reads it at the host's address
+enum { hipHostMallocDefault = 0 };
+static inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { return hipMalloc(p, bytes); }
+static inline hipError_t hipHostFree(void* p) { return hipFree(p); }
+static inline hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned) {
+  *dev = host;
+  return host ? hipSuccess : hipErrorInvalidValue;
 }
 static inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
   memcpy(dst, src, bytes);

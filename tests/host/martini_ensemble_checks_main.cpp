@@ -1,4 +1,4 @@
-// Stand-alone host program for mythos_amd/csrc/martini_ensemble_checks.h, built with -fsanitize=address,undefined by
+// Stand-alone host program for mythos_amd/csrc/martini_ensemble_checks.h and the chunking of martini_exchange_checks.h, built with -fsanitize=address,undefined by
 // tests/test_martini_ensemble_cpu.py: the refusals of the ensemble's creation and load on arrays of exactly the length
 // they are said to have, and the chunking of an advance under a barostat over R records per row, written into buffers of
 // exactly the size the C ABI documents.  Exit code 0 and "ok" on success.
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "martini_ensemble_checks.h"
+#include "martini_exchange_checks.h"
 
 namespace mythos {
 static std::string g_error;
@@ -52,7 +53,7 @@ int main() {
     CHECK(mm_box_fits(edge, 1.1 + 0.25, "t") == 0);
     CHECK(mm_box_fits(nullptr, 1.35, "t") == -1);
   }
-  // ---- chunking: every combination walks the call as mm_advance_npt does and writes its rows
+  // ---- chunking: every combination walks the call as mm_advance_chunked does under a barostat alone and writes its rows
   long chunks = 0;
   for (int copies : {1, 3, 16})
     for (int every : {1, 2, 3, 10, 12})
@@ -65,10 +66,10 @@ int main() {
             int64_t step = step0;
             int done = 0, rows = 0, events = 0;
             while (done < n_steps) {
-              const MmNptChunk c = mm_npt_chunk(step, every, done, n_steps, save_every);
+              const MmEventChunk c = mm_event_chunk(step, every, 0, done, n_steps, save_every);
               CHECK(c.len >= 1 && done + c.len <= n_steps);
               step += c.len, done += c.len, ++chunks;
-              CHECK(c.event == (step % every == 0));
+              CHECK(c.couple == (step % every == 0) && !c.exchange);
               CHECK(c.save == (save_every > 0 && done % save_every == 0));
               CHECK(c.last == (done == n_steps));
               if (c.save) {
@@ -81,7 +82,7 @@ int main() {
                 }
                 ++rows;
               }
-              if (c.event) ++events;
+              if (c.couple) ++events;
             }
             CHECK(done == n_steps && rows == n_rows);
             CHECK(events == (int)((step0 + n_steps) / every - step0 / every));

@@ -1,6 +1,6 @@
 // Stand-alone host program for mythos_amd/csrc/martini_exchange_checks.h, built with -fsanitize=address,undefined by
 // tests/test_martini_exchange_cpu.py: the pair schedule of replica exchange, the chunking of an advance with coupling and
-// exchange events against a step-by-step loop, the permutation check, the choice of the reference pressure, every refusal,
+// exchange events against a step-by-step loop, what mm_chunk_plan hands the integrator for every chunk, the permutation check, the choice of the reference pressure, every refusal,
 // and detailed balance through the real mm_xchg_accept.  Exit code 0 and "ok" on success.
 // With the argument "flip" the detailed-balance chain negates d before it asks mm_xchg_accept: the program then has to fail.
 #include <cstdio>
@@ -51,6 +51,24 @@ static int walk_chunks(int64_t& step, int couple, int exchange, int n_steps, int
   return 0;
 }
 
+// the plan of every chunk of one call against its rules, written out; kind none: a call without exchange events
+static int walk_plans(int64_t& step, int couple, int exchange, int n_steps, int save_every, MmExchangeKind kind, bool close, bool energies,
+                      long& plans) {
+  int done = 0;
+  while (done < n_steps) {
+    const MmEventChunk c = mm_event_chunk(step, couple, kind == kMmNoExchange ? 0 : exchange, done, n_steps, save_every);
+    const MmChunkPlan p = mm_chunk_plan(c, close, kind, energies);
+    step += c.len, done += c.len, ++plans;
+    CHECK(p.close == (c.couple || c.exchange || (c.last && close)));
+    CHECK(p.save_every == ((c.save || (c.exchange && kind == kMmTemperatureExchange)) ? c.len : 0));
+    CHECK((p.energy == kMmCallerRow) == (c.save && energies));
+    CHECK((p.energy == kMmScratchRow) == (kind == kMmTemperatureExchange && c.exchange && !(c.save && energies)));
+    CHECK(p.energy == kMmNoEnergyRow || p.save_every == c.len);  // an energy row is a saved row of the chunk's call
+    if (kind != kMmTemperatureExchange) CHECK(p.energy == kMmNoEnergyRow || (c.save && energies));  // never a row the caller did not ask for
+  }
+  return 0;
+}
+
 static void walk_steps(int64_t& step, int couple, int exchange, int n_steps, int save_every, std::vector<Mark>& out) {
   for (int k = 1; k <= n_steps; ++k) {
     ++step;
@@ -79,7 +97,7 @@ int main(int argc, char** argv) {
   CHECK(mm_xchg_n_pairs(1, 1) == 0 && mm_xchg_n_pairs(1, 2) == 0);
 
   // ---- chunks against the step loop: (coupling every, exchange every, save_every), one call and split calls
-  long chunks = 0;
+  long chunks = 0, plans = 0;
   const int combos[4][3] = {{3, 6, 3}, {4, 6, 5}, {0, 4, 0}, {3, 4, 1}};
   const std::vector<std::vector<int>> calls = {{48}, {10, 14, 24}, {1, 1, 46}, {12, 12, 12, 12}};
   for (const auto& cb : combos)
@@ -93,6 +111,13 @@ int main(int argc, char** argv) {
         }
         CHECK(sa == sb && got.size() == want.size());
         for (size_t k = 0; k < got.size(); ++k) CHECK(got[k] == want[k]);
+        for (MmExchangeKind kind : {kMmNoExchange, kMmTemperatureExchange, kMmWindowExchange})
+          for (int flags = 0; flags < 4; ++flags) {
+            int64_t sp = step0;
+            for (int n : split)
+              if (walk_plans(sp, cb[0], cb[1], n, cb[2], kind, (flags & 1) != 0, (flags & 2) != 0, plans)) return 1;
+            CHECK(sp == sb);
+          }
         if (step0 == 0 && cb[0] == 3 && cb[1] == 6 && cb[2] == 3 && split.size() == 1) {
           // steps 6, 12, ...: a row, an exchange and a coupling event together, in that order
           size_t k = 0;
@@ -182,6 +207,6 @@ int main(int argc, char** argv) {
     for (int s = 0; s < R; ++s)
       for (int t = 0; t < R; ++t) CHECK(visited[s][t]);
   }
-  std::printf("ok (%ld chunks)\n", chunks);
+  std::printf("ok (%ld chunks, %ld plans)\n", chunks, plans);
   return 0;
 }

@@ -299,6 +299,10 @@ def test_sanitizers_are_clean_and_agree_with_the_plain_build(tmp_path):
     assert "DEVBUF upload 3 5 6 cap 8" in lines and "DEVBUF grow cap 17 held 1" in lines
     partial = next(ln for ln in lines if ln.startswith("DEVBUF partial rc"))
     assert partial.startswith("DEVBUF partial rc -2 a 1 b 1 c 0 d 0 held 2: HIP error: out of memory")
+    # PinnedBuf, the owner of pinned host memory, under the same rules
+    assert "PINNED grow cap 1 held 1" in lines and "PINNED moved held 1" in lines and "PINNED reset held 0" in lines
+    pinned = next(ln for ln in lines if ln.startswith("PINNED partial rc"))
+    assert pinned.startswith("PINNED partial rc -2 a 1 p 1 q 0 held 2: HIP error: out of memory")
 
 
 def test_md_launch_plan_boundaries():

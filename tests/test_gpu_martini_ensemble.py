@@ -321,6 +321,8 @@ def test_a_replica_box_under_the_limit_names_the_replica_and_scales_nobody():
         if baro:
             with pytest.raises(ValueError, match=r"box of replica 1 smaller than twice \(r_cut \+ skin\)"):
                 integ.advance(50, save_every=1, want_energy=False)
+            # the rows saved before the refusal stay, the same number in every log
+            assert integ.last_boxes.shape[0] == integ.last_ladder.shape[0] == integ.last_windows.shape[0]
         else:
             integ.advance(1)
         assert integ.step == 1

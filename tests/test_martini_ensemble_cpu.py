@@ -157,8 +157,8 @@ def test_lowering_follows_with_params_and_equals_the_terms_own_tables():
 
 def test_host_checks_and_npt_chunking_under_the_host_sanitizers(tmp_path):
     """tests/host/martini_ensemble_checks_main.cpp - a stand-alone program with its own main over
-    mythos_amd/csrc/martini_ensemble_checks.h (the refusals, the chunking of an advance under a barostat over R records per
-    row) - built with -fsanitize=address,undefined and run: exit code 0, nothing reported."""
+    mythos_amd/csrc/martini_ensemble_checks.h (the refusals) and mm_event_chunk of martini_exchange_checks.h with coupling
+    events alone (the chunking of an advance under a barostat over R records per row) - built with -fsanitize=address,undefined and run: exit code 0, nothing reported."""
     import os
     import subprocess
     from pathlib import Path
