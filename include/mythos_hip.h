@@ -11,6 +11,11 @@
  *
  * Conventions
  *   - plain C, no torch / HIP types: streams are passed as void* (a hipStream_t, NULL = default).
+ *   - stream order: an entry that takes a stream reads its device inputs and writes its device outputs in the order of
+ *     THAT stream (the caller orders its inputs on it and consumes the outputs on it, or waits for it); its comment says
+ *     whether the call is asynchronous or synchronises the stream.  An entry without a stream parameter that replaces
+ *     or reads back device data synchronises the DEVICE first, so it is safe against launches queued on any stream,
+ *     non-blocking ones included; entries that only touch host numbers say so.  INTEGRATION.md, "Streams", has the table.
  *   - "dev" pointers are device memory owned by the caller (PyTorch tensors) and only borrowed;
  *     "host" pointers are read during the call and may be freed afterwards.
  *   - dtype: 0 = float32 state/arithmetic, 1 = float64.  Energies and dU/dparams are always
@@ -92,12 +97,13 @@ mythos_system_t* mythos_oxdna_create(int model, int n, const int32_t* seq, const
                                      const int32_t* bonded, const double* box, int dtype, int device);
 void mythos_oxdna_destroy(mythos_system_t* sys);
 
-/* host double[n_params] in mythos_oxdna_param_name() order (oxNA: three such vectors); replaces with_params() at the boundary */
+/* host double[n_params] in mythos_oxdna_param_name() order (oxNA: three such vectors); replaces with_params() at the boundary.
+ * Synchronises the device before the tables are replaced: a launch queued earlier, on any stream, sees the old vector whole. */
 int mythos_oxdna_set_params(mythos_system_t* sys, const double* flat_params, int n_params);
 
 /* oxNA (model 4) only: which nucleotides are RNA - the `nt_type` every na1 *Configuration carries
  * (mythos/energy/na1/fene.py:22, mythos/input/topology.py NucleotideType; is_rna_pair / is_dna_rna_pair in
- * mythos/energy/na1/utils.py:9-16).  host uint8[n], 1 = RNA, 0 = DNA. */
+ * mythos/energy/na1/utils.py:9-16).  host uint8[n], 1 = RNA, 0 = DNA.  Synchronises the device before the table is replaced. */
 int mythos_oxdna_set_nucleotide_types(mythos_system_t* sys, const uint8_t* is_rna);
 
 /* Probabilistic sequence: replaces `pseq` / `pseq_constraints` of StackingConfiguration and
@@ -111,7 +117,8 @@ int mythos_oxdna_set_nucleotide_types(mythos_system_t* sys, const uint8_t* is_rn
  *   terms      bit 0: stacking, bit 1: hydrogen bonding use the expectation; 0 switches back to the discrete sequence
  * The Langevin integrator steps such a system too (since round 3): the stepping kernel has instantiations whose two
  * weight look-ups are the expectations (md_step_kernel<..., PSEQ>), as the reference's configurations carry pseq into
- * any energy function, the one a simulator steps with included (dna1/stacking.py:284-285, hydrogen_bonding.py:330-331). */
+ * any energy function, the one a simulator steps with included (dna1/stacking.py:284-285, hydrogen_bonding.py:330-331).
+ * Synchronises the device before the tables are replaced: a launch queued earlier, on any stream, sees the old distribution whole. */
 int mythos_oxdna_set_pseq(mythos_system_t* sys, const double* marginals, const int32_t* unit, int n_bp,
                           const double* bp_probs, int terms);
 
@@ -124,20 +131,26 @@ int mythos_oxdna_set_pseq(mythos_system_t* sys, const double* marginals, const i
  *                                                        constrained base pair
  * in the layout mythos_oxdna_set_pseq took; the host carries them to the reference's (unpaired, base-pair) arrays - a
  * paired nucleotide's marginal is a sum of its pair's type probabilities.  Accumulated with fp64 atomics: equal to
- * rounding between runs, not bit for bit.  Needs mythos_oxdna_set_pseq with terms != 0. */
+ * rounding between runs, not bit for bit.  Needs mythos_oxdna_set_pseq with terms != 0.  Asynchronous on the stream, as
+ * mythos_oxdna_energy. */
 int mythos_oxdna_energy_dpseq(mythos_system_t* sys, const void* center, const void* quat, int n_frames, double* e_terms,
                               void* dU_dcenter, void* dU_dquat, double* dU_dparams, double* dU_dmarginals, double* dU_dbp,
                               mythos_stream_t stream);
 
 /* Unbonded pair list, reference semantics (NoNeighborList.idx, simulators/jax_md/utils.py:48-67):
- * host int32[n_pairs][2], rows (op_i, op_j) in that role order.  Converted to per-nucleotide rows. */
+ * host int32[n_pairs][2], rows (op_i, op_j) in that role order.  Converted to per-nucleotide rows.  Synchronises the device
+ * before the rows are replaced, as the other setters of a system do: an energy or MD launch queued earlier, on any stream,
+ * walks the old rows. */
 int mythos_oxdna_set_neighbors(mythos_system_t* sys, const int32_t* pairs, int n_pairs);
 
 /* GPU Verlet list with bonded exclusions from positions (replaces mythos/utils/neighbors.py:12-59):
- * center dev real[n][3]; pairs with |c_i - c_j| < r_cut + skin are kept. */
+ * center dev real[n][3]; pairs with |c_i - c_j| < r_cut + skin are kept.  The build runs on the stream and the call
+ * synchronises it at least once (rows and cell buckets grow until the build fits): launches queued on that stream before the
+ * call have finished with the old rows, launches on other streams are the caller's to order. */
 int mythos_oxdna_build_neighbors(mythos_system_t* sys, const void* center, double r_cut, double skin,
                                  mythos_stream_t stream);
-/* max and mean row length of the current list (directed neighbours per nucleotide) */
+/* max and mean row length of the current list (directed neighbours per nucleotide); synchronises the device, as
+ * mythos_oxdna_get_rows does */
 int mythos_oxdna_neighbor_stats(mythos_system_t* sys, int* max_row, double* mean_row);
 /* The rows the device holds (diagnostics / tests; synchronises): host int32 rows[n][*stride] - the bonded slots, then the
  * close segment, then the far segment, an entry = neighbour index | role bit - row_len[n] (bonded slots included) and
@@ -154,6 +167,7 @@ int mythos_oxdna_get_rows(mythos_system_t* sys, int32_t* rows, int32_t* row_len,
  *   dU_dquat    dev real[n_frames][n][4] or NULL             (gradient w.r.t. the un-normalised quaternion,
  *                                                            as jax.grad of mythos/energy/utils.py:18-36 gives)
  *   dU_dparams  dev double[n_frames][n_params] or NULL       (flat vector; dependent entries treated as free)
+ * Asynchronous on the stream: launches only, no synchronisation, no host read.
  */
 int mythos_oxdna_energy(mythos_system_t* sys, const void* center, const void* quat, int n_frames, double* e_terms,
                         void* dU_dcenter, void* dU_dquat, double* dU_dparams, mythos_stream_t stream);
@@ -170,7 +184,8 @@ int mythos_oxdna_energy(mythos_system_t* sys, const void* center, const void* qu
  *   de_dconsts    dev double[n_kt][n_frames][MYTHOS_DEBYE_SWEEP_CONSTS] or NULL: partials with respect to the constants
  *                 (the DH_* columns of dU_dparams at each temperature, without the term weight)
  * Models 2 (oxDNA2) and 3 (oxRNA2); model 1 has no such term and model 4 (oxNA: three constant sets per temperature) is
- * refused with MYTHOS_ERR_INVALID_ARGUMENT.  n_frames = 0 or n_kt = 0 returns MYTHOS_OK.  Reproducible bit for bit. */
+ * refused with MYTHOS_ERR_INVALID_ARGUMENT.  n_frames = 0 or n_kt = 0 returns MYTHOS_OK.  Reproducible bit for bit.
+ * Asynchronous on the stream; dh_consts is copied in stream order and must stay alive until the stream has passed the call. */
 #define MYTHOS_DEBYE_SWEEP_CONSTS 5
 int mythos_oxdna_debye_sweep(mythos_system_t* sys, const void* center, const void* quat, int n_frames, int n_kt,
                              const double* dh_consts, double* e_dh, double* de_dconsts, mythos_stream_t stream);
@@ -221,11 +236,11 @@ mythos_obs_t* mythos_observables_create(int model, int n, const double* geometry
                                         int dtype, int device);
 void mythos_observables_destroy(mythos_obs_t* obs);
 int mythos_observables_width(const mythos_obs_t* obs);
-/* center dev real[n_frames][n][3], quat dev real[n_frames][n][4], out dev double[n_frames][width] */
+/* center dev real[n_frames][n][3], quat dev real[n_frames][n][4], out dev double[n_frames][width]; asynchronous on the stream */
 int mythos_observables_eval(mythos_obs_t* obs, const void* center, const void* quat, int n_frames, double* out,
                             mythos_stream_t stream);
 /* mythos_oxdna_energy with observables in the same launch: obs may be NULL (then identical to mythos_oxdna_energy);
- * obs_out dev double[n_frames][width] */
+ * obs_out dev double[n_frames][width].  Asynchronous on the stream, as both are. */
 int mythos_oxdna_energy_obs(mythos_system_t* sys, const void* center, const void* quat, int n_frames, double* e_terms,
                             void* dU_dcenter, void* dU_dquat, double* dU_dparams, mythos_obs_t* obs, double* obs_out,
                             mythos_stream_t stream);
@@ -247,7 +262,7 @@ void mythos_langevin_destroy(mythos_sim_t* sim);
  * (every <= 0: keep the list given by set_neighbors for the whole run) */
 int mythos_langevin_set_neighbor_policy(mythos_sim_t* sim, double r_cut, double skin, int every);
 
-/* draw Maxwell-Boltzmann momenta at kT (init_fn of nvt_langevin) */
+/* draw Maxwell-Boltzmann momenta at kT (init_fn of nvt_langevin); one launch, asynchronous on the stream */
 int mythos_langevin_init_momenta(mythos_sim_t* sim, void* p_lin, void* p_ang, mythos_stream_t stream);
 
 /* Run n_steps; state arrays are updated in place.
@@ -265,7 +280,9 @@ int mythos_langevin_init_momenta(mythos_sim_t* sim, void* p_lin, void* p_ang, my
  * nucleotide has more than 32 neighbours inside the range of an angular term (up to 16 the fast instantiation runs; a
  * launch that finds more aborts, nothing it wrote counts, and the step is repeated with 32 result rows per nucleotide).
  * After an error the arrays hold the positions of the last step that counted and momenta short of that step's closing
- * half kick; mythos_langevin_get_step tells how many steps that was. */
+ * half kick; mythos_langevin_get_step tells how many steps that was.
+ * The call synchronises the stream (load; advance; store - at least the one synchronisation of advance); the copy back to
+ * the caller's arrays is queued behind it, asynchronous on the stream. */
 int mythos_langevin_run(mythos_sim_t* sim, void* center, void* quat, void* p_lin, void* p_ang, int n_steps,
                         int save_every, void* traj_center, void* traj_quat, double* e_trace,
                         mythos_stream_t stream);
@@ -275,7 +292,8 @@ int mythos_langevin_run(mythos_sim_t* sim, void* center, void* quat, void* p_lin
  *   advance  n_steps on the resident state; the list and its rebuild schedule carry over from the previous advance;
  *            outputs as mythos_langevin_run.  One stream synchronisation per call (the halt-and-resume protocol
  *            needs the host to see the control words before the steps count as taken), nothing else between calls
- *   store    resident state -> caller's arrays (asynchronous on the stream); the state stays resident
+ *   store    resident state -> caller's arrays (asynchronous on the stream; an OPEN frame is closed first by one more
+ *            launch through the loop of advance, with its synchronisation); the state stays resident
  * mythos_langevin_run(...) == load; advance; store.  advance after advance continues bit for bit like one advance
  * of the summed length.  An advance that ends in MYTHOS_ERR_NUMERIC drops the resident state.
  * One force evaluation per step: advance(n) is n launches of the step kernel and leaves the resident momenta short of
@@ -293,11 +311,13 @@ int mythos_langevin_advance(mythos_sim_t* sim, int n_steps, int save_every, void
                             double* e_trace, mythos_stream_t stream);
 int mythos_langevin_store(mythos_sim_t* sim, void* center, void* quat, void* p_lin, void* p_ang, mythos_stream_t stream);
 
-/* absolute step counter (RNG stream position); settable for checkpoint/resume */
+/* absolute step counter (RNG stream position); settable for checkpoint/resume.  A host number, read when a launch is
+ * queued: neither call synchronises or touches the device, and a launch queued earlier keeps the value it was queued with. */
 int64_t mythos_langevin_get_step(const mythos_sim_t* sim);
 int mythos_langevin_set_step(mythos_sim_t* sim, int64_t step);
 /* the key of the noise (Philox key; init_momenta draws from it too): what a new `key` argument of the reference's
- * run(opt_params, init_state, n_steps, key) is (mythos/simulators/jax_md/jaxmd.py:60-68), without a new integrator */
+ * run(opt_params, init_state, n_steps, key) is (mythos/simulators/jax_md/jaxmd.py:60-68), without a new integrator.
+ * A host number passed by value to every launch: does not synchronise; launches queued earlier keep the old key. */
 int mythos_langevin_set_seed(mythos_sim_t* sim, uint64_t seed);
 
 /* Constant external forces: oxDNA's external force of `type = string` with `rate = 0` (the reference ships the
@@ -317,7 +337,8 @@ int mythos_langevin_set_seed(mythos_sim_t* sim, uint64_t seed);
  * (MYTHOS_LANGEVIN_UNFUSED); the fused oxNA kernel is supported.
  * The energy-trace rows stay what they are: the external potential -sum F.x is not part of them (it does not depend on
  * the model parameters and cancels in DiffTRe weights), and the kinetic energies of a row are taken after the external
- * kick of that launch, i.e. with the external part of the NEXT step's opening half kick already in the momenta. */
+ * kick of that launch, i.e. with the external part of the NEXT step's opening half kick already in the momenta.
+ * Synchronises the device before a list is replaced (count > 0); count = 0 only clears a host number. */
 int mythos_langevin_set_external_forces(mythos_sim_t* sim, int count, const int32_t* index, const double* force);
 
 /* Position-dependent external forces on centres of mass - the three fixes of the reference's stretch-torsion protocol
@@ -352,7 +373,8 @@ int mythos_langevin_set_external_forces(mythos_sim_t* sim, int count, const int3
  * few members.  mythos_langevin_run / _advance refuse to step with restraints on the unfused oxNA path.
  * The energy-trace rows stay what they are: neither the tether nor the sum-restraint energy is part of them (nor the
  * work of the torque, which has no potential), and the kinetic energies of a row are taken after the external kicks of
- * that launch - see mythos_langevin_set_external_forces.  mythos_langevin_eval_external returns the energies. */
+ * that launch - see mythos_langevin_set_external_forces.  mythos_langevin_eval_external returns the energies.
+ * Synchronises the device before the arrays are replaced (not when an empty set replaces an empty one). */
 enum mythos_restraint_kind { MYTHOS_RESTRAINT_SUM = 0, MYTHOS_RESTRAINT_TORQUE = 1 };
 int mythos_langevin_set_restraints(mythos_sim_t* sim, int n_tethers, const int32_t* t_index, const double* t_k, const double* t_anchor,
                                    const int32_t* t_mask, int n_groups, const int32_t* g_kind, const int32_t* g_first,
@@ -397,7 +419,8 @@ int mythos_langevin_eval_external(mythos_sim_t* sim, const void* center, void* f
  * open; an index out of range; ref_particle == particle; a value that is not finite; stiff < 0; r0 < 0; dir = 0 on a
  * string, a plane or a moving trap; MYTHOS_POINT_PBC on a system without a box, or on another kind.
  * mythos_langevin_run / _advance refuse to step with point forces on the unfused oxNA path.  The energy-trace rows do
- * not hold these energies; mythos_langevin_eval_external_at returns them. */
+ * not hold these energies; mythos_langevin_eval_external_at returns them.
+ * Synchronises the device before the arrays are replaced (not when an empty set replaces an empty one). */
 enum mythos_point_force_kind {
   MYTHOS_POINT_STRING = 0,
   MYTHOS_POINT_TRAP = 1,
@@ -418,7 +441,8 @@ int mythos_point_forces_check(int n, int has_box, int n_terms, const int32_t* ki
 /* mythos_langevin_eval_external at step count `step`, with the point forces' energies:
  *   energy_out device double[8]: the three words of mythos_langevin_eval_external, then the energy of the point terms
  *                                of each kind in the enum's order (string, trap, mutual trap, plane, sphere)
- * mythos_langevin_eval_external is this function at step = 0 with the first three words. */
+ * mythos_langevin_eval_external is this function at step = 0 with the first three words.  Asynchronous on `stream`, and one
+ * call at a time per integrator, as that one. */
 int mythos_langevin_eval_external_at(mythos_sim_t* sim, const void* center, double step, void* force_out, double* energy_out,
                                      mythos_stream_t stream);
 
@@ -438,7 +462,9 @@ int mythos_langevin_set_option(mythos_sim_t* sim, int option, int64_t value);
  *   loop_ms_per_launch   (last event - first event) / launches: includes neighbour rebuilds and
  *                        inter-kernel gaps */
 /* samples: how many dispatches of a run get their own event pair (0 = none, the default; at most 16).  A bracketed
- * dispatch costs ~8 us of queue time, so timing is something the caller switches on (bench.py does). */
+ * dispatch costs ~8 us of queue time, so timing is something the caller switches on (bench.py does).
+ * Host numbers: set_timing is read by the next run / advance, last_kernel_ms returns what the last one stored after its
+ * own stream synchronisation; neither call synchronises. */
 int mythos_langevin_set_timing(mythos_sim_t* sim, int samples);
 int mythos_langevin_last_kernel_ms(const mythos_sim_t* sim, double* kernel_ms, double* loop_ms_per_launch,
                                    int* launches, int* samples);
@@ -447,10 +473,12 @@ int mythos_langevin_last_kernel_ms(const mythos_sim_t* sim, double* kernel_ms, d
  * overflowed its rows / cell buckets.  The launches behind such an event do nothing; the run rebuilds at the last
  * valid state (growing what overflowed) and continues there, so neither is an error - the reference's neighbour
  * list signals `did_buffer_overflow` and leaves the reallocation to the caller (jax_md partition, used at
- * mythos/simulators/jax_md/utils.py:70-126).  More than 64 in one run fails with MYTHOS_ERR_OVERFLOW. */
+ * mythos/simulators/jax_md/utils.py:70-126).  More than 64 in one run fails with MYTHOS_ERR_OVERFLOW.
+ * A host number, stored by the call it describes behind that call's own stream synchronisation: the getter does not synchronise. */
 int mythos_langevin_last_recoveries(const mythos_sim_t* sim, int* recoveries);
 /* scheduled list rebuilds (every rebuild_every steps) that fell inside the last run / advance; the build that creates a
- * list and the out-of-turn ones above are not counted.  bench.py reports it next to the timed region. */
+ * list and the out-of-turn ones above are not counted.  bench.py reports it next to the timed region.  A host number, as
+ * mythos_langevin_last_recoveries: the getter does not synchronise. */
 int mythos_langevin_last_rebuilds(const mythos_sim_t* sim, int* scheduled);
 
 /* ---- umbrella sampling on the resident Langevin state ---------------------------------------------
@@ -495,7 +523,10 @@ int mythos_langevin_last_rebuilds(const mythos_sim_t* sim, int* scheduled);
  *                 them for the proposal row, bit for bit), its states, W_old, W_new, u, accept (0 / 1), then the states
  *                 the replica holds after the decision (the sample row's)
  * advance_umbrella(a) then (b) continues bit for bit like one call of a + b segments.
- * mythos_langevin_umbrella_counts: decisions accepted and taken since set_umbrella (the priming boundary is not one). */
+ * mythos_langevin_umbrella_counts: decisions accepted and taken since set_umbrella (the priming boundary is not one).
+ * Streams: set_umbrella synchronises the device before its arrays are replaced; advance_umbrella returns with the decision
+ * and commit launches of its last boundary still queued on the stream (its outputs are in stream order, as everywhere);
+ * umbrella_counts reads the device's counters and synchronises the device first. */
 int mythos_umbrella_check(int n, int n_rep, int model, int n_bonded, const int32_t* bonded, int n_ops, const int32_t* op_kind,
                           const int32_t* op_first, const int32_t* pairs, int n_pairs, const int32_t* iface_first,
                           const double* interfaces, const int32_t* table_shape, const double* table, int segment_steps);
@@ -570,6 +601,7 @@ void mythos_martini_destroy(mythos_martini_t* m);
  * (mythos/simulators/gromacs/gromacs.py:70-131).  Synchronises the device. */
 int mythos_martini_set_params(mythos_martini_t* m, const double* sigma, const double* eps, const double* bond_k, const double* bond_r0,
                               const double* angle_k, const double* angle_t0);
+/* Energies [lj, bond, angle] per frame and optionally dU/dpos; all-pairs sweep, fixed-order reduction.  Asynchronous on the stream. */
 int mythos_martini_energy(mythos_martini_t* m, const void* pos, const void* box, int n_frames, double* e_terms,
                           void* dU_dpos, mythos_stream_t stream);
 
@@ -580,7 +612,8 @@ int mythos_martini_energy(mythos_martini_t* m, const void* pos, const void* box,
  *                    pair (owner, partner), each unordered bead pair contributing half to either order: the
  *                    derivative with respect to a symmetric entry is out[a][b] + out[b][a]
  *   d_bond_k/_r0     [n_frames][n_bonds]     d_angle_k/_t0  [n_frames][n_angles]   (one value per bond / angle;
- *                    the host sums the bonds that share a named parameter) */
+ *                    the host sums the bonds that share a named parameter)
+ * Asynchronous on the stream. */
 int mythos_martini_param_grads(mythos_martini_t* m, const void* pos, const void* box, int n_frames, double* d_sigma,
                                double* d_eps, double* d_bond_k, double* d_bond_r0, double* d_angle_k,
                                double* d_angle_t0, mythos_stream_t stream);
@@ -600,7 +633,8 @@ int mythos_martini_param_grads(mythos_martini_t* m, const void* pos, const void*
  * takes the charges in force when a call of it begins (load, run, advance, store, pressure).
  * mythos_martini_coulomb: e_coul dev double[n_frames] (pairs + excluded pairs + self term), dU_dpos dev real[n_frames][n][3]
  * or NULL, written (not accumulated); all-pairs sweep and fixed-order reduction of mythos_martini_energy.  Without charges
- * both are zero. */
+ * both are zero.
+ * Streams: set_charges synchronises the device before the charge table is replaced; coulomb is asynchronous on the stream. */
 int mythos_martini_set_charges(mythos_martini_t* m, const double* q, double epsilon_r, double epsilon_rf);
 int mythos_martini_coulomb(mythos_martini_t* m, const void* pos, const void* box, int n_frames, double* e_coul,
                            void* dU_dpos, mythos_stream_t stream);
@@ -629,27 +663,42 @@ int mythos_martini_langevin_set_neighbor_policy(mythos_martini_sim_t* sim, doubl
  * bilayer with margin 0.2 nm, every 4.  margin <= 0, margin >= skin or every < 2 switches the pruned rows off.  The forces are those of the Verlet rows up to the
  * order of the sums. */
 int mythos_martini_langevin_set_inner_list(mythos_martini_sim_t* sim, double margin, int every);
+/* Maxwell-Boltzmann velocities at the integrator's kT (an ensemble: every slot at its current kT, with its seed); one
+ * launch per copy, asynchronous on the stream */
 int mythos_martini_langevin_init_velocities(mythos_martini_sim_t* sim, void* vel, mythos_stream_t stream);
+/* load; advance; store in one call: synchronises the stream (the synchronisation of advance, and one more behind the copy
+ * back: pos and vel are complete when the call returns) */
 int mythos_martini_langevin_run(mythos_martini_sim_t* sim, void* pos, void* vel, const double* box, int n_steps,
                                 int save_every, void* traj_pos, double* e_trace, mythos_stream_t stream);
 /* Resident form, as mythos_langevin_load / advance / store: the state stays in the integrator's layout on the device
  * between calls, the list and its rebuild schedule carry over, advance(n) is n launches of the step kernel and leaves the
  * frame open (velocities short of the closing half kick of step n; the next advance or store supplies it).
  * mythos_martini_langevin_run == load; advance; store.  advance(a); advance(b) == advance(a + b), bit for bit.
- * e_trace == NULL with traj_pos != NULL: positions-only rows, written by the step launch that produces the saved state. */
+ * e_trace == NULL with traj_pos != NULL: positions-only rows, written by the step launch that produces the saved state.
+ * Streams, as for oxDNA: load is asynchronous for a single copy (an ensemble's load first waits for the stream: the staging
+ * buffer of its replica table is reused); advance synchronises the stream once per call, and once more per coupling or
+ * exchange event; store is asynchronous on a closed frame and closes an open one through the loop of advance first.  The
+ * first of these calls after mythos_martini_set_params / _set_charges waits for the stream before it replaces the
+ * integrator's own tables. */
 int mythos_martini_langevin_load(mythos_martini_sim_t* sim, const void* pos, const void* vel, const double* box,
                                  mythos_stream_t stream);
 int mythos_martini_langevin_advance(mythos_martini_sim_t* sim, int n_steps, int save_every, void* traj_pos, double* e_trace,
                                     mythos_stream_t stream);
 int mythos_martini_langevin_store(mythos_martini_sim_t* sim, void* pos, void* vel, mythos_stream_t stream);
+/* the absolute step counter: a host number, the call does not synchronise */
 int64_t mythos_martini_langevin_get_step(const mythos_martini_sim_t* sim);
-/* scheduled list rebuilds inside the last advance (as mythos_langevin_last_rebuilds) */
+/* scheduled list rebuilds inside the last advance (as mythos_langevin_last_rebuilds).  This and the three entries below
+ * return host numbers the last run / advance stored behind its own stream synchronisation; set_timing sets one the next
+ * call reads: none of them synchronises. */
 int mythos_martini_langevin_last_rebuilds(const mythos_martini_sim_t* sim, int* scheduled);
 int mythos_martini_langevin_last_kernel_ms(const mythos_martini_sim_t* sim, double* kernel_ms,
                                            double* loop_ms_per_launch, int* launches, int* samples);
 int mythos_martini_langevin_set_timing(mythos_martini_sim_t* sim, int samples); /* as mythos_langevin_set_timing */
-/* out-of-turn rebuilds of the last run (same protocol as mythos_langevin_last_recoveries) */
+/* out-of-turn rebuilds of the last run (same protocol as mythos_langevin_last_recoveries; a host number, the getter does not
+ * synchronise) */
 int mythos_martini_langevin_last_recoveries(const mythos_martini_sim_t* sim, int* recoveries);
+/* longest and mean Verlet row (an ensemble: over the n_rep n rows); reads the device's row lengths and synchronises the
+ * device first, as mythos_martini_langevin_get_rows */
 int mythos_martini_langevin_neighbor_stats(const mythos_martini_sim_t* sim, int* max_row, double* mean_row);
 /* Diagnostics / tests: the neighbour rows as the device holds them, which = 0 the Verlet rows, 1 the pruned rows
  * (mythos_martini_langevin_set_inner_list).  rows host int32[n][*stride], row_len host int32[n]; with both NULL only
@@ -678,10 +727,12 @@ int mythos_martini_langevin_set_barostat(mythos_martini_sim_t* sim, int kind, in
  * and the virial -dU/dln s_d of LJ + bonds + angles, plus reaction-field Coulomb while the system holds charges), P[3] = (K + W) / V x 16.6053907 (bar), V (nm^3).  Closes an open
  * frame first, as store does; a closed frame is left bitwise as it was.  Synchronises the stream. */
 int mythos_martini_langevin_pressure(mythos_martini_sim_t* sim, double out[10], mythos_stream_t stream);
-/* the box of the resident state (host double[3]): the one loaded, rescaled by the coupling events since */
+/* the box of the resident state (host double[3]): the one loaded, rescaled by the coupling events since.  A host copy kept up
+ * to date behind the synchronisation of every coupling event: the getter does not synchronise. */
 int mythos_martini_langevin_get_box(const mythos_martini_sim_t* sim, double box[3]);
 /* The box of every row the last run / advance saved, host double[*n_rows][3] (the .gro / .trr box line of a GROMACS
- * trajectory).  A row saved at an event step holds the state before the event and its box.  boxes == NULL: only *n_rows. */
+ * trajectory).  A row saved at an event step holds the state before the event and its box.  boxes == NULL: only *n_rows.
+ * A host log: the getter does not synchronise. */
 int mythos_martini_langevin_last_boxes(const mythos_martini_sim_t* sim, double* boxes, int* n_rows);
 
 /* ---- MARTINI temperature ensemble: n_rep copies of one system, own kT, box, seed and barostat history, one launch per step
@@ -713,9 +764,12 @@ int mythos_martini_ensemble_check(int n, int n_rep, const double* kT, double r_c
 int mythos_martini_langevin_n_replicas(const mythos_martini_sim_t* sim); /* 1 for a single-copy handle */
 /* A handle made new for another run: seeds host uint64[replicas] (one for a single-copy handle), the step counter set to
  * `step`, the resident state dropped - the next call must be a load or a run.  Settings (list policy, barostat) and buffers stay.
- * After it the handle computes what a handle created with these seeds computes, bit for bit. */
+ * After it the handle computes what a handle created with these seeds computes, bit for bit.  An ensemble's ladder goes back
+ * to the identity through the path of set_ladder, which synchronises the device; a single copy's restart sets host numbers only. */
 int mythos_martini_langevin_restart(mythos_martini_sim_t* sim, const uint64_t* seeds, int64_t step);
+/* as mythos_martini_langevin_pressure for every replica: closes an open frame first, synchronises the stream */
 int mythos_martini_langevin_pressure_ensemble(mythos_martini_sim_t* sim, double* out, mythos_stream_t stream);
+/* as mythos_martini_langevin_get_box for every replica: host copies, the getter does not synchronise */
 int mythos_martini_langevin_get_box_ensemble(const mythos_martini_sim_t* sim, double* boxes);
 
 /* ---- MARTINI temperature ensemble: replica exchange between the temperatures -----------------------------------
@@ -801,7 +855,10 @@ int mythos_martini_exchange_check(int n_rep, int every, const int32_t* rung_of_s
  * constant-force - (or NULL) and xi dev double[R][n_pull] (or NULL; written with energies).  Needs no resident state.
  * mythos_martini_langevin_pull_values: xi of every coordinate of a stored trajectory, pos dev real[n_frames][R][n][3] ->
  * out dev double[n_frames][R][n_pull]; the same centre-of-mass kernel and the same evaluation as the kick.
- * mythos_martini_langevin_n_pull: coordinates of the installed set (0 without one). */
+ * mythos_martini_langevin_n_pull: coordinates of the installed set (0 without one).
+ * Streams: set_restraints synchronises the device before the set is replaced; eval_external and pull_values are asynchronous
+ * on the stream (their scratch belongs to the integrator: one call at a time per integrator; a call that needs more of it
+ * than any before reallocates it, which waits for the device). */
 int mythos_martini_restraints_check(int n, int n_rep, int n_posres, const int32_t* pr_index, const double* pr_k, const double* pr_ref,
                                     int n_flat, const int32_t* fb_index, const int32_t* fb_flags, const double* fb_param, int n_groups,
                                     const int32_t* g_first, const int32_t* g_member, const int32_t* g_pbc_ref, int n_pull,
@@ -877,6 +934,7 @@ mythos_martini_obs_t* mythos_martini_obs_create(int n, int n_groups, const int32
 void mythos_martini_obs_destroy(mythos_martini_obs_t* obs);
 /* items per frame = doubles per frame of the output */
 int64_t mythos_martini_obs_count(const mythos_martini_obs_t* obs);
+/* one launch over every group and frame, asynchronous on the stream */
 int mythos_martini_obs_eval(mythos_martini_obs_t* obs, const void* pos, const void* box, int dtype, int n_frames, double* out,
                             mythos_stream_t stream);
 
@@ -909,7 +967,8 @@ void mythos_w1_plan_destroy(mythos_w1_plan_t* plan);
  *          the same n_frames
  * w1       dev double[n_groups]
  * dw1_dweights  dev double[n_groups][max n_frames] or NULL: dW_g/dweights[s], with sign(0) = 0 where the reference
- *          differentiates jnp.abs.  Bitwise reproducible: fixed summation order, no atomics. */
+ *          differentiates jnp.abs.  Bitwise reproducible: fixed summation order, no atomics.
+ * Asynchronous on the stream (mythos_w1_plan_create synchronises it: the order is checked on the device). */
 int mythos_w1_eval(mythos_w1_plan_t* plan, const double* weights, double* w1, double* dw1_dweights, mythos_stream_t stream);
 
 /* ---- membrane observables: leaflets, thickness, area per lipid ---------------------------------
@@ -938,7 +997,8 @@ int mythos_membrane_n_lipids(const mythos_membrane_t* mem);
  *             bead), area per lipid Lx Ly (occupied leaflets) / n_lipids (nm^2), midpoint z, lipids in leaflet +1,
  *             lipids in leaflet -1, mean z of the thickness beads of leaflet +1, of leaflet -1 (NaN if none)
  *   leaflets  dev int8[n_frames][n_lipids] (+1 / -1) or NULL
- * Double sums in a fixed order, no atomics: a frame's row has the same bits whatever else is in the launch. */
+ * Double sums in a fixed order, no atomics: a frame's row has the same bits whatever else is in the launch.  Asynchronous on
+ * the stream. */
 int mythos_membrane_eval(mythos_membrane_t* mem, const void* pos, const void* box, int dtype, int n_frames, double* out,
                          int8_t* leaflets, mythos_stream_t stream);
 
@@ -962,7 +1022,8 @@ int mythos_membrane_eval(mythos_membrane_t* mem, const void* pos, const void* bo
  *       the reflection fix; here Horn's quaternion by Jacobi sweeps, then a second pass over the residuals); raw
  *       coordinates, no minimum image (rmse.py:61-65)
  * center dev real[n_frames][n][3], quat dev real[n_frames][n][4] of precision dtype, read as they are; arithmetic in
- * double, sums in a fixed order, no atomics: a frame's row has the same bits whatever else is in the launch. */
+ * double, sums in a fixed order, no atomics: a frame's row has the same bits whatever else is in the launch.
+ * mythos_duplex_obs_eval is asynchronous on the stream. */
 #define MYTHOS_DUPLEX_ROW 4
 typedef struct mythos_duplex_obs mythos_duplex_obs_t;
 mythos_duplex_obs_t* mythos_duplex_obs_create(int model, int n, const double* geometry, const double* box, int n_bp,
@@ -998,7 +1059,7 @@ int mythos_rdf_n_pairs(const mythos_rdf_t* rdf, int64_t* n_pairs);
  *             floor(r n_bins / r_max), at most n_bins - 1
  *   flags     dev int32[1]: -1, or the first frame with a box edge of a masked dimension below 2 r_max, where the
  *             minimum image no longer finds the closest pair (the counts of such a frame are not to be used)
- * Integer adds: the counts have the same bits from run to run. */
+ * Integer adds: the counts have the same bits from run to run.  Asynchronous on the stream (the counts are zeroed on it too). */
 int mythos_rdf_eval(mythos_rdf_t* rdf, const void* pos, const void* box, int dtype, int n_frames, int64_t* counts,
                     int32_t* flags, mythos_stream_t stream);
 

@@ -397,9 +397,12 @@ static int list_build_until_fit(VerletRows& L, int n, Build&& build, bool headro
   return MYTHOS_ERR_OVERFLOW;
 }
 
-// longest and mean row of n rows whose lengths are at d_len, less `fixed` slots of each (oxDNA: the bonded ones)
+// longest and mean row of n rows whose lengths are at d_len, less `fixed` slots of each (oxDNA: the bonded ones).  A
+// stream-less getter: it waits for the device, as the *_get_rows entries do - the null-stream copy below is not ordered with a
+// build queued on a non-blocking stream.
 static inline int row_stats(const int* d_len, int n, int fixed, int* max_row, double* mean_row) {
   std::vector<int> len(n);
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());
   MYTHOS_HIP_TRY(hipMemcpy(len.data(), d_len, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   long long tot = 0;
   int mx = 0;

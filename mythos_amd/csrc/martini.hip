@@ -584,6 +584,7 @@ int mythos_martini_set_charges(mythos_martini_t* m, const double* q, double epsi
   }
   if (!any && !m->has_charge) return MYTHOS_OK;  // nothing to clear: the system stays exactly as it was
   MYTHOS_HIP_TRY(hipSetDevice(m->device));
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());  // (launches that read the charges replaced below, as mythos_martini_set_params)
   if (any) {
     if (int rc = m->d_charge.upload_real(m->dtype, q, (size_t)m->n)) return rc;
     m->h_charge.assign(q, q + m->n);

@@ -37,6 +37,9 @@ int rows_from_pairs(mythos_system* sys, const int32_t* pairs, int n_pairs) {
     rows[(size_t)i * stride + len[i]++] = j;               // i plays op_i
     rows[(size_t)j * stride + len[j]++] = i | ROW_ROLE_Q;  // j plays op_j
   }
+  // blocking null-stream copies: a launch queued on a non-blocking stream may still walk the old rows (the setters of
+  // capi.hip wait in the same way before they replace a table)
+  MYTHOS_HIP_TRY(hipDeviceSynchronize());
   if (int rc = rows_reserve(sys->list, n, stride)) return rc;
   MYTHOS_HIP_TRY(hipMemcpy(sys->list.d_rows.get(), rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
   MYTHOS_HIP_TRY(hipMemcpy(sys->d_row_len.get(), len.data(), n * sizeof(int), hipMemcpyHostToDevice));
@@ -531,12 +534,13 @@ bool rows_filter_applies(const mythos_system* sys, double r_cut, double skin, do
          cell_grid(g, sys->n, r_cut + skin, sys->has_box ? sys->box : nullptr);
 }
 
-// the candidate store's buffers (first use; the rows start at a stride of 96: ~60 candidates of a duplex)
-static int cand_reserve(mythos_system* sys) {
+// the candidate store's buffers (first use; the rows start at a stride of 96: ~60 candidates of a duplex).  The overflow
+// words are cleared on the stream of the build that reads them: a null-stream memset is not ordered with a non-blocking stream.
+static int cand_reserve(mythos_system* sys, hipStream_t stream) {
   const int n = sys->n;
   if (!sys->cand.d_overflow) {
     if (int rc = sys->cand.d_overflow.alloc(kOverflowWords)) return rc;
-    MYTHOS_HIP_TRY(hipMemset(sys->cand.d_overflow.get(), 0, kOverflowWords * sizeof(int)));
+    MYTHOS_HIP_TRY(hipMemsetAsync(sys->cand.d_overflow.get(), 0, kOverflowWords * sizeof(int), stream));
   }
   if (!sys->d_cand_len)
     if (int rc = sys->d_cand_len.alloc(2 * (size_t)n)) return rc;
@@ -547,7 +551,7 @@ static int cand_reserve(mythos_system* sys) {
 }
 
 int rows_wide_build_device(mythos_system* sys, const void* p0, double r_cut, double skin, double margin, hipStream_t stream) {
-  if (int rc = cand_reserve(sys)) return rc;
+  if (int rc = cand_reserve(sys, stream)) return rc;
   const double rl = r_cut + skin + margin;
   const int rc = with_real(sys->dtype, [&](auto real) {
     using R = decltype(real);
@@ -586,7 +590,7 @@ int rows_filter_device(mythos_system* sys, const void* p0, const void* p3, const
 
 int rows_filter_until_fit(mythos_system* sys, const void* p0, const void* p3, const void* p1, double r_cut, double skin, double margin,
                           hipStream_t stream) {
-  if (int rc = cand_reserve(sys)) return rc;
+  if (int rc = cand_reserve(sys, stream)) return rc;
   // (the builder keeps two segments of a row's stride per nucleotide in LDS, 128 B per slot of a workgroup's 64 KB)
   constexpr int kCandStrideMax = 384;
   auto wide = [&]() -> int {
